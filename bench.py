@@ -7,12 +7,17 @@ north-star set (n=630, N=1024, k=1, l=3).  One "step" = one pass of the hot path
 sample extraction) over one batch of B synthetic ciphertexts per GPU, inputs already resident in HBM.  The batch shards over GPUs
 with no data-path collective (independent ciphertexts; keys replicated) -> "scaling": "weak".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started without a launcher (`WORLD_SIZE` unset) and with --gpus N > 1, it starts the N ranks itself (a torch.distributed.run child
 process, one rank per GPU, before this process touches a GPU) and exits with the child's code; it never prints a line for fewer
-GPUs than were asked for.  Rank 0 prints ONE JSON line:
+GPUs than were asked for.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the decrypt check of the timed outputs,
+and a line with the contract's fields (`ms_per_step` = wall-clock of one timed step) and the run's configuration.
+--dump-outputs DIR writes rank 0's outputs of the last timed step as float64 .npy files (see dump_outputs); the inputs are
+seeded, so two builds given the same arguments can be compared output for output.  --full adds everything below:
 
 * top level: the contract's fields, then the scalars to quote - inverse_{2x2,3x3,4x4}_s (headline engine, evaluate wall-clock),
   inverse_3x3_batched_{s_per_matrix, pbs_per_s} (16 matrices in one walk of the levels: the serving form, evaluate_many),
@@ -26,6 +31,7 @@ GPUs than were asked for.  Rank 0 prints ONE JSON line:
   the GPU, re-checked inside the run) on this box's host cores, on a bounded sample of the same ciphertexts (N=1, rank 0 only);
 * legs (N=1, rank 0; objects `secure128_torus`, `secure128_torus_wide`, `p49_field`, `torus64_unrolled_key`, `unrolled_key_49`; `--goldilocks-leg` adds the
   Goldilocks kernels): PBS/s, kernel time, output noise against the CGGI formula, latency of 1 and 256, inverse wall-clocks.
+The --no-* options, --goldilocks-leg and --inverse-sharded trim or extend what --full does.
 """
 import argparse
 import json
@@ -200,6 +206,25 @@ def compact(res):
     return sig(r)
 
 
+DUMP_ROWS = 1024      # ciphertexts kept whole in the dump: 2 x 1,024 x 1,025 x 8 B = 16.8 MB at N = 1024, far below 64 MB
+
+
+def dump_outputs(path, eng, out, dec):
+    """What a caller of the timed path receives, as float64 (exact): `messages` (every output decrypted), `phase` (every
+    output's phase as a signed fraction of the modulus: message plus noise) and a fixed sample of DUMP_ROWS whole output
+    ciphertexts (rows drawn with seed 2024, ascending) split into `ciphertexts_sample_hi32` / `_lo32`, the high and low 32 bits
+    of every word.  The full batch (B x (N + 1) words, 67 MB at the default) is larger than a dump should be."""
+    os.makedirs(path, exist_ok=True)
+    Qm = eng.modulus
+    rows = np.sort(np.random.default_rng(2024).choice(out.shape[0], min(out.shape[0], DUMP_ROWS), replace=False))
+    arrays = {"messages": dec.astype(np.float64),
+              "phase": np.array([((int(x) + Qm // 2) % Qm - Qm // 2) / Qm for x in eng.phase(out)], dtype=np.float64),
+              "ciphertexts_sample_hi32": (out[rows] >> np.uint64(32)).astype(np.float64),
+              "ciphertexts_sample_lo32": (out[rows] & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -230,11 +255,20 @@ def main():
                          "ranks (executor.py; one RCCL all-gather per split level)")
     ap.add_argument("--shard-threshold", type=int, default=None,
                     help="narrowest level that is split across ranks (default: every level wider than one kernel round)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's outputs of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, output noise, latencies, CPU baseline, "
+                         "the other engines and parameter sets, encrypted-inverse wall-clocks, the complete report")
     args = ap.parse_args()
     sharded_sizes = args.inverse_sizes or "8"
     args.inverse_sizes = args.inverse_sizes or "2,3,4"
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if (args.goldilocks_leg or args.inverse_sharded) and not args.full:
+        raise SystemExit("--goldilocks-leg and --inverse-sharded are parts of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -303,15 +337,18 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    events = []
-    clock = SclkSampler()
-    clock.start()
+    # --full: kernel time by events and the shader clock during the timed steps, for the roofline
+    events = [] if args.full else None
+    clock = SclkSampler() if args.full else None
+    if clock:
+        clock.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step(events)
     barrier()
     elapsed = time.perf_counter() - t0
-    clock.stop()
+    if clock:
+        clock.stop()
     per_rank_s = [elapsed]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -320,13 +357,14 @@ def main():
         per_rank_s = [float(x.item()) for x in allt]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    br_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
 
     # correctness of what was timed: every output decrypts to LUT[m]
     out = d_out.cpu().numpy().view(np.uint64)
     dec = eng.decrypt(out, DL)
     want = np.where(lut_sel == 0, msgs, rnd_table[msgs + 8])
     verified = bool(np.array_equal(dec, want))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, out, dec)
 
     KERNEL = {64: "k_blind_rotate_tp<2>", 49: "k_blind_rotate_tpx49<13, 3, 15>", 65: "k_blind_rotate_t64f<3, 10, false>"}
     ARITH = {64: "integers mod 2^64-2^32+1 in u64 (64-bit integer VALU)",
@@ -337,6 +375,41 @@ def main():
                  "words as the oracle's integer arithmetic; keyswitch: int8 matrix cores"}
     DTYPE = {64: "u64", 49: "f64", 65: "u64/f64"}
     CTS_PER_WG = {64: 2, 49: 4, 65: 4}       # ciphertexts per workgroup of the wave-pair kernels (one workgroup per compute unit)
+
+    total_pbs = B * world * args.steps
+    value = total_pbs / elapsed
+    res = {
+        "metric": "PBS/sec per GPU + encrypted n x n inverse wall-clock (n=2,3,4)", "value": value, "unit": "PBS/s",
+        "n_gpus": world, "world_size_seen": (dist.get_world_size() if dist is not None else 1),
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPE[eng.q_bits], "data": "synthetic",
+        "config": {"workload": f"pbs_batch: B={B} LWE ciphertexts per GPU per step, TFHE n=630 N=1024 k=1 l=3 "
+                               f"(Bg=2^{P.bs_base_log}, ks 8x4 bits), q_bits={eng.q_bits}, 4-bit signed messages, 2 LUTs (identity, random)",
+                   "arithmetic": ARITH[eng.q_bits],
+                   "keys": "bmi_keygen_insecure_deterministic(0x5EED): one key set replicated on every rank without an exchange",
+                   "batch_per_gpu": B, "pbs_per_gpu_per_s": value / world,
+                   "per_rank_pbs_per_s": [B * args.steps / t for t in per_rank_s],
+                   "verified_decrypt": verified,
+                   "multi_gpu_placement": "PBS batches shard over the ranks (contiguous ranges, no data-path collective); the encrypted "
+                                          "inverses of configs 2-4 are placed on ONE GPU by design (their levels are at most 256-1,024 wide: "
+                                          "one kernel round); --inverse-sharded splits the wide levels of the 8x8 across the ranks",
+                   "derived_reference_pbs_per_s_64core_cpu": "35-69 (derived, BASELINE.md section 1)"},
+    }
+
+    def close():
+        """ends the run on every rank; exits non-zero when the timed outputs failed the decrypt check"""
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        eng.close()
+        if not verified:
+            raise SystemExit("bench outputs failed decrypt verification")
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res))
+        return close()
 
     def key_weights(e):
         sk_small, sk_big = e.export_keys()[:2]
@@ -364,6 +437,7 @@ def main():
                 "log2_max_abs": float(np.log2(np.abs(err).max())), "log2_half_box": -6.0,
                 "bsk_precision_bits": int(prec)}
 
+    br_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
     # shader clock while the timed kernels ran (sysfs, sampled by a thread during the timed region); the spec maximum if unreadable
     sclk_mhz, sclk_src = clock.result()
 
@@ -392,8 +466,6 @@ def main():
                 "source": "static ISA count (profiles/r04_isa_counts.json) x live launch rate; peak = 256 CUs x 4 SIMDs x sclk",
                 "modmul_per_s": MODMUL_PER_PBS * count / (kernel_ms * 1e-3), "modmul_per_pbs": MODMUL_PER_PBS}
 
-    total_pbs = B * world * args.steps
-    value = total_pbs / elapsed
     achieved_gbs = BSK_BYTES_PER_PBS * B / (br_ms * 1e-3) / 1e9
     traffic = valu_busy = None
     tpath = os.path.join(REPO, "profiles", "hbm_traffic.json")
@@ -428,26 +500,8 @@ def main():
                 "kernel_cycles_per_cmux": cycles_per_cmux(br_ms, B, P.n, CTS_PER_WG[eng.q_bits], sclk_mhz),
                 "sclk_mhz": sclk_mhz,
                 "north_star_frac": achieved_gbs / HBM_PEAK_GBS, "north_star": north_star, "alu": alu}
-    res = {
-        "metric": "PBS/sec per GPU + encrypted n x n inverse wall-clock (n=2,3,4)", "value": value, "unit": "PBS/s",
-        "n_gpus": world, "world_size_seen": (dist.get_world_size() if dist is not None else 1),
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": DTYPE[eng.q_bits], "data": "synthetic",
-        "config": {"workload": f"pbs_batch: B={B} LWE ciphertexts per GPU per step, TFHE n=630 N=1024 k=1 l=3 "
-                               f"(Bg=2^{P.bs_base_log}, ks 8x4 bits), q_bits={eng.q_bits}, 4-bit signed messages, 2 LUTs (identity, random)",
-                   "arithmetic": ARITH[eng.q_bits],
-                   "keys": "bmi_keygen_insecure_deterministic(0x5EED): one key set replicated on every rank without an exchange",
-                   "batch_per_gpu": B, "pbs_per_gpu_per_s": value / world,
-                   "per_rank_pbs_per_s": [B * args.steps / t for t in per_rank_s],
-                   "verified_decrypt": verified,
-                   "output_noise": output_noise(eng, out, want) if rank == 0 else None,
-                   "multi_gpu_placement": "PBS batches shard over the ranks (contiguous ranges, no data-path collective); the encrypted "
-                                          "inverses of configs 2-4 are placed on ONE GPU by design (their levels are at most 256-1,024 wide: "
-                                          "one kernel round); --inverse-sharded splits the wide levels of the 8x8 across the ranks",
-                   "derived_reference_pbs_per_s_64core_cpu": "35-69 (derived, BASELINE.md section 1)"},
-        "roofline": roofline,
-    }
+    res["config"]["output_noise"] = output_noise(eng, out, want) if rank == 0 else None
+    res["roofline"] = roofline
 
     def latency_ms(e, d_small_x, d_ids_x, d_out_x, cnt):
         e.blind_rotate(d_small_x, d_ids_x, cnt, d_out_x, stream)
@@ -734,12 +788,7 @@ def main():
         except Exception:
             pass
         print(json.dumps(compact(res)))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    eng.close()
-    if not verified:
-        raise SystemExit("bench outputs failed decrypt verification")
+    close()
 
 
 if __name__ == "__main__":

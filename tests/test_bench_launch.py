@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,3 +69,29 @@ def test_bench_gpus2_on_one_gpu_reports_two_ranks():
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["world_size_seen"] == 2 and rec["value"] > 0
     assert rec["config"]["verified_decrypt"] is True and rec["scaling"] == "weak"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """a plain run times exactly --steps steps and, with --dump-outputs, writes the last step's outputs as float64 .npy
+    (at most 64 MB): the decrypted messages are the look-ups of the seeded inputs, and a second run writes the same arrays"""
+    B = 512
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        p, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--dump-outputs", str(d)], {}, 600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["config"]["verified_decrypt"] is True
+        assert "roofline" not in rec and "cpu_baseline" not in rec           # --full only
+        files = sorted(d.iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert {"messages", "phase", "ciphertexts_sample_hi32", "ciphertexts_sample_lo32"} <= set(arrays)
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        dumps.append(arrays)
+    msgs = np.random.default_rng(1234).integers(-8, 8, B)
+    want = np.where(np.arange(B) & 1, np.random.default_rng(99).integers(-8, 8, 16)[msgs + 8], msgs)
+    assert np.array_equal(dumps[0]["messages"], want)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])

@@ -569,7 +569,11 @@ def test_reference_whole_inverse_traced_unmodified_simulate():
             assert ours.simulate(v["inputs"]) == v["expected"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/matrix_inversion"), reason="needs the reference checkout (build container only)")
+REF_MODULES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "matrix_inversion")
+
+
+@pytest.mark.skipif(not os.path.isfile(os.path.join(REF_MODULES, "qfloat_matrix_inversion.pyc")),
+                    reason="needs the reference's modules, which build() compiles into oracle/_ref only where a reference checkout is readable")
 def test_shim_retraces_the_reference_to_the_committed_fixture():
     """Generator guard, build container only: the Concrete-compatible front end (bmi_amd/compat) run again on the reference's
     unmodified `base_p_subtraction` and `QFloat.__mul__` gives circuits that agree with the committed fixture on its
@@ -582,7 +586,7 @@ def test_shim_retraces_the_reference_to_the_committed_fixture():
     code = r'''
 import json, os, random, sys
 repo = sys.argv[1]
-sys.path[:0] = [os.path.join(repo, "bounty-matrix-inversion_amd", "bmi_amd", "compat"), "/root/reference/matrix_inversion", os.path.join(repo, "bounty-matrix-inversion_amd")]
+sys.path[:0] = [os.path.join(repo, "bounty-matrix-inversion_amd", "bmi_amd", "compat"), sys.argv[2], os.path.join(repo, "bounty-matrix-inversion_amd")]
 import numpy as np
 from concrete import fhe
 import base_p_arrays as ref
@@ -634,7 +638,7 @@ whole(2, 20, 8, False, True, False)
 whole(3, 16, 8, True, True, True)
 print("ok")
 '''
-    out = subprocess.run([sys.executable, "-c", code, repo], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "-c", code, repo, REF_MODULES], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 

@@ -56,18 +56,18 @@ PY
     # the driver's exact command, on a cold program cache as on the driver's box
     CMD="--steps 20 --warmup 5"
     echo "bench ($CMD)" > $F/progress.log; T0=$(date +%s)
-    BMI_CACHE_DIR=/tmp/bmi_cold_cache_$$ python bench.py $CMD > $F/bench_default.json 2> $F/bench_default.err || { tail -5 $F/bench_default.err; exit 1; }
+    BMI_CACHE_DIR=/tmp/bmi_cold_cache_$$ python bench.py $CMD --full > $F/bench_default.json 2> $F/bench_default.err || { tail -5 $F/bench_default.err; exit 1; }
     cp gpurun_out/bench_details.json $F/bench_details.json 2>/dev/null
     echo "bench took $(( $(date +%s) - T0 )) s" >> $F/progress.log
     # the same timed region under the profiler (legs, CPU baseline and inverses off: they are not the timed region)
-    PROF="python3 bench.py $CMD --batch $B --no-cpu-baseline --no-inverse --no-second-field"
+    PROF="python3 bench.py $CMD --full --batch $B --no-cpu-baseline --no-inverse --no-second-field"
     echo trace >> $F/progress.log
     rocprofv3 --kernel-trace --stats --output-format csv -d $F/prof/trace -- $PROF > $F/prof_trace.log 2>&1 || { tail -5 $F/prof_trace.log; exit 1; }
     grep -o '"sclk_mhz": [0-9.]*' $F/prof_trace.log | head -1 > $F/summary/sclk_during_trace.txt
     for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT"; do
       set -- $pass; name=$1; shift
       echo "pmc $name" >> $F/progress.log
-      rocprofv3 --pmc "$@" --output-format csv -d $F/prof/$name -- python3 bench.py --steps 2 --warmup 1 --batch $B --no-cpu-baseline --no-inverse --no-second-field > $F/prof_$name.log 2>&1 || echo "$name pass failed"
+      rocprofv3 --pmc "$@" --output-format csv -d $F/prof/$name -- python3 bench.py --steps 2 --warmup 1 --full --batch $B --no-cpu-baseline --no-inverse --no-second-field > $F/prof_$name.log 2>&1 || echo "$name pass failed"
     done
     python3 tools/summarize_prof.py $TAG $B $F/prof $F/summary $F/prof_trace.log > $F/summary/summary.log 2>&1 || { tail -20 $F/summary/summary.log; exit 1; }
     rm -rf $F/prof
