@@ -231,7 +231,6 @@ struct bmi_ctx {
     size_t ks_partial_bytes = 0;
     // keyswitch on the matrix cores: limb-wise key (per keygen), digit matrix and int32 sums (growable scratch)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
-    bool no_big_lds = false;  // set when a > 64 KB LDS kernel could not be configured on this device (auto mode only)
     bool ks_mfma_ok = false;
     signed char *d_ks_limbs = nullptr, *d_ks_digits = nullptr;
     int *d_ks_sums = nullptr;
@@ -1173,11 +1172,8 @@ int bmi_set_kernel_variant(bmi_ctx *c, int variant) {
     if (!c) return -1;
     if (variant < 0 || variant > 6) return fail(c, -1, "variant must be 0..6");
     if (variant >= 5 && !c->t64()) return fail(c, -1, "kernel variants 5 and 6 (floating-point transform) exist on the 2^64 torus only");
-#ifndef BMI_AB_KERNELS
     if (c->f64() && !c->wide() && !c->quad() && (variant == 1 || variant == 4))
-        return fail(c, -1, "kernel variants 1 and 4 of the 49-bit field (the predecessors of the wave-pair and latency kernels) are not "
-                           "in the product build: make -C csrc ab builds libbmi_tfhe_ab.so with them");
-#endif
+        return fail(c, -1, "kernel variants 1 and 4 are refused on the 49-bit field at N = 1024: 3 and 2 replaced their kernels there");
     c->variant = variant;
     return 0;
 }
@@ -1265,123 +1261,83 @@ int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *
     if (!c || (count && (!d_small || !d_lut_ids || !d_out))) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     HIP_OK(c, hipSetDevice(c->device));
+    // unrolled key (49-bit field at N = 1024 / 2048, 2^64 torus at N = 1024: bmi_set_bsk_unroll refuses the rest): one kernel
+    // (one workgroup per ciphertext) for every batch size, so that a ciphertext's bits never depend on the batch it travelled in
+    if (c->unroll == 2 && !c->have_bsk3)
+        return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
     // variant 0 = auto: the latency kernel (one workgroup per ciphertext) while the batch cannot fill the chip
     // with wave-pair work, the throughput kernel beyond that (49-bit field: the exchange-once form).
     const bool latency = c->variant == 2 || (c->variant == 0 && count <= c->lat_threshold);
+    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
+    hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (c->t64() && c->wide() && c->d_bsk_w2 && (c->variant == 1 || c->variant == 3 || (c->variant == 0 && count > 256))) {
-        // N = 2048, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins the
-        // one-ciphertext form below); the same words
-        rc = bmit::launch_blind_rotate_wide2(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk_w2, c->d_tw_fq, d_out, count, c->P.n, c->bsk_prec,
-                                             c->P.bs_levels, c->P.bs_base_log, (hipStream_t)stream);
-        return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-    }
-    if (c->t64() && (c->wide() || c->quad())) {   // 2^64 torus at N = 2048 / 4096: one workgroup per ciphertext (N = 2048: up to 256 ciphertexts, see above)
-        rc = (c->quad() ? bmit::launch_blind_rotate_quad : bmit::launch_blind_rotate_wide)(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk_w, c->d_tw_fq, d_out, count, c->P.n,
-                                            c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, nullptr, (hipStream_t)stream);
-        return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-    }
-    if (c->t64()) {   // 2^64 torus: latency kernel (one workgroup per ciphertext) for small batches, wave pairs beyond
-        if (c->unroll == 2) {   // unrolled key: one kernel (one workgroup per ciphertext) for every batch size
-            if (!c->have_bsk3) return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
+    if (c->t64()) {
+        const u64 *luts = (const u64 *)c->d_luts;
+        const int prec = c->bsk_prec;
+        if (c->wide() && c->d_bsk_w2 && (c->variant == 1 || c->variant == 3 || (c->variant == 0 && count > 256))) {
+            // N = 2048, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins the
+            // one-ciphertext form below); the same words
+            rc = bmit::launch_blind_rotate_wide2(d_small, d_lut_ids, luts, c->d_bsk_w2, c->d_tw_fq, d_out, count, n, prec, lv, bl, st);
+        } else if (c->wide() || c->quad()) {   // N = 2048 / 4096: one workgroup per ciphertext (N = 2048: up to 256 ciphertexts, see above)
+            rc = (c->quad() ? bmit::launch_blind_rotate_quad : bmit::launch_blind_rotate_wide)(d_small, d_lut_ids, luts, c->d_bsk_w, c->d_tw_fq, d_out,
+                                                                                               count, n, prec, lv, bl, nullptr, st);
+        } else if (c->unroll == 2) {
             // the floating-point-transform route (42-bit key): one ciphertext per workgroup up to a full round of 256, two per workgroup
             // (key words shared in registers: half the key bytes per bootstrap) beyond - the same words either way; variant 2 pins
             // the former, variants 1 / 3 the latter
-            const bool ufft = bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
+            const bool ufft = bmit::shape_supported_unrolled_fft(prec, lv, bl);
             const bool two = ufft && (c->variant == 1 || c->variant == 3 || (c->variant == 0 && count > 256));
-            rc = two ? bmit::launch_blind_rotate_tp2u_fft(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out,
-                                                          count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, (hipStream_t)stream)
-                 : ufft
-                     ? bmit::launch_blind_rotate_lat2u_fft(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out,
-                                                           count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, nullptr, (hipStream_t)stream)
-                     : bmit::launch_blind_rotate_lat2u(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out,
-                                                       count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, (hipStream_t)stream);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+            if (two)
+                rc = bmit::launch_blind_rotate_tp2u_fft(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out, count, n, prec,
+                                                        lv, bl, st);
+            else if (ufft)
+                rc = bmit::launch_blind_rotate_lat2u_fft(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out, count, n,
+                                                         prec, lv, bl, nullptr, st);
+            else
+                rc = bmit::launch_blind_rotate_lat2u(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out, count, n, prec,
+                                                     lv, bl, st);
+        } else {   // N = 1024: latency kernel (one workgroup per ciphertext) for small batches, wave pairs beyond
+            if (!c->d_bsk_fft && !bmit::shape_supported(prec, lv, bl))
+                return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
+            if ((c->variant == 5 || c->variant == 6) && !c->d_bsk_fft)
+                return fail(c, -1, "kernel variant " + std::to_string(c->variant) +
+                                       " needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
+            // (floating-point-transform kernels: two rounds of 256 one-workgroup bootstraps, 7.7 ms, still beat the wave-pair kernel's
+            // 8.4 ms up to 1,024 ciphertexts; three rounds do not)
+            const bool lat_t = c->variant == 2 || c->variant == 4 || c->variant == 6 || (c->variant == 0 && count <= c->lat_threshold);
+            // through the floating-point transform where its key copy exists (48-bit key, base 2^10): variants 4 (latency) and
+            // 1 / 3 (wave pairs) pin the exact transform mod 2^49 - 720895, 5 and 6 the floating-point one
+            const bool fft = c->d_bsk_fft && (lat_t ? c->variant != 4 : c->variant == 0 || c->variant == 5);
+            if (!fft)
+                if (int rcb = build_exact_torus_copies(c, nullptr)) return rcb;   // (a no-op once built)
+            if (lat_t && fft)
+                rc = bmit::launch_blind_rotate_lat_fft(d_small, d_lut_ids, luts, c->d_bsk_latf, c->d_tw_fh, d_out, count, n, prec, lv, bl, nullptr, st);
+            else if (lat_t)
+                rc = bmit::launch_blind_rotate_lat(d_small, d_lut_ids, luts, c->d_bsk_lat, c->d_tw_half, d_out, count, n, prec, lv, bl, st);
+            else if (fft)
+                rc = bmit::launch_blind_rotate_fft(d_small, d_lut_ids, luts, c->d_bsk_fft, c->d_tw_fft, d_out, count, n, prec, lv, bl, nullptr, st);
+            else
+                rc = bmit::launch_blind_rotate(d_small, d_lut_ids, luts, (const double *)c->d_bsk, (const double *)c->d_tw, d_out, count, n, prec,
+                                               lv, bl, st);
         }
-        if (!c->d_bsk_fft && !bmit::shape_supported(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
-            return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
-        // (floating-point-transform kernels: two rounds of 256 one-workgroup bootstraps, 7.7 ms, still beat the wave-pair kernel's
-        // 8.4 ms up to 1,024 ciphertexts; three rounds do not)
-        const bool lat_t = c->variant == 2 || c->variant == 4 || c->variant == 6 || (c->variant == 0 && count <= c->lat_threshold);
-        if (c->variant == 6 && !c->d_bsk_fft)
-            return fail(c, -1, "kernel variant 6 needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
-        if (lat_t && c->d_bsk_fft && c->variant != 4) {   // latency form through the floating-point transform (variant 4 pins the exact one)
-            rc = bmit::launch_blind_rotate_lat_fft(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk_latf, c->d_tw_fh, d_out, count,
-                                                   c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, nullptr, (hipStream_t)stream);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        if (lat_t) {
-            if (int rcb = build_exact_torus_copies(c, nullptr)) return rcb;   // (variant 4, or a key without FFT copies: a no-op once built)
-            rc = bmit::launch_blind_rotate_lat(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk_lat, c->d_tw_half, d_out,
-                                               count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, (hipStream_t)stream);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        // wave pairs: through the floating-point transform where its key copy exists (48-bit key, base 2^10; variant 5 pins it,
-        // variants 1 / 3 pin the exact transform mod 2^49 - 720895)
-        if (c->variant == 5 && !c->d_bsk_fft)
-            return fail(c, -1, "kernel variant 5 needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
-        if (c->d_bsk_fft && (c->variant == 0 || c->variant == 5)) {
-            rc = bmit::launch_blind_rotate_fft(d_small, d_lut_ids, (const u64 *)c->d_luts, c->d_bsk_fft, c->d_tw_fft, d_out, count, c->P.n,
-                                               c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, nullptr, (hipStream_t)stream);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        if (int rcb = build_exact_torus_copies(c, nullptr)) return rcb;       // (variants 1 / 3, or a key without FFT copies)
-        rc = bmit::launch_blind_rotate(d_small, d_lut_ids, (const u64 *)c->d_luts, (const double *)c->d_bsk,
-                                       (const double *)c->d_tw, d_out, count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log,
-                                       (hipStream_t)stream);
-        return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-    }
-    if (c->f64()) {
+    } else if (c->f64()) {
         const double *luts = (const double *)c->d_luts, *bsk = (const double *)c->d_bsk, *tw = (const double *)c->d_tw;
-        hipStream_t st = (hipStream_t)stream;
-        if (c->wide() && c->unroll == 2) {   // N = 2048 with the unrolled key
-            if (!c->have_bsk3) return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
-            rc = bmi49::launch_blind_rotate_wide_u(d_small, d_lut_ids, luts, c->d_bsk3_lat, tw, c->d_tw_wide, c->d_root_pow, d_out, count,
-                                                   c->P.n, c->P.bs_levels, c->P.bs_base_log, st);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        if (c->wide() || c->quad()) {   // N = 2048 / 4096: one kernel for every batch size
-            rc = c->quad() ? bmi49::launch_blind_rotate_quad(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, c->P.n, st)
-                           : bmi49::launch_blind_rotate_wide(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, c->P.n,
-                                                             c->P.bs_levels, c->P.bs_base_log, st);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        // auto mode falls back from the kernels that need > 64 KB of LDS per workgroup to their predecessors (still on
-        // the GPU) if the device refuses the configuration; a pinned variant reports the error instead
-        const bool lb3 = c->P.bs_levels == 3 && c->P.bs_base_log == 15;   // variants 1 and 4 exist for (3, 2^15) only
-        if (!lb3 && (c->variant == 1 || c->variant == 4))
-            return fail(c, -1, "kernel variants 1 and 4 exist for (l, Bg) = (3, 2^15) only");
-        const uint32_t lv = c->P.bs_levels, bl = c->P.bs_base_log;
-        if (c->unroll == 2) {   // unrolled key: one kernel (one workgroup per ciphertext) for every batch size, so that a
-                                // ciphertext's bits never depend on the batch it travelled in
-            if (!c->have_bsk3) return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
-            rc = bmi49::launch_blind_rotate_lat2u(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out, count,
-                                                  c->P.n, lv, bl, st);
-            return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-        }
-        if (c->variant == 4 || (latency && c->no_big_lds && lb3)) {
-            rc = bmi49::launch_blind_rotate_lat(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, st);
-        } else if (latency) {
-            rc = bmi49::launch_blind_rotate_lat2(d_small, d_lut_ids, luts, c->d_bsk_lat, c->d_tw_half, d_out, count, c->P.n, lv, bl, st);
-            if (rc && c->variant == 0 && lb3) {
-                (void)hipGetLastError();
-                c->no_big_lds = true;
-                rc = bmi49::launch_blind_rotate_lat(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, st);
-            }
-        } else if (c->variant == 1 || (c->no_big_lds && lb3)) {
-            rc = bmi49::launch_blind_rotate_tp(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, st);
-        } else {
-            rc = bmi49::launch_blind_rotate_tpx(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, lv, bl, st);
-            if (rc && c->variant == 0 && lb3) {
-                (void)hipGetLastError();
-                c->no_big_lds = true;
-                rc = bmi49::launch_blind_rotate_tp(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, st);
-            }
-        }
+        if (c->wide() && c->unroll == 2)   // N = 2048 with the unrolled key
+            rc = bmi49::launch_blind_rotate_wide_u(d_small, d_lut_ids, luts, c->d_bsk3_lat, tw, c->d_tw_wide, c->d_root_pow, d_out, count, n, lv,
+                                                   bl, st);
+        else if (c->wide() || c->quad())   // N = 2048 / 4096: one kernel for every batch size
+            rc = c->quad() ? bmi49::launch_blind_rotate_quad(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, n, st)
+                           : bmi49::launch_blind_rotate_wide(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, n, lv, bl, st);
+        else if (c->unroll == 2)
+            rc = bmi49::launch_blind_rotate_lat2u(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out, count, n, lv, bl, st);
+        else if (latency)
+            rc = bmi49::launch_blind_rotate_lat2(d_small, d_lut_ids, luts, c->d_bsk_lat, c->d_tw_half, d_out, count, n, lv, bl, st);
+        else
+            rc = bmi49::launch_blind_rotate_tpx(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, lv, bl, st);
     } else {
         const u64 *luts = (const u64 *)c->d_luts, *bsk = (const u64 *)c->d_bsk, *tw = (const u64 *)c->d_tw;
-        rc = latency ? bmi::launch_blind_rotate_lat(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, (hipStream_t)stream)
-                     : bmi::launch_blind_rotate_tp(d_small, d_lut_ids, luts, bsk, tw, d_out, count, c->P.n, (hipStream_t)stream);
+        rc = latency ? bmi::launch_blind_rotate_lat(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, st)
+                     : bmi::launch_blind_rotate_tp(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, st);
     }
     return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
 }

@@ -9,11 +9,6 @@
 #define BMI_DEFAULT_Q_BITS 65  // modulus of bmi_default_params(): 65 = BMI_Q_TORUS64 (q = 2^64, Concrete's own: the default since round 4), 49 (f64 kernels mod 2^49 - 720895) or 64 (Goldilocks)
 #endif
 
-#ifndef BMI_TP49_CTS
-#define BMI_TP49_CTS 2              // ciphertexts per workgroup, f64 throughput kernel (3 with a 168-VGPR budget spills: measured slower)
-#define BMI_TP49_WAVES_PER_SIMD 2
-#endif
-
 #ifndef BMI_TPX49_PF
 #define BMI_TPX49_PF 13  // exchange-once kernel: where the two GGSW rows of a level are requested (see the kernel)
 #endif
@@ -22,19 +17,6 @@
 #define BMI_TPX49_RESYNC 4  // workgroup barrier every so many CMUX iterations (0: never): keeps the four pairs on the same key rows, which they share through L1 (83.5 -> 80.6 ms)
 #endif
 
-#ifndef BMI_TPX49_SYNC
-#define BMI_TPX49_SYNC 0  // pair synchronisation of the exchange-once kernel: 0 = LDS counters (pairs only), 1 = workgroup barrier
-#endif
-
-#ifndef BMI_TPX49_PRIO
-#define BMI_TPX49_PRIO 3  // s_setprio inside a CMUX of the exchange-once kernel: 0 = none, 1 = raised until the partial sums are published, 2 = raised after, 3 = stepping down 3,3,2,1 over decomposition and the three levels, 0 from the exchange on (the wavefront that is behind on a SIMD gets the issue slots: 80.0 -> 78.1 ms), 4 = raised for the inverse only (no gain)
-#endif
-#ifndef BMI_LAT2_PRIO
-#define BMI_LAT2_PRIO 2  // s_setprio in the forward tasks of the latency kernels (N = 1024 two-wave transforms, N = 2048, N = 4096): tasks sharing a SIMD step down 3,2,1,0 as they advance, so they finish together instead of the last one running its tail alone (4.02 -> 3.57 ms per bootstrap at N = 1024; 1: three steps, 3.60 ms; 0: none)
-#endif
-#ifndef BMI_WIDE_STAGE
-#define BMI_WIDE_STAGE 2  // key-word requests of the N = 2048 kernel: 0 = all before the task, 1 = half before / half after the decomposition, 2 = a quarter each before the task, after the decomposition, mid-transform and before its last transpose (8.95 -> 8.55 ms per bootstrap in one session)
-#endif
 // Capacity of a context's look-up table buffer (tables of N words, allocated at creation).  A power of two: the kernels
 // mask the ids they are handed with it, so that a wrong id in a device-resident id array reads a wrong (possibly
 // unregistered) table instead of faulting; the host-buffer entry points refuse unknown ids outright.
@@ -100,8 +82,6 @@ using gl::i64;
 using gl::u64;
 int launch_bsk_to_ntt(const u64 *std_polys, double *ntt_polys, const double *g_tw, uint32_t n_polys, hipStream_t s);
 int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw, uint32_t count, hipStream_t s);
-int launch_blind_rotate_tp(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                           const double *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s);
 // third parameter set N = 4096: key copy in slot order (scaled by 1/4); g_t = T_1, T_2, T_3, then their inverses ([6][1024])
 int launch_bsk_to_quad(const u64 *std_polys, double *quad_polys, const double *g_tw, const double *g_t, uint32_t n_polys,
                        hipStream_t s);
@@ -121,7 +101,7 @@ int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, co
 // paired: A_lo[p], A_hi[p] side by side (one 16-byte request per slot; the unrolled kernel's layout), else [A_lo 512][A_hi 512]
 int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, bool paired, hipStream_t s);
 // (levels, base log) of the bootstrap decomposition: (3, 15), (2, 15) and (1, 23) are instantiated in the three kernels
-// below; the other 49-bit kernels (variants 1 and 4, N = 4096) and the Goldilocks ones take (3, 15) only
+// below; the 49-bit N = 4096 kernel and the Goldilocks ones take (3, 15) only
 int launch_blind_rotate_lat2(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat,
                              const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
                              hipStream_t s);
@@ -133,8 +113,6 @@ int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, con
 int launch_blind_rotate_tpx(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
                             const double *g_tw, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
                             hipStream_t s);
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                            const double *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s);
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
                      uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
                      hipStream_t s);

@@ -8,8 +8,7 @@
 //   k_blind_rotate_lat2_49   LATENCY: one workgroup of 16 wavefronts per ciphertext, two wavefronts per transform
 //   k_blind_rotate_wide49 / wide49u / quad49   N = 2048 (plain, unrolled key) and N = 4096
 //   keyswitch / lincomb      ks_lincomb.hpp with the Field49 policy
-// (the unrolled N = 1024 kernel lives in bmi_kernels_f64u.hip; the predecessors k_blind_rotate_tp49 / lat49 - kernel variants
-// 1 and 4 - are A/B builds only: ab/bmi_kernels_f64_ab.inc, `make ab`)
+// (the unrolled N = 1024 kernel lives in bmi_kernels_f64u.hip)
 #include <hip/hip_runtime.h>
 
 #include "bmi_internal.hpp"
@@ -78,28 +77,9 @@ __device__ unsigned long long g_phase[128];
         ph_[k] += t_ - tl_;                      \
         tl_ = t_;                                \
     } while (0)
-#define PH_FLUSH()                                                           \
-    do {                                                                     \
-        if (blockIdx.x == gridDim.x / 2 && lane == 0)                        \
-            for (int k_ = 0; k_ < 8; k_++) g_phase[wave * 8 + k_] = ph_[k_]; \
-    } while (0)
 #else
 #define PH_DECL()
 #define PH_MARK(k)
-#define PH_FLUSH()
-#endif
-
-// Peels the least significant remaining digit off r: returns it and leaves floor(r / 2^15 + 1/2) in r.
-// Walking the levels 2, 1, 0 this way keeps ONE array live (digit_of() from r would keep r, r1 and r2).
-__device__ __forceinline__ double peel_digit(double &r) {
-    const double rn = round_half_up(r, 0x1p-15);
-    const double d = __builtin_fma(-32768.0, rn, r);
-    r = rn;
-    return d;
-}
-
-#ifdef BMI_AB_KERNELS
-#include "ab/bmi_kernels_f64_ab.inc"
 #endif
 
 // THROUGHPUT, second form: one exchange per CMUX instead of three.
@@ -122,11 +102,6 @@ __device__ __forceinline__ void pair_post(uint32_t *flag, uint32_t v) {
 // The poll loop is one opaque asm block: as C++ control flow it splits the loop body into several blocks and the
 // register allocator then spills ~180 dwords per lane (measured); all lanes read the same LDS word.
 __device__ __forceinline__ void pair_wait(uint32_t *flag, uint32_t v) {
-#if BMI_TPX49_SYNC == 1
-    (void)flag;
-    (void)v;
-    __syncthreads();
-#else
     const uint32_t addr = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)flag;
     uint32_t tmp;
     asm volatile(
@@ -141,7 +116,6 @@ __device__ __forceinline__ void pair_wait(uint32_t *flag, uint32_t v) {
         : "=&v"(tmp)
         : "v"(addr), "s"(v)
         : "vcc", "memory");
-#endif
 }
 
 // keeps memory operations and the machine scheduler from moving work across this point (register pressure control)
@@ -193,13 +167,9 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
 #endif
         const uint32_t a_t = at[i];
         const double *bsk_c = bsk + ((size_t)i * 4 * L + c * 2 * L) * N;  // this wavefront's L GGSW rows (two columns each)
-#if BMI_TPX49_PRIO == 1
-        __builtin_amdgcn_s_setprio(1);
-#elif BMI_TPX49_PRIO == 2 || BMI_TPX49_PRIO == 4
-        __builtin_amdgcn_s_setprio(0);
-#elif BMI_TPX49_PRIO == 3
+        // priority steps down 3, 3, 2, 1 over the decomposition and the three levels, 0 from the exchange on: the wavefront
+        // that is behind on a SIMD gets the issue slots (80.0 -> 78.1 ms)
         __builtin_amdgcn_s_setprio(3);
-#endif
         wave_sync();
         double r[16];
         {
@@ -227,9 +197,7 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
             auto load_m = [&]() { static_for<0, 8>([&](auto VP) { bm[VP] = row_m[VP * 64 + lane]; }); };
             auto load_o = [&]() { static_for<0, 8>([&](auto VP) { bo[VP] = row_o[VP * 64 + lane]; }); };
             pin();
-#if BMI_TPX49_PRIO == 3
             __builtin_amdgcn_s_setprio(lev + 1);
-#endif
             if constexpr (PM == 0) load_m();
             if constexpr (PO == 0) load_o();
             double x[16];
@@ -275,11 +243,7 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
             reinterpret_cast<double2 *>(tile)[VP * 64 + lane] = double2{ao[2 * VP], ao[2 * VP + 1]};
         });
         pair_post(f_pub, i + 1);
-#if BMI_TPX49_PRIO == 1 || BMI_TPX49_PRIO == 3
         __builtin_amdgcn_s_setprio(0);
-#elif BMI_TPX49_PRIO == 2
-        __builtin_amdgcn_s_setprio(1);
-#endif
         pair_wait(f_pub_partner, i + 1);
         static_for<0, 8>([&](auto VP) {
             const double2 p = reinterpret_cast<const double2 *>(ptile)[VP * 64 + lane];
@@ -288,9 +252,6 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
         });
         pair_post(f_ack, i + 1);          // release: the reads above have landed
         pair_wait(f_ack_partner, i + 1);  // the partner has read this tile: the inverse transform may overwrite it
-#if BMI_TPX49_PRIO == 4
-        __builtin_amdgcn_s_setprio(1);
-#endif
         inverse(am, lane, lds, tile);
         static_for<0, 16>([&](auto J) { accl[lane + 64 * J] = f49::red(accl[lane + 64 * J] + am[J]); });
     }
@@ -408,9 +369,7 @@ __global__ void __launch_bounds__(L2_THREADS)
             const int pz = wave >> 1;
             const double *ac = acc + c * N;
             double x[8];
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(3);
-#endif
             static_for<0, 8>([&](auto J) {
                 const uint32_t m = lane + 64 * J;
                 const uint32_t e = (2 * m + h + 2 * N - a_t) & (2 * N - 1);
@@ -424,9 +383,7 @@ __global__ void __launch_bounds__(L2_THREADS)
             else ntth::forward_half<false>(x, lane, lds, tile);
             wave_sync();
             static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         }
         PH_MARK(0);
         __syncthreads();
@@ -501,9 +458,7 @@ static_assert(W_LDS_WORDS <= BMI_LDS_WORDS_MAX, "W_LDS_WORDS exceeds the 160 KB 
 // (measured on the N = 1024 latency kernel: 4.02 -> 3.57 ms per bootstrap).
 template <int P>
 __device__ __forceinline__ void prio() {
-#if BMI_LAT2_PRIO
     __builtin_amdgcn_s_setprio(P);
-#endif
 }
 struct PrioStep1 {
     __device__ __forceinline__ void operator()() const { prio<1>(); }
@@ -593,7 +548,8 @@ __global__ void __launch_bounds__(W_THREADS)
             // One CU takes its key words in at ~29 B per cycle with 8-byte requests, ~48 with 16-byte ones (131 KB in the first
             // round; the (A[p], A[p + 1024]) pairs are stored side by side for that), and a wavefront cannot run
             // ahead of a load it has not been able to issue: the rows are requested in stages between the pieces of
-            // the task instead of all up front (BMI_WIDE_STAGE: 0 = all first, 1 = two stages, 2 = four).
+            // the task instead of all up front: a quarter each before the task, after the decomposition, mid-transform and
+            // before its last transpose (8.95 -> 8.55 ms per bootstrap against all up front).
             auto load_rows = [&](auto RA_, auto RB_) {
                 static_for<RA_, RB_>([&](auto R) {
                     constexpr int r = R;
@@ -608,9 +564,9 @@ __global__ void __launch_bounds__(W_THREADS)
             };
             using IC0 = std::integral_constant<int, 0>;
             using ICN = std::integral_constant<int, NR>;
-            constexpr int S1 = BMI_WIDE_STAGE == 0 ? NR : (BMI_WIDE_STAGE == 1 ? NR / 2 : NR / 4);   // rows requested first
-            constexpr int S2 = BMI_WIDE_STAGE == 2 ? NR / 2 : NR;                                    // ... by the end of the decomposition
-            constexpr int S3 = BMI_WIDE_STAGE == 2 ? (3 * NR + 3) / 4 : NR;                          // ... by the middle of the transform
+            constexpr int S1 = NR / 4;             // rows requested first
+            constexpr int S2 = NR / 2;             // ... by the end of the decomposition
+            constexpr int S3 = (3 * NR + 3) / 4;   // ... by the middle of the transform
             if (wave < 2 * NR) {
                 load_rows(IC0(), std::integral_constant<int, S1>());
                 pin();
@@ -788,7 +744,7 @@ __global__ void __launch_bounds__(W_THREADS)
             };
             using IC0 = std::integral_constant<int, 0>;
             using ICN = std::integral_constant<int, NR>;
-            constexpr int S1 = NR / 4, S2 = NR / 2, S3 = (3 * NR + 3) / 4;   // key 0's rows are requested in four stages (BMI_WIDE_STAGE 2)
+            constexpr int S1 = NR / 4, S2 = NR / 2, S3 = (3 * NR + 3) / 4;   // key 0's rows are requested in four stages (as in k_blind_rotate_wide49)
             if (wave < 2 * NR) {
                 load_rows(b, 0, IC0(), std::integral_constant<int, S1>());
                 pin();
@@ -1176,24 +1132,6 @@ int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw
     return 0;
 }
 
-#ifdef BMI_AB_KERNELS
-int launch_blind_rotate_tp(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                           const double *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    if (count == 0) return 0;
-    constexpr int CTS = BMI_TP49_CTS;
-    hipLaunchKernelGGL((k_blind_rotate_tp49<CTS>), dim3((count + CTS - 1) / CTS), dim3(128 * CTS), 0, s, small_cts, lut_ids,
-                       luts, bsk, g_tw, out, count, n);
-    BMI49_LAUNCH_CHECK();
-    return 0;
-}
-#else
-// variants 1 and 4 are A/B kernels (make ab): not in the product build
-int launch_blind_rotate_tp(const u64 *, const uint32_t *, const double *, const double *, const double *, u64 *, uint32_t, uint32_t, hipStream_t) {
-    return (int)hipErrorNotSupported;
-}
-#endif
-
-
 // (levels, base log) pairs the templated kernels are instantiated for
 #define BMI49_FOR_LB(levels, base_log, F)                            \
     do {                                                             \
@@ -1343,24 +1281,6 @@ int launch_blind_rotate_lat2(const u64 *small_cts, const uint32_t *lut_ids, cons
     launch9_t f = pick_lat2(levels, base_log);
     return f ? f(small_cts, lut_ids, luts, bsk_lat, g_tw_h, out, count, n, s) : (int)hipErrorInvalidValue;
 }
-
-#ifdef BMI_AB_KERNELS
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                            const double *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    if (count == 0) return 0;
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)LAT_LDS_WORDS * sizeof(double);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(k_blind_rotate_lat49), lds, configured)) return rc;
-    hipLaunchKernelGGL(k_blind_rotate_lat49, dim3(count), dim3(LAT_THREADS), lds, s, small_cts, lut_ids, luts, bsk, g_tw,
-                       out, count, n);
-    BMI49_LAUNCH_CHECK();
-    return 0;
-}
-#else
-int launch_blind_rotate_lat(const u64 *, const uint32_t *, const double *, const double *, const double *, u64 *, uint32_t, uint32_t, hipStream_t) {
-    return (int)hipErrorNotSupported;
-}
-#endif
 
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
                      uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,

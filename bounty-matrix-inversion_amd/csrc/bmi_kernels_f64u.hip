@@ -108,9 +108,7 @@ __global__ void __launch_bounds__(L2_THREADS)
             const int pz = wave >> 1;
             const double *ac = acc + c * N + h * ntth::HALF;
             double x[8];
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(3);
-#endif
             static_for<0, 8>([&](auto J) {
                 x[J] = Dec<L, BG>::digit(round_half_up(ac[lane + 64 * J], Dec<L, BG>::SC), lev);
             });
@@ -119,9 +117,7 @@ __global__ void __launch_bounds__(L2_THREADS)
             else ntth::forward_half<false>(x, lane, lds, tile);
             wave_sync();
             static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         }
         PH_MARK(0);
         __syncthreads();
@@ -204,13 +200,6 @@ __global__ void __launch_bounds__(L2_THREADS)
     }
 }
 
-#ifndef BMI_LAT2U_PIPE
-#define BMI_LAT2U_PIPE 0   // 1: the flag-synchronised form of the kernel above (an experiment that measured slower: ab/bmi_kernels_f64u_pipe.inc)
-#endif
-#if BMI_LAT2U_PIPE
-#include "ab/bmi_kernels_f64u_pipe.inc"
-#endif
-
 }  // namespace
 
 #ifdef BMI_PHASE_PROF
@@ -235,13 +224,8 @@ struct LaunchLat2u {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat, const double *g_tw_h,
                   const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
         static std::atomic<uint64_t> configured{0};
-#if BMI_LAT2U_PIPE
-        const size_t lds = (size_t)L2UP_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_lat2up_49<L, BG>;
-#else
         const size_t lds = (size_t)L2U_LDS_WORDS * sizeof(double);
         auto kern = k_blind_rotate_lat2u_49<L, BG>;
-#endif
         if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
         hipLaunchKernelGGL(kern, dim3(count), dim3(L2_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out,
                            count, n);

@@ -34,17 +34,8 @@ using namespace nttf;
 
 namespace {
 
-#ifndef BMI_T64_DB
-#define BMI_T64_DB 0      // key rows: 1 = one row requested ahead of the one being multiplied (12 spilled registers), 0 = request, then multiply (no spills); measured equal (156.5 vs 156.7 ms): the kernel is VALU-issue bound
-#endif
 #ifndef BMI_T64_RESYNC
 #define BMI_T64_RESYNC BMI_TPX49_RESYNC   // workgroup barrier every so many CMUXes (keeps the four pairs on the same key rows)
-#endif
-#ifndef BMI_T64_ACCF
-#define BMI_T64_ACCF 1    // wave-pair kernel, 48-bit key: accumulator as the exact integer word / 2^16 in a double (0: u64 words)
-#endif
-#ifndef BMI_T64_PRIO
-#define BMI_T64_PRIO 1    // 1 = issue priority steps down through the forward transforms (3, 2, 1), 0 in the limb loop; 0 = none
 #endif
 using t64::f64_to_word;
 using t64::Scheme;
@@ -91,7 +82,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
     // accumulator is then kept as the exact integer word / 2^PRE, centred mod 2^AB (AB = 64 - PRE <= 52), in a DOUBLE - rotation,
     // difference and limb accumulation are a handful of f64 instructions instead of half-rate 64-bit integer ones, and the result
     // is the same word (the reduction mod 2^AB is the wrap of the u64 arithmetic).  The exact key (PRE = 0) keeps u64 words.
-    constexpr bool ACCF = BMI_T64_ACCF && PREC == 48;   // (the 42-bit option would spill registers in this form: it keeps u64 words)
+    constexpr bool ACCF = PREC == 48;   // (the 42-bit option would spill registers in this form: it keeps u64 words)
     constexpr int AB = ACCF ? 64 - PRE : 52;   // (unused without ACCF)
     u64 *accs = reinterpret_cast<u64 *>(tiles + 2 * CTS * SCRATCH_WORDS);
     double *at_base = reinterpret_cast<double *>(accs + 2 * CTS * N);
@@ -137,9 +128,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
         const uint32_t a_t = at[i];
         // this wavefront's three GGSW rows: [row = 3 c + lev][column][limb][N]
         const double *bsk_c = bsk + ((size_t)i * 4 * L + c * 2 * L) * LIMBS * N;
-#if BMI_T64_PRIO
-        __builtin_amdgcn_s_setprio(3);
-#endif
+        __builtin_amdgcn_s_setprio(3);   // issue priority steps down through the forward transforms (3, 2, 1), 0 in the limb loop
         wave_sync();
         double r[16];
         if constexpr (ACCF) {
@@ -171,9 +160,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = L - 1 - LEV;  // least significant digit first
             pin();
-#if BMI_T64_PRIO
             __builtin_amdgcn_s_setprio(lev + 1);
-#endif
             static_for<0, 16>([&](auto J) {
                 if constexpr (lev == 0) {
                     X[0][J] = r[J];
@@ -185,9 +172,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
             });
             forward(X[lev], lane, lds, tile);
         });
-#if BMI_T64_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         static_for<0, LIMBS>([&](auto JL) {
             constexpr int j = JL;
             // 2 L key rows of this limb, partner's column first (its partial sum is published while the own column is
@@ -196,20 +181,17 @@ __global__ void __launch_bounds__(128 * T64_CTS)
                 const int lev = q % L, col = q < L ? (c ^ 1) : c;
                 return reinterpret_cast<const double2 *>(bsk_c + ((size_t)(lev * 2 + col) * LIMBS + j) * N);
             };
-            double2 kb[BMI_T64_DB ? 2 : 1][8];
-            if constexpr (BMI_T64_DB) static_for<0, 8>([&](auto VP) { kb[0][VP] = row_ptr(0)[VP * 64 + lane]; });
+            // each key row is requested, then multiplied: requesting one row ahead spills 12 registers and measured equal
+            // (156.5 against 156.7 ms): the kernel is VALU-issue bound
+            double2 kb[8];
             double acc[16];
             hand++;
             static_for<0, 2 * L>([&](auto Q) {
-                constexpr int q = Q, lev = q % L, cur = BMI_T64_DB ? (q & 1) : 0;
-                if constexpr (BMI_T64_DB) {
-                    if constexpr (q < 2 * L - 1) static_for<0, 8>([&](auto VP) { kb[cur ^ 1][VP] = row_ptr(q + 1)[VP * 64 + lane]; });
-                } else {
-                    static_for<0, 8>([&](auto VP) { kb[0][VP] = row_ptr(q)[VP * 64 + lane]; });
-                }
+                constexpr int q = Q, lev = q % L;
+                static_for<0, 8>([&](auto VP) { kb[VP] = row_ptr(q)[VP * 64 + lane]; });
                 sched_fence();
                 static_for<0, 8>([&](auto VP) {
-                    const double m0 = f49::mul(X[lev][2 * VP], kb[cur][VP].x), m1 = f49::mul(X[lev][2 * VP + 1], kb[cur][VP].y);
+                    const double m0 = f49::mul(X[lev][2 * VP], kb[VP].x), m1 = f49::mul(X[lev][2 * VP + 1], kb[VP].y);
                     if constexpr (lev == 0) {
                         acc[2 * VP] = m0;
                         acc[2 * VP + 1] = m1;

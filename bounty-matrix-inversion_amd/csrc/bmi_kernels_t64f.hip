@@ -29,9 +29,6 @@ namespace {
 #ifndef BMI_T64F_RESYNC
 #define BMI_T64F_RESYNC 1   // workgroup barrier every so many CMUXes: keeps the four pairs on the same key rows, which they share through L1 (0: 83.2 ms, 4: 70.1, 1: 68.9 per 8,192)
 #endif
-#ifndef BMI_T64F_PRIO
-#define BMI_T64F_PRIO 1     // issue priority steps down through the forward transforms (3, 2, 1), 0 in the limb loop
-#endif
 
 #ifdef BMI_PHASE_PROF   // make -C csrc prof; tools/phase_prof_t64f.py
 __device__ unsigned long long g_phase_f[128];
@@ -51,14 +48,8 @@ using t64::Scheme;
 #ifndef BMI_T64F_CTS
 #define BMI_T64F_CTS 4      // ciphertexts (wavefront pairs) per workgroup: 4 fill the CU's LDS; 3 and 2 measured slower per ciphertext
 #endif
-#ifndef BMI_T64F_LDSKEY
-#define BMI_T64F_LDSKEY 0   // TIMING-ONLY A/B (wrong results on purpose; EXPERIMENTS A15): key rows staged once per workgroup in an LDS ring
-                            // by LDS-DMA (each wavefront of a column group requests a third of a row) and read back from LDS, with NO
-                            // hand-off between the wavefronts - the lower bound of what any correct staging scheme costs.  Needs BMI_T64F_CTS=3.
-#endif
 constexpr int TF_CTS = BMI_T64F_CTS;
-constexpr int TF_RING_WORDS = BMI_T64F_LDSKEY ? 2 * 2 * N + 128 : 0;   // [column group 2][slot 2][512 complex] + 1 KiB of slack
-constexpr int TF_LDS_WORDS = TW_WORDS + 2 * TF_CTS * (SCRATCH_WORDS + N) + TF_CTS * BMI_AT_WORDS + 4 * TF_CTS + TF_RING_WORDS;
+constexpr int TF_LDS_WORDS = TW_WORDS + 2 * TF_CTS * (SCRATCH_WORDS + N) + TF_CTS * BMI_AT_WORDS + 4 * TF_CTS;
 static_assert(TF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "TF_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(SCRATCH_WORDS >= N, "a tile carries 512 complex partial sums to the partner");
 
@@ -99,9 +90,6 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     double *accs = tiles + 2 * CTS * SCRATCH_WORDS;          // accumulators: exact integers word / 2^PRE, centred mod 2^AB
     double *at_base = accs + 2 * CTS * N;
     uint32_t *flags = reinterpret_cast<uint32_t *>(at_base + CTS * BMI_AT_WORDS);  // [2 CTS] published, [2 CTS] consumed
-#if BMI_T64F_LDSKEY
-    double2 *ring = reinterpret_cast<double2 *>(at_base + CTS * BMI_AT_WORDS + 4 * CTS);
-#endif
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ctl = wave >> 1, c = wave & 1;
     if (threadIdx.x < 4 * CTS) flags[threadIdx.x] = 0;
@@ -145,9 +133,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         const uint32_t a_t = at[i];
         // this wavefront's L GGSW rows: [row = L c + lev][column][limb][N]
         const double *bsk_c = bsk + ((size_t)i * 4 * L + c * 2 * L) * LIMBS * N;
-#if BMI_T64F_PRIO
-        __builtin_amdgcn_s_setprio(3);
-#endif
+        __builtin_amdgcn_s_setprio(3);   // issue priority steps down through the forward transforms (3, 2, 1), 0 in the limb loop
         wave_sync();
         double r[16];
         {
@@ -174,30 +160,11 @@ __global__ void __launch_bounds__(128 * TF_CTS)
             return reinterpret_cast<const double2 *>(bsk_c + ((size_t)(lev * 2 + col) * LIMBS + j) * N);
         };
         double2 kb[2][8];
-#if BMI_T64F_LDSKEY
-        // a row: this wavefront's share of the LDS-DMA requests (slices ctl, ctl + 3, ctl + 6 of the eight 1-KiB slices), then the whole
-        // row read back from the ring slot (no hand-off: timing only)
-        auto fetch = [&](double2 (&dst)[8], int t) {
-            double2 *slot = ring + ((size_t)c * 2 + (t & 1)) * (N / 2);
-            // this wavefront's three consecutive 1-KiB slices, starting at slice 0 / 3 / 5 (slice 5 is requested twice: every request stays
-            // inside the row); the instruction offset moves the global and the LDS address alike
-            const int first = ctl * 3 - (ctl >> 1);
-            const double2 *g = row_ptr(t) + first * 64 + lane;
-            double2 *l = slot + first * 64;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l, 16, 1024, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l, 16, 2048, 0);
-            static_for<0, 8>([&](auto P) { dst[P] = slot[P * 64 + lane]; });
-        };
-#else
         auto fetch = [&](double2 (&dst)[8], int t) { static_for<0, 8>([&](auto P) { dst[P] = row_ptr(t)[P * 64 + lane]; }); };
-#endif
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = L - 1 - LEV;  // least significant digit first
             pin();
-#if BMI_T64F_PRIO
             __builtin_amdgcn_s_setprio(lev + 1);
-#endif
             static_for<0, 16>([&](auto J) {
                 if constexpr (lev == 0) {
                     X[0][J] = r[J];
@@ -213,9 +180,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
             }
             forward(X[lev], lane, lds, tile);
         });
-#if BMI_T64F_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         PH_MARK(2);   // digits + L forward transforms
         double acc[16];
         static_for<0, LIMBS * 2 * L>([&](auto T) {
@@ -313,9 +278,6 @@ __global__ void __launch_bounds__(128 * TF_CTS)
 //      coefficient into the accumulator (the two limbs of a coefficient meet there)
 // The accumulator is the exact integer word / 2^16 in a double, as in the wave-pair kernel, but only re-centred mod 2^48 every
 // LF_RECENTRE steps (the atomic adds cannot reduce): 2^47 + 8 (2^45 + 2^47) < 2^51 keeps every sum exact.
-#ifndef BMI_LATF_ATOMIC
-#define BMI_LATF_ATOMIC 1   // phase C of the latency form: 1 = eight tasks (limb, output, parity) meeting by LDS f64 atomics, 0 = four tasks (output, parity) on wavefronts 12-15 running both limbs' inverse halves with plain read-modify-writes (A/B r04: 3.80 / 4.01 ms for 1 / 256 against 3.60 / 3.95 - four wavefronts leave the SIMDs idle; kept as an option)
-#endif
 constexpr int LF_THREADS = 1024;
 constexpr int LF_MAX_L = 3;
 constexpr int LF_HALF = N / 2;
@@ -466,7 +428,8 @@ __global__ void __launch_bounds__(LF_THREADS)
             sd[LF_HALF / 2 + mq] = double2{d.r, d.i};
         }
         __syncthreads();
-#if BMI_LATF_ATOMIC
+        // phase C: eight tasks (limb, output, parity) meeting by LDS f64 atomics; four tasks running both limbs' inverse halves
+        // with plain read-modify-writes measured 3.80 / 4.01 ms for 1 / 256 against 3.60 / 3.95 (four wavefronts leave the SIMDs idle)
         if (wave < 4 * LIMBS) {
             const int j = wave >> 2, o = (wave >> 1) & 1, h = wave & 1;
             const double2 *sd = SD + (size_t)(j * 2 + o) * LF_HALF + h * (LF_HALF / 2);
@@ -492,37 +455,6 @@ __global__ void __launch_bounds__(LF_THREADS)
                 atomicAdd(ao + 64 * R + 256, place(im[R]));    // ... + 512
             });
         }
-#else
-        if (wave >= 12) {   // (wavefronts 12 .. 15 had no forward task) = (output polynomial, parity): the inverse halves of BOTH limbs
-            const int o = (wave >> 1) & 1, h = wave & 1;
-            double re[LIMBS][4], im[LIMBS][4];
-            static_for<0, LIMBS>([&](auto J) {
-                const double2 *sd = SD + (size_t)(J * 2 + o) * LF_HALF + h * (LF_HALF / 2);
-                ffth::C v[4];
-                static_for<0, 4>([&](auto R) {
-                    const double2 t = sd[R * 64 + lane];
-                    v[R] = ffth::C{t.x, t.y};
-                });
-                if (h) ffth::inverse_half<1>(v, re[J], im[J], lane, lds);
-                else ffth::inverse_half<0>(v, re[J], im[J], lane, lds);
-            });
-            double *ao = acc + o * N + h * LF_HALF + lane;
-            // a limb's exact integer (|.| < 2^45: nearest integer of the transform's output); limb 1 shifted into place: x 2^LB mod 2^AB,
-            // of which only the low AB - LB bits survive
-            auto place = [&](double v0, double v1) {
-                const double x0 = __builtin_rint(v0);
-                double x1 = __builtin_rint(v1);
-                if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fmax(__builtin_fabs(v0 - x0), __builtin_fabs(v1 - x1)));
-                constexpr double W = (double)(1ull << (AB - LB));
-                x1 = __builtin_fma(-W, __builtin_rint(x1 * (1.0 / W)), x1);
-                return __builtin_fma(x1, (double)(1ull << LB), x0);
-            };
-            static_for<0, 4>([&](auto R) {
-                ao[64 * R] += place(re[0][R], re[1][R]);              // coefficient 2 (lane + 64 R) + h
-                ao[64 * R + 256] += place(im[0][R], im[1][R]);        // ... + 512
-            });
-        }
-#endif
         __syncthreads();
         if (++since_centred == LF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;

@@ -115,9 +115,7 @@ __global__ void __launch_bounds__(LU_THREADS)
             const int pz = wave >> 1;
             const u64 *ac = acc + c * N + h * ntth::HALF;
             double x[8];
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(3);
-#endif
             static_for<0, 8>([&](auto J) {
                 double r = t64::rounded_top<L, BG>(ac[lane + 64 * J]);   // round half up to L BG bits
                 double d = r;                                           // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
@@ -134,9 +132,7 @@ __global__ void __launch_bounds__(LU_THREADS)
             else ntth::forward_half<false>(x, lane, lds, tile);
             wave_sync();
             static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
-#if BMI_LAT2_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         }
         PH_MARK(0);
         __syncthreads();

@@ -197,7 +197,8 @@ int bmi_sync(bmi_ctx *ctx, void *stream);
 /* Selects the blind-rotation kernel: 0 = auto (by batch size), 1 = throughput, a pair of wavefronts per
  * ciphertext exchanging every level, 2 = latency (one workgroup of 8 wavefronts per ciphertext), 3 = throughput,
  * a pair of wavefronts per ciphertext exchanging once per CMUX (49-bit field; what auto picks for large batches),
- * 4 = the one-wavefront-per-transform latency kernel (2 is the two-wavefronts-per-transform one on the 49-bit field),
+ * 4 = the one-wavefront-per-transform latency kernel (the 49-bit field at N = 1024 refuses 1 and 4: its wave-pair kernel 3 and
+ *     its two-wavefronts-per-transform latency kernel 2 replaced them),
  * 5 = 2^64 torus only, bootstrap key at 48 bits in base 2^10 (the torus default): the wave-pair kernel whose exact limb
  *     products are carried by a folded 512-point complex FFT in f64 and rounded to the nearest integer (same words as 1 / 3,
  *     which pin the exact transform mod 2^49 - 720895; what auto picks for large batches on that key),

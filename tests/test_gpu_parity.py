@@ -178,7 +178,7 @@ def test_blind_rotate_every_kernel_variant(eng, ora, variant):
             eng.set_kernel_variant(variant)
         return
     if eng.q_bits == 49 and variant in (1, 4):
-        # the predecessors of the 49-bit kernels are A/B builds (make -C csrc ab), not in the product library: refused, not run
+        # the predecessors of the 49-bit kernels are retired (variants 3 and 2 replaced them): refused, not run
         from bmi_amd import tfhe
         with pytest.raises(tfhe.BmiError):
             eng.set_kernel_variant(variant)
@@ -533,7 +533,7 @@ def test_other_parameter_shape_bit_exact(q_bits, kw):
         ids = np.full(5, lid, np.uint32)
         want = ctx.blind_rotate(want_small[:5], tv, np.zeros(5, np.uint32))
         for variant in (0, 1, 2, 3, 4):
-            if variant in (1, 4) and q_bits == 49:       # the predecessors of the 49-bit kernels are A/B builds (make ab), not product
+            if variant in (1, 4) and q_bits == 49:       # the predecessors of the 49-bit kernels are retired: refused
                 with pytest.raises(tfhe.BmiError):
                     e.set_kernel_variant(variant)
                 continue
