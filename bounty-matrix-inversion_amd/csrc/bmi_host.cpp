@@ -180,11 +180,58 @@ void parallel_for(size_t n, F f) {
     for (auto &x : th) x.join();
 }
 
+// One device allocation, owned: freed when the buffer is destroyed, reset or assigned over.  Move-only.
+template <class T>
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        reset();
+        std::swap(p_, o.p_);
+        std::swap(bytes_, o.bytes_);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t bytes) {   // replaces the buffer held (if any)
+        reset();
+        const hipError_t e = hipMalloc(&p_, bytes);
+        if (e == hipSuccess) bytes_ = bytes;
+        else p_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        bytes_ = 0;
+    }
+    T *get() const { return p_; }
+    size_t bytes() const { return bytes_; }
+    bool empty() const { return !p_; }
+
+  private:
+    T *p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+// The launchers that differ by modulus only: bmi_ctx_create picks one table per context.  The two NTT operations exist on the
+// prime fields only (null on the torus) and take the context: each field has its own twiddle table and key copy.
+struct FieldOps {
+    decltype(&bmi::launch_keyswitch) keyswitch;
+    decltype(&bmi::launch_keyswitch_mfma) keyswitch_mfma;
+    decltype(&bmi::launch_ksk_to_limbs) ksk_to_limbs;
+    decltype(&bmi::launch_lincomb) lincomb;
+    int (*bsk_to_ntt)(bmi_ctx *c, const u64 *std_polys);   // builds the NTT-domain key copy
+    int (*negacyclic_mul)(const bmi_ctx *c, const u64 *a, const u64 *b, u64 *out, uint32_t count);
+    uint32_t ks_limbs;   // limbs per keyswitch-key word of the matrix-core keyswitch
+};
+
 }  // namespace
 
 struct bmi_ctx {
     bmi_params P{};
     Fq f;
+    const FieldOps *ops = nullptr;
     int device = 0;
     uint32_t N = 0, big_n = 0, rows = 0, ks_stride = 0;
     hipStream_t stream = nullptr;  // the context's own stream (host-buffer entry points)
@@ -197,45 +244,72 @@ struct bmi_ctx {
     bool secure_rng = false;       // true: keys / encryptions drawn from the CSPRNG below; false: test-only seeded streams
     ChaKey rng_secret, rng_public; // independent ChaCha20 keys from getrandom(): secrets + noise / public masks
     std::vector<u64> sk_small, sk_big, bsk_std, ksk;
-    void *d_bsk = nullptr, *d_tw = nullptr, *d_luts = nullptr;  // u64 words (Goldilocks) or f64 words (49-bit field)
-    double *d_tw_half = nullptr, *d_bsk_lat = nullptr;          // 49-bit field: tables and key copy of the split-transform latency kernel
-    double *d_tw_fft = nullptr, *d_bsk_fft = nullptr;           // 2^64 torus, key at 48 bits: tables and key copy of the floating-point-transform wave-pair kernel (bmi_kernels_t64f.hip)
-    double *d_tw_fh = nullptr, *d_bsk_latf = nullptr;           // ... and of its latency form (half transforms, fft_half_f64.hpp; key in slot-pair order)
-    double *d_zeta_pow = nullptr;                               // 2^64 torus at N = 1024: zeta^x, x in [0, 1024) as (re, im) - the factors X^c of the unrolled floating-point-transform kernel
-    double *d_tw_fq = nullptr, *d_bsk_w = nullptr;              // 2^64 torus at N = 2048, key at 46 bits: tables and key copy of bmi_kernels_t64w.hip (quarter transforms, fft_quarter_f64.hpp);
-                                                                // at N = 4096, key at 44 bits: those of bmi_kernels_t64q.hip (eighth transforms, fft_eighth_f64.hpp)
-    double *d_bsk_w2 = nullptr;                                 // N = 2048: the key copy of the two-ciphertexts-per-workgroup kernel (bmi_kernels_t64w2.hip: [t 4][256 slots] per polynomial and limb)
-    double *d_tw_wide = nullptr;                                // N = 2048: T / T^-1 of the even/odd combination (d_bsk_lat then holds the wide key copy)
+    // Tables (bmi_ctx_create), with the kernels that read them; empty where the context's modulus and N have no such kernel.
+    DevBuf<u64> tw_gl;          // Goldilocks: wave-NTT twiddles (ntt_wave.hpp) - bsk_to_ntt, negacyclic_mul, blind_rotate_lat / _tp
+    DevBuf<double> tw_wave;     // 49-bit field and torus: the same mod 2^49 - 720895, centred doubles - 49-bit bsk_to_ntt, blind_rotate_tpx
+                                // and their N = 2048 / 4096 forms, negacyclic_mul; torus bsk_to_limbs, blind_rotate
+    DevBuf<double> tw_half;     // 49-bit field and torus: half transform (ntt_half_f64.hpp) - bsk_to_lat, blind_rotate_lat2 / _lat / _lat2u
+    DevBuf<double> root_pow;    // 49-bit N <= 2048 and torus: psi^x, x < 2048 (psi_2048; N = 2048: psi_4096) - blind_rotate_lat2u, 49-bit _wide_u
+    DevBuf<double> tw_wide49;   // 49-bit N = 2048: T / T^-1 of the even/odd combination - bsk_to_wide, blind_rotate_wide / _wide_u
+    DevBuf<double> tw_quad49;   // 49-bit N = 4096: T_1..T_3, then their inverses - bsk_to_quad, blind_rotate_quad
+    DevBuf<double> tw_fft;      // torus N = 1024: folded complex FFT (fft_wave_f64.hpp) - bsk_to_fft, blind_rotate_fft
+    DevBuf<double> tw_fft_half; // torus N = 1024: half FFT (fft_half_f64.hpp) - bsk_to_latf, blind_rotate_lat_fft / _lat2u_fft / _tp2u_fft
+    DevBuf<double> zeta_pow;    // torus N = 1024: exp(i pi x / 1024), x in [0, 1024) as (re, im) - blind_rotate_lat2u_fft / _tp2u_fft
+    DevBuf<double> tw_quarter;  // torus N = 2048: quarter transforms (fft_quarter_f64.hpp) - bsk_to_wide / _wide2, blind_rotate_wide / _wide2
+    DevBuf<double> tw_eighth;   // torus N = 4096: eighth transforms (fft_eighth_f64.hpp) - bsk_to_quad, blind_rotate_quad
+    DevBuf<u64> luts;           // BMI_LUT_CAP test polynomials of N words (49-bit field: centred doubles) - every blind rotation
+    // The bootstrap key on the device, one field per layout (with its conversion and the kernel that reads it).  A copy exists where
+    // its kernel is selectable on the context (upload_eval_keys; the torus exact-transform pair when first chosen:
+    // build_exact_torus_copies).  A field that is not empty holds a whole copy (build_copy).  Replaced with the key set.
+    struct BskCopies {
+        DevBuf<u64> ntt_gl;        // Goldilocks, NTT domain (bsk_to_ntt): blind_rotate_lat / _tp
+        DevBuf<double> ntt49;      // 49-bit N = 1024, NTT domain (bsk_to_ntt): blind_rotate_tpx
+        DevBuf<double> lat49;      // 49-bit N = 1024, split-transform slot order (bsk_to_lat): blind_rotate_lat2
+        DevBuf<double> wide49;     // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide
+        DevBuf<double> quad49;     // 49-bit N = 4096 (bsk_to_quad): blind_rotate_quad
+        DevBuf<double> exact;      // torus N = 1024, limb polynomials of the exact transform (bsk_to_limbs): blind_rotate
+        DevBuf<double> exact_lat;  // ... in the slot order of its latency form (bsk_to_lat): blind_rotate_lat
+        DevBuf<double> fft;        // torus N = 1024, floating-point transform (bsk_to_fft): blind_rotate_fft
+        DevBuf<double> fft_lat;    // ... in half-transform slot pairs (bsk_to_latf): blind_rotate_lat_fft
+        DevBuf<double> wide;       // torus N = 2048 (bsk_to_wide): blind_rotate_wide
+        DevBuf<double> wide2;      // torus N = 2048, two ciphertexts per workgroup (bsk_to_wide2): blind_rotate_wide2
+        DevBuf<double> quad;       // torus N = 4096 (bsk_to_quad): blind_rotate_quad
+        size_t bytes() const {
+            return ntt_gl.bytes() + ntt49.bytes() + lat49.bytes() + wide49.bytes() + quad49.bytes() + exact.bytes() + exact_lat.bytes() +
+                   fft.bytes() + fft_lat.bytes() + wide.bytes() + wide2.bytes() + quad.bytes();
+        }
+    } bsk;
     // bootstrap-key unrolling (49-bit field at N = 1024 / 2048, 2^64 torus; bmi_set_bsk_unroll): per pair of LWE coefficients the GGSW encryptions of
-    // s s', s (1 - s'), (1 - s) s'; host copy in the standard domain, device copy in the slot order of the latency kernel
+    // s s', s (1 - s'), (1 - s) s'; host copy in the standard domain, device copy in the layout of the context's unrolled kernel (upload_bsk3)
     uint32_t unroll = 1;
     std::vector<u64> bsk3_std;
-    double *d_bsk3_lat = nullptr, *d_root_pow = nullptr;        // d_root_pow: psi^x, x in [0, 2N), centred doubles
+    struct Bsk3Copies {
+        DevBuf<double> lat49;      // 49-bit N = 1024, paired slot order (bsk_to_lat): blind_rotate_lat2u
+        DevBuf<double> wide49;     // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide_u
+        DevBuf<double> exact_lat;  // torus, exact transform (bsk_to_lat): blind_rotate_lat2u
+        DevBuf<double> fft_lat;    // torus, key at 42 bits: floating-point transform (bsk_to_latf): blind_rotate_lat2u_fft / _tp2u_fft
+        size_t bytes() const { return lat49.bytes() + wide49.bytes() + exact_lat.bytes() + fft_lat.bytes(); }
+    } bsk3;
     bool have_bsk3 = false;
     uint32_t pairs() const { return (P.n + 1) / 2; }
     size_t bsk3_words() const { return (size_t)pairs() * 3 * rows * (P.k + 1) * N; }
     bool wide() const { return N == 2048; }
-    bool quad() const { return N == 4096; }   // d_tw_wide then holds T_1..T_3 and their inverses, d_bsk_lat the quad key copy
-    u64 *d_ksk = nullptr, *d_ks_bias = nullptr;
+    bool quad() const { return N == 4096; }
+    DevBuf<u64> ksk_padded, ks_bias;   // keyswitch key, rows padded to ks_stride words, and its bias vector - keyswitch
+    DevBuf<signed char> ks_limbs;      // the keyswitch key as ops->ks_limbs limbs in MFMA operand order - keyswitch_mfma
     uint32_t n_luts = 0, lut_cap = 0;
     std::vector<std::vector<u64>> luts_host;
-    // growable device scratch
-    u64 *d_small = nullptr;
-    size_t small_cap = 0;
-    u64 *d_io_a = nullptr, *d_io_b = nullptr;
-    uint32_t *d_io_ids = nullptr;
-    size_t io_cap = 0;
+    // growable device scratch (grow)
+    DevBuf<u64> small;                 // keyswitched ciphertexts of bmi_pbs_batch and of the host-buffer forms
+    DevBuf<u64> io_a, io_b;            // host-buffer forms: input and output ciphertexts, and look-up ids
+    DevBuf<uint32_t> io_ids;
+    DevBuf<unsigned __int128> ks_partial;   // partial sums of the sliced scalar keyswitch
+    DevBuf<signed char> ks_digits;     // matrix-core keyswitch: digit matrix ...
+    DevBuf<int> ks_sums;               // ... and int32 sums
     int variant = 0;
     uint32_t lat_threshold = 512;  // 2 rounds of 256 one-workgroup PBS (11.2 ms) tie with one round of the wave-pair kernel (11.3 ms)
-    void *d_ks_partial = nullptr;
-    size_t ks_partial_bytes = 0;
-    // keyswitch on the matrix cores: limb-wise key (per keygen), digit matrix and int32 sums (growable scratch)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
     bool ks_mfma_ok = false;
-    signed char *d_ks_limbs = nullptr, *d_ks_digits = nullptr;
-    int *d_ks_sums = nullptr;
-    size_t ks_digits_bytes = 0, ks_sums_bytes = 0;
-    uint32_t ks_limbs() const { return f64() ? bmi49::KS_LIMBS : (f.torus ? bmit::KS_LIMBS : bmi::KS_LIMBS); }
     mutable std::string err;
     bool f64() const { return f.bits == 49; }
     bool t64() const { return f.torus; }
@@ -255,31 +329,36 @@ int fail(const bmi_ctx *c, int code, const std::string &msg) {
             return fail(ctx, -2, std::string(#call) + ": " + hipGetErrorString(e__));                  \
     } while (0)
 
+// a new device buffer holding the `count` host words at src
+template <class T>
+hipError_t upload(DevBuf<T> &dst, const T *src, size_t count) {
+    const hipError_t e = dst.alloc(count * sizeof(T));
+    return e != hipSuccess ? e : hipMemcpy(dst.get(), src, count * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// Grows a device scratch buffer to at least max(need, floor_bytes) bytes; never shrinks.  Queued work may still read the old
+// buffer: a growth synchronises the device before freeing it.
+template <class T>
+int grow(bmi_ctx *c, DevBuf<T> &b, size_t need, size_t floor_bytes) {
+    if (need <= b.bytes()) return 0;
+    if (!b.empty()) HIP_OK(c, hipDeviceSynchronize());
+    HIP_OK(c, b.alloc(std::max(need, floor_bytes)));
+    return 0;
+}
+// keyswitched ciphertexts of a batch (room for 1,024 at least)
 int ensure_small(bmi_ctx *c, size_t count) {
-    if (count <= c->small_cap) return 0;
-    if (c->d_small) {   // queued work may still read the old buffer
-        HIP_OK(c, hipDeviceSynchronize());
-        HIP_OK(c, hipFree(c->d_small));
-        c->d_small = nullptr;
-        c->small_cap = 0;
-    }
-    size_t cap = std::max<size_t>(count, 1024);
-    HIP_OK(c, hipMalloc(&c->d_small, cap * (c->P.n + 1) * sizeof(u64)));
-    c->small_cap = cap;
-    return 0;
+    const size_t w = (size_t)(c->P.n + 1) * sizeof(u64);
+    return grow(c, c->small, count * w, 1024 * w);
 }
+// ... and the host-buffer forms' input / output ciphertexts and look-up ids (room for 256 at least)
 int ensure_io(bmi_ctx *c, size_t count) {
-    if (count <= c->io_cap) return 0;
-    if (c->d_io_a) HIP_OK(c, hipFree(c->d_io_a));
-    if (c->d_io_b) HIP_OK(c, hipFree(c->d_io_b));
-    if (c->d_io_ids) HIP_OK(c, hipFree(c->d_io_ids));
-    size_t cap = std::max<size_t>(count, 256);
-    HIP_OK(c, hipMalloc(&c->d_io_a, cap * (c->big_n + 1) * sizeof(u64)));
-    HIP_OK(c, hipMalloc(&c->d_io_b, cap * (c->big_n + 1) * sizeof(u64)));
-    HIP_OK(c, hipMalloc(&c->d_io_ids, cap * sizeof(uint32_t)));
-    c->io_cap = cap;
-    return 0;
+    const size_t w = (size_t)(c->big_n + 1) * sizeof(u64);
+    int rc = ensure_small(c, count);
+    if (!rc) rc = grow(c, c->io_a, count * w, 256 * w);
+    if (!rc) rc = grow(c, c->io_b, count * w, 256 * w);
+    return rc ? rc : grow(c, c->io_ids, count * sizeof(uint32_t), 256 * sizeof(uint32_t));
 }
+constexpr size_t KS_PARTIAL_BYTES = (size_t)96 << 20;  // covers every split configuration (<= 1024 workgroups x 8 ciphertexts)
 
 // out += X^t * a  (negacyclic), coefficient-wise in Z_q
 void add_shifted(const Fq &f, u64 *out, const u64 *a, uint32_t t, uint32_t N) {
@@ -400,6 +479,400 @@ bool params_supported(const bmi_params &P, std::string &why) {
     return true;
 }
 
+// fresh CSPRNG keys for this context (secret-class and public-class streams, never shared between them)
+int rekey_csprng(bmi_ctx *c) {
+    if (!c->rng_secret.fill_from_os() || !c->rng_public.fill_from_os())
+        return fail(c, -2, "getrandom() failed: no entropy source for key generation");
+    c->secure_rng = true;
+    c->enc_counter = 0;   // a new key: the (key, nonce) pairs of the new streams have never been used
+    return 0;
+}
+int gen_secret_keys(bmi_ctx *c, uint64_t seed) {
+    const uint32_t n = c->P.n, kN = c->P.k * c->N;
+    c->sk_small.assign(n, 0);
+    c->sk_big.assign(kN, 0);
+    Stream s1(seed, S_SK_SMALL, c->f), s2(seed, S_SK_BIG, c->f);
+    RowRng r1(&s1, c->rng_secret, S_SK_SMALL, 0, c->secure_rng), r2(&s2, c->rng_secret, S_SK_BIG, 0, c->secure_rng);
+    for (uint32_t i = 0; i < n; i++) c->sk_small[i] = r1.bit(i);
+    for (uint32_t i = 0; i < kN; i++) c->sk_big[i] = r2.bit(i);
+    return 0;
+}
+
+// GGSW encryptions (standard domain) of the bits msg[0..) under the GLWE key, rows numbered g * rows + comp * l + lev:
+// B = sum_j A_j * S_j + E by shifted adds (S binary); mask / noise streams as in oracle/tfhe_oracle.c ggsw_rows.
+void gen_ggsw_rows(bmi_ctx *c, uint64_t seed, u64 mask_stream, u64 noise_stream, const std::vector<u64> &msg, u64 *out) {
+    const bmi_params &P = c->P;
+    const uint32_t N = c->N, k = P.k, l = P.bs_levels, rows = c->rows;
+    const Stream sm_det(seed, mask_stream, c->f), se_det(seed, noise_stream, c->f);
+    const Stream *smp = &sm_det, *sep = &se_det;
+    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
+    const bool secure = c->secure_rng;
+    const Fq f = c->f;
+    const u64 *skb = c->sk_big.data();
+    const u64 *bits = msg.data();
+    const double sigma = P.glwe_noise;
+    const uint32_t bl = P.bs_base_log;
+    parallel_for(msg.size() * rows, [=](size_t ir) {
+        RowRng sm(smp, *kpub, mask_stream, ir, secure), se(sep, *ksec, noise_stream, ir, secure);
+        const uint32_t i = (uint32_t)(ir / rows), r = (uint32_t)(ir % rows), comp = r / l, lev = r % l;
+        u64 *row = out + ir * (k + 1) * N;
+        u64 *B = row + (size_t)k * N;
+        for (uint32_t x = 0; x < N; x++) B[x] = se.gauss((u64)ir * N + x, sigma);
+        for (uint32_t j = 0; j < k; j++) {
+            u64 *A = row + (size_t)j * N;
+            for (uint32_t x = 0; x < N; x++) A[x] = sm.uniform(((u64)ir * (k + 1) + j) * N + x);
+            for (uint32_t t = 0; t < N; t++)
+                if (skb[(size_t)j * N + t]) add_shifted(f, B, A, t, N);
+        }
+        if (bits[i]) row[(size_t)comp * N] = f.add(row[(size_t)comp * N], (u64)1 << (f.bits - bl * (lev + 1)));
+    });
+}
+
+// the unrolled bootstrap key of the secret keys held: per pair (s, s') = (s_2i, s_2i+1) the GGSW encryptions of s s', s (1 - s'),
+// (1 - s) s'; an odd n is completed by s_n = 0 (host copy only; upload_bsk3 sends it to the device)
+void gen_bsk3(bmi_ctx *c, uint64_t seed) {
+    const uint32_t n = c->P.n;
+    std::vector<u64> msg((size_t)c->pairs() * 3);
+    for (uint32_t i = 0; i < c->pairs(); i++) {
+        const u64 s1 = c->sk_small[2 * i], s2 = 2 * i + 1 < n ? c->sk_small[2 * i + 1] : 0;
+        msg[3 * i] = s1 & s2;
+        msg[3 * i + 1] = s1 & (s2 ^ 1);
+        msg[3 * i + 2] = (s1 ^ 1) & s2;
+    }
+    c->bsk3_std.assign(c->bsk3_words(), 0);
+    gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, msg, c->bsk3_std.data());
+}
+
+// Builds one key copy of `bytes` bytes into a fresh buffer (launch(buffer) converts into it on the context's stream) and moves
+// it into dst only once the launch and the stream synchronisation have succeeded: a field that is not empty holds a whole copy.
+template <class T, class Launch>
+int build_copy(bmi_ctx *c, DevBuf<T> &dst, size_t bytes, const char *what, Launch launch) {
+    DevBuf<T> fresh;
+    HIP_OK(c, fresh.alloc(bytes));
+    if (launch(fresh.get())) return fail(c, -2, std::string(what) + " launch failed");
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    dst = std::move(fresh);
+    return 0;
+}
+
+// 2^64 torus at N = 1024: the key copies of the exact-transform kernels (bsk.exact, bsk.exact_lat).  d_std = the standard-domain
+// key on the device, or null to upload it from the host copy.  Contexts whose key has floating-point-transform copies build these
+// on demand only (kernel variants 1 / 3 / 4).
+int build_exact_torus_copies(bmi_ctx *c, const u64 *d_std) {
+    if (!c->bsk.exact.empty() && !c->bsk.exact_lat.empty()) return 0;
+    DevBuf<u64> own;
+    if (!d_std) {
+        HIP_OK(c, upload(own, c->bsk_std.data(), c->bsk_std.size()));
+        d_std = own.get();
+    }
+    const size_t bytes = c->bsk_std.size() * 8 * c->bsk_limbs();
+    const uint32_t polys = (uint32_t)(c->bsk_std.size() / c->N);
+    int rc = 0;
+    if (c->bsk.exact.empty())
+        rc = build_copy(c, c->bsk.exact, bytes, "bsk_to_limbs",
+                        [&](double *d) { return bmit::launch_bsk_to_limbs(d_std, d, c->tw_wave.get(), polys, c->bsk_prec, c->stream); });
+    if (!rc && c->bsk.exact_lat.empty())
+        rc = build_copy(c, c->bsk.exact_lat, bytes, "bsk_to_lat (torus)",
+                        [&](double *d) { return bmit::launch_bsk_to_lat(d_std, d, c->tw_half.get(), polys, c->bsk_prec, c->stream); });
+    return rc;
+}
+
+// The bootstrap key (host copy in c->bsk_std) -> device, in the layout of every kernel selectable on this context
+int upload_bsk(bmi_ctx *c) {
+    DevBuf<u64> d_std;
+    HIP_OK(c, upload(d_std, c->bsk_std.data(), c->bsk_std.size()));
+    const u64 *std_polys = d_std.get();
+    const uint32_t polys = (uint32_t)(c->bsk_std.size() / c->N);
+    const size_t bytes = d_std.bytes() * (c->t64() ? c->bsk_limbs() : 1);
+    const int prec = c->bsk_prec;
+    const hipStream_t st = c->stream;
+    auto &K = c->bsk;
+    if (c->t64() && c->wide()) {   // N = 2048: one ciphertext per workgroup, and two (batches beyond 256)
+        const int rc = build_copy(c, K.wide, bytes, "bsk_to_wide (torus)",
+                                  [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+        return rc ? rc : build_copy(c, K.wide2, bytes, "bsk_to_wide2 (torus)",
+                                    [&](double *d) { return bmit::launch_bsk_to_wide2(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    }
+    if (c->t64() && c->quad())
+        return build_copy(c, K.quad, bytes, "bsk_to_quad (torus)",
+                          [&](double *d) { return bmit::launch_bsk_to_quad(std_polys, d, c->tw_eighth.get(), polys, prec, st); });
+    if (c->t64() && !c->tw_fft.empty() && bmit::shape_supported_fft(prec, c->P.bs_levels, c->P.bs_base_log)) {
+        // the kernels auto dispatch runs on this key (48 bits, base 2^10): the wave-pair and the latency form of
+        // bmi_kernels_t64f.hip, exact limb products through the floating-point transform.  The two copies of the
+        // exact-transform kernels (variants 1 / 3 / 4: A/B only) are built when such a variant is first pinned.
+        const int rc = build_copy(c, K.fft, bytes, "bsk_to_fft (torus)",
+                                  [&](double *d) { return bmit::launch_bsk_to_fft(std_polys, d, c->tw_fft.get(), polys, prec, st); });
+        return rc ? rc : build_copy(c, K.fft_lat, bytes, "bsk_to_latf (torus)",
+                                    [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
+    }
+    if (c->t64())   // (a precision that only the unrolled kernel takes - 42 bits at base 2^10: no plain key copy)
+        return bmit::shape_supported(prec, c->P.bs_levels, c->P.bs_base_log) ? build_exact_torus_copies(c, std_polys) : 0;
+    if (c->wide())
+        return build_copy(c, K.wide49, bytes, "bsk_to_wide",
+                          [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
+    if (c->quad())
+        return build_copy(c, K.quad49, bytes, "bsk_to_quad",
+                          [&](double *d) { return bmi49::launch_bsk_to_quad(std_polys, d, c->tw_wave.get(), c->tw_quad49.get(), polys, st); });
+    const int rc = c->ops->bsk_to_ntt(c, std_polys);
+    if (rc || !c->f64()) return rc;
+    // second copy of the key, in the slot order of the split-transform latency kernel
+    return build_copy(c, K.lat49, bytes, "bsk_to_lat",
+                      [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, false, st); });
+}
+
+// Evaluation keys (host copies in c->bsk_std / c->ksk) -> device: bootstrap key (upload_bsk), keyswitch key in word form
+// (+ bias vector) and in limb form.
+int upload_eval_keys(bmi_ctx *c) {
+    const bmi_params &P = c->P;
+    const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels;
+    if (c->t64() && c->bsk_prec != 64) {
+        // key stored at 48 / 42 bits of precision: every word rounded (half up, as a signed integer) to a multiple of 2^16 / 2^22.
+        // The rounded key IS the key from here on (bmi_export_keys returns it), so every consumer agrees on it.
+        for (u64 &w : c->bsk_std) w = t64::round_key_word(w, c->bsk_prec);
+    }
+    c->have_keys = false;
+    c->bsk = {};    // the copies of the previous key set
+    c->bsk3 = {};
+    if (int rc = upload_bsk(c)) return rc;
+    const size_t ksk_rows = (size_t)k * N * lk;
+    HIP_OK(c, c->ksk_padded.alloc(ksk_rows * c->ks_stride * sizeof(u64)));
+    HIP_OK(c, hipMemset(c->ksk_padded.get(), 0, c->ksk_padded.bytes()));
+    HIP_OK(c, hipMemcpy2D(c->ksk_padded.get(), c->ks_stride * sizeof(u64), c->ksk.data(), (n + 1) * sizeof(u64),
+                          (n + 1) * sizeof(u64), ksk_rows, hipMemcpyHostToDevice));
+    // bias vector of the unsigned-digit keyswitch: (B/2) * sum_rows ksk[row][col]
+    {
+        std::vector<u64> bias(c->ks_stride, 0);
+        const u64 half = (u64)1 << (P.ks_base_log - 1);
+        for (size_t r = 0; r < ksk_rows; r++) {
+            const u64 *row = c->ksk.data() + r * (n + 1);
+            for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.add(bias[x], row[x]);
+        }
+        for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.mul(bias[x], half);
+        HIP_OK(c, upload(c->ks_bias, bias.data(), bias.size()));
+    }
+    // limb-wise copy of the keyswitch key for the matrix-core keyswitch (int8 operands, int32 sums: the digits must
+    // fit int8 and a column sum of rows * (B/2) * 128 must stay below 2^31)
+    c->ks_mfma_ok = ksk_rows % 32 == 0 && P.ks_levels <= 16 && P.ks_base_log <= 7 &&
+                    (ksk_rows << (P.ks_base_log - 1)) < ((size_t)1 << 24);
+    if (c->ks_mfma_ok) {
+        const uint32_t cbs = (n + 1 + 31) / 32;
+        const size_t bytes = (size_t)cbs * (ksk_rows / 32) * c->ops->ks_limbs * 1024;
+        if (int rc = build_copy(c, c->ks_limbs, bytes, "ksk_to_limbs", [&](signed char *d) {
+                return c->ops->ksk_to_limbs(c->ksk_padded.get(), d, (uint32_t)ksk_rows, n, c->ks_stride, c->stream);
+            }))
+            return rc;
+    }
+    c->have_keys = true;
+    return 0;
+}
+
+// unrolled bootstrap key (host copy in c->bsk3_std) -> device, in the layout of the context's unrolled kernel (bmi_ctx::Bsk3Copies)
+int upload_bsk3(bmi_ctx *c) {
+    HIP_OK(c, hipSetDevice(c->device));
+    const size_t words = c->bsk3_words();
+    if (c->bsk3_std.size() != words) return fail(c, -1, "no unrolled bootstrap key to upload");
+    // torus: the key stored at bsk_prec bits IS the key from here on (what bmi_export_bsk_unrolled returns)
+    if (c->t64() && c->bsk_prec != 64)
+        for (u64 &w : c->bsk3_std) w = t64::round_key_word(w, c->bsk_prec);
+    c->have_bsk3 = false;
+    c->bsk3 = {};
+    DevBuf<u64> d_std;
+    HIP_OK(c, upload(d_std, c->bsk3_std.data(), words));
+    const u64 *std_polys = d_std.get();
+    const uint32_t polys = (uint32_t)(words / c->N);
+    const size_t bytes = words * 8 * (c->t64() ? c->bsk_limbs() : 1);
+    const int prec = c->bsk_prec;
+    const hipStream_t st = c->stream;
+    const char *what = "bsk_to_lat (unrolled key)";
+    int rc;
+    if (c->t64() && bmit::shape_supported_unrolled_fft(prec, c->P.bs_levels, c->P.bs_base_log))   // slot-pair order of the half FFT
+        rc = build_copy(c, c->bsk3.fft_lat, bytes, what,
+                        [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
+    else if (c->t64())
+        rc = build_copy(c, c->bsk3.exact_lat, bytes, what,
+                        [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
+    else if (c->wide())
+        rc = build_copy(c, c->bsk3.wide49, bytes, what,
+                        [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
+    else
+        rc = build_copy(c, c->bsk3.lat49, bytes, what,
+                        [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, true, st); });
+    if (rc) return rc;
+    c->have_bsk3 = true;
+    return 0;
+}
+
+const FieldOps GOLDILOCKS_OPS = {bmi::launch_keyswitch, bmi::launch_keyswitch_mfma, bmi::launch_ksk_to_limbs, bmi::launch_lincomb,
+    [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt_gl, c->bsk_std.size() * 8, "bsk_to_ntt", [&](u64 *d) {
+        return bmi::launch_bsk_to_ntt(std_polys, d, c->tw_gl.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
+    [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi::launch_negacyclic_mul(a, b, o, c->tw_gl.get(), m, c->stream); },
+    bmi::KS_LIMBS};
+const FieldOps FIELD49_OPS = {bmi49::launch_keyswitch, bmi49::launch_keyswitch_mfma, bmi49::launch_ksk_to_limbs, bmi49::launch_lincomb,
+    [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt49, c->bsk_std.size() * 8, "bsk_to_ntt", [&](double *d) {
+        return bmi49::launch_bsk_to_ntt(std_polys, d, c->tw_wave.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
+    [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi49::launch_negacyclic_mul(a, b, o, c->tw_wave.get(), m, c->stream); },
+    bmi49::KS_LIMBS};
+const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfma, bmit::launch_ksk_to_limbs, bmit::launch_lincomb,
+                              nullptr, nullptr, bmit::KS_LIMBS};
+
+// evaluation keys for the secret keys held in c->sk_small / c->sk_big, deterministic in `seed`
+int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
+    HIP_OK(c, hipSetDevice(c->device));
+    const bmi_params &P = c->P;
+    const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels, rows = c->rows;
+    c->seed = seed;
+    if (!c->secure_rng) c->enc_counter = 0;   // deterministic test keys: encryption i of a key set is reproducible
+    // --- bootstrap key: GGSW(s_i) rows, standard domain
+    c->bsk_std.assign((size_t)n * rows * (k + 1) * N, 0);
+    // (A torus key at 42 bits of precision is ROUNDED from this full-precision key at upload.  Drawing the masks on the
+    // 2^22 grid instead would keep the rounding error away from the secret key - measured: output noise 2^-20 - but the
+    // body's noise, std 2^20, is then rounded to the grid too and vanishes in 95 % of the words: not an LWE sample any more.)
+    gen_ggsw_rows(c, seed, S_BSK_MASK, S_BSK_NOISE, c->sk_small, c->bsk_std.data());
+    c->have_bsk3 = false;
+    if (c->unroll == 2) gen_bsk3(c, seed);
+    // --- keyswitch key
+    c->ksk.assign((size_t)k * N * lk * (n + 1), 0);
+    {
+        const Stream sm_det(seed, S_KSK_MASK, c->f), se_det(seed, S_KSK_NOISE, c->f);
+        const Stream *smp = &sm_det, *sep = &se_det;
+        const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
+        const bool secure = c->secure_rng;
+        const Fq f = c->f;
+        const u64 *skb = c->sk_big.data();
+        const u64 *sks = c->sk_small.data();
+        u64 *ksk = c->ksk.data();
+        const double sigma = P.lwe_noise;
+        const uint32_t bl = P.ks_base_log;
+        parallel_for((size_t)k * N * lk, [=](size_t jr) {
+            RowRng sm(smp, *kpub, S_KSK_MASK, jr, secure), se(sep, *ksec, S_KSK_NOISE, jr, secure);
+            const uint32_t j = (uint32_t)(jr / lk), lev = (uint32_t)(jr % lk);
+            u64 *row = ksk + jr * (n + 1);
+            u64 b = se.gauss(jr, sigma);
+            for (uint32_t x = 0; x < n; x++) {
+                row[x] = sm.uniform((u64)jr * (n + 1) + x);
+                if (sks[x]) b = f.add(b, row[x]);
+            }
+            if (skb[j]) b = f.add(b, (u64)1 << (f.bits - bl * (lev + 1)));
+            row[n] = b;
+        });
+    }
+    c->have_secret = true;
+    if (int rc = upload_eval_keys(c)) return rc;
+    return c->unroll == 2 ? upload_bsk3(c) : 0;
+}
+
+// ------------------------------------------------------------------------------- the hot path
+// K-slices of the matrix-core keyswitch: enough wavefronts (tiles x column blocks x slices) to fill 1024 SIMDs twice
+uint32_t ks_mfma_slices(const bmi_ctx *c, uint32_t count) {
+    const uint32_t tiles = (count + 31) / 32, cbs = (c->P.n + 1 + 31) / 32;
+    const uint32_t ksteps = c->big_n * c->P.ks_levels / 32;
+    uint32_t slices = 1;
+    while (slices < 64 && slices * 2 <= ksteps && ksteps % (slices * 2) == 0 && (size_t)tiles * cbs * slices < 2048) slices *= 2;
+    return slices;
+}
+
+int ensure_ks_mfma(bmi_ctx *c, uint32_t count) {
+    const uint32_t cbs = (c->P.n + 1 + 31) / 32;
+    const size_t sums = (size_t)ks_mfma_slices(c, count) * count * c->ops->ks_limbs * cbs * 32 * sizeof(int);
+    const int rc = grow(c, c->ks_digits, (size_t)count * c->big_n * c->P.ks_levels, (size_t)8 << 20);
+    return rc ? rc : grow(c, c->ks_sums, sums, (size_t)32 << 20);
+}
+
+// The blind-rotation launchers (bmi_internal.hpp), one member each: choose_rotation picks one, launch_rotation runs it.
+enum class Rot {
+    t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
+    f49_wide_u, f49_wide, f49_quad, f49_lat2u, f49_lat2, f49_tpx,                                                   // 49-bit field
+    gl_lat, gl_tp,                                                                                                  // Goldilocks
+};
+
+// The kernel of bmi_blind_rotate_batch for a batch of `count` on this context: 0 and *rot, or a refusal.
+int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
+    // unrolled key (49-bit field at N = 1024 / 2048, 2^64 torus at N = 1024: bmi_set_bsk_unroll refuses the rest): one kernel
+    // (one workgroup per ciphertext) for every batch size, so that a ciphertext's bits never depend on the batch it travelled in
+    if (c->unroll == 2 && !c->have_bsk3)
+        return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
+    const int v = c->variant;
+    // variant 0 = auto: the latency kernel (one workgroup per ciphertext) while the batch cannot fill the chip
+    // with wave-pair work, the throughput kernel beyond that (49-bit field: the exchange-once form).
+    const bool latency = v == 2 || (v == 0 && count <= c->lat_threshold);
+    // torus, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins
+    // the one-ciphertext form); the same words either way
+    const bool two_per_wg = v == 1 || v == 3 || (v == 0 && count > 256);
+    const int prec = c->bsk_prec;
+    const uint32_t lv = c->P.bs_levels, bl = c->P.bs_base_log;
+    if (c->t64()) {
+        if (c->wide() && !c->bsk.wide2.empty() && two_per_wg) *rot = Rot::t64_wide2;
+        else if (c->wide()) *rot = Rot::t64_wide;   // N = 2048 / 4096: one workgroup per ciphertext
+        else if (c->quad()) *rot = Rot::t64_quad;
+        else if (c->unroll == 2)   // the floating-point-transform route where the key is at 42 bits, else the exact transform
+            *rot = !bmit::shape_supported_unrolled_fft(prec, lv, bl) ? Rot::t64_lat2u : two_per_wg ? Rot::t64_tp2u_fft : Rot::t64_lat2u_fft;
+        else {   // N = 1024: latency kernel (one workgroup per ciphertext) for small batches, wave pairs beyond
+            if (c->bsk.fft.empty() && !bmit::shape_supported(prec, lv, bl))
+                return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
+            if ((v == 5 || v == 6) && c->bsk.fft.empty())
+                return fail(c, -1, "kernel variant " + std::to_string(v) + " needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
+            // (floating-point-transform kernels: two rounds of 256 one-workgroup bootstraps, 7.7 ms, still beat the wave-pair kernel's
+            // 8.4 ms up to 1,024 ciphertexts; three rounds do not)
+            const bool lat_t = v == 2 || v == 4 || v == 6 || (v == 0 && count <= c->lat_threshold);
+            // through the floating-point transform where its key copy exists (48-bit key, base 2^10): variants 4 (latency) and
+            // 1 / 3 (wave pairs) pin the exact transform mod 2^49 - 720895, 5 and 6 the floating-point one
+            const bool fft = !c->bsk.fft.empty() && (lat_t ? v != 4 : v == 0 || v == 5);
+            *rot = lat_t ? (fft ? Rot::t64_lat_fft : Rot::t64_lat) : (fft ? Rot::t64_fft : Rot::t64_exact);
+        }
+    } else if (c->f64()) {
+        if (c->wide()) *rot = c->unroll == 2 ? Rot::f49_wide_u : Rot::f49_wide;   // N = 2048 / 4096: one kernel for every batch size
+        else if (c->quad()) *rot = Rot::f49_quad;
+        else *rot = c->unroll == 2 ? Rot::f49_lat2u : latency ? Rot::f49_lat2 : Rot::f49_tpx;
+    } else {
+        *rot = latency ? Rot::gl_lat : Rot::gl_tp;
+    }
+    return 0;
+}
+
+// Launches `rot` on the context's key copies and tables.  stat: as in bmit::launch_blind_rotate_fft, for the kernels that take it.
+int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *out, unsigned long long *stat,
+                    hipStream_t st) {
+    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
+    const int p = c->bsk_prec;
+    const u64 *luts = c->luts.get();
+    const double *luts49 = reinterpret_cast<const double *>(luts);   // the 49-bit field's test polynomials are centred doubles
+    const bmi_ctx::BskCopies &K = c->bsk;
+    const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
+    switch (rot) {
+    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, st);
+    case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_tp2u_fft: return bmit::launch_blind_rotate_tp2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(), out,
+                                                                      count, n, p, lv, bl, st);
+    case Rot::t64_lat2u_fft: return bmit::launch_blind_rotate_lat2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(),
+                                                                        out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_lat2u: return bmit::launch_blind_rotate_lat2u(cts, ids, luts, K3.exact_lat.get(), c->tw_half.get(), c->root_pow.get(), out, count,
+                                                                n, p, lv, bl, st);
+    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_lat: return bmit::launch_blind_rotate_lat(cts, ids, luts, K.exact_lat.get(), c->tw_half.get(), out, count, n, p, lv, bl, st);
+    case Rot::t64_fft: return bmit::launch_blind_rotate_fft(cts, ids, luts, K.fft.get(), c->tw_fft.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_exact: return bmit::launch_blind_rotate(cts, ids, luts, K.exact.get(), c->tw_wave.get(), out, count, n, p, lv, bl, st);
+    case Rot::f49_wide_u: return bmi49::launch_blind_rotate_wide_u(cts, ids, luts49, K3.wide49.get(), c->tw_wave.get(), c->tw_wide49.get(),
+                                                                   c->root_pow.get(), out, count, n, lv, bl, st);
+    case Rot::f49_wide: return bmi49::launch_blind_rotate_wide(cts, ids, luts49, K.wide49.get(), c->tw_wave.get(), c->tw_wide49.get(), out, count, n, lv, bl, st);
+    case Rot::f49_quad: return bmi49::launch_blind_rotate_quad(cts, ids, luts49, K.quad49.get(), c->tw_wave.get(), c->tw_quad49.get(), out, count, n, st);
+    case Rot::f49_lat2u: return bmi49::launch_blind_rotate_lat2u(cts, ids, luts49, K3.lat49.get(), c->tw_half.get(), c->root_pow.get(), out, count, n, lv, bl, st);
+    case Rot::f49_lat2: return bmi49::launch_blind_rotate_lat2(cts, ids, luts49, K.lat49.get(), c->tw_half.get(), out, count, n, lv, bl, st);
+    case Rot::f49_tpx: return bmi49::launch_blind_rotate_tpx(cts, ids, luts49, K.ntt49.get(), c->tw_wave.get(), out, count, n, lv, bl, st);
+    case Rot::gl_lat: return bmi::launch_blind_rotate_lat(cts, ids, luts, K.ntt_gl.get(), c->tw_gl.get(), out, count, n, st);
+    case Rot::gl_tp: return bmi::launch_blind_rotate_tp(cts, ids, luts, K.ntt_gl.get(), c->tw_gl.get(), out, count, n, st);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// a look-up id beyond the registered tables would make the kernels read past the table buffer: refused on the host
+// (the device-pointer entry points cannot look at their ids without a synchronisation; their contract is ids < count)
+int check_lut_ids(bmi_ctx *c, const uint32_t *lut_ids, uint32_t count) {
+    for (uint32_t i = 0; i < count; i++)
+        if (lut_ids[i] >= c->n_luts) return fail(c, -1, "look-up id " + std::to_string(lut_ids[i]) + " is not registered");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -471,34 +944,28 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
         c->f = Fq{0, 64, true};
         c->bsk_prec = default_bsk_precision(c->P);
     }
+    c->ops = c->f64() ? &FIELD49_OPS : c->t64() ? &TORUS64_OPS : &GOLDILOCKS_OPS;
     c->device = device;
     c->N = 1u << params->log_N;
     c->big_n = params->k * c->N;
     c->rows = (params->k + 1) * params->bs_levels;
     c->ks_stride = (params->n + 1 + 7) & ~7u;
-    auto bail = [&](const std::string &m) {
-        g_create_error = m;
-        delete c;
-        return -2;
+    auto bail = [&](const std::string &m) {   // releases whatever the context holds so far
+        bmi_ctx_destroy(c);
+        return fail(nullptr, -2, m);
     };
     if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
-    {
-        const bool f64 = c->f64() || c->t64();   // the torus kernels transform mod the 49-bit prime as well
-        const Fq f49q{f49::Q, 49};
-        const std::vector<u64> tw = f64 ? build_twiddles(f49q, nttf::PSI_U, nttf::PSI_INV_U, nttf::N_INV_U)
-                                        : build_twiddles(c->f, nttw::PSI, nttw::PSI_INV, nttw::N_INV);
-        const std::vector<double> twd = f64 ? to_centred_doubles(tw) : std::vector<double>();
-        const void *src = f64 ? (const void *)twd.data() : (const void *)tw.data();
-        if (hipMalloc(&c->d_tw, tw.size() * 8) != hipSuccess) return bail("hipMalloc(twiddles) failed");
-        if (hipMemcpy(c->d_tw, src, tw.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(twiddles) failed");
-    }
+    hipError_t up = hipSuccess;   // the first failure of the table uploads below
+    auto put = [&](auto &dst, const auto &host) {
+        if (up == hipSuccess) up = upload(dst, host.data(), host.size());
+    };
+    const Fq f49q{f49::Q, 49};   // the torus kernels transform mod the 49-bit prime as well
     if (c->f64() || c->t64()) {
-        const std::vector<double> th = to_centred_doubles(build_twiddles_half(Fq{f49::Q, 49}, nttf::PSI_U, nttf::PSI_INV_U));
-        if (hipMalloc(&c->d_tw_half, th.size() * 8) != hipSuccess) return bail("hipMalloc(half-transform twiddles) failed");
-        if (hipMemcpy(c->d_tw_half, th.data(), th.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(half-transform twiddles) failed");
+        put(c->tw_wave, to_centred_doubles(build_twiddles(f49q, nttf::PSI_U, nttf::PSI_INV_U, nttf::N_INV_U)));
+        put(c->tw_half, to_centred_doubles(build_twiddles_half(f49q, nttf::PSI_U, nttf::PSI_INV_U)));
+    } else {
+        put(c->tw_gl, build_twiddles(c->f, nttw::PSI, nttw::PSI_INV, nttw::N_INV));
     }
     if (c->t64() && c->N == 1024) {   // tables of the folded 512-point complex transform (fft_wave_f64.hpp): powers of zeta = exp(i pi / 1024)
         std::vector<double> tf(fftw::TW_WORDS);
@@ -511,49 +978,34 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
             for (uint32_t lane = 0; lane < 64; lane++) zeta_pow(lane * (4 * k2 + 1), &tf[fftw::TW_T1 + (k2 * 64 + lane) * 2]);
         for (uint32_t d = 0; d < 8; d++)
             for (uint32_t a = 0; a < 8; a++) zeta_pow(32 * a * d, &tf[fftw::TW_T2 + (d * 8 + a) * 2]);
-        if (hipMalloc(&c->d_tw_fft, tf.size() * 8) != hipSuccess) return bail("hipMalloc(fft twiddles) failed");
-        if (hipMemcpy(c->d_tw_fft, tf.data(), tf.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(fft twiddles) failed");
+        put(c->tw_fft, tf);
         std::vector<double> th(ffth::HT_WORDS);
         ffth::build_tables(th.data());
-        if (hipMalloc(&c->d_tw_fh, th.size() * 8) != hipSuccess) return bail("hipMalloc(half-fft twiddles) failed");
-        if (hipMemcpy(c->d_tw_fh, th.data(), th.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(half-fft twiddles) failed");
+        put(c->tw_fft_half, th);
         std::vector<double> zp(2048);
         for (uint32_t x = 0; x < 1024; x++) zeta_pow(x, &zp[2 * x]);
-        if (hipMalloc(&c->d_zeta_pow, zp.size() * 8) != hipSuccess) return bail("hipMalloc(zeta powers) failed");
-        if (hipMemcpy(c->d_zeta_pow, zp.data(), zp.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(zeta powers) failed");
+        put(c->zeta_pow, zp);
     }
     if ((c->f64() && !c->quad()) || c->t64()) {   // psi^x for the unrolled blind rotation (X^c at the root psi^e is psi^(e c))
         // N = 1024: psi = psi_2048, x in [0, 2048).  N = 2048: psi = psi_4096, x in [0, 2048) (the upper half is the negative)
         std::vector<u64> rp(2048);
-        const Fq fp{f49::Q, 49};   // the torus kernels transform mod the 49-bit prime as well
-        const u64 psi = c->wide() ? fp.pow(f49::GEN, (fp.q - 1) / 4096) : (u64)nttf::PSI_U;
+        const u64 psi = c->wide() ? f49q.pow(f49::GEN, (f49q.q - 1) / 4096) : (u64)nttf::PSI_U;
         rp[0] = 1;
-        for (uint32_t x = 1; x < 2048; x++) rp[x] = fp.mul(rp[x - 1], psi);
-        const std::vector<double> rpd = to_centred_doubles(rp);
-        if (hipMalloc(&c->d_root_pow, rpd.size() * 8) != hipSuccess) return bail("hipMalloc(root powers) failed");
-        if (hipMemcpy(c->d_root_pow, rpd.data(), rpd.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(root powers) failed");
+        for (uint32_t x = 1; x < 2048; x++) rp[x] = f49q.mul(rp[x - 1], psi);
+        put(c->root_pow, to_centred_doubles(rp));
     }
     if (c->t64() && (c->wide() || c->quad())) {   // tables of the quarter / eighth transforms: powers of zeta = exp(i pi / N)
         static_assert(ffte::ET_WORDS == fftq::QT_WORDS, "the two table sets share a size");
         std::vector<double> tq(fftq::QT_WORDS);
         if (c->quad()) ffte::build_tables(tq.data());
         else fftq::build_tables(tq.data());
-        if (hipMalloc(&c->d_tw_fq, tq.size() * 8) != hipSuccess) return bail("hipMalloc(quarter-fft twiddles) failed");
-        if (hipMemcpy(c->d_tw_fq, tq.data(), tq.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(quarter-fft twiddles) failed");
+        put(c->quad() ? c->tw_eighth : c->tw_quarter, tq);
     }
-    if ((c->wide() || c->quad()) && !c->t64()) {
-        const std::vector<double> tw = to_centred_doubles(c->quad() ? build_twiddles_quad(c->f) : build_twiddles_wide(c->f));
-        if (hipMalloc(&c->d_tw_wide, tw.size() * 8) != hipSuccess) return bail("hipMalloc(wide twiddles) failed");
-        if (hipMemcpy(c->d_tw_wide, tw.data(), tw.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail("hipMemcpy(wide twiddles) failed");
-    }
+    if (c->wide() && !c->t64()) put(c->tw_wide49, to_centred_doubles(build_twiddles_wide(c->f)));
+    if (c->quad() && !c->t64()) put(c->tw_quad49, to_centred_doubles(build_twiddles_quad(c->f)));
     c->lut_cap = BMI_LUT_CAP;
-    if (hipMalloc(&c->d_luts, (size_t)c->lut_cap * c->N * 8) != hipSuccess) return bail("hipMalloc(luts) failed");
+    if (up == hipSuccess) up = c->luts.alloc((size_t)c->lut_cap * c->N * 8);
+    if (up != hipSuccess) return bail(std::string("uploading the context's tables: ") + hipGetErrorString(up));
     *out = c;
     return 0;
 }
@@ -561,49 +1013,14 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
 void bmi_ctx_destroy(bmi_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void *p : {c->d_bsk, (void *)c->d_ksk, (void *)c->d_ks_bias, c->d_tw, c->d_luts, (void *)c->d_small,
-                    (void *)c->d_io_a, (void *)c->d_io_b, (void *)c->d_io_ids, c->d_ks_partial,
-                    (void *)c->d_ks_limbs, (void *)c->d_ks_digits, (void *)c->d_ks_sums, (void *)c->d_tw_half,
-                    (void *)c->d_bsk_lat, (void *)c->d_tw_wide, (void *)c->d_bsk3_lat, (void *)c->d_root_pow,
-                    (void *)c->d_tw_fft, (void *)c->d_bsk_fft, (void *)c->d_tw_fh, (void *)c->d_bsk_latf, (void *)c->d_tw_fq,
-                    (void *)c->d_bsk_w, (void *)c->d_bsk_w2, (void *)c->d_zeta_pow})
-        if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the device buffers free themselves
 }
 
 int bmi_get_params(const bmi_ctx *c, bmi_params *out) {
     if (!c || !out) return -1;
     *out = c->P;
     return 0;
-}
-
-namespace {
-int upload_eval_keys(bmi_ctx *c);
-int upload_bsk3(bmi_ctx *c);
-int build_exact_torus_copies(bmi_ctx *c, const u64 *d_std);
-}
-
-namespace {
-int gen_eval_keys(bmi_ctx *c, uint64_t seed);
-// fresh CSPRNG keys for this context (secret-class and public-class streams, never shared between them)
-int rekey_csprng(bmi_ctx *c) {
-    if (!c->rng_secret.fill_from_os() || !c->rng_public.fill_from_os())
-        return fail(c, -2, "getrandom() failed: no entropy source for key generation");
-    c->secure_rng = true;
-    c->enc_counter = 0;   // a new key: the (key, nonce) pairs of the new streams have never been used
-    return 0;
-}
-int gen_secret_keys(bmi_ctx *c, uint64_t seed) {
-    const uint32_t n = c->P.n, kN = c->P.k * c->N;
-    c->sk_small.assign(n, 0);
-    c->sk_big.assign(kN, 0);
-    Stream s1(seed, S_SK_SMALL, c->f), s2(seed, S_SK_BIG, c->f);
-    RowRng r1(&s1, c->rng_secret, S_SK_SMALL, 0, c->secure_rng), r2(&s2, c->rng_secret, S_SK_BIG, 0, c->secure_rng);
-    for (uint32_t i = 0; i < n; i++) c->sk_small[i] = r1.bit(i);
-    for (uint32_t i = 0; i < kN; i++) c->sk_big[i] = r2.bit(i);
-    return 0;
-}
 }
 
 int bmi_keygen(bmi_ctx *c) {
@@ -660,271 +1077,6 @@ int bmi_field_to_torus64(uint32_t q_bits, const uint64_t *in, uint64_t words, ui
     return 0;
 }
 
-namespace {
-// GGSW encryptions (standard domain) of the bits msg[0..) under the GLWE key, rows numbered g * rows + comp * l + lev:
-// B = sum_j A_j * S_j + E by shifted adds (S binary); mask / noise streams as in oracle/tfhe_oracle.c ggsw_rows.
-void gen_ggsw_rows(bmi_ctx *c, uint64_t seed, u64 mask_stream, u64 noise_stream, const std::vector<u64> &msg, u64 *out) {
-    const bmi_params &P = c->P;
-    const uint32_t N = c->N, k = P.k, l = P.bs_levels, rows = c->rows;
-    const Stream sm_det(seed, mask_stream, c->f), se_det(seed, noise_stream, c->f);
-    const Stream *smp = &sm_det, *sep = &se_det;
-    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-    const bool secure = c->secure_rng;
-    const Fq f = c->f;
-    const u64 *skb = c->sk_big.data();
-    const u64 *bits = msg.data();
-    const double sigma = P.glwe_noise;
-    const uint32_t bl = P.bs_base_log;
-    parallel_for(msg.size() * rows, [=](size_t ir) {
-        RowRng sm(smp, *kpub, mask_stream, ir, secure), se(sep, *ksec, noise_stream, ir, secure);
-        const uint32_t i = (uint32_t)(ir / rows), r = (uint32_t)(ir % rows), comp = r / l, lev = r % l;
-        u64 *row = out + ir * (k + 1) * N;
-        u64 *B = row + (size_t)k * N;
-        for (uint32_t x = 0; x < N; x++) B[x] = se.gauss((u64)ir * N + x, sigma);
-        for (uint32_t j = 0; j < k; j++) {
-            u64 *A = row + (size_t)j * N;
-            for (uint32_t x = 0; x < N; x++) A[x] = sm.uniform(((u64)ir * (k + 1) + j) * N + x);
-            for (uint32_t t = 0; t < N; t++)
-                if (skb[(size_t)j * N + t]) add_shifted(f, B, A, t, N);
-        }
-        if (bits[i]) row[(size_t)comp * N] = f.add(row[(size_t)comp * N], (u64)1 << (f.bits - bl * (lev + 1)));
-    });
-}
-
-// the unrolled bootstrap key of the secret keys held: per pair (s, s') = (s_2i, s_2i+1) the GGSW encryptions of s s', s (1 - s'),
-// (1 - s) s'; an odd n is completed by s_n = 0 (host copy only; upload_bsk3 sends it to the device)
-void gen_bsk3(bmi_ctx *c, uint64_t seed) {
-    const uint32_t n = c->P.n;
-    std::vector<u64> msg((size_t)c->pairs() * 3);
-    for (uint32_t i = 0; i < c->pairs(); i++) {
-        const u64 s1 = c->sk_small[2 * i], s2 = 2 * i + 1 < n ? c->sk_small[2 * i + 1] : 0;
-        msg[3 * i] = s1 & s2;
-        msg[3 * i + 1] = s1 & (s2 ^ 1);
-        msg[3 * i + 2] = (s1 ^ 1) & s2;
-    }
-    c->bsk3_std.assign(c->bsk3_words(), 0);
-    gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, msg, c->bsk3_std.data());
-}
-
-// evaluation keys for the secret keys held in c->sk_small / c->sk_big, deterministic in `seed`
-int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
-    HIP_OK(c, hipSetDevice(c->device));
-    const bmi_params &P = c->P;
-    const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels, rows = c->rows;
-    c->seed = seed;
-    if (!c->secure_rng) c->enc_counter = 0;   // deterministic test keys: encryption i of a key set is reproducible
-    // --- bootstrap key: GGSW(s_i) rows, standard domain
-    c->bsk_std.assign((size_t)n * rows * (k + 1) * N, 0);
-    // (A torus key at 42 bits of precision is ROUNDED from this full-precision key at upload.  Drawing the masks on the
-    // 2^22 grid instead would keep the rounding error away from the secret key - measured: output noise 2^-20 - but the
-    // body's noise, std 2^20, is then rounded to the grid too and vanishes in 95 % of the words: not an LWE sample any more.)
-    gen_ggsw_rows(c, seed, S_BSK_MASK, S_BSK_NOISE, c->sk_small, c->bsk_std.data());
-    c->have_bsk3 = false;
-    if (c->unroll == 2) gen_bsk3(c, seed);
-    // --- keyswitch key
-    c->ksk.assign((size_t)k * N * lk * (n + 1), 0);
-    {
-        const Stream sm_det(seed, S_KSK_MASK, c->f), se_det(seed, S_KSK_NOISE, c->f);
-        const Stream *smp = &sm_det, *sep = &se_det;
-        const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-        const bool secure = c->secure_rng;
-        const Fq f = c->f;
-        const u64 *skb = c->sk_big.data();
-        const u64 *sks = c->sk_small.data();
-        u64 *ksk = c->ksk.data();
-        const double sigma = P.lwe_noise;
-        const uint32_t bl = P.ks_base_log;
-        parallel_for((size_t)k * N * lk, [=](size_t jr) {
-            RowRng sm(smp, *kpub, S_KSK_MASK, jr, secure), se(sep, *ksec, S_KSK_NOISE, jr, secure);
-            const uint32_t j = (uint32_t)(jr / lk), lev = (uint32_t)(jr % lk);
-            u64 *row = ksk + jr * (n + 1);
-            u64 b = se.gauss(jr, sigma);
-            for (uint32_t x = 0; x < n; x++) {
-                row[x] = sm.uniform((u64)jr * (n + 1) + x);
-                if (sks[x]) b = f.add(b, row[x]);
-            }
-            if (skb[j]) b = f.add(b, (u64)1 << (f.bits - bl * (lev + 1)));
-            row[n] = b;
-        });
-    }
-    c->have_secret = true;
-    if (int rc = upload_eval_keys(c)) return rc;
-    return c->unroll == 2 ? upload_bsk3(c) : 0;
-}
-
-// unrolled bootstrap key (host copy in c->bsk3_std) -> device, in the slot order of the latency kernel
-int upload_bsk3(bmi_ctx *c) {
-    HIP_OK(c, hipSetDevice(c->device));
-    const size_t words = c->bsk3_words();
-    if (c->bsk3_std.size() != words) return fail(c, -1, "no unrolled bootstrap key to upload");
-    // torus: the key stored at bsk_prec bits IS the key from here on (what bmi_export_bsk_unrolled returns)
-    if (c->t64() && c->bsk_prec != 64)
-        for (u64 &w : c->bsk3_std) w = t64::round_key_word(w, c->bsk_prec);
-    u64 *d_tmp = nullptr;
-    HIP_OK(c, hipMalloc(&d_tmp, words * 8));
-    const size_t lat_bytes = words * 8 * (c->t64() ? c->bsk_limbs() : 1);
-    if (!c->d_bsk3_lat && hipMalloc(&c->d_bsk3_lat, lat_bytes) != hipSuccess) {
-        (void)hipFree(d_tmp);
-        return fail(c, -2, "hipMalloc(unrolled key) failed");
-    }
-    HIP_OK(c, hipMemcpy(d_tmp, c->bsk3_std.data(), words * 8, hipMemcpyHostToDevice));
-    const bool ufft = c->t64() && bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
-    const int rc = ufft ? bmit::launch_bsk_to_latf(d_tmp, c->d_bsk3_lat, c->d_tw_fh, (uint32_t)(words / c->N), c->bsk_prec, c->stream)   // slot-pair order of the half FFT
-                   : c->t64() ? bmit::launch_bsk_to_lat(d_tmp, c->d_bsk3_lat, c->d_tw_half, (uint32_t)(words / c->N), c->bsk_prec, c->stream)
-                   : c->wide() ? bmi49::launch_bsk_to_wide(d_tmp, c->d_bsk3_lat, (const double *)c->d_tw, c->d_tw_wide, (uint32_t)(words / c->N), c->stream)
-                               : bmi49::launch_bsk_to_lat(d_tmp, c->d_bsk3_lat, c->d_tw_half, (uint32_t)(words / c->N), true, c->stream);
-    if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_lat (unrolled key) launch failed"); }
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipFree(d_tmp));
-    c->have_bsk3 = true;
-    return 0;
-}
-
-// 2^64 torus at N = 1024: the key copies of the exact-transform kernels (wave pairs: d_bsk; latency form: d_bsk_lat).  d_std = the
-// standard-domain key on the device, or null to upload it from the host copy.  Contexts whose key has floating-point-transform
-// copies build these on demand only (kernel variants 1 / 3 / 4).
-int build_exact_torus_copies(bmi_ctx *c, const u64 *d_std) {
-    if (c->d_bsk && c->d_bsk_lat) return 0;
-    const size_t bsk_words = c->bsk_std.size();
-    u64 *d_own = nullptr;
-    if (!d_std) {
-        HIP_OK(c, hipMalloc(&d_own, bsk_words * 8));
-        HIP_OK(c, hipMemcpy(d_own, c->bsk_std.data(), bsk_words * 8, hipMemcpyHostToDevice));
-        d_std = d_own;
-    }
-    auto bail = [&](const char *m) {
-        if (d_own) (void)hipFree(d_own);
-        return fail(c, -2, m);
-    };
-    if (!c->d_bsk) {
-        if (hipMalloc(&c->d_bsk, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) return bail("hipMalloc(torus limb key) failed");
-        if (bmit::launch_bsk_to_limbs(d_std, (double *)c->d_bsk, (const double *)c->d_tw, (uint32_t)(bsk_words / c->N), c->bsk_prec, c->stream))
-            return bail("bsk_to_limbs launch failed");
-    }
-    if (!c->d_bsk_lat) {
-        if (hipMalloc(&c->d_bsk_lat, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) return bail("hipMalloc(torus latency-kernel key) failed");
-        if (bmit::launch_bsk_to_lat(d_std, c->d_bsk_lat, c->d_tw_half, (uint32_t)(bsk_words / c->N), c->bsk_prec, c->stream))
-            return bail("bsk_to_lat (torus) launch failed");
-    }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (d_own) (void)hipFree(d_own);
-    return e == hipSuccess ? 0 : fail(c, -2, "hipStreamSynchronize failed");
-}
-
-// Evaluation keys (host copies in c->bsk_std / c->ksk) -> device: bootstrap key to the NTT domain (both layouts for
-// the 49-bit field), keyswitch key in word form (+ bias vector) and in limb form.
-int upload_eval_keys(bmi_ctx *c) {
-    const bmi_params &P = c->P;
-    const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels;
-    // --- upload: bootstrap key -> NTT domain on the GPU; keyswitch key with padded rows
-    if (c->t64() && c->bsk_prec != 64) {
-        // key stored at 48 / 42 bits of precision: every word rounded (half up, as a signed integer) to a multiple of 2^16 / 2^22.
-        // The rounded key IS the key from here on (bmi_export_keys returns it), so every consumer agrees on it.
-        for (u64 &w : c->bsk_std) w = t64::round_key_word(w, c->bsk_prec);
-    }
-    const size_t bsk_words = c->bsk_std.size();
-    if (!c->d_bsk && !c->wide() && !c->quad() && !c->t64()) HIP_OK(c, hipMalloc(&c->d_bsk, bsk_words * 8));
-    u64 *d_tmp = nullptr;
-    HIP_OK(c, hipMalloc(&d_tmp, bsk_words * sizeof(u64)));
-    HIP_OK(c, hipMemcpy(d_tmp, c->bsk_std.data(), bsk_words * sizeof(u64), hipMemcpyHostToDevice));
-    int rc = 0;
-    if (c->t64() && (c->wide() || c->quad())) {  // 2^64 torus at N = 2048 / 4096: ONE key copy, two limb polynomials per key polynomial in the order of bmi_kernels_t64w.hip / t64q.hip
-        if (c->d_bsk_w) { (void)hipFree(c->d_bsk_w); c->d_bsk_w = nullptr; }
-        if (hipMalloc(&c->d_bsk_w, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) {
-            (void)hipFree(d_tmp);
-            return fail(c, -2, "hipMalloc(torus N = 2048 / 4096 key) failed");
-        }
-        rc = (c->quad() ? bmit::launch_bsk_to_quad : bmit::launch_bsk_to_wide)(d_tmp, c->d_bsk_w, c->d_tw_fq, (uint32_t)(bsk_words / N), c->bsk_prec, c->stream);
-        if (!rc && c->wide()) {   // ... and at N = 2048 the copy of the throughput form (two ciphertexts per workgroup: batches beyond 256)
-            if (c->d_bsk_w2) { (void)hipFree(c->d_bsk_w2); c->d_bsk_w2 = nullptr; }
-            if (hipMalloc(&c->d_bsk_w2, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) {
-                (void)hipFree(d_tmp);
-                return fail(c, -2, "hipMalloc(torus N = 2048 throughput-form key) failed");
-            }
-            rc = bmit::launch_bsk_to_wide2(d_tmp, c->d_bsk_w2, c->d_tw_fq, (uint32_t)(bsk_words / N), c->bsk_prec, c->stream);
-        }
-        if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_wide (torus) launch failed"); }
-    } else if (c->t64()) {  // 2^64 torus at N = 1024: bsk_limbs transform-domain limb polynomials per key polynomial
-        for (void **p : {&c->d_bsk, (void **)&c->d_bsk_lat, (void **)&c->d_bsk_fft, (void **)&c->d_bsk_latf})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        const bool fft = c->d_tw_fft && bmit::shape_supported_fft(c->bsk_prec, P.bs_levels, P.bs_base_log);
-        if (fft) {
-            // the kernels auto dispatch runs on this key (48 bits, base 2^10): the wave-pair and the latency form of
-            // bmi_kernels_t64f.hip, exact limb products through the floating-point transform.  The two copies of the
-            // exact-transform kernels (variants 1 / 3 / 4: A/B only) are built when such a variant is first pinned.
-            if (hipMalloc(&c->d_bsk_fft, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) {
-                (void)hipFree(d_tmp);
-                return fail(c, -2, "hipMalloc(torus fft key) failed");
-            }
-            rc = bmit::launch_bsk_to_fft(d_tmp, c->d_bsk_fft, c->d_tw_fft, (uint32_t)(bsk_words / N), c->bsk_prec, c->stream);
-            if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_fft (torus) launch failed"); }
-            if (hipMalloc(&c->d_bsk_latf, bsk_words * 8 * c->bsk_limbs()) != hipSuccess) {
-                (void)hipFree(d_tmp);
-                return fail(c, -2, "hipMalloc(torus fft latency-kernel key) failed");
-            }
-            rc = bmit::launch_bsk_to_latf(d_tmp, c->d_bsk_latf, c->d_tw_fh, (uint32_t)(bsk_words / N), c->bsk_prec, c->stream);
-            if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_latf (torus) launch failed"); }
-        } else if (bmit::shape_supported(c->bsk_prec, P.bs_levels, P.bs_base_log)) {
-            HIP_OK(c, hipStreamSynchronize(c->stream));
-            if (int rc2 = build_exact_torus_copies(c, d_tmp)) { (void)hipFree(d_tmp); return rc2; }
-        }   // (else: a precision that only the unrolled kernel takes - 42 bits at base 2^10: no plain key copy)
-    } else if (c->wide() || c->quad()) {  // N = 2048 / 4096: one key copy, in the slot order of k_blind_rotate_wide49 / quad49
-        if (!c->d_bsk_lat && hipMalloc(&c->d_bsk_lat, bsk_words * 8) != hipSuccess) {
-            (void)hipFree(d_tmp);
-            return fail(c, -2, "hipMalloc(wide key) failed");
-        }
-        rc = (c->quad() ? bmi49::launch_bsk_to_quad : bmi49::launch_bsk_to_wide)(d_tmp, c->d_bsk_lat, (const double *)c->d_tw, c->d_tw_wide, (uint32_t)(bsk_words / N), c->stream);
-        if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_wide launch failed"); }
-    } else {
-        rc = c->f64() ? bmi49::launch_bsk_to_ntt(d_tmp, (double *)c->d_bsk, (const double *)c->d_tw, (uint32_t)(bsk_words / N), c->stream)
-                      : bmi::launch_bsk_to_ntt(d_tmp, (u64 *)c->d_bsk, (const u64 *)c->d_tw, (uint32_t)(bsk_words / N), c->stream);
-        if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_ntt launch failed"); }
-        if (c->f64()) {  // second copy of the key, in the slot order of the split-transform latency kernel
-            if (!c->d_bsk_lat && hipMalloc(&c->d_bsk_lat, bsk_words * 8) != hipSuccess) {
-                (void)hipFree(d_tmp);
-                return fail(c, -2, "hipMalloc(latency-kernel key) failed");
-            }
-            rc = bmi49::launch_bsk_to_lat(d_tmp, c->d_bsk_lat, c->d_tw_half, (uint32_t)(bsk_words / N), false, c->stream);
-            if (rc) { (void)hipFree(d_tmp); return fail(c, -2, "bsk_to_lat launch failed"); }
-        }
-    }
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipFree(d_tmp));
-    const size_t ksk_rows = (size_t)k * N * lk;
-    if (!c->d_ksk) HIP_OK(c, hipMalloc(&c->d_ksk, ksk_rows * c->ks_stride * sizeof(u64)));
-    HIP_OK(c, hipMemset(c->d_ksk, 0, ksk_rows * c->ks_stride * sizeof(u64)));
-    HIP_OK(c, hipMemcpy2D(c->d_ksk, c->ks_stride * sizeof(u64), c->ksk.data(), (n + 1) * sizeof(u64),
-                          (n + 1) * sizeof(u64), ksk_rows, hipMemcpyHostToDevice));
-    // bias vector of the unsigned-digit keyswitch: (B/2) * sum_rows ksk[row][col]
-    {
-        std::vector<u64> bias(c->ks_stride, 0);
-        const u64 half = (u64)1 << (P.ks_base_log - 1);
-        for (size_t r = 0; r < ksk_rows; r++) {
-            const u64 *row = c->ksk.data() + r * (n + 1);
-            for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.add(bias[x], row[x]);
-        }
-        for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.mul(bias[x], half);
-        if (!c->d_ks_bias) HIP_OK(c, hipMalloc(&c->d_ks_bias, c->ks_stride * sizeof(u64)));
-        HIP_OK(c, hipMemcpy(c->d_ks_bias, bias.data(), c->ks_stride * sizeof(u64), hipMemcpyHostToDevice));
-    }
-    // limb-wise copy of the keyswitch key for the matrix-core keyswitch (int8 operands, int32 sums: the digits must
-    // fit int8 and a column sum of rows * (B/2) * 128 must stay below 2^31)
-    c->ks_mfma_ok = ksk_rows % 32 == 0 && P.ks_levels <= 16 && P.ks_base_log <= 7 &&
-                    (ksk_rows << (P.ks_base_log - 1)) < ((size_t)1 << 24);
-    if (c->ks_mfma_ok) {
-        const uint32_t cbs = (n + 1 + 31) / 32;
-        const size_t bytes = (size_t)cbs * (ksk_rows / 32) * c->ks_limbs() * 1024;
-        if (!c->d_ks_limbs) HIP_OK(c, hipMalloc(&c->d_ks_limbs, bytes));
-        rc = (c->f64() ? bmi49::launch_ksk_to_limbs : (c->t64() ? bmit::launch_ksk_to_limbs : bmi::launch_ksk_to_limbs))(c->d_ksk, c->d_ks_limbs, (uint32_t)ksk_rows, n,
-                                                                                c->ks_stride, c->stream);
-        if (rc) return fail(c, -2, "ksk_to_limbs launch failed");
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-    }
-    c->have_keys = true;
-    return 0;
-}
-}  // namespace
-
 int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big, const uint64_t *bsk, const uint64_t *ksk) {
     if (!c || !bsk || !ksk) return -1;
     if ((sk_small == nullptr) != (sk_big == nullptr)) return fail(c, -1, "pass both secret keys or neither");
@@ -968,14 +1120,8 @@ int bmi_export_keys(const bmi_ctx *c, uint64_t *sk_small, uint64_t *sk_big, uint
 
 int bmi_key_bytes(const bmi_ctx *c, uint64_t *bsk_bytes, uint64_t *ksk_bytes) {
     if (!c) return -1;
-    if (bsk_bytes) {   // every resident device copy (one per kernel family that is selectable on this context), plus the unrolled key
-        const u64 one = (u64)c->P.n * c->rows * (c->P.k + 1) * c->N * 8 * (c->t64() ? c->bsk_limbs() : 1);
-        u64 copies = 0;
-        for (const void *p : {(const void *)c->d_bsk, (const void *)c->d_bsk_lat, (const void *)c->d_bsk_fft, (const void *)c->d_bsk_latf,
-                              (const void *)c->d_bsk_w, (const void *)c->d_bsk_w2})
-            copies += p != nullptr;
-        *bsk_bytes = one * copies + (c->have_bsk3 ? (u64)c->bsk3_words() * 8 * (c->t64() ? c->bsk_limbs() : 1) : 0);
-    }
+    // every resident device copy (one per kernel family that is selectable on this context), plus the unrolled key
+    if (bsk_bytes) *bsk_bytes = c->bsk.bytes() + (c->have_bsk3 ? c->bsk3.bytes() : 0);
     if (ksk_bytes) *ksk_bytes = (u64)c->big_n * c->P.ks_levels * (c->P.n + 1) * 8;
     return 0;
 }
@@ -1065,7 +1211,7 @@ int bmi_lut_register(bmi_ctx *c, const int64_t *table, uint32_t msg_bits, uint32
     {
         const std::vector<double> tvd = c->f64() ? to_centred_doubles(tv) : std::vector<double>();
         const void *src = c->f64() ? (const void *)tvd.data() : (const void *)tv.data();
-        HIP_OK(c, hipMemcpy((char *)c->d_luts + (size_t)c->n_luts * N * 8, src, N * 8, hipMemcpyHostToDevice));
+        HIP_OK(c, hipMemcpy(c->luts.get() + (size_t)c->n_luts * N, src, N * 8, hipMemcpyHostToDevice));
     }
     c->luts_host.push_back(std::move(tv));
     *lut_id = c->n_luts++;
@@ -1179,57 +1325,17 @@ int bmi_set_kernel_variant(bmi_ctx *c, int variant) {
 }
 
 // ------------------------------------------------------------------------------- the hot path
-namespace {
-// grows a device scratch buffer (never shrinks); the old one may still be in use by queued work -> synchronise first
-int ensure_bytes(bmi_ctx *c, void **p, size_t *cap, size_t need, size_t floor_bytes) {
-    if (need <= *cap) return 0;
-    if (*p) {
-        HIP_OK(c, hipDeviceSynchronize());
-        HIP_OK(c, hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t bytes = std::max(need, floor_bytes);
-    HIP_OK(c, hipMalloc(p, bytes));
-    *cap = bytes;
-    return 0;
-}
-
-// K-slices of the matrix-core keyswitch: enough wavefronts (tiles x column blocks x slices) to fill 1024 SIMDs twice
-uint32_t ks_mfma_slices(const bmi_ctx *c, uint32_t count) {
-    const uint32_t tiles = (count + 31) / 32, cbs = (c->P.n + 1 + 31) / 32;
-    const uint32_t ksteps = c->big_n * c->P.ks_levels / 32;
-    uint32_t slices = 1;
-    while (slices < 64 && slices * 2 <= ksteps && ksteps % (slices * 2) == 0 && (size_t)tiles * cbs * slices < 2048) slices *= 2;
-    return slices;
-}
-
-int ensure_ks_mfma(bmi_ctx *c, uint32_t count) {
-    const uint32_t cbs = (c->P.n + 1 + 31) / 32;
-    const size_t dig = (size_t)count * c->big_n * c->P.ks_levels;
-    const size_t sums = (size_t)ks_mfma_slices(c, count) * count * c->ks_limbs() * cbs * 32 * sizeof(int);
-    int rc = ensure_bytes(c, (void **)&c->d_ks_digits, &c->ks_digits_bytes, dig, (size_t)8 << 20);
-    if (rc) return rc;
-    return ensure_bytes(c, (void **)&c->d_ks_sums, &c->ks_sums_bytes, sums, (size_t)32 << 20);
-}
-
-int keyswitch_mfma(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64_t *d_small, hipStream_t stream) {
-    if (count == 0) return 0;
-    int rc = ensure_ks_mfma(c, count);
-    if (rc) return rc;
-    rc = (c->f64() ? bmi49::launch_keyswitch_mfma : (c->t64() ? bmit::launch_keyswitch_mfma : bmi::launch_keyswitch_mfma))(
-        d_in, c->d_ks_limbs, c->d_ks_digits, c->d_ks_sums, d_small, ks_mfma_slices(c, count), count, c->P.n, c->big_n,
-        c->P.ks_levels, c->P.ks_base_log, stream);
-    return rc ? fail(c, -2, std::string("keyswitch (matrix cores) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
-}
-}  // namespace
-
 int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64_t *d_small, void *stream) {
     if (!c || (count && (!d_in || !d_small))) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     if (count == 0) return 0;
     HIP_OK(c, hipSetDevice(c->device));
-    if (c->ks_variant == 0 && c->ks_mfma_ok && count >= BMI_KS_MFMA_MIN) return keyswitch_mfma(c, d_in, count, d_small, (hipStream_t)stream);
+    if (c->ks_variant == 0 && c->ks_mfma_ok && count >= BMI_KS_MFMA_MIN) {
+        if (int rc = ensure_ks_mfma(c, count)) return rc;
+        const int rc = c->ops->keyswitch_mfma(d_in, c->ks_limbs.get(), c->ks_digits.get(), c->ks_sums.get(), d_small, ks_mfma_slices(c, count),
+                                              count, c->P.n, c->big_n, c->P.ks_levels, c->P.ks_base_log, (hipStream_t)stream);
+        return rc ? fail(c, -2, std::string("keyswitch (matrix cores) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    }
     if (c->P.n + 1 > 3 * 256)   // ks_lincomb.hpp: KS_COLS x KS_THREADS output columns per workgroup
         return fail(c, -1, "the scalar keyswitch kernel takes n <= 767; this parameter set needs the matrix-core form");
     // Scalar form.  The row walk (k*N*levels rows) of one workgroup is the latency of a small batch, so it is split over
@@ -1239,20 +1345,10 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
     uint32_t slices = 1;
     if (c->variant == 0 || c->variant == 2)
         while (slices < 64 && tiles * slices * 2 <= 1024) slices *= 2;
-    const size_t need = (size_t)slices * count * c->ks_stride * 16;
-    if (slices > 1 && need > c->ks_partial_bytes) {
-        if (c->d_ks_partial) {
-            HIP_OK(c, hipDeviceSynchronize());
-            HIP_OK(c, hipFree(c->d_ks_partial));
-            c->d_ks_partial = nullptr;
-        }
-        const size_t cap = std::max(need, (size_t)96 << 20);
-        HIP_OK(c, hipMalloc(&c->d_ks_partial, cap));
-        c->ks_partial_bytes = cap;
-    }
-    int rc = (c->f64() ? bmi49::launch_keyswitch : (c->t64() ? bmit::launch_keyswitch : bmi::launch_keyswitch))(
-        d_in, c->d_ksk, c->d_ks_bias, d_small, slices > 1 ? c->d_ks_partial : nullptr, slices, count, c->P.n, c->big_n,
-        c->P.ks_levels, c->P.ks_base_log, c->ks_stride, (hipStream_t)stream);
+    if (slices > 1)
+        if (int rc = grow(c, c->ks_partial, (size_t)slices * count * c->ks_stride * 16, KS_PARTIAL_BYTES)) return rc;
+    int rc = c->ops->keyswitch(d_in, c->ksk_padded.get(), c->ks_bias.get(), d_small, slices > 1 ? c->ks_partial.get() : nullptr, slices,
+                               count, c->P.n, c->big_n, c->P.ks_levels, c->P.ks_base_log, c->ks_stride, (hipStream_t)stream);
     return rc ? fail(c, -2, std::string("keyswitch launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
 }
 
@@ -1261,84 +1357,11 @@ int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *
     if (!c || (count && (!d_small || !d_lut_ids || !d_out))) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     HIP_OK(c, hipSetDevice(c->device));
-    // unrolled key (49-bit field at N = 1024 / 2048, 2^64 torus at N = 1024: bmi_set_bsk_unroll refuses the rest): one kernel
-    // (one workgroup per ciphertext) for every batch size, so that a ciphertext's bits never depend on the batch it travelled in
-    if (c->unroll == 2 && !c->have_bsk3)
-        return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
-    // variant 0 = auto: the latency kernel (one workgroup per ciphertext) while the batch cannot fill the chip
-    // with wave-pair work, the throughput kernel beyond that (49-bit field: the exchange-once form).
-    const bool latency = c->variant == 2 || (c->variant == 0 && count <= c->lat_threshold);
-    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (c->t64()) {
-        const u64 *luts = (const u64 *)c->d_luts;
-        const int prec = c->bsk_prec;
-        if (c->wide() && c->d_bsk_w2 && (c->variant == 1 || c->variant == 3 || (c->variant == 0 && count > 256))) {
-            // N = 2048, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins the
-            // one-ciphertext form below); the same words
-            rc = bmit::launch_blind_rotate_wide2(d_small, d_lut_ids, luts, c->d_bsk_w2, c->d_tw_fq, d_out, count, n, prec, lv, bl, st);
-        } else if (c->wide() || c->quad()) {   // N = 2048 / 4096: one workgroup per ciphertext (N = 2048: up to 256 ciphertexts, see above)
-            rc = (c->quad() ? bmit::launch_blind_rotate_quad : bmit::launch_blind_rotate_wide)(d_small, d_lut_ids, luts, c->d_bsk_w, c->d_tw_fq, d_out,
-                                                                                               count, n, prec, lv, bl, nullptr, st);
-        } else if (c->unroll == 2) {
-            // the floating-point-transform route (42-bit key): one ciphertext per workgroup up to a full round of 256, two per workgroup
-            // (key words shared in registers: half the key bytes per bootstrap) beyond - the same words either way; variant 2 pins
-            // the former, variants 1 / 3 the latter
-            const bool ufft = bmit::shape_supported_unrolled_fft(prec, lv, bl);
-            const bool two = ufft && (c->variant == 1 || c->variant == 3 || (c->variant == 0 && count > 256));
-            if (two)
-                rc = bmit::launch_blind_rotate_tp2u_fft(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out, count, n, prec,
-                                                        lv, bl, st);
-            else if (ufft)
-                rc = bmit::launch_blind_rotate_lat2u_fft(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow, d_out, count, n,
-                                                         prec, lv, bl, nullptr, st);
-            else
-                rc = bmit::launch_blind_rotate_lat2u(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out, count, n, prec,
-                                                     lv, bl, st);
-        } else {   // N = 1024: latency kernel (one workgroup per ciphertext) for small batches, wave pairs beyond
-            if (!c->d_bsk_fft && !bmit::shape_supported(prec, lv, bl))
-                return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
-            if ((c->variant == 5 || c->variant == 6) && !c->d_bsk_fft)
-                return fail(c, -1, "kernel variant " + std::to_string(c->variant) +
-                                       " needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
-            // (floating-point-transform kernels: two rounds of 256 one-workgroup bootstraps, 7.7 ms, still beat the wave-pair kernel's
-            // 8.4 ms up to 1,024 ciphertexts; three rounds do not)
-            const bool lat_t = c->variant == 2 || c->variant == 4 || c->variant == 6 || (c->variant == 0 && count <= c->lat_threshold);
-            // through the floating-point transform where its key copy exists (48-bit key, base 2^10): variants 4 (latency) and
-            // 1 / 3 (wave pairs) pin the exact transform mod 2^49 - 720895, 5 and 6 the floating-point one
-            const bool fft = c->d_bsk_fft && (lat_t ? c->variant != 4 : c->variant == 0 || c->variant == 5);
-            if (!fft)
-                if (int rcb = build_exact_torus_copies(c, nullptr)) return rcb;   // (a no-op once built)
-            if (lat_t && fft)
-                rc = bmit::launch_blind_rotate_lat_fft(d_small, d_lut_ids, luts, c->d_bsk_latf, c->d_tw_fh, d_out, count, n, prec, lv, bl, nullptr, st);
-            else if (lat_t)
-                rc = bmit::launch_blind_rotate_lat(d_small, d_lut_ids, luts, c->d_bsk_lat, c->d_tw_half, d_out, count, n, prec, lv, bl, st);
-            else if (fft)
-                rc = bmit::launch_blind_rotate_fft(d_small, d_lut_ids, luts, c->d_bsk_fft, c->d_tw_fft, d_out, count, n, prec, lv, bl, nullptr, st);
-            else
-                rc = bmit::launch_blind_rotate(d_small, d_lut_ids, luts, (const double *)c->d_bsk, (const double *)c->d_tw, d_out, count, n, prec,
-                                               lv, bl, st);
-        }
-    } else if (c->f64()) {
-        const double *luts = (const double *)c->d_luts, *bsk = (const double *)c->d_bsk, *tw = (const double *)c->d_tw;
-        if (c->wide() && c->unroll == 2)   // N = 2048 with the unrolled key
-            rc = bmi49::launch_blind_rotate_wide_u(d_small, d_lut_ids, luts, c->d_bsk3_lat, tw, c->d_tw_wide, c->d_root_pow, d_out, count, n, lv,
-                                                   bl, st);
-        else if (c->wide() || c->quad())   // N = 2048 / 4096: one kernel for every batch size
-            rc = c->quad() ? bmi49::launch_blind_rotate_quad(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, n, st)
-                           : bmi49::launch_blind_rotate_wide(d_small, d_lut_ids, luts, c->d_bsk_lat, tw, c->d_tw_wide, d_out, count, n, lv, bl, st);
-        else if (c->unroll == 2)
-            rc = bmi49::launch_blind_rotate_lat2u(d_small, d_lut_ids, luts, c->d_bsk3_lat, c->d_tw_half, c->d_root_pow, d_out, count, n, lv, bl, st);
-        else if (latency)
-            rc = bmi49::launch_blind_rotate_lat2(d_small, d_lut_ids, luts, c->d_bsk_lat, c->d_tw_half, d_out, count, n, lv, bl, st);
-        else
-            rc = bmi49::launch_blind_rotate_tpx(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, lv, bl, st);
-    } else {
-        const u64 *luts = (const u64 *)c->d_luts, *bsk = (const u64 *)c->d_bsk, *tw = (const u64 *)c->d_tw;
-        rc = latency ? bmi::launch_blind_rotate_lat(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, st)
-                     : bmi::launch_blind_rotate_tp(d_small, d_lut_ids, luts, bsk, tw, d_out, count, n, st);
-    }
+    Rot rot;
+    if (int rc = choose_rotation(c, count, &rot)) return rc;
+    if (rot == Rot::t64_lat || rot == Rot::t64_exact)
+        if (int rc = build_exact_torus_copies(c, nullptr)) return rc;   // (a no-op once built)
+    const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, (hipStream_t)stream);
     return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
 }
 
@@ -1348,9 +1371,9 @@ int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, u
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_small(c, count);
     if (rc) return rc;
-    rc = bmi_keyswitch_batch(c, d_in, count, c->d_small, stream);
+    rc = bmi_keyswitch_batch(c, d_in, count, c->small.get(), stream);
     if (rc) return rc;
-    return bmi_blind_rotate_batch(c, c->d_small, d_lut_ids, count, d_out, stream);
+    return bmi_blind_rotate_batch(c, c->small.get(), d_lut_ids, count, d_out, stream);
 }
 
 int bmi_lincomb_batch(bmi_ctx *c, const uint64_t *d_store, const uint32_t *d_row_ptr, const uint32_t *d_idx,
@@ -1358,9 +1381,7 @@ int bmi_lincomb_batch(bmi_ctx *c, const uint64_t *d_store, const uint32_t *d_row
                       void *stream) {
     if (!c || (count && (!d_store || !d_row_ptr || !d_const_body || !d_out))) return -1;
     HIP_OK(c, hipSetDevice(c->device));
-    int rc = (c->f64() ? bmi49::launch_lincomb : (c->t64() ? bmit::launch_lincomb : bmi::launch_lincomb))(d_store, d_row_ptr, d_idx, (const i64 *)d_coef,
-                                                                      d_const_body, d_out, count, c->big_n + 1,
-                                                                      (hipStream_t)stream);
+    int rc = c->ops->lincomb(d_store, d_row_ptr, d_idx, (const i64 *)d_coef, d_const_body, d_out, count, c->big_n + 1, (hipStream_t)stream);
     return rc ? fail(c, -2, std::string("lincomb launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
 }
 
@@ -1376,10 +1397,7 @@ int bmi_reserve(bmi_ctx *c, uint32_t max_count) {
     if (!c) return -1;
     HIP_OK(c, hipSetDevice(c->device));
     HIP_OK(c, hipDeviceSynchronize());
-    if (!c->d_ks_partial) {
-        c->ks_partial_bytes = (size_t)96 << 20;  // covers every split configuration (<= 1024 workgroups x 8 ciphertexts)
-        HIP_OK(c, hipMalloc(&c->d_ks_partial, c->ks_partial_bytes));
-    }
+    if (int rc = grow(c, c->ks_partial, KS_PARTIAL_BYTES, KS_PARTIAL_BYTES)) return rc;
     if (c->ks_mfma_ok) {
         // the sums buffer peaks where the K-split is still active (small batches), not at max_count, and the slice
         // count is not monotonic in the batch size: take the largest need over every tile count up to max_count
@@ -1405,16 +1423,6 @@ int bmi_sync(bmi_ctx *c, void *stream) {
 }
 
 // ------------------------------------------------------------------- host-buffer convenience forms
-namespace {
-// a look-up id beyond the registered tables would make the kernels read past the table buffer: refused on the host
-// (the device-pointer entry points cannot look at their ids without a synchronisation; their contract is ids < count)
-int check_lut_ids(bmi_ctx *c, const uint32_t *lut_ids, uint32_t count) {
-    for (uint32_t i = 0; i < count; i++)
-        if (lut_ids[i] >= c->n_luts) return fail(c, -1, "look-up id " + std::to_string(lut_ids[i]) + " is not registered");
-    return 0;
-}
-}  // namespace
-
 int bmi_pbs_batch_host(bmi_ctx *c, const uint64_t *in, const uint32_t *lut_ids, uint32_t count, uint64_t *out) {
     if (!c || !in || !lut_ids || !out) return -1;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
@@ -1422,11 +1430,11 @@ int bmi_pbs_batch_host(bmi_ctx *c, const uint64_t *in, const uint32_t *lut_ids, 
     int rc = ensure_io(c, count);
     if (rc) return rc;
     const size_t w = (size_t)(c->big_n + 1) * 8;
-    HIP_OK(c, hipMemcpyAsync(c->d_io_a, in, count * w, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_io_ids, lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_pbs_batch(c, c->d_io_a, c->d_io_ids, count, c->d_io_b, c->stream);
+    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, count * w, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_pbs_batch(c, c->io_a.get(), c->io_ids.get(), count, c->io_b.get(), c->stream);
     if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->d_io_b, count * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), count * w, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1436,12 +1444,10 @@ int bmi_keyswitch_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uin
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_io(c, count);
     if (rc) return rc;
-    rc = ensure_small(c, count);
+    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, (size_t)count * (c->big_n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_keyswitch_batch(c, c->io_a.get(), count, c->small.get(), c->stream);
     if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->d_io_a, in, (size_t)count * (c->big_n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_keyswitch_batch(c, c->d_io_a, count, c->d_small, c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(small_out, c->d_small, (size_t)count * (c->P.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(small_out, c->small.get(), (size_t)count * (c->P.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1453,13 +1459,11 @@ int bmi_blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_io(c, count);
     if (rc) return rc;
-    rc = ensure_small(c, count);
+    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_blind_rotate_batch(c, c->small.get(), c->io_ids.get(), count, c->io_b.get(), c->stream);
     if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->d_small, small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->d_io_ids, lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_blind_rotate_batch(c, c->d_small, c->d_io_ids, count, c->d_io_b, c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->d_io_b, (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1468,36 +1472,29 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
                         double *max_distance) {
     if (!c || !small_in || !lut_ids || !out || !max_distance) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
+    // its own kernel rule (batch size plays no part): the unrolled kernel where the unrolled 42-bit key is in use, else at N = 1024
+    // the latency form when kernel variant 6 / 2 is selected, else the N = 2048 / 4096 kernel, else the wave-pair kernel
     const bool ufft = c->t64() && c->unroll == 2 && c->have_bsk3 && bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
-    if (!c->d_bsk_fft && !c->d_bsk_w && !ufft)
+    const bool wide_key = !c->bsk.wide.empty() || !c->bsk.quad.empty();
+    if (c->bsk.fft.empty() && !wide_key && !ufft)
         return fail(c, -1, "the floating-point-transform kernels exist on the 2^64 torus with the bootstrap key at 48 bits (N = 1024), 46 bits "
                            "(N = 2048) or 44 bits (N = 4096) in base 2^10");
+    const Rot rot = ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
+                    : wide_key ? (c->quad() ? Rot::t64_quad : Rot::t64_wide) : Rot::t64_fft;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_io(c, count);
     if (rc) return rc;
-    rc = ensure_small(c, count);
-    if (rc) return rc;
-    unsigned long long *d_stat = nullptr;
-    HIP_OK(c, hipMalloc(&d_stat, 8));
-    hipError_t e = hipMemsetAsync(d_stat, 0, 8, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_small, small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_io_ids, lut_ids, count * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = ufft ? (hipError_t)bmit::launch_blind_rotate_lat2u_fft(c->d_small, c->d_io_ids, (const u64 *)c->d_luts, c->d_bsk3_lat, c->d_tw_fh, c->d_zeta_pow,
-                                                                   c->d_io_b, count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, d_stat, c->stream)
-            : (!c->d_bsk_w && (c->variant == 6 || c->variant == 2))   // the latency form of the N = 1024 transform (kernel variant 6 / 2 selected)
-                ? (hipError_t)bmit::launch_blind_rotate_lat_fft(c->d_small, c->d_io_ids, (const u64 *)c->d_luts, c->d_bsk_latf, c->d_tw_fh, c->d_io_b,
-                                                                count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, d_stat, c->stream)
-            : c->d_bsk_w ? (hipError_t)(c->quad() ? bmit::launch_blind_rotate_quad : bmit::launch_blind_rotate_wide)(c->d_small, c->d_io_ids, (const u64 *)c->d_luts, c->d_bsk_w, c->d_tw_fq, c->d_io_b,
-                                                                    count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, d_stat, c->stream)
-                       : (hipError_t)bmit::launch_blind_rotate_fft(c->d_small, c->d_io_ids, (const u64 *)c->d_luts, c->d_bsk_fft, c->d_tw_fft, c->d_io_b,
-                                                                   count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log, d_stat, c->stream);
+    DevBuf<unsigned long long> d_stat;
+    HIP_OK(c, d_stat.alloc(8));
+    hipError_t e = hipMemsetAsync(d_stat.get(), 0, 8, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)launch_rotation(c, rot, c->small.get(), c->io_ids.get(), count, c->io_b.get(), d_stat.get(), c->stream);
     unsigned long long bits = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_io_b, (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bits, d_stat, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bits, d_stat.get(), 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_stat);
     if (e != hipSuccess) return fail(c, -2, std::string("bmi_fft_margin_host: ") + hipGetErrorString(e));
     std::memcpy(max_distance, &bits, 8);
     return 0;
@@ -1508,19 +1505,14 @@ int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, ui
     if (c->wide() || c->quad()) return fail(c, -1, "the transform test hook exists for N = 1024 only");
     if (c->t64()) return fail(c, -1, "no transform exists mod 2^64: the test hook covers the two prime fields");
     HIP_OK(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)count * c->N * 8;
-    u64 *da = nullptr, *db = nullptr, *dc = nullptr;
-    HIP_OK(c, hipMalloc(&da, bytes));
-    HIP_OK(c, hipMalloc(&db, bytes));
-    HIP_OK(c, hipMalloc(&dc, bytes));
-    HIP_OK(c, hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
-    HIP_OK(c, hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
-    int rc = c->f64() ? bmi49::launch_negacyclic_mul(da, db, dc, (const double *)c->d_tw, count, c->stream)
-                      : bmi::launch_negacyclic_mul(da, db, dc, (const u64 *)c->d_tw, count, c->stream);
-    if (rc) return fail(c, -2, "negacyclic_mul launch failed");
+    const size_t words = (size_t)count * c->N;
+    DevBuf<u64> da, db, dc;
+    HIP_OK(c, upload(da, a, words));
+    HIP_OK(c, upload(db, b, words));
+    HIP_OK(c, dc.alloc(words * 8));
+    if (c->ops->negacyclic_mul(c, da.get(), db.get(), dc.get(), count)) return fail(c, -2, "negacyclic_mul launch failed");
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(out, dc, bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc);
+    HIP_OK(c, hipMemcpy(out, dc.get(), words * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,8 +1,9 @@
 """CPU-side checks of the drop-in boundary: libbmi_tfhe.so loads and exports every symbol that
-include/bmi_tfhe.h declares; without a GPU the context constructor fails loudly (no CPU fallback)."""
+include/bmi_tfhe.h declares, and no other function; without a GPU the context constructor fails loudly (no CPU fallback)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -25,6 +26,10 @@ def test_library_exports_every_declared_symbol():
     # and the binding wires every one of them
     bound = set(tfhe._SIGS) | {"bmi_ctx_destroy", "bmi_last_error"}
     assert set(syms) <= bound, set(syms) - bound
+    # nothing else: internal helpers and launchers stay local (csrc/bmi_tfhe.map), so a host's own names never collide with ours
+    nm = subprocess.run(["nm", "-D", "--defined-only", tfhe.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    functions = {f[2].split("@")[0] for f in map(str.split, nm.splitlines()) if len(f) == 3 and f[1] in "TtWwi"}
+    assert functions == set(syms), sorted(functions ^ set(syms))
 
 
 def test_default_params_are_the_north_star_set():
