@@ -1,4 +1,5 @@
-// Internal declarations shared by the kernel TU (bmi_kernels.hip) and the host TU (bmi_host.cpp).
+// Internal declarations shared by every kernel TU (bmi_kernels*.hip) and the host TU (bmi_host.cpp): tunables and LDS limits,
+// the launch scaffolding of the kernel TUs, and the launchers the host calls (one namespace per modulus).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +38,7 @@ constexpr int BMI_LDS_WORDS_MAX = 160 * 1024 / 8;   // 160 KB of LDS per workgro
 // hipFuncSetAttribute acts on the current device only: remember per kernel which devices have been configured
 // (several contexts on several GPUs may live in one process).
 #include <atomic>
+#include <type_traits>
 inline int set_max_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint64_t> &done_devices) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -46,6 +48,41 @@ inline int set_max_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uin
     if (e != hipSuccess) return (int)e;
     if (dev < 64) done_devices.fetch_or((uint64_t)1 << dev);
     return 0;
+}
+
+// after a kernel launch, inside a launcher returning int: the launch error, if any, is the launcher's result
+#define BMI_LAUNCH_CHECK()                      \
+    do {                                        \
+        hipError_t e__ = hipGetLastError();     \
+        if (e__ != hipSuccess) return (int)e__; \
+    } while (0)
+
+// Launch of a kernel that takes more dynamic LDS than the default limit.  KERN is a template parameter so that every kernel
+// instantiation has its own "configured on these devices" flag.
+template <auto KERN>
+inline std::atomic<uint64_t> &lds_configured() {
+    static std::atomic<uint64_t> configured{0};
+    return configured;
+}
+template <auto KERN, typename... Args>
+inline int launch_with_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args... args) {
+    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(KERN), lds_bytes, lds_configured<KERN>())) return rc;
+    hipLaunchKernelGGL(KERN, grid, block, lds_bytes, s, args...);
+    BMI_LAUNCH_CHECK();
+    return 0;
+}
+
+// The runtime (levels, statistics wanted) of the floating-point-transform families -> their instantiations: calls
+// f(L, STATS) with L = std::integral_constant<int, 3 or 2> (the callers have checked the shape) and STATS = std::true_type
+// or std::false_type, usable as template arguments.  The kernels without a STATS form take with_levels alone.
+template <typename F>
+inline int with_levels(uint32_t levels, F f) {
+    if (levels == 3) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 2>{});
+}
+template <typename F>
+inline int with_levels_stats(uint32_t levels, bool stats, F f) {
+    return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
 namespace bmi {
@@ -127,7 +164,7 @@ int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *id
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
 }  // namespace bmi49
 
-// The 2^64 torus (bmi_kernels_t64.hip, bmi_kernels_t64u.hip): ciphertexts, test polynomials and keyswitch key are plain u64
+// The 2^64 torus (bmi_kernels_t64*.hip): ciphertexts, test polynomials and keyswitch key are plain u64
 // words; the bootstrap key is LIMBS transform-domain f64 limb polynomials per key polynomial ([poly][limb][N]); the limb
 // scheme follows from the precision `prec` (64, 48 or 42 bits) the key is stored at (t64_common.hpp).
 namespace bmit {

@@ -329,12 +329,6 @@ struct FieldG {
 // ------------------------------------------------------------------------------------- launchers
 namespace bmi {
 
-#define BMI_LAUNCH_CHECK()                      \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 int launch_bsk_to_ntt(const u64 *std_polys, u64 *ntt_polys, const u64 *g_tw, uint32_t n_polys, hipStream_t s) {
     hipLaunchKernelGGL(k_bsk_to_ntt, dim3((n_polys + 3) / 4), dim3(256), 0, s, std_polys, ntt_polys, g_tw, n_polys);
     BMI_LAUNCH_CHECK();
@@ -360,13 +354,8 @@ int launch_blind_rotate_tp(const u64 *small_cts, const uint32_t *lut_ids, const 
 int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const u64 *bsk,
                             const u64 *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
     if (count == 0) return 0;
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)LAT_LDS_WORDS * sizeof(u64);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(k_blind_rotate_lat), lds, configured)) return rc;
-    hipLaunchKernelGGL(k_blind_rotate_lat, dim3(count), dim3(LAT_THREADS), lds, s, small_cts, lut_ids, luts, bsk, g_tw, out,
-                       count, n);
-    BMI_LAUNCH_CHECK();
-    return 0;
+    return launch_with_lds<k_blind_rotate_lat>(dim3(count), dim3(LAT_THREADS), (size_t)LAT_LDS_WORDS * sizeof(u64), s, small_cts, lut_ids, luts,
+                                               bsk, g_tw, out, count, n);
 }
 
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
@@ -402,8 +391,8 @@ __global__ void __launch_bounds__(256) k_scatter_rows(const u64 *__restrict__ sr
 int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32_t count, uint32_t width, hipStream_t s) {
     if (count == 0) return 0;
     hipLaunchKernelGGL(k_scatter_rows, dim3(count), dim3(256), 0, s, src, store, rows, width);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    BMI_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace bmi

@@ -17,6 +17,7 @@
 #include "ks_mfma.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
+#include "phase_prof.hpp"
 
 using f49::i64;
 using f49::u64;
@@ -68,19 +69,7 @@ __global__ void __launch_bounds__(256) k_negacyclic_mul49(const u64 *__restrict_
 }
 
 // Phase timing (debug build only: make prof): wall-clock cycles per phase of one wavefront, see tools/phase_prof.py
-#ifdef BMI_PHASE_PROF
-__device__ unsigned long long g_phase[128];
-#define PH_DECL() unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64()
-#define PH_MARK(k)                               \
-    do {                                         \
-        const unsigned long long t_ = clock64(); \
-        ph_[k] += t_ - tl_;                      \
-        tl_ = t_;                                \
-    } while (0)
-#else
-#define PH_DECL()
-#define PH_MARK(k)
-#endif
+PH_ARRAY(g_phase)
 
 // THROUGHPUT, second form: one exchange per CMUX instead of three.
 // Wavefront c of a pair owns INPUT polynomial c of the CMUX: it decomposes rot(acc_c) - acc_c, transforms the three
@@ -418,10 +407,7 @@ __global__ void __launch_bounds__(L2_THREADS)
         __syncthreads();
         PH_MARK(5);
     }
-#ifdef BMI_PHASE_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase[wave * 8 + k_] = ph_[k_];
-#endif
+    PH_STORE(g_phase, wave, lane);
     u64 *o = out + (size_t)ct * (N + 1);
     {
         const uint32_t nn = tid;
@@ -651,10 +637,7 @@ __global__ void __launch_bounds__(W_THREADS)
         __syncthreads();
         PH_MARK(6);
     }
-#ifdef BMI_PHASE_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase[wave * 8 + k_] = ph_[k_];
-#endif
+    PH_STORE(g_phase, wave, lane);
     u64 *o = out + (size_t)ct * (W_N + 1);
     for (uint32_t nn = tid; nn < (uint32_t)W_N; nn += W_THREADS) {
         const double a0 = acc[(nn & 1) * N + (nn >> 1)];
@@ -1106,29 +1089,19 @@ struct Field49 {
 
 }  // namespace
 
-#ifdef BMI_PHASE_PROF
-extern "C" int bmi_debug_phase_prof(unsigned long long *out64) {
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 128);
-}
-#endif
+PH_EXPORT(bmi_debug_phase_prof, g_phase)
 
 namespace bmi49 {
 
-#define BMI49_LAUNCH_CHECK()                    \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 int launch_bsk_to_ntt(const u64 *std_polys, double *ntt_polys, const double *g_tw, uint32_t n_polys, hipStream_t s) {
     hipLaunchKernelGGL(k_bsk_to_ntt49, dim3((n_polys + 3) / 4), dim3(256), 0, s, std_polys, ntt_polys, g_tw, n_polys);
-    BMI49_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw, uint32_t count, hipStream_t s) {
     hipLaunchKernelGGL(k_negacyclic_mul49, dim3((count + 3) / 4), dim3(256), 0, s, a, b, c, g_tw, count);
-    BMI49_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1145,14 +1118,9 @@ template <int L, int BG>
 struct LaunchTpx {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk, const double *g_tw,
                   u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        static std::atomic<uint64_t> configured{0};
-        const size_t lds = (size_t)TPX_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3((count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS), lds, s, small_cts, lut_ids, luts,
-                           bsk, g_tw, out, count, n);
-        BMI49_LAUNCH_CHECK();
-        return 0;
+        return launch_with_lds<k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>>(dim3((count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS),
+                                                                           (size_t)TPX_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
+                                                                           luts, bsk, g_tw, out, count, n);
     }
 };
 typedef int (*launch9_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, u64 *, uint32_t, uint32_t,
@@ -1173,26 +1141,21 @@ int launch_blind_rotate_tpx(const u64 *small_cts, const uint32_t *lut_ids, const
 int launch_bsk_to_quad(const u64 *std_polys, double *quad_polys, const double *g_tw, const double *g_t, uint32_t n_polys,
                        hipStream_t s) {
     hipLaunchKernelGGL(k_bsk_to_quad49, dim3(n_polys), dim3(256), 0, s, std_polys, quad_polys, g_tw, g_t, n_polys);
-    BMI49_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_quad,
                              const double *g_tw, const double *g_t, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
     if (count == 0) return 0;
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)Q_LDS_WORDS * sizeof(double);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(k_blind_rotate_quad49), lds, configured)) return rc;
-    hipLaunchKernelGGL(k_blind_rotate_quad49, dim3(count), dim3(Q_THREADS), lds, s, small_cts, lut_ids, luts, bsk_quad, g_tw,
-                       g_t, out, count, n);
-    BMI49_LAUNCH_CHECK();
-    return 0;
+    return launch_with_lds<k_blind_rotate_quad49>(dim3(count), dim3(Q_THREADS), (size_t)Q_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
+                                                  luts, bsk_quad, g_tw, g_t, out, count, n);
 }
 
 int launch_bsk_to_wide(const u64 *std_polys, double *wide_polys, const double *g_tw, const double *g_tw_wide,
                        uint32_t n_polys, hipStream_t s) {
     hipLaunchKernelGGL(k_bsk_to_wide49, dim3(n_polys), dim3(128), 0, s, std_polys, wide_polys, g_tw, g_tw_wide, n_polys);
-    BMI49_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1200,14 +1163,8 @@ template <int L, int BG>
 struct LaunchWide {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_wide, const double *g_tw,
                   const double *g_tw_wide, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        static std::atomic<uint64_t> configured{0};
-        const size_t lds = (size_t)W_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_wide49<L, BG>;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(count), dim3(W_THREADS), lds, s, small_cts, lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out,
-                           count, n);
-        BMI49_LAUNCH_CHECK();
-        return 0;
+        return launch_with_lds<k_blind_rotate_wide49<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)W_LDS_WORDS * sizeof(double), s, small_cts,
+                                                              lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out, count, n);
     }
 };
 typedef int (*launch10_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *, u64 *,
@@ -1226,14 +1183,8 @@ template <int L, int BG>
 struct LaunchWideU {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_wide, const double *g_tw,
                   const double *g_tw_wide, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        static std::atomic<uint64_t> configured{0};
-        const size_t lds = (size_t)WU_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_wide49u<L, BG>;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(count), dim3(W_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_wide, g_tw, g_tw_wide,
-                           g_root_pow, out, count, n);
-        BMI49_LAUNCH_CHECK();
-        return 0;
+        return launch_with_lds<k_blind_rotate_wide49u<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s, small_cts,
+                                                               lut_ids, luts, bsk3_wide, g_tw, g_tw_wide, g_root_pow, out, count, n);
     }
 };
 typedef int (*launch11_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *,
@@ -1255,7 +1206,7 @@ int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, co
 int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, bool paired, hipStream_t s) {
     if (paired) hipLaunchKernelGGL(k_bsk_to_lat49<true>, dim3((n_polys + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys);
     else hipLaunchKernelGGL(k_bsk_to_lat49<false>, dim3((n_polys + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys);
-    BMI49_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1263,13 +1214,8 @@ template <int L, int BG>
 struct LaunchLat2 {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat, const double *g_tw_h,
                   u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        static std::atomic<uint64_t> configured{0};
-        const size_t lds = (size_t)L2_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_lat2_49<L, BG>;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(count), dim3(L2_THREADS), lds, s, small_cts, lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
-        BMI49_LAUNCH_CHECK();
-        return 0;
+        return launch_with_lds<k_blind_rotate_lat2_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2_LDS_WORDS * sizeof(double), s, small_cts,
+                                                               lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
     }
 };
 static launch9_t pick_lat2(uint32_t levels, uint32_t base_log) { BMI49_FOR_LB(levels, base_log, LaunchLat2); }

@@ -3,12 +3,11 @@
 // with -amdgpu-sched-strategy=max-ilp, which costs this kernel 3 % (2.28 against 2.23 ms per bootstrap, A/B in one call).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "bmi_internal.hpp"
 #include "dec49.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
+#include "phase_prof.hpp"
 
 using f49::i64;
 using f49::u64;
@@ -19,19 +18,9 @@ using dec49::round_half_up;
 namespace {
 
 // Phase timing (debug build only: make prof; tools/phase_prof.py with unroll = 2)
+PH_ARRAY(g_phase_u)
 #ifdef BMI_PHASE_PROF
-__device__ unsigned long long g_phase_u[128];
-__device__ unsigned long long g_wg_times_u[1024][2];   // [workgroup][start, end] in ticks of the 100 MHz real-time counter
-#define PH_DECL() unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64()
-#define PH_MARK(k)                               \
-    do {                                         \
-        const unsigned long long t_ = clock64(); \
-        ph_[k] += t_ - tl_;                      \
-        tl_ = t_;                                \
-    } while (0)
-#else
-#define PH_DECL()
-#define PH_MARK(k)
+__device__ unsigned long long g_wg_times_u[1024][2];   // [workgroup][start, end] in ticks of the 100 MHz real-time counter (tools/wg_times.py)
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -182,9 +171,8 @@ __global__ void __launch_bounds__(L2_THREADS)
         __syncthreads();
         PH_MARK(5);
     }
+    PH_STORE(g_phase_u, wave, lane);
 #ifdef BMI_PHASE_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase_u[wave * 8 + k_] = ph_[k_];
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_wg_times_u[blockIdx.x][1] = wall_clock64();
 #endif
     u64 *o = out + (size_t)ct * (N + 1);
@@ -202,10 +190,8 @@ __global__ void __launch_bounds__(L2_THREADS)
 
 }  // namespace
 
+PH_EXPORT(bmi_debug_phase_prof_unrolled, g_phase_u)
 #ifdef BMI_PHASE_PROF
-extern "C" int bmi_debug_phase_prof_unrolled(unsigned long long *out64) {
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phase_u), sizeof(unsigned long long) * 128);
-}
 extern "C" int bmi_debug_wg_times_unrolled(unsigned long long *out2048) {
     return (int)hipMemcpyFromSymbol(out2048, HIP_SYMBOL(g_wg_times_u), sizeof(unsigned long long) * 2048);
 }
@@ -213,24 +199,12 @@ extern "C" int bmi_debug_wg_times_unrolled(unsigned long long *out2048) {
 
 namespace bmi49 {
 
-#define BMI49_LAUNCH_CHECK()                    \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 template <int L, int BG>
 struct LaunchLat2u {
     static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat, const double *g_tw_h,
                   const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        static std::atomic<uint64_t> configured{0};
-        const size_t lds = (size_t)L2U_LDS_WORDS * sizeof(double);
-        auto kern = k_blind_rotate_lat2u_49<L, BG>;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(count), dim3(L2_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out,
-                           count, n);
-        BMI49_LAUNCH_CHECK();
-        return 0;
+        return launch_with_lds<k_blind_rotate_lat2u_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2U_LDS_WORDS * sizeof(double), s, small_cts,
+                                                                lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
     }
 };
 typedef int (*launch10_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *, u64 *,

@@ -38,14 +38,13 @@ namespace {
 #define BMI_T64_RESYNC BMI_TPX49_RESYNC   // workgroup barrier every so many CMUXes (keeps the four pairs on the same key rows)
 #endif
 using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 using t64::word_to_f64;
 constexpr int T64_CTS = 4;
 constexpr int T64_AT_WORDS = BMI_AT_WORDS;
 constexpr int T64_LDS_WORDS = TW_WORDS + 2 * T64_CTS * (SCRATCH_WORDS + N) + T64_CTS * T64_AT_WORDS + 4 * T64_CTS;
 static_assert(T64_LDS_WORDS <= BMI_LDS_WORDS_MAX, "T64_LDS_WORDS exceeds the 160 KB of LDS");
-
-__device__ __forceinline__ uint32_t modswitch_t64(u64 a) { return t64::modswitch<LOG_N + 1>(a); }
 
 // standard-domain GGSW polynomials (u64 torus words) -> LIMBS transform-domain limb polynomials each, lane layout
 __global__ void __launch_bounds__(256) k_bsk_to_limbs_t64(const u64 *__restrict__ std_polys, double *__restrict__ limb_polys,
@@ -98,15 +97,11 @@ __global__ void __launch_bounds__(128 * T64_CTS)
     const double *ptile = tiles + (wave ^ 1) * SCRATCH_WORDS;
     u64 *accl = accs + wave * N;
     double *accf = reinterpret_cast<double *>(accl);     // the same LDS words, read as doubles when ACCF
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53
-        // (ties go to the negative end, like the two's complement reading of the u64 word: + 2^(AB-1) is - 2^(AB-1))
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     uint16_t *at = reinterpret_cast<uint16_t *>(at_base + ctl * T64_AT_WORDS);
     uint32_t *f_pub = flags + wave, *f_pub_partner = flags + (wave ^ 1);
     uint32_t *f_ack = flags + 2 * CTS + wave, *f_ack_partner = flags + 2 * CTS + (wave ^ 1);
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = lane + 64 * c; i <= n; i += 128) at[i] = (uint16_t)modswitch_t64(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, lane + 64 * c, 128);   // by the pair of wavefronts
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
@@ -115,7 +110,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
             const uint32_t e = (lane + 64 * J + bt) & (2 * N - 1);
             const u64 v = tv[e & (N - 1)];
             const u64 w0 = c ? ((e & N) ? (u64)0 - v : v) : (u64)0;
-            if constexpr (ACCF) accf[lane + 64 * J] = (double)((i64)w0 >> PRE);     // test polynomials are multiples of 2^(59 or so)
+            if constexpr (ACCF) t64::set_acc<PRE>(accf[lane + 64 * J], w0);
             else accl[lane + 64 * J] = w0;
         });
     }
@@ -140,8 +135,8 @@ __global__ void __launch_bounds__(128 * T64_CTS)
             sched_fence();
             static_for<0, 16>([&](auto J) {
                 const uint32_t e = (lane + 64 * J + 2 * N - a_t) & (2 * N - 1);
-                const double d = mod_ab(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
-                r[J] = __builtin_floor(__builtin_fma(d, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
+                const double d = mod_ab<AB>(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
+                r[J] = t64::rounded_top_f64<L, BG, AB>(d);
             });
         } else {
             u64 vr[16], vs[16];  // all 32 reads in flight before the first use
@@ -227,9 +222,9 @@ __global__ void __launch_bounds__(128 * T64_CTS)
                     if constexpr (j > 0) {
                         constexpr double W = (double)(1ull << (AB - LB * j));
                         x = __builtin_fma(-W, __builtin_rint(x * (1.0 / W)), x);
-                        accf[lane + 64 * J] = mod_ab(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
+                        accf[lane + 64 * J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
                     } else {
-                        accf[lane + 64 * J] = mod_ab(accf[lane + 64 * J] + x);
+                        accf[lane + 64 * J] = mod_ab<AB>(accf[lane + 64 * J] + x);
                     }
                 } else {
                     accl[lane + 64 * J] += f64_to_word(f49::red(acc[J])) << (PRE + LB * j);
@@ -265,6 +260,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
 //   C  wavefronts 0 .. 11 = (limb, o, parity): inverse half transform, conversion of the exact integers to words,
 //      shift into place and ONE LDS atomic add per coefficient into the accumulator (the limbs of a coefficient meet in a slot)
 constexpr int LT_THREADS = 1024;
+constexpr t64::ResidueSlot<N, 1> lt_acc_slot{};   // accumulator words (u64) are kept split by parity
 constexpr int LT_LDS_WORDS = ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + 3 * 2 * N + BMI_AT_WORDS;   // sized for 3 limbs
 static_assert(LT_LDS_WORDS <= BMI_LDS_WORDS_MAX, "LT_LDS_WORDS exceeds the 160 KB of LDS");
 
@@ -323,16 +319,12 @@ __global__ void __launch_bounds__(LT_THREADS)
     for (int i = tid; i < ntth::HT_WORDS; i += LT_THREADS) lds[i] = g_tw_h[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += LT_THREADS) at[i] = (uint16_t)modswitch_t64(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, LT_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const u64 v = tv[e & (N - 1)];
-        acc[(nn & 1) * ntth::HALF + (nn >> 1)] = 0;
-        acc[N + (nn & 1) * ntth::HALF + (nn >> 1)] = (e & N) ? (u64)0 - v : v;
+        t64::load_test_poly<N, PRE>(acc, lt_acc_slot, tv, bt, tid);
     }
     __syncthreads();
     const int mo = tid >> 9, mp = tid & 511;  // phase B: output polynomial, slot
@@ -365,15 +357,7 @@ __global__ void __launch_bounds__(LT_THREADS)
                 const uint32_t n2 = e & (N - 1);
                 u64 v = ac[(n2 & 1) * ntth::HALF + (n2 >> 1)];
                 v = (e & N) ? (u64)0 - v : v;
-                double r = t64::rounded_top<L, BG>(v - ac[h * ntth::HALF + m]);        // round half up to L BG bits
-                double d = r;                                                          // digit `lev`, balanced [-2^14, 2^14)
-#pragma unroll
-                for (int s = L - 1; s > 0; s--) {
-                    const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                    if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                    r = rn;
-                }
-                x[J] = lev == 0 ? r : d;
+                x[J] = t64::peel_digit<L, BG>(t64::rounded_top<L, BG>(v - ac[h * ntth::HALF + m]), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
             if (h) ntth::forward_half<true>(x, lane, lds, tile);
@@ -437,17 +421,7 @@ __global__ void __launch_bounds__(LT_THREADS)
         }
         __syncthreads();
     }
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const u64 a0 = acc[(nn & 1) * ntth::HALF + (nn >> 1)];
-        if (nn == 0) {
-            o[0] = a0;
-            o[N] = acc[N];
-        } else {
-            o[N - nn] = (u64)0 - a0;
-        }
-    }
+    t64::extract_sample<N, PRE, 64 - PRE>(out + (size_t)ct * (N + 1), acc, lt_acc_slot, tid);
 }
 
 // keyswitch / linear combinations: wrap-around arithmetic, the oracle's 64-bit decomposition rule
@@ -478,31 +452,12 @@ struct FieldT {
 
 namespace bmit {
 
-#define BMIT_LAUNCH_CHECK()                     \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 int launch_bsk_to_limbs(const u64 *std_polys, double *limb_polys, const double *g_tw, uint32_t n_polys, int prec,
                         hipStream_t s) {
     if (!t64::precision_ok(prec)) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_limbs_t64, dim3((items + 3) / 4), dim3(256), 0, s, std_polys, limb_polys, g_tw, n_polys, prec);
-    BMIT_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int PREC, int L, int BG>
-static int launch_t64(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_limbs,
-                      const double *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)T64_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_t64<PREC, L, BG>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3((count + T64_CTS - 1) / T64_CTS), dim3(128 * T64_CTS), lds, s, small_cts, lut_ids, luts,
-                       bsk_limbs, g_tw, out, count, n);
-    BMIT_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -522,7 +477,10 @@ int launch_blind_rotate(const u64 *small_cts, const uint32_t *lut_ids, const u64
                         uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B) return launch_t64<P, L, B>(small_cts, lut_ids, luts, bsk_limbs, g_tw, out, count, n, s);
+    if (prec == P && levels == L && base_log == B)                                                                                          \
+        return launch_with_lds<k_blind_rotate_t64<P, L, B>>(dim3((count + T64_CTS - 1) / T64_CTS), dim3(128 * T64_CTS),                      \
+                                                             (size_t)T64_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_limbs, \
+                                                             g_tw, out, count, n);
     BMIT_FOR_EACH_SHAPE(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;
@@ -532,19 +490,7 @@ int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_t
     if (!t64::precision_ok(prec)) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_lat_t64, dim3((items + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys, prec);
-    BMIT_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int PREC, int L, int BG>
-static int launch_lat_t64(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_lat,
-                          const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)LT_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_lat_t64<L, PREC, BG>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(LT_THREADS), lds, s, small_cts, lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
-    BMIT_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -553,7 +499,9 @@ int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const
                             uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B) return launch_lat_t64<P, L, B>(small_cts, lut_ids, luts, bsk_lat, g_tw_h, out, count, n, s);
+    if (prec == P && levels == L && base_log == B)                                                                                             \
+        return launch_with_lds<k_blind_rotate_lat_t64<L, P, B>>(dim3(count), dim3(LT_THREADS), (size_t)LT_LDS_WORDS * sizeof(double), s, small_cts, \
+                                                                 lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
     BMIT_FOR_EACH_SHAPE(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;

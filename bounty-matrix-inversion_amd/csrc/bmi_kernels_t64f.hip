@@ -18,6 +18,7 @@
 #include "fft_half_f64.hpp"
 #include "fft_wave_f64.hpp"
 #include "pair_sync.hpp"
+#include "phase_prof.hpp"
 #include "t64_common.hpp"
 
 using t64::i64;
@@ -30,20 +31,9 @@ namespace {
 #define BMI_T64F_RESYNC 1   // workgroup barrier every so many CMUXes: keeps the four pairs on the same key rows, which they share through L1 (0: 83.2 ms, 4: 70.1, 1: 68.9 per 8,192)
 #endif
 
-#ifdef BMI_PHASE_PROF   // make -C csrc prof; tools/phase_prof_t64f.py
-__device__ unsigned long long g_phase_f[128];
-#define PH_DECL() unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64()
-#define PH_MARK(k)                               \
-    do {                                         \
-        const unsigned long long t_ = clock64(); \
-        ph_[k] += t_ - tl_;                      \
-        tl_ = t_;                                \
-    } while (0)
-#else
-#define PH_DECL()
-#define PH_MARK(k)
-#endif
+PH_ARRAY(g_phase_f)   // make -C csrc prof; tools/phase_prof_t64f.py
 using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 #ifndef BMI_T64F_CTS
 #define BMI_T64F_CTS 4      // ciphertexts (wavefront pairs) per workgroup: 4 fill the CU's LDS; 3 and 2 measured slower per ciphertext
@@ -100,15 +90,11 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     double *tile = tiles + wave * SCRATCH_WORDS;
     const double *ptile = tiles + (wave ^ 1) * SCRATCH_WORDS;
     double *accf = accs + wave * N;
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53
-        // (ties go to the negative end, like the two's complement reading of the u64 word: + 2^(AB-1) is - 2^(AB-1))
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     uint16_t *at = reinterpret_cast<uint16_t *>(at_base + ctl * BMI_AT_WORDS);
     uint32_t *f_pub = flags + wave, *f_pub_partner = flags + (wave ^ 1);
     uint32_t *f_ack = flags + 2 * CTS + wave, *f_ack_partner = flags + 2 * CTS + (wave ^ 1);
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = lane + 64 * c; i <= n; i += 128) at[i] = (uint16_t)t64::modswitch<LOG_N + 1>(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, lane + 64 * c, 128);   // by the pair of wavefronts
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
@@ -117,7 +103,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
             const uint32_t e = (lane + 64 * J + bt) & (2 * N - 1);
             const u64 v = tv[e & (N - 1)];
             const u64 w0 = c ? ((e & N) ? (u64)0 - v : v) : (u64)0;
-            accf[lane + 64 * J] = (double)((i64)w0 >> PRE);     // test polynomials are multiples of 2^(59 or so)
+            t64::set_acc<PRE>(accf[lane + 64 * J], w0);
         });
     }
 
@@ -145,8 +131,8 @@ __global__ void __launch_bounds__(128 * TF_CTS)
             sched_fence();
             static_for<0, 16>([&](auto J) {
                 const uint32_t e = (lane + 64 * J + 2 * N - a_t) & (2 * N - 1);
-                const double d = mod_ab(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
-                r[J] = __builtin_floor(__builtin_fma(d, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
+                const double d = mod_ab<AB>(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
+                r[J] = t64::rounded_top_f64<L, BG, AB>(d);
             });
         }
         PH_MARK(1);   // accumulator reads, difference, rounding
@@ -234,7 +220,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                         // x 2^(LB j) mod 2^AB: only the low AB - LB j bits of the limb's integer survive the shift
                         constexpr double W = (double)(1ull << (AB - LB * j));
                         x = __builtin_fma(-W, __builtin_rint(x * (1.0 / W)), x);
-                        accf[lane + 64 * J] = mod_ab(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
+                        accf[lane + 64 * J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
                     } else {
                         accf[lane + 64 * J] += x;   // (reduced mod 2^AB with the last limb: 2^47 + 2^45 + 2^47 stays exact)
                     }
@@ -244,11 +230,8 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         });
     }
 
-#ifdef BMI_PHASE_PROF
     PH_MARK(7);
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase_f[wave * 8 + k_] = ph_[k_];
-#endif
+    PH_STORE(g_phase_f, wave, lane);
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
     if (!live) return;
     wave_sync();
@@ -286,7 +269,7 @@ constexpr int LF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * LF_MAX_L * N + 2 * 2 *
 static_assert(LF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "LF_LDS_WORDS exceeds the 160 KB of LDS");
 
 // accumulator words are kept split by parity (a lane's four points are 128 coefficients apart and of one parity)
-__device__ __forceinline__ uint32_t acc_slot(uint32_t n) { return (n & 1) * LF_HALF + (n >> 1); }
+constexpr t64::ResidueSlot<N, 1> acc_slot{};
 
 // standard-domain GGSW polynomials -> per (polynomial, limb) 256 slots of [F_k, F_{k+256}] (k = ffth::slot_freq of the slot)
 __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__ std_polys, double *__restrict__ lat_polys,
@@ -339,9 +322,6 @@ __global__ void __launch_bounds__(LF_THREADS)
     static_assert(LIMBS == 2 && L <= LF_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *acc = lds + ffth::HT_WORDS;                                     // [2 components][2 parities][512]: word / 2^16, exact, |.| < 2^51
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53 (ties to the negative end, like the u64 word)
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     double2 *tiles = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + 2 * N);   // [2L rows][2 halves][256 slots] complex
     double2 *SD = tiles + LF_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
     uint16_t *at = reinterpret_cast<uint16_t *>(SD + 2 * N);
@@ -349,16 +329,12 @@ __global__ void __launch_bounds__(LF_THREADS)
     for (int i = tid; i < ffth::HT_WORDS; i += LF_THREADS) lds[i] = g_tw_h[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += LF_THREADS) at[i] = (uint16_t)t64::modswitch<LOG_N + 1>(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, LF_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const u64 v = tv[e & (N - 1)];
-        acc[acc_slot(nn)] = 0.0;
-        acc[N + acc_slot(nn)] = (double)((i64)((e & N) ? (u64)0 - v : v) >> PRE);     // test polynomials are multiples of 2^(59 or so)
+        t64::load_test_poly<N, PRE>(acc, acc_slot, tv, bt, tid);
     }
     __syncthreads();
     const int mj = tid >> 9, mo = (tid >> 8) & 1, mq = tid & 255;   // phase B: limb, output polynomial, slot
@@ -392,16 +368,8 @@ __global__ void __launch_bounds__(LF_THREADS)
             });
             static_for<0, 8>([&](auto J) {
                 const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                const double dd = mod_ab(((t >> 9) & 1) ? -vr[J] - vs[J] : vr[J] - vs[J]);   // the centred lift of the u64 difference, / 2^PRE
-                double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
-                double d = r;                                                          // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                for (int s = L - 1; s > 0; s--) {
-                    const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                    if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                    r = rn;
-                }
-                x[J] = lev == 0 ? r : d;
+                const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J] - vs[J] : vr[J] - vs[J]);   // the centred lift of the u64 difference, / 2^PRE
+                x[J] = t64::digit<L, BG, AB>(dd, lev);
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
@@ -442,56 +410,28 @@ __global__ void __launch_bounds__(LF_THREADS)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
             double *ao = acc + o * N + h * LF_HALF + lane;
-            auto place = [&](double v) {   // the limb's exact integer (|.| < 2^45: nearest integer of the transform's output), shifted into place
-                double xr = __builtin_rint(v);
-                if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(v - xr));
-                if (j == 0) return xr;
-                constexpr double W = (double)(1ull << (AB - LB));   // x 2^LB mod 2^AB: only the low AB - LB bits survive the shift
-                xr = __builtin_fma(-W, __builtin_rint(xr * (1.0 / W)), xr);
-                return xr * (double)(1ull << LB);
-            };
             static_for<0, 4>([&](auto R) {
-                atomicAdd(ao + 64 * R, place(re[R]));          // coefficient 2 (lane + 64 R) + h
-                atomicAdd(ao + 64 * R + 256, place(im[R]));    // ... + 512
+                atomicAdd(ao + 64 * R, t64::place_limb<AB, LB, STATS>(re[R], j, dev));          // coefficient 2 (lane + 64 R) + h
+                atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB, STATS>(im[R], j, dev));    // ... + 512
             });
         }
         __syncthreads();
         if (++since_centred == LF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            acc[tid] = mod_ab(acc[tid]);
-            acc[N + tid] = mod_ab(acc[N + tid]);
+            acc[tid] = mod_ab<AB>(acc[tid]);
+            acc[N + tid] = mod_ab<AB>(acc[N + tid]);
             __syncthreads();
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-        if (nn == 0) {
-            o[0] = a0;
-            o[N] = f64_to_word(mod_ab(acc[N + acc_slot(0)])) << PRE;
-        } else {
-            o[N - nn] = (u64)0 - a0;
-        }
-    }
+    t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
 
 }  // namespace
 
-#ifdef BMI_PHASE_PROF
-extern "C" int bmi_debug_phase_prof_t64f(unsigned long long *out64) {
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phase_f), sizeof(unsigned long long) * 128);
-}
-#endif
+PH_EXPORT(bmi_debug_phase_prof_t64f, g_phase_f)
 
 namespace bmit {
-
-#define BMITF_LAUNCH_CHECK()                    \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
 
 // (precision, levels, base log) combinations the transform's error bound was established for
 bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log) {
@@ -502,20 +442,7 @@ int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_
     if (prec != 48) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_fft_t64, dim3((items + 3) / 4), dim3(256), 0, s, std_polys, limb_polys, g_tw_fft, n_polys, prec);
-    BMITF_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int L, int BG, bool STATS>
-static int launch_t64f(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                       const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, unsigned long long *stat, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)TF_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_t64f<L, BG, STATS>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3((count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS), lds, s, small_cts, lut_ids, luts, bsk_fft,
-                       g_tw_fft, out, count, n, stat);
-    BMITF_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -523,19 +450,7 @@ int launch_bsk_to_latf(const u64 *std_polys, double *lat_polys, const double *g_
     if (prec != 48 && prec != 42) return (int)hipErrorInvalidValue;   // (42: the unrolled key of bmi_kernels_t64fu.hip)
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_latf_t64, dim3((items + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys, prec);
-    BMITF_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int L, int BG, bool STATS>
-static int launch_lat_t64f(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                           const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, unsigned long long *stat, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)LF_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_lat_t64f<L, BG, STATS>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(LF_THREADS), lds, s, small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
-    BMITF_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -544,12 +459,10 @@ int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, c
                                 uint32_t base_log, unsigned long long *stat, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (stat) {
-        if (levels == 3) return launch_lat_t64f<3, 10, true>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat, s);
-        return launch_lat_t64f<2, 10, true>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat, s);
-    }
-    if (levels == 3) return launch_lat_t64f<3, 10, false>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, nullptr, s);
-    return launch_lat_t64f<2, 10, false>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, nullptr, s);
+    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
+        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS>>(dim3(count), dim3(LF_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
+                                                                       small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
+    });
 }
 
 int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
@@ -557,12 +470,11 @@ int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const
                             uint32_t base_log, unsigned long long *stat, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (stat) {
-        if (levels == 3) return launch_t64f<3, 10, true>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat, s);
-        return launch_t64f<2, 10, true>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat, s);
-    }
-    if (levels == 3) return launch_t64f<3, 10, false>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, nullptr, s);
-    return launch_t64f<2, 10, false>(small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, nullptr, s);
+    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
+        return launch_with_lds<k_blind_rotate_t64f<L, 10, STATS>>(dim3((count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS),
+                                                                   (size_t)TF_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_fft,
+                                                                   g_tw_fft, out, count, n, stat);
+    });
 }
 
 }  // namespace bmit

@@ -27,8 +27,6 @@
 //      coefficient; the accumulator is re-centred mod 2^42 every eight steps
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "bmi_internal.hpp"
 #include "fft_half_f64.hpp"
 #include "pair_sync.hpp"
@@ -40,7 +38,7 @@ using t64::u64;
 namespace {
 
 using fftw::static_for;
-using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 
 constexpr int N = ffth::N;
@@ -54,7 +52,7 @@ constexpr int UF_ZP_WORDS = 2 * N;   // zeta^x for x in [0, 1024) as (re, im); z
 constexpr int UF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * UF_MAX_L * N + 2 * 2 * N + BMI_AT_WORDS + UF_ZP_WORDS;
 static_assert(UF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "UF_LDS_WORDS exceeds the 160 KB of LDS");
 
-__device__ __forceinline__ uint32_t acc_slot(uint32_t n) { return (n & 1) * UF_HALF + (n >> 1); }
+constexpr t64::ResidueSlot<N, 1> acc_slot{};   // accumulator words are kept split by parity
 
 template <int L, int BG, int PREC, bool STATS>
 __global__ void __launch_bounds__(UF_THREADS)
@@ -67,9 +65,6 @@ __global__ void __launch_bounds__(UF_THREADS)
     static_assert(LIMBS == 2 && L <= UF_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *acc = lds + ffth::HT_WORDS;                                     // [2 components][2 parities][512]: word / 2^PRE, exact, |.| < 2^51
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53 (ties to the negative end, like the u64 word)
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     double2 *tiles = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + 2 * N);   // [2L rows][2 halves][256 slots] complex
     double2 *SD = tiles + UF_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
     uint16_t *at = reinterpret_cast<uint16_t *>(SD + 2 * N);
@@ -82,16 +77,12 @@ __global__ void __launch_bounds__(UF_THREADS)
     }
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += UF_THREADS) at[i] = (uint16_t)t64::modswitch<LOG_N + 1>(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, UF_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const u64 v = tv[e & (N - 1)];
-        acc[acc_slot(nn)] = 0.0;
-        acc[N + acc_slot(nn)] = (double)((i64)((e & N) ? (u64)0 - v : v) >> PRE);     // test polynomials are multiples of 2^PRE (host-checked)
+        t64::load_test_poly<N, PRE>(acc, acc_slot, tv, bt, tid);
     }
     __syncthreads();
     const int mj = tid >> 9, mo = (tid >> 8) & 1, mq = tid & 255;   // phase B: limb, output polynomial, slot
@@ -126,16 +117,8 @@ __global__ void __launch_bounds__(UF_THREADS)
             const double *ac = acc + c * N + h * UF_HALF;
             double x[8];   // re[r] = x[r], im[r] = x[r + 4]
             static_for<0, 8>([&](auto J) {
-                const double dd = mod_ab(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);    // coefficient 2 (lane + 64 (J & 3)) + h + 512 (J >> 2)
-                double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
-                double d = r;                                                          // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                for (int s = L - 1; s > 0; s--) {
-                    const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                    if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                    r = rn;
-                }
-                x[J] = lev == 0 ? r : d;
+                const double dd = mod_ab<AB>(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);    // coefficient 2 (lane + 64 (J & 3)) + h + 512 (J >> 2)
+                x[J] = t64::digit<L, BG, AB>(dd, lev);
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
@@ -193,39 +176,21 @@ __global__ void __launch_bounds__(UF_THREADS)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
             double *ao = acc + o * N + h * UF_HALF + lane;
-            auto place = [&](double v) {   // the limb's exact integer (|.| < 2^45: nearest integer of the transform's output), shifted into place
-                double xr = __builtin_rint(v);
-                if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(v - xr));
-                if (j == 0) return xr;
-                constexpr double W = (double)(1ull << (AB - LB));   // x 2^LB mod 2^AB: only the low AB - LB bits survive the shift
-                xr = __builtin_fma(-W, __builtin_rint(xr * (1.0 / W)), xr);
-                return xr * (double)(1ull << LB);
-            };
             static_for<0, 4>([&](auto R) {
-                atomicAdd(ao + 64 * R, place(re[R]));          // coefficient 2 (lane + 64 R) + h
-                atomicAdd(ao + 64 * R + 256, place(im[R]));    // ... + 512
+                atomicAdd(ao + 64 * R, t64::place_limb<AB, LB, STATS>(re[R], j, dev));          // coefficient 2 (lane + 64 R) + h
+                atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB, STATS>(im[R], j, dev));    // ... + 512
             });
         }
         __syncthreads();
         if (++since_centred == UF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            acc[tid] = mod_ab(acc[tid]);
-            acc[N + tid] = mod_ab(acc[N + tid]);
+            acc[tid] = mod_ab<AB>(acc[tid]);
+            acc[N + tid] = mod_ab<AB>(acc[N + tid]);
             __syncthreads();
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-        if (nn == 0) {
-            o[0] = a0;
-            o[N] = f64_to_word(mod_ab(acc[N + acc_slot(0)])) << PRE;
-        } else {
-            o[N - nn] = (u64)0 - a0;
-        }
-    }
+    t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
 
 
@@ -259,9 +224,6 @@ __global__ void __launch_bounds__(UF_THREADS)
     double *acc_all = lds + ffth::HT_WORDS + U2_ZQ_WORDS;                 // [2 ciphertexts][2 components][2 parities][512]
     double2 *tiles_all = reinterpret_cast<double2 *>(acc_all + 2 * 2 * N);   // [2 ciphertexts][TILE_CPLX]; the sums overlay them
     uint16_t *at_all = reinterpret_cast<uint16_t *>(tiles_all + 2 * TILE_CPLX);   // [2][BMI_AT_WORDS * 4]
-    auto mod_ab = [](double t) {
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i < ffth::HT_WORDS; i += UF_THREADS) lds[i] = g_tw_h[i];
     for (int i = tid; i < U2_ZQ_WORDS; i += UF_THREADS) lds[ffth::HT_WORDS + i] = g_zeta_pow[i];   // the first 512 powers
@@ -270,18 +232,13 @@ __global__ void __launch_bounds__(UF_THREADS)
     static_for<0, 2>([&](auto Z) {
         const u64 *lwe = small_cts + (size_t)cts[Z] * (n + 1);
         uint16_t *at = at_all + Z * BMI_AT_WORDS * 4;
-        for (uint32_t i = tid; i <= n; i += UF_THREADS) at[i] = (uint16_t)t64::modswitch<LOG_N + 1>(lwe[i]);
+        t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, UF_THREADS);
     });
     __syncthreads();
     static_for<0, 2>([&](auto Z) {
         const u64 *tv = luts + (size_t)(lut_ids[cts[Z]] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at_all[Z * BMI_AT_WORDS * 4 + n];
-        const uint32_t nn = tid;
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const u64 v = tv[e & (N - 1)];
-        double *acc = acc_all + Z * 2 * N;
-        acc[acc_slot(nn)] = 0.0;
-        acc[N + acc_slot(nn)] = (double)((i64)((e & N) ? (u64)0 - v : v) >> PRE);
+        t64::load_test_poly<N, PRE>(acc_all + Z * 2 * N, acc_slot, tv, bt, tid);
     });
     __syncthreads();
     const int mj = tid >> 9, mo = (tid >> 8) & 1, mq = tid & 255;
@@ -326,16 +283,8 @@ __global__ void __launch_bounds__(UF_THREADS)
             const double *ac = acc_all + z * 2 * N + c * N + h * UF_HALF;
             double x[8];
             static_for<0, 8>([&](auto J) {
-                const double dd = mod_ab(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);
-                double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));
-                double d = r;
-#pragma unroll
-                for (int s = L - 1; s > 0; s--) {
-                    const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                    if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                    r = rn;
-                }
-                x[J] = lev == 0 ? r : d;
+                const double dd = mod_ab<AB>(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);
+                x[J] = t64::digit<L, BG, AB>(dd, lev);
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
@@ -407,37 +356,21 @@ __global__ void __launch_bounds__(UF_THREADS)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
             double *ao = acc_all + z * 2 * N + o * N + h * UF_HALF + lane;
-            auto place = [&](double v) {
-                double xr = __builtin_rint(v);
-                if (j == 0) return xr;
-                constexpr double W = (double)(1ull << (AB - LB));
-                xr = __builtin_fma(-W, __builtin_rint(xr * (1.0 / W)), xr);
-                return xr * (double)(1ull << LB);
-            };
             static_for<0, 4>([&](auto R) {
-                atomicAdd(ao + 64 * R, place(re[R]));
-                atomicAdd(ao + 64 * R + 256, place(im[R]));
+                atomicAdd(ao + 64 * R, t64::place_limb<AB, LB>(re[R], j));
+                atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB>(im[R], j));
             });
         }
         __syncthreads();
         if (++since_centred == UF_RECENTRE) {
             since_centred = 0;
-            static_for<0, 4>([&](auto Q) { acc_all[tid + UF_THREADS * Q] = mod_ab(acc_all[tid + UF_THREADS * Q]); });
+            static_for<0, 4>([&](auto Q) { acc_all[tid + UF_THREADS * Q] = mod_ab<AB>(acc_all[tid + UF_THREADS * Q]); });
             __syncthreads();
         }
     }
     static_for<0, 2>([&](auto Z) {
         if (Z == 1 && cts[1] == cts[0]) return;   // the padding copy of an odd batch
-        const double *acc = acc_all + Z * 2 * N;
-        u64 *o = out + (size_t)cts[Z] * (N + 1);
-        const uint32_t nn = tid;
-        const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-        if (nn == 0) {
-            o[0] = a0;
-            o[N] = f64_to_word(mod_ab(acc[N + acc_slot(0)])) << PRE;
-        } else {
-            o[N - nn] = (u64)0 - a0;
-        }
+        t64::extract_sample<N, PRE, AB>(out + (size_t)cts[Z] * (N + 1), acc_all + Z * 2 * N, acc_slot, tid);
     });
 }
 
@@ -450,38 +383,16 @@ bool shape_supported_unrolled_fft(int prec, uint32_t levels, uint32_t base_log) 
     return prec == 42 && base_log == 10 && (levels == 3 || levels == 2);
 }
 
-template <int L, int BG, int PREC, bool STATS>
-static int launch_lat2u_t64f(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf, const double *g_tw_h,
-                             const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, unsigned long long *stat, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)UF_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_lat2u_t64f<L, BG, PREC, STATS>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(UF_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-template <int L, int BG, int PREC>
-static int launch_tp2u_t64f(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf, const double *g_tw_h,
-                            const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)U2_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_tp2u_t64f<L, BG, PREC>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3((count + 1) / 2), dim3(UF_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 // two ciphertexts per workgroup (key words shared in registers): the throughput form, same words as launch_blind_rotate_lat2u_fft
 int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
                                  uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (levels == 3) return launch_tp2u_t64f<3, 10, 42>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, s);
-    return launch_tp2u_t64f<2, 10, 42>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, s);
+    return with_levels(levels, [&](auto L) {
+        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42>>(dim3((count + 1) / 2), dim3(UF_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
+                                                                     small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
+    });
 }
 
 int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
@@ -489,12 +400,10 @@ int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids,
                                   uint32_t levels, uint32_t base_log, unsigned long long *stat, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (stat) {
-        if (levels == 3) return launch_lat2u_t64f<3, 10, 42, true>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat, s);
-        return launch_lat2u_t64f<2, 10, 42, true>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat, s);
-    }
-    if (levels == 3) return launch_lat2u_t64f<3, 10, 42, false>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, nullptr, s);
-    return launch_lat2u_t64f<2, 10, 42, false>(small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, nullptr, s);
+    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
+        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS>>(dim3(count), dim3(UF_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
+                                                                             small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
+    });
 }
 
 }  // namespace bmit

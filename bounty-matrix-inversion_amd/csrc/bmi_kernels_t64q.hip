@@ -18,8 +18,6 @@
 //   inverse eighth, nearest integer, shift into place, plain read-modify-write of the accumulator (the limbs take turns).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "bmi_internal.hpp"
 #include "fft_eighth_f64.hpp"
 #include "pair_sync.hpp"
@@ -32,7 +30,7 @@ namespace {
 
 using ffte::C;
 using ffte::static_for;
-using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 
 constexpr int QN = 4096, QLOG = 12;
@@ -46,7 +44,7 @@ constexpr int QF_TILE_CPLX = 2 * 8 * QS;         // complex words of one level's
 constexpr int QF_LDS_WORDS = ffte::ET_WORDS + 2 * QN + 2 * QF_TILE_CPLX + BMI_AT_WORDS;
 static_assert(QF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "QF_LDS_WORDS exceeds the 160 KB of LDS");
 
-__device__ __forceinline__ uint32_t acc_slot(uint32_t n) { return (n & 7) * QF_RES + (n >> 3); }
+constexpr t64::ResidueSlot<QN, 3> acc_slot{};   // accumulator words are kept split by residue mod 8
 
 // an empty statement that reads and writes the eight sums: they must be in registers here
 __device__ __forceinline__ void keep(fftw::C (&y)[8]) {
@@ -103,9 +101,6 @@ __global__ void __launch_bounds__(QF_THREADS)
     static_assert(LIMBS == 2 && L <= QF_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *acc = lds + ffte::ET_WORDS;                                     // [2 components][8 residues][512]: word / 2^PRE, exact, |.| < 2^51
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53 (ties to the negative end, like the u64 word)
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     double2 *tiles = reinterpret_cast<double2 *>(acc + 2 * QN);             // [2 components][8 eighths][256 slots] of the current level
     double2 *SD = tiles;                                                    // one limb's sums [2 outputs][8 eighths][256 slots]
     uint16_t *at = reinterpret_cast<uint16_t *>(tiles + QF_TILE_CPLX);
@@ -113,18 +108,12 @@ __global__ void __launch_bounds__(QF_THREADS)
     for (int i = tid; i < ffte::ET_WORDS; i += QF_THREADS) lds[i] = g_tw[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += QF_THREADS) at[i] = (uint16_t)t64::modswitch<QLOG + 1>(lwe[i]);
+    t64::stage_lwe<QLOG + 1>(at, lwe, n, tid, QF_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * QN;
         const uint32_t bt = at[n];
-        static_for<0, 4>([&](auto Q) {
-            const uint32_t nn = tid + QF_THREADS * Q;  // coefficient index
-            const uint32_t e = (nn + bt) & (2 * QN - 1);
-            const u64 v = tv[e & (QN - 1)];
-            acc[acc_slot(nn)] = 0.0;
-            acc[QN + acc_slot(nn)] = (double)((i64)((e & QN) ? (u64)0 - v : v) >> PRE);     // test polynomials are multiples of 2^PRE (host-checked)
-        });
+        static_for<0, 4>([&](auto Q) { t64::load_test_poly<QN, PRE>(acc, acc_slot, tv, bt, tid + QF_THREADS * Q); });
     }
     __syncthreads();
     // phase B: slot, output polynomial, limb (the four combinations of a slot sit 16 lanes apart: their tile reads coincide)
@@ -161,16 +150,8 @@ __global__ void __launch_bounds__(QF_THREADS)
                     static_for<0, 4>([&](auto J4) {
                         constexpr int J = G * 4 + J4;
                         const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                        const double dd = mod_ab(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
-                        double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
-                        double d = r;                                                          // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                        for (int s = L - 1; s > 0; s--) {
-                            const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                            if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                            r = rn;
-                        }
-                        x[J] = lev == 0 ? r : d;
+                        const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
+                        x[J] = t64::digit<L, BG, AB>(dd, lev);
                     });
                     pin();
                 });
@@ -226,54 +207,28 @@ __global__ void __launch_bounds__(QF_THREADS)
                 double re[4], im[4];
                 ffte::inverse_eighth(h, v, re, im, lane, lds);
                 double *ao = acc + o * QN + h * QF_RES + lane;
-                // the limb's exact integer (|.| < 2^45: nearest integer of the transform's output), shifted into place: limb 1 x 2^LB mod
-                // 2^AB, of which only the low AB - LB bits survive
                 constexpr int j = J;
-                auto place = [&](double v0) {
-                    double xr = __builtin_rint(v0);
-                    if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(v0 - xr));
-                    if constexpr (j > 0) {
-                        constexpr double W = (double)(1ull << (AB - LB));
-                        xr = __builtin_fma(-W, __builtin_rint(xr * (1.0 / W)), xr) * (double)(1ull << LB);
-                    }
-                    return xr;
-                };
                 static_for<0, 4>([&](auto R) {
-                    ao[64 * R] += place(re[R]);              // coefficient 8 (lane + 64 R) + h
-                    ao[64 * R + 256] += place(im[R]);        // ... + 2048
+                    ao[64 * R] += t64::place_limb<AB, LB, STATS>(re[R], j, dev);              // coefficient 8 (lane + 64 R) + h
+                    ao[64 * R + 256] += t64::place_limb<AB, LB, STATS>(im[R], j, dev);        // ... + 2048
                 });
             }
             __syncthreads();
         });
         if (++since_centred == QF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            static_for<0, 8>([&](auto Q) { acc[tid + QF_THREADS * Q] = mod_ab(acc[tid + QF_THREADS * Q]); });
+            static_for<0, 8>([&](auto Q) { acc[tid + QF_THREADS * Q] = mod_ab<AB>(acc[tid + QF_THREADS * Q]); });
             __syncthreads();
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
     u64 *o = out + (size_t)ct * (QN + 1);
-    static_for<0, 4>([&](auto Q) {
-        const uint32_t nn = tid + QF_THREADS * Q;
-        const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-        if (nn == 0) {
-            o[0] = a0;
-            o[QN] = f64_to_word(mod_ab(acc[QN + acc_slot(0)])) << PRE;
-        } else {
-            o[QN - nn] = (u64)0 - a0;
-        }
-    });
+    static_for<0, 4>([&](auto Q) { t64::extract_sample<QN, PRE, AB>(o, acc, acc_slot, tid + QF_THREADS * Q); });
 }
 
 }  // namespace
 
 namespace bmit {
-
-#define BMITQ_LAUNCH_CHECK()                    \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
 
 // (precision, levels, base log) combinations the N = 4096 transform's error bound was established for
 bool shape_supported_quad(int prec, uint32_t levels, uint32_t base_log) {
@@ -284,19 +239,7 @@ int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw
     if (prec != 44) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_q_t64, dim3(items), dim3(512), 0, s, std_polys, q_polys, g_tw_e, n_polys, prec);
-    BMITQ_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int L, int BG, int PREC, bool STATS>
-static int launch_q(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e, u64 *out,
-                    uint32_t count, uint32_t n, unsigned long long *stat, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)QF_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_q_t64f<L, BG, PREC, STATS>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(QF_THREADS), lds, s, small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat);
-    BMITQ_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -305,12 +248,10 @@ int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, cons
                              hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_quad(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (stat) {
-        if (levels == 3) return launch_q<3, 10, 44, true>(small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat, s);
-        return launch_q<2, 10, 44, true>(small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat, s);
-    }
-    if (levels == 3) return launch_q<3, 10, 44, false>(small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, nullptr, s);
-    return launch_q<2, 10, 44, false>(small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, nullptr, s);
+    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
+        return launch_with_lds<k_blind_rotate_q_t64f<L, 10, 44, STATS>>(dim3(count), dim3(QF_THREADS), (size_t)QF_LDS_WORDS * sizeof(double), s,
+                                                                         small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat);
+    });
 }
 
 }  // namespace bmit

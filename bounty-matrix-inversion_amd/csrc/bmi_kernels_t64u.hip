@@ -20,11 +20,10 @@
 // < 3 * 2 * 2 L N 2^(BG-1) 2^(BITS-1) = 2^47.2 at (L, BG, BITS) = (3, 10, 24) < p/2: its centred residue IS the integer.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "bmi_internal.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
+#include "phase_prof.hpp"
 #include "t64_common.hpp"
 
 using f49::i64;
@@ -35,21 +34,10 @@ using t64::Scheme;
 
 namespace {
 
-#ifdef BMI_PHASE_PROF
-__device__ unsigned long long g_phase_tu[128];
-#define PH_DECL() unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64()
-#define PH_MARK(k)                               \
-    do {                                         \
-        const unsigned long long t_ = clock64(); \
-        ph_[k] += t_ - tl_;                      \
-        tl_ = t_;                                \
-    } while (0)
-#else
-#define PH_DECL()
-#define PH_MARK(k)
-#endif
+PH_ARRAY(g_phase_tu)   // make -C csrc prof
 
 constexpr int LU_THREADS = 1024;
+constexpr t64::ResidueSlot<N, 1> acc_slot{};   // accumulator words (u64) are kept split by parity
 // twiddles, accumulator (u64), twelve tiles, sums / differences per limb, mod-switched ciphertext, root powers
 template <int LIMBS>
 constexpr int lu_lds_words() { return ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + LIMBS * 2 * N + BMI_AT_WORDS + 2 * N; }
@@ -75,16 +63,12 @@ __global__ void __launch_bounds__(LU_THREADS)
     for (int i = tid; i < 2 * N; i += LU_THREADS) RP[i ^ ((i >> 5) & 31)] = g_root_pow[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += LU_THREADS) at[i] = (uint16_t)t64::modswitch<LOG_N + 1>(lwe[i]);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, LU_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const u64 v = tv[e & (N - 1)];
-        acc[(nn & 1) * ntth::HALF + (nn >> 1)] = 0;
-        acc[N + (nn & 1) * ntth::HALF + (nn >> 1)] = (e & N) ? (u64)0 - v : v;
+        t64::load_test_poly<N, PRE>(acc, acc_slot, tv, bt, tid);
     }
     __syncthreads();
     const int mo = tid >> 9, mp = tid & 511;  // phase B: output polynomial, slot
@@ -117,15 +101,7 @@ __global__ void __launch_bounds__(LU_THREADS)
             double x[8];
             __builtin_amdgcn_s_setprio(3);
             static_for<0, 8>([&](auto J) {
-                double r = t64::rounded_top<L, BG>(ac[lane + 64 * J]);   // round half up to L BG bits
-                double d = r;                                           // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                for (int s = L - 1; s > 0; s--) {
-                    const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                    if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                    r = rn;
-                }
-                x[J] = lev == 0 ? r : d;
+                x[J] = t64::peel_digit<L, BG>(t64::rounded_top<L, BG>(ac[lane + 64 * J]), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
             if (h) ntth::forward_half<true>(x, lane, lds, tile);
@@ -211,30 +187,13 @@ __global__ void __launch_bounds__(LU_THREADS)
         __syncthreads();
         PH_MARK(5);
     }
-#ifdef BMI_PHASE_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase_tu[wave * 8 + k_] = ph_[k_];
-#endif
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const u64 a0 = acc[(nn & 1) * ntth::HALF + (nn >> 1)];
-        if (nn == 0) {
-            o[0] = a0;
-            o[N] = acc[N];
-        } else {
-            o[N - nn] = (u64)0 - a0;
-        }
-    }
+    PH_STORE(g_phase_tu, wave, lane);
+    t64::extract_sample<N, PRE, 64 - PRE>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
 
 }  // namespace
 
-#ifdef BMI_PHASE_PROF
-extern "C" int bmi_debug_phase_prof_unrolled_t64(unsigned long long *out64) {
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phase_tu), sizeof(unsigned long long) * 128);
-}
-#endif
+PH_EXPORT(bmi_debug_phase_prof_unrolled_t64, g_phase_tu)
 
 namespace bmit {
 
@@ -247,26 +206,15 @@ bool shape_supported_unrolled(int prec, uint32_t levels, uint32_t base_log) {
     return false;
 }
 
-template <int PREC, int L, int BG>
-static int launch_lat2u_t64(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_lat,
-                            const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)lu_lds_words<Scheme<PREC>::LIMBS>() * sizeof(double);
-    auto kern = k_blind_rotate_lat2u_t64<L, BG, PREC>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(LU_THREADS), lds, s, small_cts, lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out,
-                       count, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_lat,
                               const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, int prec,
                               uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B)  \
-        return launch_lat2u_t64<P, L, B>(small_cts, lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n, s);
+    if (prec == P && levels == L && base_log == B)                                                                                            \
+        return launch_with_lds<k_blind_rotate_lat2u_t64<L, B, P>>(dim3(count), dim3(LU_THREADS),                                               \
+                                                                   (size_t)lu_lds_words<Scheme<P>::LIMBS>() * sizeof(double), s, small_cts,    \
+                                                                   lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
     BMIT_FOR_EACH_SHAPE_U(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;

@@ -26,6 +26,7 @@
 #include "bmi_internal.hpp"
 #include "fft_quarter_f64.hpp"
 #include "pair_sync.hpp"
+#include "phase_prof.hpp"
 #include "t64_common.hpp"
 
 using t64::i64;
@@ -35,25 +36,13 @@ namespace {
 
 using fftq::C;
 using fftq::static_for;
-using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 
 #ifndef BMI_T64W_KEY_ROWS_AHEAD
 #define BMI_T64W_KEY_ROWS_AHEAD 2   // key rows (of 2 l) a thread holds in registers: requested before phase A, then row r + this many when row r is done
 #endif
-#ifdef BMI_PHASE_PROF   // make -C csrc prof; tools/phase_prof_t64w.py
-__device__ unsigned long long g_phase_w[128];
-#define PH_DECL() unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64()
-#define PH_MARK(k)                               \
-    do {                                         \
-        const unsigned long long t_ = clock64(); \
-        ph_[k] += t_ - tl_;                      \
-        tl_ = t_;                                \
-    } while (0)
-#else
-#define PH_DECL()
-#define PH_MARK(k)
-#endif
+PH_ARRAY(g_phase_w)   // make -C csrc prof; tools/phase_prof_t64w.py
 constexpr int WN = 2048, WLOG = 11;
 constexpr int WQ = fftq::QUARTER;
 constexpr int WF_THREADS = 1024;
@@ -67,7 +56,7 @@ static_assert(WF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "WF_LDS_WORDS exceeds the 160 K
 static_assert(2 * 2 * 4 * WQ <= WF_TILE_CPLX, "the sums S of both limbs and outputs fit over the tiles");
 
 // accumulator words are kept split by residue mod 4 (a lane's points of a quarter are 256 coefficients apart and of one residue)
-__device__ __forceinline__ uint32_t acc_slot(uint32_t n) { return (n & 3) * WF_RES + (n >> 2); }
+constexpr t64::ResidueSlot<WN, 2> acc_slot{};
 
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per (polynomial, limb) 1,024
 // complex words A_k / 2 in the order the multiplying threads read them: thread (w8 = slot / 32, lane) of phase B owns slot
@@ -124,9 +113,6 @@ __global__ void __launch_bounds__(WF_THREADS)
     constexpr int KD = BMI_T64W_KEY_ROWS_AHEAD < 2 * L ? BMI_T64W_KEY_ROWS_AHEAD : 2 * L;
     extern __shared__ double lds[];
     double *acc = lds + fftq::QT_WORDS;                                     // [2 components][4 residues][512]: word / 2^PRE, exact, |.| < 2^51
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53 (ties to the negative end, like the u64 word)
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     double2 *tiles = reinterpret_cast<double2 *>(acc + 2 * WN);             // [2L rows][4 quarters][256 slots] complex
     double2 *SD = tiles;                                                    // [limb][output][4 quarters][256 slots], once the tiles are read
     uint16_t *at = reinterpret_cast<uint16_t *>(tiles + WF_TILE_CPLX);
@@ -134,18 +120,12 @@ __global__ void __launch_bounds__(WF_THREADS)
     for (int i = tid; i < fftq::QT_WORDS; i += WF_THREADS) lds[i] = g_tw[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    for (uint32_t i = tid; i <= n; i += WF_THREADS) at[i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
+    t64::stage_lwe<WLOG + 1>(at, lwe, n, tid, WF_THREADS);
     __syncthreads();
     {
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * WN;
         const uint32_t bt = at[n];
-        static_for<0, 2>([&](auto Q) {
-            const uint32_t nn = tid + WF_THREADS * Q;  // coefficient index
-            const uint32_t e = (nn + bt) & (2 * WN - 1);
-            const u64 v = tv[e & (WN - 1)];
-            acc[acc_slot(nn)] = 0.0;
-            acc[WN + acc_slot(nn)] = (double)((i64)((e & WN) ? (u64)0 - v : v) >> PRE);     // test polynomials are multiples of 2^PRE (host-checked)
-        });
+        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + WF_THREADS * Q); });
     }
     __syncthreads();
     // phase B: output polynomial, slot, and which half of the radix-4 butterfly this lane starts from
@@ -201,16 +181,8 @@ __global__ void __launch_bounds__(WF_THREADS)
                 static_for<0, 4>([&](auto J4) {
                     constexpr int J = G * 4 + J4;
                     const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                    const double dd = mod_ab(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
-                    double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
-                    double d = r;                                                          // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                    for (int s = L - 1; s > 0; s--) {
-                        const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                        if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                        r = rn;
-                    }
-                    x[J] = lev == 0 ? r : d;
+                    const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
+                    x[J] = t64::digit<L, BG, AB>(dd, lev);
                 });
                 pin();
             });
@@ -297,64 +269,32 @@ __global__ void __launch_bounds__(WF_THREADS)
                 fftq::inverse_quarter(v, re[J], im[J], lane, lds);
             });
             double *ao = acc + o * WN + h * WF_RES + lane;
-            // a limb's exact integer (|.| < 2^45: nearest integer of the transform's output); limb 1 shifted into place: x 2^LB mod 2^AB,
-            // of which only the low AB - LB bits survive
-            auto place = [&](double v0, double v1) {
-                const double x0 = __builtin_rint(v0);
-                double x1 = __builtin_rint(v1);
-                if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fmax(__builtin_fabs(v0 - x0), __builtin_fabs(v1 - x1)));
-                constexpr double W = (double)(1ull << (AB - LB));
-                x1 = __builtin_fma(-W, __builtin_rint(x1 * (1.0 / W)), x1);
-                return __builtin_fma(x1, (double)(1ull << LB), x0);
-            };
             static_for<0, 4>([&](auto R) {
-                ao[64 * R] += place(re[0][R], re[1][R]);              // coefficient 4 (lane + 64 R) + h
-                ao[64 * R + 256] += place(im[0][R], im[1][R]);        // ... + 1024
+                ao[64 * R] += t64::place_limbs<AB, LB, STATS>(re[0][R], re[1][R], dev);              // coefficient 4 (lane + 64 R) + h
+                ao[64 * R + 256] += t64::place_limbs<AB, LB, STATS>(im[0][R], im[1][R], dev);        // ... + 1024
             });
         }
         PH_MARK(6);   // inverse quarters of both limbs, rounding, accumulation
         __syncthreads();
         if (++since_centred == WF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            static_for<0, 4>([&](auto Q) { acc[tid + WF_THREADS * Q] = mod_ab(acc[tid + WF_THREADS * Q]); });
+            static_for<0, 4>([&](auto Q) { acc[tid + WF_THREADS * Q] = mod_ab<AB>(acc[tid + WF_THREADS * Q]); });
             __syncthreads();
         }
         PH_MARK(7);   // closing barrier (+ re-centring every eighth step)
         i = i_next;
     }
-#ifdef BMI_PHASE_PROF
-    if (blockIdx.x == 0 && lane == 0)
-        for (int k_ = 0; k_ < 8; k_++) g_phase_w[wave * 8 + k_] = ph_[k_];
-#endif
+    PH_STORE(g_phase_w, wave, lane);
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
     u64 *o = out + (size_t)ct * (WN + 1);
-    static_for<0, 2>([&](auto Q) {
-        const uint32_t nn = tid + WF_THREADS * Q;
-        const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-        if (nn == 0) {
-            o[0] = a0;
-            o[WN] = f64_to_word(mod_ab(acc[WN + acc_slot(0)])) << PRE;
-        } else {
-            o[WN - nn] = (u64)0 - a0;
-        }
-    });
+    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + WF_THREADS * Q); });
 }
 
 }  // namespace
 
-#ifdef BMI_PHASE_PROF
-extern "C" int bmi_debug_phase_prof_t64w(unsigned long long *out128) {
-    return (int)hipMemcpyFromSymbol(out128, HIP_SYMBOL(g_phase_w), sizeof(unsigned long long) * 128);
-}
-#endif
+PH_EXPORT(bmi_debug_phase_prof_t64w, g_phase_w)
 
 namespace bmit {
-
-#define BMITW_LAUNCH_CHECK()                    \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
 
 // (precision, levels, base log) combinations the N = 2048 transform's error bound was established for
 bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log) {
@@ -365,19 +305,7 @@ int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw
     if (prec != 46) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_w_t64, dim3(items), dim3(256), 0, s, std_polys, w_polys, g_tw_q, n_polys, prec);
-    BMITW_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int L, int BG, int PREC, bool STATS>
-static int launch_w(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q, u64 *out,
-                    uint32_t count, uint32_t n, unsigned long long *stat, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)WF_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_w_t64f<L, BG, PREC, STATS>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3(count), dim3(WF_THREADS), lds, s, small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat);
-    BMITW_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -386,12 +314,10 @@ int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, cons
                              hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (stat) {
-        if (levels == 3) return launch_w<3, 10, 46, true>(small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat, s);
-        return launch_w<2, 10, 46, true>(small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat, s);
-    }
-    if (levels == 3) return launch_w<3, 10, 46, false>(small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, nullptr, s);
-    return launch_w<2, 10, 46, false>(small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, nullptr, s);
+    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
+        return launch_with_lds<k_blind_rotate_w_t64f<L, 10, 46, STATS>>(dim3(count), dim3(WF_THREADS), (size_t)WF_LDS_WORDS * sizeof(double), s,
+                                                                         small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat);
+    });
 }
 
 }  // namespace bmit

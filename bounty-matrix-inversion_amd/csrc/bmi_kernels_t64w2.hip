@@ -29,7 +29,7 @@ namespace {
 
 using fftq::C;
 using fftq::static_for;
-using t64::f64_to_word;
+using t64::mod_ab;
 using t64::Scheme;
 
 constexpr int WN = 2048, WLOG = 11;
@@ -43,7 +43,7 @@ constexpr int W2_TILE_CPLX = 2 * 2 * 4 * WS;     // one level's tiles [ciphertex
 constexpr int W2_LDS_WORDS = fftq::QT_WORDS + 2 * 2 * WN + 2 * W2_TILE_CPLX + 2 * BMI_AT_WORDS;
 static_assert(W2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "W2_LDS_WORDS exceeds the 160 KB of LDS");
 
-__device__ __forceinline__ uint32_t acc_slot(uint32_t n) { return (n & 3) * W2_RES + (n >> 2); }
+constexpr t64::ResidueSlot<WN, 2> acc_slot{};   // accumulator words are kept split by residue mod 4
 
 // an empty statement that reads and writes the sums: they must be in registers here (the branches of the next task would otherwise
 // let the compiler sink the multiply-adds below them: bmi_kernels_t64q.hip)
@@ -115,9 +115,6 @@ __global__ void __launch_bounds__(W2_THREADS)
     static_assert(LIMBS == 2 && L <= W2_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *accs = lds + fftq::QT_WORDS;                                    // [ciphertext][2 components][4 residues][512]: word / 2^PRE, exact
-    auto mod_ab = [](double t) {   // centred residue mod 2^AB of an exact integer |t| < 2^53 (ties to the negative end, like the u64 word)
-        return __builtin_fma(-(double)(1ull << AB), __builtin_floor(__builtin_fma(t, 1.0 / (double)(1ull << AB), 0.5)), t);
-    };
     double2 *tiles = reinterpret_cast<double2 *>(accs + 2 * 2 * WN);        // [ciphertext 2][component 2][quarter 4][256 slots] of the current level
     double2 *SD = tiles;                                                    // one limb's sums [ciphertext 2][output 2][quarter 4][256 slots]
     uint16_t *at = reinterpret_cast<uint16_t *>(tiles + W2_TILE_CPLX);      // [ciphertext 2][BMI_AT_WORDS * 4]
@@ -130,6 +127,7 @@ __global__ void __launch_bounds__(W2_THREADS)
     const uint32_t cts[2] = {ct0, live1 ? ct0 + 1 : ct0};
     for (int b = 0; b < 2; b++) {
         const u64 *lwe = small_cts + (size_t)cts[b] * (n + 1);
+        // (t64::stage_lwe written out: handing it at + b * AT_STRIDE turns the guard of the step loop around in the generated code)
         for (uint32_t i = tid; i <= n; i += W2_THREADS) at[b * AT_STRIDE + i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
     }
     __syncthreads();
@@ -137,13 +135,7 @@ __global__ void __launch_bounds__(W2_THREADS)
         const u64 *tv = luts + (size_t)(lut_ids[cts[b]] & (BMI_LUT_CAP - 1)) * WN;
         const uint32_t bt = at[b * AT_STRIDE + n];
         double *acc = accs + b * 2 * WN;
-        static_for<0, 2>([&](auto Q) {
-            const uint32_t nn = tid + W2_THREADS * Q;  // coefficient index
-            const uint32_t e = (nn + bt) & (2 * WN - 1);
-            const u64 v = tv[e & (WN - 1)];
-            acc[acc_slot(nn)] = 0.0;
-            acc[WN + acc_slot(nn)] = (double)((i64)((e & WN) ? (u64)0 - v : v) >> PRE);     // test polynomials are multiples of 2^PRE (host-checked)
-        });
+        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + W2_THREADS * Q); });
     }
     __syncthreads();
     // phase B: slot, output polynomial, limb (the four combinations of a slot sit 16 lanes apart: their tile reads coincide)
@@ -181,16 +173,8 @@ __global__ void __launch_bounds__(W2_THREADS)
                     static_for<0, 4>([&](auto J4) {
                         constexpr int J = G * 4 + J4;
                         const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                        const double dd = mod_ab(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
-                        double r = __builtin_floor(__builtin_fma(dd, 1.0 / (double)(1ull << (AB - L * BG)), 0.5));   // round half up to L BG bits
-                        double d = r;                                                          // digit `lev`, balanced [-2^(BG-1), 2^(BG-1))
-#pragma unroll
-                        for (int s = L - 1; s > 0; s--) {
-                            const double rn = __builtin_floor(__builtin_fma(r, 1.0 / (double)(1ull << BG), 0.5));
-                            if (s == lev) d = __builtin_fma(-(double)(1ull << BG), rn, r);
-                            r = rn;
-                        }
-                        x[J] = lev == 0 ? r : d;
+                        const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
+                        x[J] = t64::digit<L, BG, AB>(dd, lev);
                     });
                     pin();
                 });
@@ -248,43 +232,24 @@ __global__ void __launch_bounds__(W2_THREADS)
                 double re[4], im[4];
                 fftq::inverse_quarter(v, re, im, lane, lds);
                 double *ao = accs + wb * 2 * WN + wc * WN + wh * W2_RES + lane;
-                // the limb's exact integer (|.| < 2^45: nearest integer of the transform's output), shifted into place: limb 1 x 2^LB mod
-                // 2^AB, of which only the low AB - LB bits survive
                 constexpr int j = J;
-                auto place = [&](double v0) {
-                    double xr = __builtin_rint(v0);
-                    if constexpr (j > 0) {
-                        constexpr double W = (double)(1ull << (AB - LB));
-                        xr = __builtin_fma(-W, __builtin_rint(xr * (1.0 / W)), xr) * (double)(1ull << LB);
-                    }
-                    return xr;
-                };
                 static_for<0, 4>([&](auto R) {
-                    ao[64 * R] += place(re[R]);              // coefficient 4 (lane + 64 R) + h
-                    ao[64 * R + 256] += place(im[R]);        // ... + 1024
+                    ao[64 * R] += t64::place_limb<AB, LB>(re[R], j);              // coefficient 4 (lane + 64 R) + h
+                    ao[64 * R + 256] += t64::place_limb<AB, LB>(im[R], j);        // ... + 1024
                 });
             }
             __syncthreads();
         });
         if (++since_centred == W2_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulators' magnitude below 2^51
             since_centred = 0;
-            static_for<0, 8>([&](auto Q) { accs[tid + W2_THREADS * Q] = mod_ab(accs[tid + W2_THREADS * Q]); });
+            static_for<0, 8>([&](auto Q) { accs[tid + W2_THREADS * Q] = mod_ab<AB>(accs[tid + W2_THREADS * Q]); });
             __syncthreads();
         }
     }
     for (int b = 0; b < (live1 ? 2 : 1); b++) {
         const double *acc = accs + b * 2 * WN;
         u64 *o = out + (size_t)cts[b] * (WN + 1);
-        static_for<0, 2>([&](auto Q) {
-            const uint32_t nn = tid + W2_THREADS * Q;
-            const u64 a0 = f64_to_word(mod_ab(acc[acc_slot(nn)])) << PRE;
-            if (nn == 0) {
-                o[0] = a0;
-                o[WN] = f64_to_word(mod_ab(acc[WN + acc_slot(0)])) << PRE;
-            } else {
-                o[WN - nn] = (u64)0 - a0;
-            }
-        });
+        static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W2_THREADS * Q); });
     }
 }
 
@@ -292,29 +257,11 @@ __global__ void __launch_bounds__(W2_THREADS)
 
 namespace bmit {
 
-#define BMITW2_LAUNCH_CHECK()                   \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s) {
     if (prec != 46) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_w2_t64, dim3(items), dim3(256), 0, s, std_polys, w2_polys, g_tw_q, n_polys, prec);
-    BMITW2_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int L, int BG, int PREC>
-static int launch_w2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q, u64 *out,
-                     uint32_t count, uint32_t n, hipStream_t s) {
-    static std::atomic<uint64_t> configured{0};
-    const size_t lds = (size_t)W2_LDS_WORDS * sizeof(double);
-    auto kern = k_blind_rotate_w2_t64f<L, BG, PREC>;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured)) return rc;
-    hipLaunchKernelGGL(kern, dim3((count + 1) / 2), dim3(W2_THREADS), lds, s, small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
-    BMITW2_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -322,8 +269,10 @@ int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, con
                               u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    if (levels == 3) return launch_w2<3, 10, 46>(small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n, s);
-    return launch_w2<2, 10, 46>(small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n, s);
+    return with_levels(levels, [&](auto L) {
+        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46>>(dim3((count + 1) / 2), dim3(W2_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
+                                                                   small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
+    });
 }
 
 }  // namespace bmit

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmi_internal.hpp"   // BMI_LAUNCH_CHECK
+
 namespace ksl {
 
 typedef uint64_t u64;
@@ -174,12 +176,6 @@ __global__ void __launch_bounds__(256)
 }
 
 
-#define KSL_LAUNCH_CHECK()                      \
-    do {                                        \
-        hipError_t e__ = hipGetLastError();     \
-        if (e__ != hipSuccess) return (int)e__; \
-    } while (0)
-
 template <class F>
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
                      uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
@@ -190,17 +186,17 @@ int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out
         const size_t lds = (size_t)KS_TILE * big_n * levels;
         hipLaunchKernelGGL((k_keyswitch<false, F>), tiles, dim3(KS_THREADS), lds, s, in, ksk, ks_bias, out,
                            (unsigned __int128 *)nullptr, count, n, big_n, levels, base_log, ks_stride, big_n);
-        KSL_LAUNCH_CHECK();
+        BMI_LAUNCH_CHECK();
         return 0;
     }
     const uint32_t per = (big_n + slices - 1) / slices;
     const size_t lds = (size_t)KS_TILE * per * levels;
     hipLaunchKernelGGL((k_keyswitch<true, F>), dim3(tiles.x, slices), dim3(KS_THREADS), lds, s, in, ksk, ks_bias, out,
                        (unsigned __int128 *)partial, count, n, big_n, levels, base_log, ks_stride, per);
-    KSL_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     hipLaunchKernelGGL((k_keyswitch_reduce<F>), dim3(count), dim3(256), 0, s, in, (const unsigned __int128 *)partial,
                        ks_bias, out, count, n, big_n, ks_stride, slices);
-    KSL_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -209,7 +205,7 @@ int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *id
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s) {
     if (count == 0) return 0;
     hipLaunchKernelGGL((k_lincomb<F>), dim3(count), dim3(256), 0, s, store, row_ptr, idx, coef, const_body, out, width);
-    KSL_LAUNCH_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmi_internal.hpp"   // BMI_LAUNCH_CHECK
+
 namespace ksm {
 
 typedef uint64_t u64;
@@ -198,12 +200,6 @@ inline size_t s_bytes(uint32_t count, uint32_t n, uint32_t L, uint32_t slices) {
     return (size_t)slices * count * L * cbs * TILE * sizeof(int);
 }
 
-#define KSM_CHECK()                              \
-    do {                                         \
-        hipError_t e__ = hipGetLastError();      \
-        if (e__ != hipSuccess) return (int)e__;  \
-    } while (0)
-
 template <class F>
 int launch_ksk_to_limbs(const u64 *ksk, signed char *Bm, uint32_t rows, uint32_t n, uint32_t ks_stride, uint32_t L,
                         hipStream_t s) {
@@ -211,7 +207,7 @@ int launch_ksk_to_limbs(const u64 *ksk, signed char *Bm, uint32_t rows, uint32_t
     const size_t total = (size_t)rows * cbs * TILE;
     hipLaunchKernelGGL((k_ksk_to_limbs<F>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ksk, Bm, rows, n,
                        ks_stride, L);
-    KSM_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
@@ -224,14 +220,14 @@ int launch_keyswitch(const u64 *in, const signed char *Bm, signed char *D, int *
     const size_t coefs = (size_t)count * big_n;
     hipLaunchKernelGGL((k_ks_digits<F>), dim3((unsigned)((coefs + 255) / 256)), dim3(256), 0, s, in, D, count, big_n, levels,
                        base_log);
-    KSM_CHECK();
+    BMI_LAUNCH_CHECK();
     const uint32_t tiles = (count + TILE - 1) / TILE;
     const uint32_t per_slice = (ksteps + slices - 1) / slices;
     hipLaunchKernelGGL((k_ks_mfma<L>), dim3((tiles + WAVES - 1) / WAVES, cbs, slices), dim3(64 * WAVES), 0, s, D, Bm, S, count,
                        K, cbs, per_slice);
-    KSM_CHECK();
+    BMI_LAUNCH_CHECK();
     hipLaunchKernelGGL((k_ks_combine<F, L>), dim3(count), dim3(256), 0, s, in, S, out, count, n, big_n, cbs, slices);
-    KSM_CHECK();
+    BMI_LAUNCH_CHECK();
     return 0;
 }
 
