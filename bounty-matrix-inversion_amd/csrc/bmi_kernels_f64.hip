@@ -17,6 +17,7 @@
 #include "ks_mfma.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
+#include "pair_sync.hpp"
 #include "phase_prof.hpp"
 
 using f49::i64;
@@ -84,34 +85,6 @@ constexpr int TPX_CTS = 4;
 constexpr int TPX_AT_WORDS = BMI_AT_WORDS;
 constexpr int TPX_LDS_WORDS = TW_WORDS + 2 * TPX_CTS * (SCRATCH_WORDS + N) + TPX_CTS * TPX_AT_WORDS + 4 * TPX_CTS;
 static_assert(TPX_LDS_WORDS <= BMI_LDS_WORDS_MAX, "TPX_LDS_WORDS exceeds the 160 KB of LDS");
-
-__device__ __forceinline__ void pair_post(uint32_t *flag, uint32_t v) {
-    __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// The poll loop is one opaque asm block: as C++ control flow it splits the loop body into several blocks and the
-// register allocator then spills ~180 dwords per lane (measured); all lanes read the same LDS word.
-__device__ __forceinline__ void pair_wait(uint32_t *flag, uint32_t v) {
-    const uint32_t addr = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)flag;
-    uint32_t tmp;
-    asm volatile(
-        "1:\n\t"
-        "ds_read_b32 %0, %1\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_cmp_eq_u32 vcc, %2, %0\n\t"
-        "s_cbranch_vccnz 2f\n\t"
-        "s_sleep 1\n\t"
-        "s_branch 1b\n"
-        "2:"
-        : "=&v"(tmp)
-        : "v"(addr), "s"(v)
-        : "vcc", "memory");
-}
-
-// keeps memory operations and the machine scheduler from moving work across this point (register pressure control)
-__device__ __forceinline__ void pin() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 template <int PF, int L = 3, int BG = 15>
 __global__ void __launch_bounds__(128 * TPX_CTS)
@@ -239,7 +212,7 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
             am[2 * VP] = f49::red(am[2 * VP] + p.x);          // <= 2 * 3 * 1.3p before the reduction
             am[2 * VP + 1] = f49::red(am[2 * VP + 1] + p.y);
         });
-        pair_post(f_ack, i + 1);          // release: the reads above have landed
+        pair_post(f_ack, i + 1);          // release: the reads above have landed (pair_ack not adopted here: no settled A/B, pair_handoff_ab.txt)
         pair_wait(f_ack_partner, i + 1);  // the partner has read this tile: the inverse transform may overwrite it
         inverse(am, lane, lds, tile);
         static_for<0, 16>([&](auto J) { accl[lane + 64 * J] = f49::red(accl[lane + 64 * J] + am[J]); });

@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(128 * T64_CTS)
                 acc[2 * VP] = f49::red(acc[2 * VP] + p.x);          // <= 2 * 3 * 1.4p before the reduction
                 acc[2 * VP + 1] = f49::red(acc[2 * VP + 1] + p.y);
             });
-            pair_post(f_ack, hand);          // release: the reads above have landed
+            pair_post(f_ack, hand);          // release: the reads above have landed (pair_ack not adopted here: no settled A/B, pair_handoff_ab.txt)
             pair_wait(f_ack_partner, hand);  // the partner has read this tile: the inverse transform may overwrite it
             inverse(acc, lane, lds, tile);
             // the limb's exact integer result (|.| < 2^47.6 < p/2: the centred residue is the integer), shifted into place

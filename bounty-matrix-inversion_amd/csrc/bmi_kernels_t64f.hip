@@ -12,6 +12,23 @@
 // Structure = k_blind_rotate_t64: a pair of wavefronts per ciphertext, four ciphertexts per workgroup; wavefront c owns input
 // polynomial c (decomposes it, transforms its L digit polynomials once, multiplies them with both key columns per limb),
 // publishes the partner's partial sum through its LDS tile, adds the partner's, and runs the inverse transform of output c.
+//
+// Who may touch a tile when (pair_sync.hpp; `hand` counts the hand-offs of the pair: 2 per CMUX, one per limb, strictly increasing;
+// pub[w] / ack[w] are written by wavefront w only).  Tile T_w of wavefront w is WRITTEN by w alone - the exchanges of its forward
+// transforms, the partial it publishes, the exchanges of its inverse transform - and READ by the partner w' only between w'
+// seeing pub[w] = h and w' storing ack[w'] = h:
+//   w:  stores partial h into T_w; pub[w] = h (release: the stores are visible before the flag)
+//   w': sees pub[w] = h; reads T_w (8 reads per lane); waits until they have returned (lgkmcnt(0)); ack[w'] = h
+//   w:  first DFT8 of inverse transform h (registers only); sees ack[w'] = h; only then the first store of the transform into T_w
+// Every later write of T_w follows that store in w's program order: the rest of inverse transform h; then partial h + 1 (second
+// limb: stored after inverse transform h has returned), guarded in turn by ack[w'] = h + 1; then, in the next CMUX, the forward
+// transforms (after inverse transform h + 1) and partial h + 2.  So no write of T_w can overtake a read of it by w', for both limbs
+// and across consecutive CMUXes.  Reads by w' never see a stale partial: it reads only after pub[w] = h, which w stores after the
+// partial.  The flags need no reset: each is compared for equality with a value its only writer stores exactly once.
+// No deadlock: w waits for pub[w'] = h and for ack[w'] = h; w' stores pub[w'] = h before any of its waits of hand-off h (its last
+// wait before that is for ack[w] = h - 1, stored by w before w reached hand-off h), and stores ack[w'] = h after waiting for
+// pub[w] = h only, which w has stored before either of its waits.  Dead pairs (beyond `count`) run the whole protocol on a copy of
+// the last ciphertext.  The per-CMUX workgroup barrier is reached by every wavefront outside any hand-off.
 #include <hip/hip_runtime.h>
 
 #include "bmi_internal.hpp"
@@ -125,12 +142,12 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         {
             double vr[16], vs[16];  // all 32 reads in flight before the first use
             static_for<0, 16>([&](auto J) {
-                vr[J] = accf[(lane + 64 * J + 2 * N - a_t) & (N - 1)];
+                vr[J] = accf[((lane + 2 * N - a_t) + 64 * J) & (N - 1)];   // (= lane + 64 J + 2 N - a_t; in this association <3, 10> compiles to 28 B of scratch per lane, in the other to 36)
                 vs[J] = accf[lane + 64 * J];
             });
             sched_fence();
             static_for<0, 16>([&](auto J) {
-                const uint32_t e = (lane + 64 * J + 2 * N - a_t) & (2 * N - 1);
+                const uint32_t e = ((lane + 2 * N - a_t) + 64 * J) & (2 * N - 1);
                 const double d = mod_ab<AB>(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
                 r[J] = t64::rounded_top_f64<L, BG, AB>(d);
             });
@@ -172,7 +189,8 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         static_for<0, LIMBS * 2 * L>([&](auto T) {
             constexpr int t = T, j = t / (2 * L), q = t % (2 * L), lev = q % L, cur = t & 1;
             if constexpr (q == 0) hand++;
-            // (the first row of the next limb is requested after the inverse transform, which needs the registers)
+            // (the first row of the next limb is requested after the inverse transform: requested before the hand-off instead it
+            // compiles without more scratch but measured 1.2 ms per 8,192 slower - profiles/pair_handoff_ab.txt)
             if constexpr (t + 1 < LIMBS * 2 * L && q != 2 * L - 1) fetch(kb[cur ^ 1], t + 1);
             sched_fence();
             static_for<0, 8>([&](auto P) {
@@ -203,11 +221,18 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                     acc[P] += p.x;
                     acc[P + 8] += p.y;
                 });
-                pair_post(f_ack, hand);          // release: the reads above have landed
-                pair_wait(f_ack_partner, hand);  // the partner has read this tile: the inverse transform may overwrite it
-                PH_MARK(5);   // adding the partner's partial, acknowledging
-                inverse(acc, lane, lds, tile);
-                PH_MARK(6);   // inverse transform
+                pin();
+                pair_ack(f_ack, hand);           // the eight reads above have landed: the partner may overwrite its tile
+                pin();
+                PH_MARK(5);   // adding the partner's partial, posting the acknowledgement (the WAIT for the partner's is in phase 6)
+                // the partner has read this tile once its acknowledgement is seen: the inverse transform waits for it just before its
+                // first store to the tile, with its first DFT8 (registers only) already done
+                inverse(acc, lane, lds, tile, [&]() {
+                    pin();
+                    pair_wait(f_ack_partner, hand);
+                    pin();
+                });
+                PH_MARK(6);   // inverse transform, including the wait for the partner's acknowledgement after its first DFT8
                 if constexpr (t + 1 < LIMBS * 2 * L) {
                     fetch(kb[cur ^ 1], t + 1);
                     pin();

@@ -159,7 +159,10 @@ __device__ __forceinline__ void forward(double (&x)[16], int lane, const double 
 }
 
 // Inverse transform (includes 1/512): evaluation layout in, x[J] = a[lane + 64 J] out (not yet rounded to integers).
-__device__ __forceinline__ void inverse(double (&x)[16], int lane, const double *tw, double *scratch) {
+// pre() runs after the first DFT8 (registers only) and immediately before the first store to scratch: a caller whose scratch is
+// still being read by another wavefront waits for that reader there, under the DFT8, instead of before the transform.
+template <class Pre = NoHook>
+__device__ __forceinline__ void inverse(double (&x)[16], int lane, const double *tw, double *scratch, Pre pre = Pre()) {
     const double2 *tw2 = reinterpret_cast<const double2 *>(tw);
     double2 *sc = reinterpret_cast<double2 *>(scratch);
     const int r1 = ex1_row(lane), a = lane & 7, base = ex2_base(lane);
@@ -169,6 +172,7 @@ __device__ __forceinline__ void inverse(double (&x)[16], int lane, const double 
     C v[8];
     static_for<0, 8>([&](auto Cc) { v[Cc] = C{x[Cc], x[Cc + 8]}; });
     dft8<true>(v);   // over c -> a
+    pre();
     wave_sync();
     static_for<0, 8>([&](auto A) { sc[base + a * 8 + ((A + a) & 7)] = double2{v[A].r, v[A].i}; });
     wave_sync();

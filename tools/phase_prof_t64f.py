@@ -8,7 +8,7 @@ import numpy as np, torch
 from bmi_amd import tfhe
 tfhe.LIB_PATH = tfhe.LIB_PATH.replace("libbmi_tfhe.so", "libbmi_tfhe_prof.so")
 NAMES = ["resync barrier", "accumulator reads + rounding", "digits + 3 forward transforms", "products (12 rows, both limbs) + publishing",
-         "waiting for the partner's partial", "adding it + acknowledging", "inverse transforms (2)", "recombination + loop head"]
+         "waiting for the partner's partial", "adding it + posting the acknowledgement", "inverse transforms (2) + acknowledgement wait", "recombination + loop head"]
 for B in [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "8192").split(",")]:
     eng = tfhe.Engine(tfhe.default_params(q_bits=65)); eng.keygen(0x5EED)
     DL = eng.delta_log(); lid = eng.lut_register(np.arange(-8, 8), 4, DL)
