@@ -50,7 +50,12 @@ struct Fq {
     u64 sub(u64 a, u64 b) const { return torus ? a - b : (a >= b ? a - b : (u64)((unsigned __int128)a + q - b)); }
     u64 neg(u64 a) const { return torus ? (u64)0 - a : (a ? q - a : 0); }
     u64 mul(u64 a, u64 b) const { return torus ? a * b : (u64)(((unsigned __int128)a * b) % q); }
-    u64 from_i64(long long v) const { return torus ? (u64)v : (v >= 0 ? (u64)v % q : q - ((u64)(-v) % q)); }
+    u64 from_i64(long long v) const {  // as f49::from_i64: |v| in unsigned arithmetic, canonical for -(multiple of q)
+        if (torus) return (u64)v;
+        if (v >= 0) return (u64)v % q;
+        const u64 m = ((u64)0 - (u64)v) % q;
+        return m ? q - m : 0;
+    }
     long long centered(u64 a) const { return torus ? (long long)a : (a > (q >> 1) ? (long long)(a - q) : (long long)a); }
     bool canonical(u64 a) const { return torus || a < q; }
     u64 pow(u64 b, u64 e) const {

@@ -47,7 +47,11 @@ F49_HD u64 addq(u64 a, u64 b) { u64 s = a + b; return s >= Q ? s - Q : s; }
 F49_HD u64 subq(u64 a, u64 b) { return a >= b ? a - b : a + Q - b; }
 F49_HD u64 negq(u64 a) { return a ? Q - a : 0; }
 F49_HD u64 mulq(u64 a, u64 b) { return (u64)(((unsigned __int128)a * b) % Q); }
-F49_HD u64 from_i64(i64 v) { return v >= 0 ? (u64)v % Q : Q - ((u64)(-v) % Q); }
+F49_HD u64 from_i64(i64 v) {  // any v: |v| is formed in unsigned arithmetic (INT64_MIN), -(multiple of Q) is 0, not Q
+    if (v >= 0) return (u64)v % Q;
+    const u64 m = ((u64)0 - (u64)v) % Q;
+    return m ? Q - m : 0;
+}
 F49_HD i64 centered(u64 a) { return a > (Q >> 1) ? (i64)a - (i64)Q : (i64)a; }
 F49_HD uint32_t modswitch(u64 a, uint32_t log2N) {
     return (uint32_t)(((a << log2N) + (Q >> 1)) / Q) & ((1u << log2N) - 1u);  // a < 2^49, log2N <= 14: no overflow

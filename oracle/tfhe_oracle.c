@@ -106,7 +106,12 @@ int ora_selftest_mulq(u64 seed, uint32_t iters) {
     return 1;
 }
 static u64 powq(u64 b, u64 e) { u64 r = 1; while (e) { if (e & 1) r = mulq(r, b); b = mulq(b, b); e >>= 1; } return r; }
-static inline u64 from_i64(i64 v) { if (TORUS) return (u64)v; return v >= 0 ? (u64)v % Q : Q - ((u64)(-v) % Q); }
+static inline u64 from_i64(i64 v) { /* any v: |v| in unsigned arithmetic (INT64_MIN); canonical for -(multiple of Q) */
+    if (TORUS) return (u64)v;
+    if (v >= 0) return (u64)v % Q;
+    u64 m = ((u64)0 - (u64)v) % Q;
+    return m ? Q - m : 0;
+}
 static inline i64 centered(u64 a) { if (TORUS) return (i64)a; return a > (Q >> 1) ? (i64)(a - Q) : (i64)a; } /* (-q/2, q/2] */
 
 /* ------------------------------------------------------- deterministic RNG -- */
