@@ -81,6 +81,13 @@ def _log_erfc(x):
     return out
 
 
+def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0):
+    """(sigma in positions of the 2N circle, half box / sigma) of look-ups through tables of `lut_bits` bits (scalars or arrays)"""
+    N = 1 << P.log_N
+    sigma_pos = np.sqrt(((input_variance + v_ks) * (2.0 * N) ** 2 + (1 + hs) / 12.0) * variance_scale)
+    return sigma_pos, N / (2.0 ** (lut_bits + 1)) / sigma_pos
+
+
 def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None):
     """Error budget of `prog` (a program.Program) under the parameter set `P` (tfhe.Params or anything with its fields).
 
@@ -109,12 +116,10 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     log_terms = []
     if nn:
         v_in, amp = lincomb_var(prog.node_ptr, prog.term_leaf, prog.term_coef)
-        sigma_pos = np.sqrt((v_in + v_ks) * (2.0 * N) ** 2 + (1 + hs) / 12.0)
         p_node = prog.lut_p[prog.node_lut].astype(np.int64)
         if (1 << (int(p_node.max()) + 1)) > N:
             raise ValueError(f"a {int(p_node.max())}-bit look-up does not fit N = {N}")
-        half_box = N / (2.0 ** (p_node + 1))
-        margin = half_box / sigma_pos
+        sigma_pos, margin = _lookup_margin(P, p_node, v_in, v_ks, hs)
         lp = _log_erfc(margin / math.sqrt(2.0))
         log_terms.append(lp)
         res.update(worst_margin_sigma=float(margin.min()), log10_p_fail_worst_lookup=float(lp.max()),
@@ -133,6 +138,22 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     else:
         res.update(log10_p_fail=-math.inf, p_fail=0.0)
     return res
+
+
+def lookup_failure_probability(P, lut_bits, input_variance=0.0, bsk_precision=None, unroll=False, hw_small=None, hw_big=None,
+                               variance_scale=1.0):
+    """The per-look-up term of failure_probability on its own: the probability that one look-up through a table of `lut_bits`
+    bits decodes a neighbouring box, for an input of variance `input_variance` (relative to q^2: 2 glwe_noise^2 for the sum of
+    two fresh encryptions, pbs_output_variance(P, bsk_precision, unroll, ...) times the squared coefficients for bootstrapped
+    leaves - the only place the key's precision and unrolling enter, so those two arguments are accepted and unused here).
+    `variance_scale` multiplies the variance in positions^2 (the +-15 % the variance terms are held to give the band a measured
+    failure count is accepted in: tests/test_gpu_decrypt_device.py)."""
+    N = 1 << P.log_N
+    if (1 << (int(lut_bits) + 1)) > N:
+        raise ValueError(f"a {int(lut_bits)}-bit look-up does not fit N = {N}")
+    hs = P.n / 2.0 if hw_small is None else float(hw_small)
+    _, margin = _lookup_margin(P, int(lut_bits), float(input_variance), keyswitch_variance(P, hw_big), hs, float(variance_scale))
+    return float(10.0 ** _log_erfc(np.array([margin / math.sqrt(2.0)]))[0])
 
 
 def candidate_sets(msg_bits, q_bits=None, secure=False):

@@ -197,6 +197,27 @@ class Executor:
     def run(self, ct_inputs):
         """ct_inputs: (n_inputs, k*N+1) uint64 ciphertexts (host) -> (n_outputs, k*N+1) uint64 (host); with batch > 1:
         (batch, n_inputs, k*N+1) -> (batch, n_outputs, k*N+1)"""
+        self._walk(ct_inputs)
+        if self.on_gpu:
+            self.torch.cuda.synchronize(self.dev)
+        res = self.out[: self.n_out].cpu().numpy().view(np.uint64)
+        return res if self.batch == 1 else res.reshape(self.batch, -1, self.big)
+
+    def run_decrypted(self, ct_inputs):
+        """run() with the outputs decrypted where they are (Engine.decrypt_device on the output rows: the context must hold the
+        secret key): int64 messages (n_outputs,), with batch > 1 (batch, n_outputs) - 8 bytes per output come home instead of a
+        ciphertext"""
+        torch = self.torch
+        stream = self._walk(ct_inputs)
+        with torch.cuda.device(self.dev):
+            msgs = torch.empty(max(self.n_out, 1), dtype=torch.int64, device=self.dev)
+            self.eng.decrypt_device(self.out, self.n_out, self.delta_log, msgs, stream=stream)
+            torch.cuda.synchronize(self.dev)
+        res = msgs[: self.n_out].cpu().numpy()
+        return res if self.batch == 1 else res.reshape(self.batch, -1)
+
+    def _walk(self, ct_inputs):
+        """the level walk of run(): leaves the output ciphertexts in self.out, queued on the stream it returns"""
         torch = self.torch
         n_in = self.prog.n_inputs
         ct = np.ascontiguousarray(ct_inputs, dtype=np.uint64).reshape(self.batch, n_in, self.big)
@@ -224,10 +245,7 @@ class Executor:
                 eng.scatter_rows(lvl, width, self.store, self.d_rows[pos:], stream)
             rp, ix, cf, cs = self.out_csr
             eng.lincomb(self.store, rp, ix, cf, cs, self.n_out, self.out, stream)
-            if self.on_gpu:
-                torch.cuda.synchronize(self.dev)
-            res = self.out[: self.n_out].cpu().numpy().view(np.uint64)
-            return res if self.batch == 1 else res.reshape(self.batch, -1, self.big)
+            return stream
 
     def _all_gather_rows(self, region, per):
         """in-place all-gather of a level buffer: rank r contributed rows [r*per, (r+1)*per) (rows of the last rank past

@@ -62,6 +62,8 @@ _SIGS = {
     "bmi_lincomb_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                           C.c_void_p, C.c_void_p],
     "bmi_scatter_rows": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bmi_phase_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_decrypt_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bmi_pbs_batch_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
     "bmi_keyswitch_batch_host": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
     "bmi_blind_rotate_batch_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
@@ -531,6 +533,32 @@ class Engine:
     def scatter_rows(self, d_src, count, d_store, d_rows, stream=0):
         self._ck(self.lib.bmi_scatter_rows(self.h, _ptr(d_src), count, _ptr(d_store), _ptr(d_rows), C.c_void_p(stream)),
                  "bmi_scatter_rows")
+
+    def phase_device(self, d_ct, count, d_phase, stream=0):
+        """d_phase[i] = phase of the big-key ciphertext d_ct[i] (bmi_phase_batch); the context keeps a copy of the big secret key
+        on the device from the first call on (include/bmi_tfhe.h)"""
+        self._ck(self.lib.bmi_phase_batch(self.h, _ptr(d_ct), count, _ptr(d_phase), C.c_void_p(stream)), "bmi_phase_batch")
+
+    def decrypt_device(self, d_ct, count, delta_log, d_msgs, d_expected=None, d_err=None, stream=0):
+        """d_msgs[i] = the message of d_ct[i] at delta_log, by decrypt()'s rule (bmi_decrypt_batch); d_err (optional) = the signed
+        centred residue phase - e 2^delta_log, e = d_expected[i] if given, else the decoded message"""
+        self._ck(self.lib.bmi_decrypt_batch(self.h, _ptr(d_ct), count, delta_log, _ptr(d_expected), _ptr(d_msgs), _ptr(d_err),
+                                            C.c_void_p(stream)), "bmi_decrypt_batch")
+
+    def noise_stats(self, d_ct, count, delta_log, d_expected):
+        """Decrypts `count` device ciphertexts against the int64 device tensor d_expected and reduces on the device; only the
+        scalars come home: {count, wrong (messages != expected), mean, std (of the error about the expected value, as a
+        fraction of q), max_abs (of that error, in units of the modulus' words)}"""
+        import torch
+        with torch.cuda.device(d_ct.device):
+            msgs = torch.empty(count, dtype=torch.int64, device=d_ct.device)
+            err = torch.empty(count, dtype=torch.int64, device=d_ct.device)
+            self.decrypt_device(d_ct, count, delta_log, msgs, d_expected, err, torch.cuda.current_stream().cuda_stream)
+            e = err.double() / float(self.modulus)
+            return {"count": int(count), "wrong": int((msgs != d_expected[:count]).sum().item()),
+                    "mean": float(e.mean().item()) if count else 0.0,
+                    "std": float(e.std(unbiased=False).item()) if count else 0.0,
+                    "max_abs": int(err.abs().max().item()) if count else 0}
 
     def reserve(self, max_count):
         self._ck(self.lib.bmi_reserve(self.h, int(max_count)), "bmi_reserve")

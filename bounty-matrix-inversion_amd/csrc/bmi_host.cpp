@@ -226,6 +226,7 @@ struct FieldOps {
     decltype(&bmi::launch_keyswitch_mfma) keyswitch_mfma;
     decltype(&bmi::launch_ksk_to_limbs) ksk_to_limbs;
     decltype(&bmi::launch_lincomb) lincomb;
+    decltype(&bmi::launch_lwe_phase) lwe_phase;
     int (*bsk_to_ntt)(bmi_ctx *c, const u64 *std_polys);   // builds the NTT-domain key copy
     int (*negacyclic_mul)(const bmi_ctx *c, const u64 *a, const u64 *b, u64 *out, uint32_t count);
     uint32_t ks_limbs;   // limbs per keyswitch-key word of the matrix-core keyswitch
@@ -302,6 +303,8 @@ struct bmi_ctx {
     bool quad() const { return N == 4096; }
     DevBuf<u64> ksk_padded, ks_bias;   // keyswitch key, rows padded to ks_stride words, and its bias vector - keyswitch
     DevBuf<signed char> ks_limbs;      // the keyswitch key as ops->ks_limbs limbs in MFMA operand order - keyswitch_mfma
+    DevBuf<u64> sk_mask;               // the big SECRET key as big_n / 64 words of bits, built on first use (ensure_sk_mask), zeroed and
+                                       // dropped with the key set (drop_sk_mask) - lwe_phase
     uint32_t n_luts = 0, lut_cap = 0;
     std::vector<std::vector<u64>> luts_host;
     // growable device scratch (grow)
@@ -349,6 +352,27 @@ int grow(bmi_ctx *c, DevBuf<T> &b, size_t need, size_t floor_bytes) {
     if (!b.empty()) HIP_OK(c, hipDeviceSynchronize());
     HIP_OK(c, b.alloc(std::max(need, floor_bytes)));
     return 0;
+}
+// The device copy of the big secret key (bmi_phase_batch / bmi_decrypt_batch): bit x % 64 of word x / 64 is key bit x.
+int ensure_sk_mask(bmi_ctx *c) {
+    if (!c->sk_mask.empty()) return 0;
+    std::vector<u64> mask(c->big_n / 64, 0);
+    for (uint32_t x = 0; x < c->big_n; x++) mask[x >> 6] |= (c->sk_big[x] & 1) << (x & 63);
+    const hipError_t e = upload(c->sk_mask, mask.data(), mask.size());
+    if (e != hipSuccess) {
+        c->sk_mask.reset();
+        return fail(c, -2, std::string("uploading the secret-key mask: ") + hipGetErrorString(e));
+    }
+    return 0;
+}
+// ... overwritten with zeros and freed when the key set is replaced or the context destroyed (queued kernels may still read it:
+// the device is synchronised first)
+void drop_sk_mask(bmi_ctx *c) {
+    if (c->sk_mask.empty()) return;
+    (void)hipDeviceSynchronize();
+    (void)hipMemset(c->sk_mask.get(), 0, c->sk_mask.bytes());
+    (void)hipDeviceSynchronize();
+    c->sk_mask.reset();
 }
 // keyswitched ciphertexts of a batch (room for 1,024 at least)
 int ensure_small(bmi_ctx *c, size_t count) {
@@ -707,22 +731,23 @@ int upload_bsk3(bmi_ctx *c) {
     return 0;
 }
 
-const FieldOps GOLDILOCKS_OPS = {bmi::launch_keyswitch, bmi::launch_keyswitch_mfma, bmi::launch_ksk_to_limbs, bmi::launch_lincomb,
+const FieldOps GOLDILOCKS_OPS = {bmi::launch_keyswitch, bmi::launch_keyswitch_mfma, bmi::launch_ksk_to_limbs, bmi::launch_lincomb, bmi::launch_lwe_phase,
     [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt_gl, c->bsk_std.size() * 8, "bsk_to_ntt", [&](u64 *d) {
         return bmi::launch_bsk_to_ntt(std_polys, d, c->tw_gl.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
     [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi::launch_negacyclic_mul(a, b, o, c->tw_gl.get(), m, c->stream); },
     bmi::KS_LIMBS};
-const FieldOps FIELD49_OPS = {bmi49::launch_keyswitch, bmi49::launch_keyswitch_mfma, bmi49::launch_ksk_to_limbs, bmi49::launch_lincomb,
+const FieldOps FIELD49_OPS = {bmi49::launch_keyswitch, bmi49::launch_keyswitch_mfma, bmi49::launch_ksk_to_limbs, bmi49::launch_lincomb, bmi49::launch_lwe_phase,
     [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt49, c->bsk_std.size() * 8, "bsk_to_ntt", [&](double *d) {
         return bmi49::launch_bsk_to_ntt(std_polys, d, c->tw_wave.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
     [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi49::launch_negacyclic_mul(a, b, o, c->tw_wave.get(), m, c->stream); },
     bmi49::KS_LIMBS};
-const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfma, bmit::launch_ksk_to_limbs, bmit::launch_lincomb,
+const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfma, bmit::launch_ksk_to_limbs, bmit::launch_lincomb, bmit::launch_lwe_phase,
                               nullptr, nullptr, bmit::KS_LIMBS};
 
 // evaluation keys for the secret keys held in c->sk_small / c->sk_big, deterministic in `seed`
 int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
     HIP_OK(c, hipSetDevice(c->device));
+    drop_sk_mask(c);
     const bmi_params &P = c->P;
     const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels, rows = c->rows;
     c->seed = seed;
@@ -1018,6 +1043,7 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
 void bmi_ctx_destroy(bmi_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    drop_sk_mask(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;   // the device buffers free themselves
 }
@@ -1093,6 +1119,7 @@ int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big
     for (size_t i = 0; i < ksk_words; i++)
         if (!c->f.canonical(ksk[i])) return fail(c, -1, "keyswitch key word not reduced mod q");
     c->have_keys = false;
+    drop_sk_mask(c);
     c->have_bsk3 = false;   // an unrolled key belongs to the key set it was generated with: import it again (bmi_import_bsk_unrolled)
     c->bsk_std.assign(bsk, bsk + bsk_words);
     c->ksk.assign(ksk, ksk + ksk_words);
@@ -1388,6 +1415,31 @@ int bmi_lincomb_batch(bmi_ctx *c, const uint64_t *d_store, const uint32_t *d_row
     HIP_OK(c, hipSetDevice(c->device));
     int rc = c->ops->lincomb(d_store, d_row_ptr, d_idx, (const i64 *)d_coef, d_const_body, d_out, count, c->big_n + 1, (hipStream_t)stream);
     return rc ? fail(c, -2, std::string("lincomb launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+// phase (d_msgs null) or decryption of device-resident ciphertexts: the checks of bmi_phase, then one launch of k_lwe_phase
+static int phase_decrypt_batch(bmi_ctx *c, const uint64_t *d_ct, uint32_t count, uint32_t delta_log, const int64_t *d_expected,
+                               uint64_t *d_phase, int64_t *d_msgs, int64_t *d_err, void *stream) {
+    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
+    if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (int rc = ensure_sk_mask(c)) return rc;
+    const int rc = c->ops->lwe_phase(d_ct, c->sk_mask.get(), d_phase, (const i64 *)d_expected, (i64 *)d_msgs, (i64 *)d_err, count, c->big_n,
+                                     delta_log, (hipStream_t)stream);
+    return rc ? fail(c, -2, std::string("lwe_phase launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+int bmi_phase_batch(bmi_ctx *c, const uint64_t *d_ct, uint32_t count, uint64_t *d_phase, void *stream) {
+    if (!c || (count && (!d_ct || !d_phase))) return -1;
+    return phase_decrypt_batch(c, d_ct, count, 0, nullptr, d_phase, nullptr, nullptr, stream);
+}
+
+int bmi_decrypt_batch(bmi_ctx *c, const uint64_t *d_ct, uint32_t count, uint32_t delta_log, const int64_t *d_expected,
+                      int64_t *d_msgs, int64_t *d_err, void *stream) {
+    if (!c || (count && (!d_ct || !d_msgs))) return -1;
+    if (delta_log == 0 || delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
+    return phase_decrypt_batch(c, d_ct, count, delta_log, d_expected, nullptr, d_msgs, d_err, stream);
 }
 
 int bmi_scatter_rows(bmi_ctx *c, const uint64_t *d_src, uint32_t count, uint64_t *d_store, const uint32_t *d_rows,

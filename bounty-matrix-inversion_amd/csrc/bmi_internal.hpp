@@ -111,6 +111,10 @@ int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *id
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
 // store[rows[i]] = src[i] (rows of `width` words); field independent
 int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32_t count, uint32_t width, hipStream_t s);
+// lwe_phase.hpp: phase (and, with msgs, the decoded message and the signed error) of big-key ciphertexts; key_mask = the big
+// secret key as big_n / 64 words of bits
+int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
 }  // namespace bmi
 
 // The same launchers for the 49-bit field (bmi_kernels_f64.hip): NTT-domain key, twiddles and test polynomials are f64.
@@ -162,6 +166,8 @@ int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *
                           uint32_t base_log, hipStream_t s);
 int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
+int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
 }  // namespace bmi49
 
 // The 2^64 torus (bmi_kernels_t64*.hip): ciphertexts, test polynomials and keyswitch key are plain u64
@@ -245,4 +251,6 @@ int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *
                           uint32_t base_log, hipStream_t s);
 int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
+int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
 }  // namespace bmit

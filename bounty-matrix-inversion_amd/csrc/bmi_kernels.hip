@@ -19,6 +19,7 @@
 
 #include "bmi_internal.hpp"
 #include "ks_lincomb.hpp"
+#include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
 #include "ntt_wave.hpp"
 
@@ -393,6 +394,11 @@ int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32
     hipLaunchKernelGGL(k_scatter_rows, dim3(count), dim3(256), 0, s, src, store, rows, width);
     BMI_LAUNCH_CHECK();
     return 0;
+}
+
+int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s) {
+    return lwp::launch_lwe_phase<FieldG>(ct, key_mask, phase, expected, msgs, err, count, big_n, delta_log, s);
 }
 
 }  // namespace bmi

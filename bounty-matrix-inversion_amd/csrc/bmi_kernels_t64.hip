@@ -22,6 +22,7 @@
 
 #include "bmi_internal.hpp"
 #include "ks_lincomb.hpp"
+#include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
@@ -527,6 +528,11 @@ int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *
 int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s) {
     return ksl::launch_lincomb<FieldT>(store, row_ptr, idx, coef, const_body, out, count, width, s);
+}
+
+int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s) {
+    return lwp::launch_lwe_phase<FieldT>(ct, key_mask, phase, expected, msgs, err, count, big_n, delta_log, s);
 }
 
 }  // namespace bmit

@@ -172,6 +172,16 @@ int bmi_lincomb_batch(bmi_ctx *ctx, const uint64_t *d_store, const uint32_t *d_r
  * value lifetimes to Concrete's runtime inside circuit.run, main.py:81). */
 int bmi_scatter_rows(bmi_ctx *ctx, const uint64_t *d_src, uint32_t count, uint64_t *d_store, const uint32_t *d_rows,
                      void *stream);
+/* Device-pointer forms of bmi_phase and bmi_decrypt (results read where they were computed: noise statistics, failure counts,
+ * an executor's outputs): d_ct [count][k*N+1] device words, d_phase / d_msgs / d_err [count] device words.  The decoding rule and
+ * the refusals are the host forms'; count == 0 launches nothing.  d_err[i] (may be NULL) is the centred residue of
+ * phase - e * 2^delta_log mod q as a signed value, with e = d_expected[i], or the decoded message where d_expected is NULL: with
+ * the expected result given it is the noise of a look-up, and a wrong result shows as |err| >= 2^delta_log / 2.
+ * These calls keep A COPY OF THE BIG SECRET KEY ON THE DEVICE (a bit mask of k*N/64 words, owned by the context): it is built by
+ * the first call, and overwritten with zeros and freed when the context generates or imports another key set or is destroyed. */
+int bmi_phase_batch(bmi_ctx *ctx, const uint64_t *d_ct, uint32_t count, uint64_t *d_phase, void *stream);
+int bmi_decrypt_batch(bmi_ctx *ctx, const uint64_t *d_ct, uint32_t count, uint32_t delta_log, const int64_t *d_expected,
+                      int64_t *d_msgs, int64_t *d_err, void *stream);
 /* Host-buffer convenience forms (what a ctypes/cgo binding over numpy buffers would call):
  * copy in, run on the context's own stream, copy out, synchronise. */
 int bmi_pbs_batch_host(bmi_ctx *ctx, const uint64_t *in, const uint32_t *lut_ids, uint32_t count, uint64_t *out);

@@ -13,6 +13,8 @@
 #   preset <preset> [batches]    tools/preset_timing.py
 #   phase  <t64f|t64w> [batches] per-phase cycles of the debug build (make -C csrc prof)
 #   inverse [sizes]              encrypted-inverse wall-clocks on the default engine (bmi_amd/inverse_bench.py)
+#   calibrate [preset:bits:rounds ...]   failure-rate calibration of the error budget + phase-kernel time (tools/gpu_failure_rate.py)
+#                                                                                                     -> profiles/failure_rate_calibration.json (--out FILE: elsewhere)
 #   smoke                        __graft_entry__.smoke()
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -49,6 +51,7 @@ eng = tfhe.Engine(); eng.keygen(0x5EED)
 print(json.dumps(inverse_bench.run(eng, tuple(int(x) for x in sys.argv[1].split(","))), indent=1))
 PY
     ;;
+  calibrate) timeout -k 10 ${BMI_T:-300} python tools/gpu_failure_rate.py "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) timeout -k 10 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/smoke.log ;;
   final)
     TAG=${1:-r04}; B=8192; F=gpurun_out/final
@@ -72,5 +75,5 @@ PY
     python3 tools/summarize_prof.py $TAG $B $F/prof $F/summary $F/prof_trace.log > $F/summary/summary.log 2>&1 || { tail -20 $F/summary/summary.log; exit 1; }
     rm -rf $F/prof
     tail -c 1500 $F/bench_default.json; echo; cat $F/summary/summary.log ;;
-  *) sed -n 2,20p "$0"; exit 2 ;;
+  *) sed -n 2,22p "$0"; exit 2 ;;
 esac
