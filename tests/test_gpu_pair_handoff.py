@@ -20,6 +20,8 @@ import os
 import numpy as np
 import pytest
 
+import pbs_cases as pc
+
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED
@@ -36,24 +38,11 @@ def _engine(levels):
     return e
 
 
-def _oracle(eng):
-    from oracle import tfhe_oracle as to
-    to.set_field(QB)
-    _, _, bsk, ksk = eng.export_keys()
-    P = to.default_params(q_bits=QB, n=eng.P.n, bs_levels=eng.P.bs_levels, bs_base_log=eng.P.bs_base_log)
-    return to.Ctx(P, bsk, ksk)
-
-
-def random_words(rng, count, width):
-    """uniformly random 64-bit words (not valid encryptions: they drive the digits to their full range)"""
-    return rng.integers(0, 1 << 63, (count, width), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (count, width), dtype=np.uint64)
-
-
 def margin_inputs(eng):
     """the inputs of the recorded rounding distance: a pure function of the seeds (no encryption randomness)"""
     rng = np.random.default_rng(23)
     lid = eng.lut_register(rng.integers(-8, 8, 16), 4, eng.delta_log())
-    small = random_words(rng, MARGIN_COUNT, eng.P.n + 1)
+    small = pc.uniform_words(rng, (MARGIN_COUNT, eng.P.n + 1))
     small[1] = 0
     small[2] = np.uint64(0xFFFFFFFFFFFFFFFF)
     return small, np.full(MARGIN_COUNT, lid, np.uint32)
@@ -62,10 +51,11 @@ def margin_inputs(eng):
 @pytest.fixture(scope="module", params=LEVELS, ids=[f"l{l}" for l in LEVELS])
 def ctx(request):
     e = _engine(request.param)   # (the two level counts the floating-point transform is certified for: shape_supported_fft)
-    o = _oracle(e)
-    yield e, o
-    o.close()
-    e.close()
+    try:
+        with pc.oracle_for(e) as o:
+            yield e, o.ctx
+    finally:
+        e.close()
 
 
 @pytest.mark.parametrize("count", [1, 3, 4, 5, 255, 257, 1023])
@@ -80,14 +70,11 @@ def test_throughput_kernel_equals_latency_kernel_and_oracle(ctx, count):
     small = eng.keyswitch_host(eng.encrypt(msgs, eng.delta_log()))
     # every other ciphertext of the first and of the last workgroup is random words: the partners of a pair then differ most
     for k in list(range(0, min(count, 4), 2)) + list(range(max(count - 4, 0), count, 2)):
-        small[k] = random_words(rng, 1, small.shape[1])[0]
-    try:
-        eng.set_kernel_variant(5)
+        small[k] = pc.uniform_words(rng, (1, small.shape[1]))[0]
+    with pc.pinned_variant(eng, 5):
         got = eng.blind_rotate_host(small, ids[sel])
-        eng.set_kernel_variant(6)
+    with pc.pinned_variant(eng, 6):
         lat = eng.blind_rotate_host(small, ids[sel])
-    finally:
-        eng.set_kernel_variant(0)
     assert np.array_equal(got, lat), "throughput kernel differs from the latency kernel"
     if count <= 5:
         pick = np.arange(count)
@@ -107,11 +94,8 @@ def test_rounding_distance_unchanged_to_the_last_bit(levels):
         out, dist = e.fft_margin_host(small, ids)
         print(f"\nl = {levels}: rounding distance {dist.hex()} (recorded {recorded['distance_hex']})")
         assert dist.hex() == recorded["distance_hex"]
-        try:
-            e.set_kernel_variant(6)
+        with pc.pinned_variant(e, 6):
             lat = e.blind_rotate_host(small, ids)
-        finally:
-            e.set_kernel_variant(0)
         assert np.array_equal(out, lat)
     finally:
         e.close()

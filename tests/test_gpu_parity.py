@@ -4,19 +4,11 @@ All calls go through the C ABI (include/bmi_tfhe.h) via bmi_amd.tfhe."""
 import numpy as np
 import pytest
 
+import pbs_cases as pc
+
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED
-
-
-def rand_q(rng, shape, Q):
-    """uniform canonical words of Z_q (top values included)"""
-    if Q >> 64:      # the 2^64 torus: every word is canonical
-        return rng.integers(0, 2**63, shape, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, shape, dtype=np.uint64)
-    if Q >> 63:
-        v = rng.integers(0, 2**63, shape, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, shape, dtype=np.uint64)
-        return np.where(v >= np.uint64(Q), v - np.uint64(Q), v)
-    return rng.integers(0, Q, shape, dtype=np.uint64)
 
 
 def words(values, Q):
@@ -37,12 +29,8 @@ def eng(request):
 
 @pytest.fixture(scope="module")
 def ora(eng):
-    from oracle import tfhe_oracle as to
-    sk_small, sk_big, bsk, ksk = eng.export_keys()
-    P = to.default_params(q_bits=eng.q_bits)
-    assert P.glwe_noise == eng.P.glwe_noise and P.lwe_noise == eng.P.lwe_noise
-    ctx = to.Ctx(P, bsk, ksk)   # selects the oracle's field
-    return to, P, ctx, sk_small, sk_big, bsk, ksk
+    with pc.oracle_for(eng) as o:
+        yield o
 
 
 @pytest.fixture(autouse=True)
@@ -57,10 +45,10 @@ def _select_oracle_field(request):
 def test_negacyclic_product_matches_oracle(eng, ora):
     if eng.q_bits == 65:
         pytest.skip("no transform exists mod 2^64 (the torus product is covered by the blind-rotation tests)")
-    to = ora[0]
+    to = ora.to
     rng = np.random.default_rng(1)
     Q = eng.modulus
-    a, b = rand_q(rng, (9, 1024), Q), rand_q(rng, (9, 1024), Q)
+    a, b = pc.rand_q(rng, (9, 1024), Q), pc.rand_q(rng, (9, 1024), Q)
     # edge rows: zeros, ones, X^(N-1) * X = -1, max values
     a[0] = 0
     a[1] = 1
@@ -76,7 +64,8 @@ def test_negacyclic_product_matches_oracle(eng, ora):
 
 def test_keygen_matches_oracle_keygen(eng, ora):
     """Same seed, same RNG specification -> identical keys (covers the host keygen's negacyclic A*S)."""
-    to, P, _, sk_small, sk_big, bsk, ksk = ora
+    to, P, sk_small, sk_big = ora.to, ora.P, ora.sk_small, ora.sk_big
+    _, _, bsk, ksk = eng.export_keys()
     K = to.keygen(P, SEED)
     assert np.array_equal(K.sk_small, sk_small) and np.array_equal(K.sk_big, sk_big)
     assert np.array_equal(K.ksk, ksk)
@@ -89,7 +78,7 @@ def test_keygen_matches_oracle_keygen(eng, ora):
 
 
 def test_encrypt_decrypt_roundtrip_and_oracle_phase(eng, ora):
-    to, P, _, _, sk_big, _, _ = ora
+    to, P, sk_big = ora.to, ora.P, ora.sk_big
     msgs = np.arange(-8, 8)
     ct = eng.encrypt(msgs, eng.delta_log())
     assert list(eng.decrypt(ct, eng.delta_log())) == list(msgs)
@@ -98,7 +87,7 @@ def test_encrypt_decrypt_roundtrip_and_oracle_phase(eng, ora):
 
 
 def test_lut_test_vector_matches_oracle(eng, ora):
-    to = ora[0]
+    to = ora.to
     rng = np.random.default_rng(3)
     for p in (1, 2, 3, 4, 6):  # 6 bits: only the test-polynomial construction is compared
         table = rng.integers(-(1 << (p - 1)), 1 << (p - 1), 1 << p)
@@ -107,12 +96,12 @@ def test_lut_test_vector_matches_oracle(eng, ora):
 
 
 def test_keyswitch_bit_exact(eng, ora):
-    to, P, ctx, sk_small, _, _, _ = ora
+    to, ctx, sk_small = ora.to, ora.ctx, ora.sk_small
     rng = np.random.default_rng(4)
     msgs = rng.integers(-8, 8, 19)  # not a multiple of the kernel tile: exercises the ragged tail
     ct = eng.encrypt(msgs, eng.delta_log())
     Q = eng.modulus
-    ct[3, :1024] = rand_q(rng, 1024, Q)     # arbitrary masks are valid inputs too
+    ct[3, :1024] = pc.rand_q(rng, 1024, Q)     # arbitrary masks are valid inputs too
     ct[4, :1024] = np.uint64(Q - 1)          # extreme words
     ct[5, :1024] = np.uint64(Q // 2)
     ct[6, :1024] = np.uint64((Q // 2 + 1) % Q)
@@ -132,18 +121,18 @@ def test_keyswitch_bit_exact(eng, ora):
 def test_keyswitch_matrix_core_path_bit_exact(eng, ora):
     """Batches >= 64 take the int8 matrix-core keyswitch (ks_mfma.hpp): ragged tile counts, extreme words, and the
     scalar kernel on the same inputs must all agree with the oracle bit for bit."""
-    to, P, ctx, sk_small, _, _, _ = ora
+    to, ctx, sk_small = ora.to, ora.ctx, ora.sk_small
     rng = np.random.default_rng(14)
     Q = eng.modulus
     for count in (64, 97):   # 97 = 3 full tiles of 32 + 1
         msgs = rng.integers(-8, 8, count)
         ct = eng.encrypt(msgs, eng.delta_log())
-        ct[3, :1024] = rand_q(rng, 1024, Q)
+        ct[3, :1024] = pc.rand_q(rng, 1024, Q)
         ct[4, :1024] = np.uint64(Q - 1)
         ct[5, :1024] = np.uint64(Q // 2)
         ct[6, :1024] = np.uint64((Q // 2 + 1) % Q)
         ct[7, :] = 0
-        ct[count - 1, :1024] = rand_q(rng, 1024, Q)   # the ragged last row
+        ct[count - 1, :1024] = pc.rand_q(rng, 1024, Q)   # the ragged last row
         want = ctx.keyswitch(ct)
         got = eng.keyswitch_host(ct)
         assert np.array_equal(got, want), count
@@ -163,14 +152,14 @@ def test_blind_rotate_every_kernel_variant(eng, ora, variant):
     """7 ciphertexts: ragged against the 2 (variant 1) and 4 (variant 3) ciphertexts per workgroup.  Variant 5 (2^64 torus: the
     wave-pair kernel whose exact limb products go through the folded complex FFT, bmi_kernels_t64f.hip) must return the same
     words as the integer arithmetic of the oracle."""
-    to, P, ctx, _, sk_big, _, _ = ora
+    to, ctx, sk_big = ora.to, ora.ctx, ora.sk_big
     rng = np.random.default_rng(15)
     tables = [np.arange(-8, 8), rng.integers(-8, 8, 16)]
     ids = [eng.lut_register(t, 4, eng.delta_log()) for t in tables]
     tvs = np.stack([eng.lut_get(i) for i in ids])
     msgs = rng.integers(-8, 8, 6)
     small = ctx.keyswitch(eng.encrypt(msgs, eng.delta_log()))
-    small = np.concatenate([small, rand_q(rng, (1, 631), eng.modulus)])
+    small = np.concatenate([small, pc.rand_q(rng, (1, 631), eng.modulus)])
     sel = np.array([0, 1, 0, 1, 0, 1, 1], np.uint32)
     if variant in (5, 6) and eng.q_bits != 65:
         from bmi_amd import tfhe
@@ -183,23 +172,20 @@ def test_blind_rotate_every_kernel_variant(eng, ora, variant):
         with pytest.raises(tfhe.BmiError):
             eng.set_kernel_variant(variant)
         return
-    eng.set_kernel_variant(variant)
-    try:
+    with pc.pinned_variant(eng, variant):
         got = eng.blind_rotate_host(small, np.array(ids, np.uint32)[sel])
-    finally:
-        eng.set_kernel_variant(0)
     assert np.array_equal(got, ctx.blind_rotate(small, tvs, sel))
 
 
 def test_blind_rotate_bit_exact(eng, ora):
-    to, P, ctx, _, sk_big, _, _ = ora
+    to, ctx, sk_big = ora.to, ora.ctx, ora.sk_big
     rng = np.random.default_rng(5)
     tables = [np.arange(-8, 8), rng.integers(-8, 8, 16)]
     ids = [eng.lut_register(t, 4, eng.delta_log()) for t in tables]
     tvs = np.stack([eng.lut_get(i) for i in ids])
     msgs = rng.integers(-8, 8, 6)
     small = ctx.keyswitch(eng.encrypt(msgs, eng.delta_log()))
-    small = np.concatenate([small, rand_q(rng, (1, 631), eng.modulus), np.zeros((1, 631), np.uint64)])  # random + all-zero ciphertexts
+    small = np.concatenate([small, pc.rand_q(rng, (1, 631), eng.modulus), np.zeros((1, 631), np.uint64)])  # random + all-zero ciphertexts
     sel = np.array([0, 1, 0, 1, 0, 1, 1, 0], np.uint32)
     got = eng.blind_rotate_host(small, np.array(ids, np.uint32)[sel])
     want = ctx.blind_rotate(small, tvs, sel)
@@ -209,7 +195,7 @@ def test_blind_rotate_bit_exact(eng, ora):
 
 
 def test_pbs_bit_exact_and_evaluates_every_entry(eng, ora):
-    to, P, ctx, _, sk_big, _, _ = ora
+    to, ctx, sk_big = ora.to, ora.ctx, ora.sk_big
     rng = np.random.default_rng(6)
     table = rng.integers(-8, 8, 16)
     sq = np.array([(m * m) // 4 % 8 for m in range(-8, 8)])
@@ -243,7 +229,7 @@ def test_small_message_space_luts(eng):
 
 def test_lincomb_device_matches_oracle(eng, ora):
     import torch
-    to, P, _, _, sk_big, _, _ = ora
+    to, P, sk_big = ora.to, ora.P, ora.sk_big
     msgs = np.array([1, -2, 3, 0, 2])
     ct = eng.encrypt(msgs, eng.delta_log())
     row_ptr = np.array([0, 2, 5, 5, 8], np.uint32)
@@ -270,7 +256,7 @@ def test_lincomb_device_matches_oracle(eng, ora):
 def test_pbs_device_pointers_and_noise_budget(eng, ora):
     """Device-resident call (torch tensors as plain device memory) + output noise inside the budget."""
     import torch
-    to, P, ctx, _, sk_big, _, _ = ora
+    to, ctx, sk_big = ora.to, ora.ctx, ora.sk_big
     rng = np.random.default_rng(8)
     B = 300  # spans several workgroups, ragged last group
     msgs = rng.integers(-8, 8, B)
@@ -291,35 +277,8 @@ def test_pbs_device_pointers_and_noise_budget(eng, ora):
     assert np.array_equal(out[pick], ctx.pbs(ct[pick], tv, np.zeros(12, np.uint32)))
     ph = eng.phase(out)
     Q, dl = eng.modulus, eng.delta_log()
-    err = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(ph, msgs)], dtype=np.float64)
+    err = pc.centred_words(ph, msgs, dl, Q)
     assert np.max(np.abs(err)) < 2.0 ** (dl - 9)  # half a box is 2^(dl-1)
-
-
-def cggi_output_variance(P, log_q, hw_small=None, hw_big=None):
-    """Analytic variance (relative to q^2) of the phase error after one blind rotation, binary keys (CGGI):
-    n CMUXes, each adding  l (k+1) N (Bg^2 + 2) / 12 * sigma_bsk^2  (digits uniform in [-Bg/2, Bg/2) against fresh key noise)
-    +  (1 + k N / 2) / (12 Bg^(2l))  (the rounding of the decomposition, carried by the binary GLWE key).
-    The rounding term as printed in the literature is a worst case: the rounding error of a CMUX is multiplied by the key bit
-    its GGSW encrypts, so only the hw_small SET bits of the LWE key contribute, and it is carried by the hw_big set bits of the
-    GLWE key.  With the weights given, the exact expectation is returned (it matters where the rounding term is not
-    negligible: the torus set, Bg = 2^10); without them, the textbook worst case."""
-    N, k, l, Bg = P.N, P.k, P.bs_levels, 2.0 ** P.bs_base_log
-    key = l * (k + 1) * N * (Bg * Bg + 2) / 12.0 * P.glwe_noise ** 2
-    rnd = (1 + (k * N / 2.0 if hw_big is None else hw_big)) * (1.0 / (12.0 * Bg ** (2 * l)) - 1.0 / (12.0 * 4.0 ** log_q))
-    return P.n * key + (P.n if hw_small is None else hw_small) * rnd
-
-
-def effective_params(eng):
-    """the engine's parameters with the key noise a bootstrap actually sees: a torus key stored at p < 64 bits carries, per row,
-    the rounding error of the body and of the mask words the GLWE key selects (uniform on 2^(64 - p): variance 2^(2 (64 - p)) / 12
-    each), on top of its Gaussian noise"""
-    from bmi_amd import tfhe
-    P = tfhe.Params(**{f: getattr(eng.P, f) for f, _ in tfhe.Params._fields_})
-    prec = eng.bsk_precision
-    if prec != 64:
-        hw = int(eng.export_keys()[1].sum())
-        P.glwe_noise = float(np.sqrt(P.glwe_noise ** 2 + (1 + hw) * 4.0 ** (64 - prec) / 12 / 2.0 ** 128))
-    return P
 
 
 def test_pbs_output_noise_matches_the_cggi_formula(eng):
@@ -345,10 +304,9 @@ def test_pbs_output_noise_matches_the_cggi_formula(eng):
     out = d_out.cpu().numpy().view(np.uint64)
     want = table[msgs + 8]
     assert np.array_equal(eng.decrypt(out, dl), want)
-    Q = eng.modulus
-    err = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(eng.phase(out), want)], dtype=np.float64) / float(Q)
+    err = pc.centred_error(eng.phase(out), want, dl, eng.modulus)
     sk_small, sk_big = eng.export_keys()[:2]
-    measured, analytic = float(np.var(err)), cggi_output_variance(effective_params(eng), eng.log_q, int(sk_small.sum()), int(sk_big.sum()))
+    measured, analytic = float(np.var(err)), pc.cggi_output_variance(pc.effective_params(eng), eng.log_q, int(sk_small.sum()), int(sk_big.sum()))
     ratio = measured / analytic
     print(f"q_bits {eng.q_bits}: log2 std measured {0.5 * np.log2(measured):.2f}, CGGI {0.5 * np.log2(analytic):.2f}, "
           f"variance ratio {ratio:.3f}, max |err| 2^{np.log2(np.abs(err).max()):.2f}")
@@ -373,7 +331,6 @@ def test_torus_key_at_42_bits_of_precision_bit_exact_and_noise():
     table = rng.integers(-8, 8, 16)
     B = 4096
     msgs = rng.integers(-8, 8, B)
-    Q = 1 << 64
     for mode in ("generated", "imported"):
         e = tfhe.Engine(tfhe.default_params(q_bits=65, bs_base_log=15))
         try:
@@ -387,32 +344,31 @@ def test_torus_key_at_42_bits_of_precision_bit_exact_and_noise():
                     e.set_bsk_precision(64)                      # only before keys exist
             else:
                 e.import_keys(exact.sk_small, exact.sk_big, exact.bsk, exact.ksk)
-            sk_small, sk_big, bsk, ksk = e.export_keys()
+            bsk = e.export_keys()[2]
             assert not (bsk & np.uint64((1 << 22) - 1)).any()    # the context's key lives on the 2^22 grid
             if mode == "imported":
                 d = (bsk.astype(np.int64) - exact.bsk.astype(np.int64))   # wrap-around difference = the rounding error
                 assert np.abs(d).max() <= 1 << 21 and abs(float(np.var(d.astype(np.float64))) / (2.0 ** 44 / 12) - 1) < 0.02
-            ctx = to.Ctx(P, bsk, ksk)
             dl = e.delta_log()
             lid = e.lut_register(table, 4, dl)
             ct = e.encrypt(msgs, dl)
             ids = np.full(B, lid, np.uint32)
             out = e.pbs_host(ct, ids)                                  # wave-pair kernel
             pick = rng.choice(B, 6, replace=False)
-            want = ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(6, np.uint32))
+            with pc.oracle_for(e) as o:
+                want = o.ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(6, np.uint32))
             assert np.array_equal(out[pick], want)
             assert np.array_equal(e.pbs_host(ct[pick], ids[:6]), want)  # latency kernel
             assert np.array_equal(e.decrypt(out, dl), table[msgs + 8])
-            err = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(e.phase(out), table[msgs + 8])], dtype=np.float64) / Q
+            err = pc.centred_error(e.phase(out), table[msgs + 8], dl, 1 << 64)
             # effective key noise: the body's rounding error + those of the k N / 2 key-selected mask words
             Pe = tfhe.default_params(q_bits=65, bs_base_log=15)
             words = 1 + Pe.k * Pe.N / 2.0
             Pe.glwe_noise = float(np.sqrt(Pe.glwe_noise ** 2 + words * 2.0 ** 44 / 12 / 2.0 ** 128))
-            ratio = float(np.var(err)) / cggi_output_variance(Pe, 64)
+            ratio = float(np.var(err)) / pc.cggi_output_variance(Pe, 64)
             print(f"torus, 42-bit key ({mode}): output log2 std {0.5 * np.log2(np.var(err)):.2f}, effective key noise 2^{np.log2(Pe.glwe_noise):.2f}, "
                   f"ratio to the CGGI formula {ratio:.3f}")
             assert 0.85 < ratio < 1.15
-            ctx.close()
         finally:
             e.close()
 
@@ -422,58 +378,43 @@ def test_secure128_preset_bit_exact_noise_and_margin():
     rotation and PBS bit-exact against the oracle at these parameters; every 4-bit message through a random table;
     keyswitch noise at its analytic value; the look-up margin it leaves (mod-switch + keyswitch noise vs half a box)."""
     from bmi_amd import tfhe
-    from oracle import tfhe_oracle as to
     P = tfhe.preset_params("secure128")
     assert (P.n, P.N, P.k, P.bs_levels, P.bs_base_log, P.q_bits, P.ks_levels, P.ks_base_log) == (742, 2048, 1, 2, 15, 49, 8, 2) and abs(np.log2(P.lwe_noise) + 17.11) < 0.01
     e = tfhe.Engine(P)
     try:
         e.keygen(SEED + 5)
-        to.set_field(49)
-        OP = to.Params(**{f: getattr(P, f) for f, _ in tfhe.Params._fields_})
-        sk_small, sk_big, bsk, ksk = e.export_keys()
-        K = to.keygen(OP, SEED + 5)
-        assert np.array_equal(K.bsk, bsk) and np.array_equal(K.ksk, ksk) and np.array_equal(K.sk_small, sk_small)
-        ctx = to.Ctx(OP, bsk, ksk)
-        rng = np.random.default_rng(41)
-        dl = e.delta_log()
-        table = rng.integers(-8, 8, 16)
-        lid = e.lut_register(table, 4, dl)
-        msgs = np.concatenate([np.arange(-8, 8)] * 32)                    # 512 ciphertexts, every message 32 times
-        ct = e.encrypt(msgs, dl)
-        small = e.keyswitch_host(ct)
-        assert np.array_equal(small[:40], ctx.keyswitch(ct[:40]))
-        out = e.pbs_host(ct, np.full(msgs.size, lid, np.uint32))
-        pick = rng.choice(msgs.size, 6, replace=False)
-        assert np.array_equal(out[pick], ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(6, np.uint32)))
-        assert np.array_equal(e.decrypt(out, dl), table[msgs + 8])
-        # keyswitch noise: phase error of the small ciphertexts, relative to q
-        Q = e.modulus
-        ph = to.lwe_phase(sk_small, small)
-        err = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(ph, msgs)], dtype=np.float64) / Q
-        B = 2.0 ** P.ks_base_log
-        kN = P.k * P.N
-        analytic = kN * P.ks_levels * (B * B + 2) / 12.0 * P.lwe_noise ** 2 + kN / 2.0 / (12.0 * B ** (2 * P.ks_levels))
+        with pc.oracle_for(e) as o:
+            to, ctx, sk_small = o.to, o.ctx, o.sk_small
+            _, _, bsk, ksk = e.export_keys()
+            K = to.keygen(o.P, SEED + 5)
+            assert np.array_equal(K.bsk, bsk) and np.array_equal(K.ksk, ksk) and np.array_equal(K.sk_small, sk_small)
+            rng = np.random.default_rng(41)
+            dl = e.delta_log()
+            table = rng.integers(-8, 8, 16)
+            lid = e.lut_register(table, 4, dl)
+            msgs = np.concatenate([np.arange(-8, 8)] * 32)                    # 512 ciphertexts, every message 32 times
+            ct = e.encrypt(msgs, dl)
+            small = e.keyswitch_host(ct)
+            assert np.array_equal(small[:40], ctx.keyswitch(ct[:40]))
+            out = e.pbs_host(ct, np.full(msgs.size, lid, np.uint32))
+            pick = rng.choice(msgs.size, 6, replace=False)
+            assert np.array_equal(out[pick], ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(6, np.uint32)))
+            assert np.array_equal(e.decrypt(out, dl), table[msgs + 8])
+            # keyswitch noise: phase error of the small ciphertexts, relative to q
+            err = pc.centred_error(to.lwe_phase(sk_small, small), msgs, dl, e.modulus)
+        analytic = pc.keyswitch_variance(P)
         ratio = float(np.var(err)) / analytic
         # what reaches the blind rotation, in units of the 2N positions of the circle: keyswitch noise + mod-switch rounding
-        sigma_pos = np.sqrt(np.var(err) * (2 * P.N) ** 2 + (P.n / 2.0 + 1) / 12.0)
-        margin = (P.N / 32.0) / sigma_pos       # half a 4-bit box (boxes are N / 2^4 positions wide) in sigmas
+        sigma_pos, margin = pc.lookup_margin(P, np.var(err), 4)
         print(f"secure128: keyswitch log2 std {0.5 * np.log2(np.var(err)):.2f} (analytic {0.5 * np.log2(analytic):.2f}, ratio "
               f"{ratio:.3f}); positions sigma {sigma_pos:.2f} of {2 * P.N}; 4-bit look-up margin {margin:.1f} sigma")
         assert 0.75 < ratio < 1.3 and margin > 8.0
         # bootstrap output noise at (l, Bg) = (2, 2^15): at the CGGI value, far below the keyswitch noise it feeds
-        want_m = table[msgs + 8]
-        oerr = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(e.phase(out), want_m)], dtype=np.float64) / Q
-        oratio = float(np.var(oerr)) / cggi_output_variance(P, 49)
+        oerr = pc.centred_error(e.phase(out), table[msgs + 8], dl, e.modulus)
+        oratio = float(np.var(oerr)) / pc.cggi_output_variance(P, 49)
         print(f"secure128: PBS output log2 std {0.5 * np.log2(np.var(oerr)):.2f} (CGGI ratio {oratio:.3f})")
         assert 0.7 < oratio < 1.4 and np.var(oerr) * 75 ** 2 < np.var(err) / 4     # x75: the widest linear combination of the circuits
-        # latency of one bootstrap and of a full round (256 ciphertexts: one workgroup per CU)
-        import time
-        ids256 = np.full(256, lid, np.uint32)
-        e.pbs_host(ct[:256], ids256)
-        t0 = time.perf_counter(); e.pbs_host(ct[:256], ids256); t256 = time.perf_counter() - t0
-        t0 = time.perf_counter(); e.pbs_host(ct[:1], ids256[:1]); t1 = time.perf_counter() - t0
-        print(f"secure128: 1 PBS {t1 * 1e3:.2f} ms, 256 PBS {t256 * 1e3:.2f} ms (host-buffer calls, copies included)")
-        ctx.close()
+        pc.time_pbs(e, ct, lid, "secure128")
     finally:
         e.close()
 
@@ -498,7 +439,6 @@ def test_other_parameter_shape_bit_exact(q_bits, kw):
     field and (2, 2^15) on the 2^64 torus: keyswitch (both kernels), every blind-rotation kernel and the fused PBS
     against the oracle, every 4-bit message through a random table; an empty batch is a no-op on every entry point."""
     from bmi_amd import tfhe
-    from oracle import tfhe_oracle as to
     kw = dict(kw)
     precision = kw.pop("_precision", None)     # torus: a non-default precision of the stored bootstrap key
     e = tfhe.Engine(tfhe.default_params(q_bits=q_bits, **kw))
@@ -506,42 +446,36 @@ def test_other_parameter_shape_bit_exact(q_bits, kw):
         if precision:
             e.set_bsk_precision(precision)
         e.keygen(SEED + 1)
-        sk_small, sk_big, bsk, ksk = e.export_keys()
-        to.set_field(q_bits)
-        P = to.default_params(q_bits=q_bits, **kw)
-        ctx = to.Ctx(P, bsk, ksk)
-        rng = np.random.default_rng(16)
-        dl = e.delta_log()
-        msgs = rng.integers(-8, 8, 70)
-        ct = e.encrypt(msgs, dl)
-        ct[1, :1024] = rand_q(rng, 1024, e.modulus)
-        want_small = ctx.keyswitch(ct)
-        assert np.array_equal(e.keyswitch_host(ct), want_small)
-        e.set_keyswitch_variant(1)
-        if e.P.n + 1 > 768:     # the scalar keyswitch kernel stops at n = 767: refused, not wrong
-            with pytest.raises(tfhe.BmiError):
-                e.keyswitch_host(ct)
-        else:
+        with pc.oracle_for(e) as o:
+            rng = np.random.default_rng(16)
+            dl = e.delta_log()
+            msgs = rng.integers(-8, 8, 70)
+            ct = e.encrypt(msgs, dl)
+            ct[1, :1024] = pc.rand_q(rng, 1024, e.modulus)
+            want_small = o.ctx.keyswitch(ct)
             assert np.array_equal(e.keyswitch_host(ct), want_small)
-        e.set_keyswitch_variant(0)
-        table = rng.integers(-8, 8, 16)
-        every = np.arange(-8, 8)
-        assert np.array_equal(e.decrypt(e.pbs_host(e.encrypt(every, dl), np.full(16, e.lut_register(table, 4, dl), np.uint32)), dl),
-                              table[every + 8])
-        lid = e.lut_register(rng.integers(-8, 8, 16), 4, dl)
-        tv = e.lut_get(lid)[None, :]
-        ids = np.full(5, lid, np.uint32)
-        want = ctx.blind_rotate(want_small[:5], tv, np.zeros(5, np.uint32))
+            e.set_keyswitch_variant(1)
+            if e.P.n + 1 > 768:     # the scalar keyswitch kernel stops at n = 767: refused, not wrong
+                with pytest.raises(tfhe.BmiError):
+                    e.keyswitch_host(ct)
+            else:
+                assert np.array_equal(e.keyswitch_host(ct), want_small)
+            e.set_keyswitch_variant(0)
+            table = rng.integers(-8, 8, 16)
+            every = np.arange(-8, 8)
+            assert np.array_equal(e.decrypt(e.pbs_host(e.encrypt(every, dl), np.full(16, e.lut_register(table, 4, dl), np.uint32)), dl),
+                                  table[every + 8])
+            lid = e.lut_register(rng.integers(-8, 8, 16), 4, dl)
+            tv = e.lut_get(lid)[None, :]
+            ids = np.full(5, lid, np.uint32)
+            want = o.ctx.blind_rotate(want_small[:5], tv, np.zeros(5, np.uint32))
         for variant in (0, 1, 2, 3, 4):
             if variant in (1, 4) and q_bits == 49:       # the predecessors of the 49-bit kernels are retired: refused
                 with pytest.raises(tfhe.BmiError):
                     e.set_kernel_variant(variant)
                 continue
-            e.set_kernel_variant(variant)
-            assert np.array_equal(e.blind_rotate_host(want_small[:5], ids), want), variant
-        e.set_kernel_variant(0)
-        if e.P.n + 1 > 768:     # the scalar keyswitch kernel stops at n = 767: refused, not wrong
-            pass
+            with pc.pinned_variant(e, variant):
+                assert np.array_equal(e.blind_rotate_host(want_small[:5], ids), want), variant
         assert np.array_equal(e.pbs_host(ct[:5], ids), want)
         empty = np.zeros((0, e.P.big), np.uint64)
         assert e.pbs_host(empty, np.zeros(0, np.uint32)).shape == (0, e.P.big)
@@ -556,7 +490,7 @@ def test_full_batch_properties(eng, ora):
     output decrypts to LUT[m]; a random sample is bit-exact against the oracle; the keyswitch is additive
     (KS(c1 + c2) and KS(c1) + KS(c2) decrypt alike although their digits differ); identical inputs at different
     batch positions give identical outputs (no dependence on the workgroup / wavefront a ciphertext lands in)."""
-    to, P, ctx, sk_small, sk_big, _, _ = ora
+    to, ctx, sk_small, sk_big = ora.to, ora.ctx, ora.sk_small, ora.sk_big
     rng = np.random.default_rng(17)
     B = 8192
     dl = eng.delta_log()
@@ -591,7 +525,6 @@ def test_context_lifecycle_rekey_growth_and_two_contexts():
     """One context re-keyed with a second seed (device keys, limb-form keyswitch key and latency-kernel key copy must
     all follow), scratch growth past bmi_reserve, and two contexts (one per field) alive on the same GPU."""
     from bmi_amd import tfhe
-    from oracle import tfhe_oracle as to
     e49 = tfhe.Engine(tfhe.default_params(q_bits=49))
     e64 = tfhe.Engine(tfhe.default_params(q_bits=64))
     try:
@@ -599,20 +532,16 @@ def test_context_lifecycle_rekey_growth_and_two_contexts():
         table = rng.integers(-8, 8, 16)
         for seed in (11, 12):
             e49.keygen(seed)
-            to.set_field(49)
-            _, _, bsk, ksk = e49.export_keys()
-            ctx = to.Ctx(to.default_params(q_bits=49), bsk, ksk)
             dl = e49.delta_log()
             lid = e49.lut_register(table, 4, dl)
             msgs = rng.integers(-8, 8, 6)
             ct = e49.encrypt(msgs, dl)
             ids = np.full(6, lid, np.uint32)
-            want = ctx.pbs(ct, e49.lut_get(lid)[None, :], np.zeros(6, np.uint32))
+            with pc.oracle_for(e49) as o:
+                want = o.ctx.pbs(ct, e49.lut_get(lid)[None, :], np.zeros(6, np.uint32))
             assert np.array_equal(e49.pbs_host(ct, ids), want), seed                     # latency kernel + its key copy
-            e49.set_kernel_variant(3)
-            assert np.array_equal(e49.pbs_host(ct, ids), want), seed                     # throughput kernel
-            e49.set_kernel_variant(0)
-            ctx.close()
+            with pc.pinned_variant(e49, 3):
+                assert np.array_equal(e49.pbs_host(ct, ids), want), seed                 # throughput kernel
         # growth: reserve small, then run a batch 40x larger (scratch buffers reallocate under queued work)
         e49.reserve(32)
         big = rng.integers(-8, 8, 1300)
@@ -685,44 +614,41 @@ def test_wider_parameter_sets_bit_exact(log_N):
     matrix-core product), blind rotation and the fused PBS against the oracle; every 4-bit message through a random
     table; ragged batch; one more message bit per doubling of N at the same margin (5-bit / 6-bit look-ups)."""
     from bmi_amd import tfhe
-    from oracle import tfhe_oracle as to
     N = 1 << log_N
     e = tfhe.Engine(tfhe.default_params(q_bits=49, log_N=log_N))
     try:
         e.keygen(SEED + 2)
-        to.set_field(49)
-        P = to.default_params(q_bits=49, log_N=log_N)
-        sk_small, sk_big, bsk, ksk = e.export_keys()
-        K = to.keygen(P, SEED + 2)
-        assert np.array_equal(K.bsk, bsk) and np.array_equal(K.ksk, ksk) and np.array_equal(K.sk_big, sk_big)
-        ctx = to.Ctx(P, bsk, ksk)
-        rng = np.random.default_rng(20)
-        dl = e.delta_log()
-        table = rng.integers(-8, 8, 16)
-        lid = e.lut_register(table, 4, dl)
-        assert np.array_equal(e.lut_get(lid), to.make_test_vector(log_N, 4, table, dl))
-        msgs = np.concatenate([np.arange(-8, 8), rng.integers(-8, 8, 5)])   # 21: ragged against every tile size
-        ct = e.encrypt(msgs, dl)
-        assert ct.shape == (21, N + 1)
-        small = e.keyswitch_host(ct)
-        assert np.array_equal(small, ctx.keyswitch(ct))
-        ids = np.full(msgs.size, lid, np.uint32)
-        out = e.pbs_host(ct, ids)
-        assert list(e.decrypt(out, dl)) == list(table[msgs + 8])
-        pick = np.array([0, 7, 15, 20])
-        want = ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(pick.size, np.uint32))
-        assert np.array_equal(out[pick], want)
-        assert np.array_equal(e.blind_rotate_host(small[pick], ids[pick]), want)
-        with pytest.raises(tfhe.BmiError):
-            e.negacyclic_mul_host(np.zeros((1, N), np.uint64), np.zeros((1, N), np.uint64))
-        # 5-bit (N = 2048) / 6-bit (N = 4096) messages fit these rings at the margin 4-bit ones have at N = 1024
-        pw = log_N - 6
-        tw = rng.integers(-(1 << (pw - 1)), 1 << (pw - 1), 1 << pw)
-        lw = e.lut_register(tw, pw, e.q_bits - 1 - pw)
-        mw = np.concatenate([rng.integers(-(1 << (pw - 1)), 1 << (pw - 1), 10), [-(1 << (pw - 1)), (1 << (pw - 1)) - 1]])
-        ow = e.pbs_host(e.encrypt(mw, e.q_bits - 1 - pw), np.full(mw.size, lw, np.uint32))
-        assert list(e.decrypt(ow, e.q_bits - 1 - pw)) == list(tw[mw + (1 << (pw - 1))])
-        ctx.close()
+        _, _, bsk, ksk = e.export_keys()
+        with pc.oracle_for(e) as o:
+            to = o.to
+            K = to.keygen(o.P, SEED + 2)
+            assert np.array_equal(K.bsk, bsk) and np.array_equal(K.ksk, ksk) and np.array_equal(K.sk_big, o.sk_big)
+            rng = np.random.default_rng(20)
+            dl = e.delta_log()
+            table = rng.integers(-8, 8, 16)
+            lid = e.lut_register(table, 4, dl)
+            assert np.array_equal(e.lut_get(lid), to.make_test_vector(log_N, 4, table, dl))
+            msgs = np.concatenate([np.arange(-8, 8), rng.integers(-8, 8, 5)])   # 21: ragged against every tile size
+            ct = e.encrypt(msgs, dl)
+            assert ct.shape == (21, N + 1)
+            small = e.keyswitch_host(ct)
+            assert np.array_equal(small, o.ctx.keyswitch(ct))
+            ids = np.full(msgs.size, lid, np.uint32)
+            out = e.pbs_host(ct, ids)
+            assert list(e.decrypt(out, dl)) == list(table[msgs + 8])
+            pick = np.array([0, 7, 15, 20])
+            want = o.ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(pick.size, np.uint32))
+            assert np.array_equal(out[pick], want)
+            assert np.array_equal(e.blind_rotate_host(small[pick], ids[pick]), want)
+            with pytest.raises(tfhe.BmiError):
+                e.negacyclic_mul_host(np.zeros((1, N), np.uint64), np.zeros((1, N), np.uint64))
+            # 5-bit (N = 2048) / 6-bit (N = 4096) messages fit these rings at the margin 4-bit ones have at N = 1024
+            pw = log_N - 6
+            tw = rng.integers(-(1 << (pw - 1)), 1 << (pw - 1), 1 << pw)
+            lw = e.lut_register(tw, pw, e.q_bits - 1 - pw)
+            mw = np.concatenate([rng.integers(-(1 << (pw - 1)), 1 << (pw - 1), 10), [-(1 << (pw - 1)), (1 << (pw - 1)) - 1]])
+            ow = e.pbs_host(e.encrypt(mw, e.q_bits - 1 - pw), np.full(mw.size, lw, np.uint32))
+            assert list(e.decrypt(ow, e.q_bits - 1 - pw)) == list(tw[mw + (1 << (pw - 1))])
     finally:
         e.close()
     with pytest.raises(tfhe.BmiError):
@@ -755,10 +681,9 @@ def test_pbs_known_answer_digests_on_gpu():
             out = e.pbs_host(ct, np.full(len(kat["msgs"]), lid, np.uint32))
             assert h(out) == case["bootstrapped"]
             for variant in (() if case["log_N"] != 10 else (2, 3) if case["q_bits"] == 49 else (1, 2, 3, 4)):
-                e.set_kernel_variant(variant)
-                assert h(e.pbs_host(ct, np.full(len(kat["msgs"]), lid, np.uint32))) == case["bootstrapped"], variant
+                with pc.pinned_variant(e, variant):
+                    assert h(e.pbs_host(ct, np.full(len(kat["msgs"]), lid, np.uint32))) == case["bootstrapped"], variant
             if "bootstrapped_unrolled" in case:      # the unrolled key of the same secrets, made at once (bmi_set_bsk_unroll)
-                e.set_kernel_variant(0)
                 e.set_bsk_unroll(2)
                 assert h(e.export_bsk_unrolled()) == case["bsk_unrolled"]
                 assert h(e.pbs_host(ct, np.full(len(kat["msgs"]), lid, np.uint32))) == case["bootstrapped_unrolled"]
@@ -788,7 +713,7 @@ def test_torus64_client_interop(q_bits):
         lid = e.lut_register(table, p, e.delta_log(p))
         msgs = np.concatenate([np.arange(-8, 8), rng.integers(-8, 8, 112)])
         # client-side encryption on the 2^64 torus (uint64 arithmetic wraps mod 2^64)
-        a = rng.integers(0, 1 << 63, (msgs.size, kN), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (msgs.size, kN), dtype=np.uint64)
+        a = pc.uniform_words(rng, (msgs.size, kN))
         noise = np.rint(rng.normal(0.0, P.glwe_noise * 2.0**64, msgs.size)).astype(np.int64).astype(np.uint64)
         body = (a * sk_big[None, :]).sum(axis=1, dtype=np.uint64) + (msgs.astype(np.int64) << (63 - p)).astype(np.uint64) + noise
         ct_torus = np.concatenate([a, body[:, None]], axis=1)

@@ -5,18 +5,18 @@ at 42 bits = two 21-bit limbs so that the six-times larger sums stay inside the 
 oracle/tfhe_oracle.c ora_blind_rotate_extract_unrolled (integer arithmetic: coefficient-domain rotation, Goldilocks transforms of
 the key's 32-bit halves) on the same rounded keys; the rounding distance of the limb sums; output noise on the formula; BASELINE
 configs 2-4 through EncryptedMatrixInversion(q_bits=65, unroll=True) against the reference's golden digits."""
-import json
-import os
-import time
-
 import numpy as np
 import pytest
+
+import pbs_cases as pc
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED
 QB = 65
 PREC = 42
+# the 42-bit key: every key and accumulator word on the 2^22 grid; 6 random rows to the oracle beside the fixed ones; f64 accumulator
+CFG = pc.UnrolledConfig(q_bits=QB, precision=PREC, grid_mask=(1 << 22) - 1, oracle_rows=6, margin_hook=True)
 
 
 def _engine(seed=SEED, **kw):
@@ -29,16 +29,6 @@ def _engine(seed=SEED, **kw):
     return e
 
 
-def _oracle(eng):
-    from oracle import tfhe_oracle as to
-    to.set_field(QB)
-    sk_small, sk_big, bsk, ksk = eng.export_keys()
-    P = to.default_params(q_bits=QB, n=eng.P.n, bs_levels=eng.P.bs_levels, bs_base_log=eng.P.bs_base_log)
-    ctx = to.Ctx(P, bsk, ksk)
-    ctx.set_bsk_unrolled(eng.export_bsk_unrolled())
-    return to, P, ctx, sk_small, sk_big
-
-
 @pytest.fixture(scope="module")
 def eng():
     e = _engine()
@@ -48,16 +38,7 @@ def eng():
 
 def test_keys_are_the_oracles_rounded_to_42_bits_and_plain_pbs_is_refused(eng):
     from bmi_amd import tfhe
-    from oracle import tfhe_oracle as to
-    to.set_field(QB)
-    P = to.default_params(q_bits=QB)
-    assert eng.bsk_precision == PREC
-    K = to.keygen(P, SEED)
-    _, _, bsk, ksk = eng.export_keys()
-    assert np.array_equal(to.round_key(K.bsk, PREC), bsk) and np.array_equal(K.ksk, ksk)
-    bsk3 = eng.export_bsk_unrolled()
-    assert np.array_equal(to.round_key(to.keygen_bsk_unrolled(P, SEED, K.sk_small, K.sk_big), PREC), bsk3)
-    assert not (bsk3 & np.uint64((1 << 22) - 1)).any()
+    pc.check_unrolled_seeded_keys(eng, CFG, SEED)
     # the 42-bit key at base 2^10 exists for the unrolled kernel only: a context in plain mode refuses the precision, and one that
     # leaves the unrolled mode with the precision pinned refuses to bootstrap
     e = tfhe.Engine(tfhe.default_params(q_bits=QB))
@@ -82,64 +63,32 @@ def test_two_ciphertexts_per_workgroup_give_the_same_words(eng, count):
     rng = np.random.default_rng(1000 + count)
     lid = eng.lut_register(rng.integers(-8, 8, 16), 4, eng.delta_log())
     ids = np.full(count, lid, np.uint32)
-    small = rng.integers(0, 1 << 63, (count, eng.P.small), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (count, eng.P.small), dtype=np.uint64)
+    small = pc.uniform_words(rng, (count, eng.P.small))
     small[0] = 0                                   # a ciphertext whose every step is skipped beside one that takes them all
     if count > 2:
         small[2, ::2] = 0
         small[count - 1, 14::16] = 0
         small[count - 1, 15::16] = 0
-    try:
-        eng.set_kernel_variant(2)
+    with pc.pinned_variant(eng, 2):
         one = eng.blind_rotate_host(small, ids)
-        eng.set_kernel_variant(1)
+    with pc.pinned_variant(eng, 1):
         two = eng.blind_rotate_host(small, ids)
-    finally:
-        eng.set_kernel_variant(0)
     assert np.array_equal(one, two)
     assert np.array_equal(eng.blind_rotate_host(small, ids), one)     # auto: whichever it picked
 
 
 @pytest.mark.parametrize("count", [1, 5, 300, 700])
 def test_unrolled_fft_pbs_bit_exact_every_batch_size(eng, count):
-    to, P, ctx, sk_small, sk_big = _oracle(eng)
-    rng = np.random.default_rng(count)
-    dl = eng.delta_log()
-    tables = [np.arange(-8, 8), rng.integers(-8, 8, 16)]
-    lids = [eng.lut_register(t, 4, dl) for t in tables]
-    tvs = np.stack([eng.lut_get(l) for l in lids])
-    msgs = rng.integers(-8, 8, count)
-    sel = rng.integers(0, 2, count).astype(np.uint32)
-    ct = eng.encrypt(msgs, dl)
-    got = eng.pbs_host(ct, np.array(lids, np.uint32)[sel])
-    assert list(eng.decrypt(got, dl)) == [int(tables[s][m + 8]) for s, m in zip(sel, msgs)]
-    assert not (got & np.uint64((1 << 22) - 1)).any()      # the accumulator lives on the key's 2^22 grid
-    pick = np.arange(count) if count <= 8 else np.unique(np.concatenate([[0, count - 1, 255, 256, 511, 512][:6], rng.integers(0, count, 6)]) % count)
-    assert np.array_equal(got[pick], ctx.pbs(ct[pick], tvs, sel[pick], unrolled=True))
-    ctx.close()
+    pc.check_unrolled_pbs_every_batch_size(eng, CFG, count)
 
 
 def test_unrolled_fft_blind_rotation_extreme_inputs_and_rounding_margin(eng):
     """arbitrary small-key words (zeros, maxima, pair sums that wrap 2N, skipped steps) straight into the blind rotation; and the
     largest distance of a limb sum from the integer it is rounded to over 512 bootstraps of uniformly random words (digits at
     their full range): far below 1/2 (a-priori bound 0.29)"""
-    to, P, ctx, sk_small, sk_big = _oracle(eng)
-    rng = np.random.default_rng(11)
-    small = rng.integers(0, 2 ** 63, (10, P.n + 1), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (10, P.n + 1), dtype=np.uint64)
-    small[0] = 0                                # every exponent zero: the accumulator is the test polynomial
-    small[1] = np.uint64(2 ** 64 - 1)
-    small[2] = np.uint64(2 ** 63)               # every a = N: the pair sums wrap to 0
-    small[3, ::2] = 0                           # first coefficient of every pair zero
-    small[4, 1::2] = 0
-    small[5, :-1] = np.uint64(2 ** 53)          # a = 1 everywhere
-    small[6, 14::16] = 0                        # a whole pair zero every eighth step: the f64 accumulator is re-centred every
-    small[6, 15::16] = 0                        # eight steps TAKEN
-    lid = eng.lut_register(rng.integers(-8, 8, 16), 4, eng.delta_log())
-    ids = np.full(10, lid, np.uint32)
-    got = eng.blind_rotate_host(small, ids)
-    assert np.array_equal(got, ctx.blind_rotate(small, eng.lut_get(lid)[None, :], np.zeros(10, np.uint32), unrolled=True))
-    ctx.close()
+    rng, lid = pc.check_unrolled_extreme_inputs(eng, CFG, rows=10)
     count = 512
-    rnd = rng.integers(0, 1 << 63, (count, P.n + 1), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (count, P.n + 1), dtype=np.uint64)
+    rnd = pc.uniform_words(rng, (count, eng.P.n + 1))
     out, dist = eng.fft_margin_host(rnd, np.full(count, lid, np.uint32))
     print(f"\nunrolled FFT kernel: largest distance from an integer before rounding 2^{np.log2(max(dist, 1e-300)):.1f}")
     assert 0.0 < dist < 2.0 ** -7, dist
@@ -150,18 +99,7 @@ def test_unrolled_fft_blind_rotation_extreme_inputs_and_rounding_margin(eng):
 def test_unrolled_fft_other_shapes_bit_exact(kw):
     e = _engine(seed=77, **kw)
     try:
-        to, P, ctx, sk_small, sk_big = _oracle(e)
-        rng = np.random.default_rng(3)
-        dl = e.delta_log()
-        table = rng.integers(-8, 8, 16)
-        lid = e.lut_register(table, 4, dl)
-        msgs = rng.integers(-8, 8, 6)
-        ct = e.encrypt(msgs, dl)
-        got = e.pbs_host(ct, np.full(6, lid, np.uint32))
-        if kw.get("n") != 1:
-            assert list(e.decrypt(got, dl)) == [int(table[m + 8]) for m in msgs]
-        assert np.array_equal(got, ctx.pbs(ct, e.lut_get(lid)[None, :], np.zeros(6, np.uint32), unrolled=True))
-        ctx.close()
+        pc.check_unrolled_other_shape(e, decrypts=kw.get("n") != 1)   # (one coefficient cannot hold a message's phase)
     finally:
         e.close()
 
@@ -181,16 +119,9 @@ def test_unrolled_fft_output_noise_on_the_formula_and_timing(eng, capsys):
     out = eng.pbs_host(ct, np.full(count, lid, np.uint32))
     want = table[msgs + 8]
     assert np.array_equal(eng.decrypt(out, dl), want)
-    Q = 1 << 64
-    err = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(eng.phase(out), want)], dtype=np.float64) / Q
-    sk_small, sk_big = eng.export_keys()[:2]
-    pairs = sk_small[0::2].copy()
-    pairs[:sk_small[1::2].size] |= sk_small[1::2]
+    err = pc.centred_error(eng.phase(out), want, dl, 1 << 64)
     P = eng.P
-    Bg = 2.0 ** P.bs_base_log
-    hb = int(sk_big.sum())
-    s2 = P.glwe_noise ** 2 + (1 + hb) * 4.0 ** (64 - PREC) / 12 / 2.0 ** 128
-    analytic = 3 * P.n * P.bs_levels * 2 * P.N * (Bg * Bg + 2) / 12.0 * s2 + 2 * int(pairs.sum()) * (1 + hb) / (12.0 * Bg ** (2 * P.bs_levels))
+    analytic = pc.unrolled_torus_variance(eng)
     ratio = float(np.var(err)) / analytic
     model = error_budget.pbs_output_variance(P, PREC, unroll=True)
     dev = torch.device("cuda:0")
@@ -218,20 +149,10 @@ def test_unrolled_fft_output_noise_on_the_formula_and_timing(eng, capsys):
 @pytest.mark.parametrize("tag", ["baseline_n2_len20_ints8", "baseline_n3_len30_ints12", "baseline_n4_len40_ints16"])
 def test_encrypted_inverse_with_the_unrolled_fft_kernel_matches_reference_golden(eng, tag, capsys):
     from bmi_amd.main import EncryptedMatrixInversion
-    with open(os.path.join(os.path.dirname(__file__), "golden", "inverse.json")) as f:
-        c = next(x for x in json.load(f) if x["tag"] == tag)
+    c = pc.golden_inverse(tag)
     emi = EncryptedMatrixInversion(c["n"], None, 2, c["len"], c["ints"], False, False, engine=eng, unroll=True)
-    M = np.array(c["M"]).reshape(c["n"], c["n"])
-    q, s = emi.quantize(M)
-    enc = emi.encrypt(q, s)
-    emi._executor()
-    emi.evaluate(enc)                           # warm-up
-    t0 = time.time()
-    res = emi.evaluate(enc)
-    wall = time.time() - t0
-    out = emi.decrypt(res)
-    assert out.tolist() == c["out"], f"circuit failure probability by noise under these parameters: {emi.error_budget['p_fail']:.1e}"
-    depth = emi.circuit.summary()["depth"]
+    out, wall, depth = pc.timed_inverse(emi, c, warm_up=True)
+    assert out == c["out"], f"circuit failure probability by noise under these parameters: {emi.error_budget['p_fail']:.1e}"
     with capsys.disabled():
         print(f"\ntorus, unrolled FFT kernel, {tag}: evaluate {wall:.2f} s, {depth} levels, {wall / depth * 1e3:.2f} ms per level, "
               f"p_fail {emi.error_budget['p_fail']:.1e}")

@@ -6,9 +6,13 @@ import time
 import numpy as np
 import pytest
 
+import pbs_cases as pc
+
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED
+# the exact key of the 49-bit field: no grid; 10 random rows to the oracle beside the fixed ones
+CFG = pc.UnrolledConfig(q_bits=49, precision=64, grid_mask=0, oracle_rows=10, margin_hook=False)
 
 
 def _engine(seed=SEED, **kw):
@@ -19,16 +23,6 @@ def _engine(seed=SEED, **kw):
     return e
 
 
-def _oracle(eng, bsk3=None):
-    from oracle import tfhe_oracle as to
-    to.set_field(49)
-    sk_small, sk_big, bsk, ksk = eng.export_keys()
-    P = to.default_params(q_bits=49, n=eng.P.n, log_N=eng.P.log_N, bs_levels=eng.P.bs_levels, bs_base_log=eng.P.bs_base_log)
-    ctx = to.Ctx(P, bsk, ksk)
-    ctx.set_bsk_unrolled(eng.export_bsk_unrolled() if bsk3 is None else bsk3)
-    return to, P, ctx, sk_small, sk_big
-
-
 @pytest.fixture(scope="module")
 def eng():
     e = _engine()
@@ -37,53 +31,16 @@ def eng():
 
 
 def test_seeded_unrolled_keygen_matches_the_oracle_keygen(eng):
-    from oracle import tfhe_oracle as to
-    to.set_field(49)
-    P = to.default_params(q_bits=49)
-    K = to.keygen(P, SEED)
-    sk_small, sk_big, bsk, _ = eng.export_keys()
-    assert np.array_equal(K.sk_small, sk_small) and np.array_equal(K.bsk, bsk)
-    assert np.array_equal(to.keygen_bsk_unrolled(P, SEED, K.sk_small, K.sk_big), eng.export_bsk_unrolled())
+    pc.check_unrolled_seeded_keys(eng, CFG, SEED)
 
 
 @pytest.mark.parametrize("count", [1, 5, 300, 700])
 def test_unrolled_pbs_bit_exact_every_batch_size(eng, count):
-    """one kernel for every batch size: the ciphertext bits do not depend on the batch a ciphertext travelled in"""
-    to, P, ctx, sk_small, sk_big = _oracle(eng)
-    rng = np.random.default_rng(count)
-    dl = eng.delta_log()
-    tables = [np.arange(-8, 8), rng.integers(-8, 8, 16)]
-    lids = [eng.lut_register(t, 4, dl) for t in tables]
-    tvs = np.stack([eng.lut_get(l) for l in lids])
-    msgs = rng.integers(-8, 8, count)
-    sel = rng.integers(0, 2, count).astype(np.uint32)
-    ct = eng.encrypt(msgs, dl)
-    got = eng.pbs_host(ct, np.array(lids, np.uint32)[sel])
-    assert list(eng.decrypt(got, dl)) == [int(tables[s][m + 8]) for s, m in zip(sel, msgs)]
-    pick = np.arange(count) if count <= 8 else np.unique(np.concatenate([[0, count - 1, 255, 256, 511, 512][:6], rng.integers(0, count, 10)]) % count)
-    want = ctx.pbs(ct[pick], tvs, sel[pick], unrolled=True)
-    assert np.array_equal(got[pick], want)
-    ctx.close()
+    pc.check_unrolled_pbs_every_batch_size(eng, CFG, count)
 
 
 def test_unrolled_blind_rotation_extreme_inputs(eng):
-    """arbitrary small-key words (zeros, maxima, the pair sums that wrap 2N) straight into the blind rotation"""
-    to, P, ctx, sk_small, sk_big = _oracle(eng)
-    Q = eng.modulus
-    rng = np.random.default_rng(11)
-    small = rng.integers(0, Q, (12, P.n + 1), dtype=np.uint64)
-    small[0] = 0                                # every exponent zero: the accumulator is the test polynomial
-    small[1] = np.uint64(Q - 1)
-    small[2] = np.uint64(Q // 2)                # every a = N: the pair sums wrap to 0
-    small[3, ::2] = 0                           # first coefficient of every pair zero
-    small[4, 1::2] = 0
-    small[5, :-1] = np.uint64((Q + 2047) // 2048)   # a = 1 everywhere
-    lid = eng.lut_register(rng.integers(-8, 8, 16), 4, eng.delta_log())
-    ids = np.full(12, lid, np.uint32)
-    got = eng.blind_rotate_host(small, ids)
-    want = ctx.blind_rotate(small, eng.lut_get(lid)[None, :], np.zeros(12, np.uint32), unrolled=True)
-    assert np.array_equal(got, want)
-    ctx.close()
+    pc.check_unrolled_extreme_inputs(eng, CFG, rows=12)
 
 
 # (l, Bg) = (1, 2^23): a 23-bit digit multiplies the key noise by 2^22 / sqrt(12); with three products per step the default
@@ -93,20 +50,12 @@ def test_unrolled_blind_rotation_extreme_inputs(eng):
                                 dict(log_N=11, bs_levels=1, bs_base_log=23, glwe_noise=2.0 ** -46)],
                          ids=["odd_n", "n1024", "l2", "l1", "n1", "N2048_l2", "N2048_l2_odd_n", "N2048_l1"])
 def test_unrolled_other_shapes_bit_exact(kw):
+    from oracle import tfhe_oracle as to
     e = _engine(seed=77, **kw)
     try:
-        to, P, ctx, sk_small, sk_big = _oracle(e)
-        rng = np.random.default_rng(3)
-        dl = e.delta_log()
-        table = rng.integers(-8, 8, 16)
-        lid = e.lut_register(table, 4, dl)
-        msgs = rng.integers(-8, 8, 6)
-        ct = e.encrypt(msgs, dl)
-        got = e.pbs_host(ct, np.full(6, lid, np.uint32))
-        if kw.get("n") != 1:      # (one coefficient cannot hold a message's phase; the bits are still compared)
-            assert list(e.decrypt(got, dl)) == [int(table[m + 8]) for m in msgs]
-        assert np.array_equal(got, ctx.pbs(ct, e.lut_get(lid)[None, :], np.zeros(6, np.uint32), unrolled=True))
-        ctx.close()
+        # the oracle's own parameter set (its key noise is the default where the engine's is lowered: evaluation does not read it)
+        P = to.default_params(q_bits=49, n=e.P.n, log_N=e.P.log_N, bs_levels=e.P.bs_levels, bs_base_log=e.P.bs_base_log)
+        pc.check_unrolled_other_shape(e, decrypts=kw.get("n") != 1, params=P)   # (one coefficient cannot hold a message's phase)
     finally:
         e.close()
 
@@ -123,35 +72,7 @@ def test_unrolling_is_refused_where_no_kernel_exists():
 
 
 def test_unrolled_key_under_csprng_and_on_an_evaluation_only_context():
-    """production key generation (no seed): the unrolled key is exported to the oracle; a second, evaluation-only context
-    imports both evaluation keys and reproduces the same ciphertexts"""
-    from bmi_amd import tfhe
-    e = tfhe.Engine(tfhe.default_params(q_bits=49))
-    e.keygen()                                  # plain keys first ...
-    e.set_bsk_unroll(2)                         # ... the unrolled key is derived from the secret keys already held
-    ev = tfhe.Engine(tfhe.default_params(q_bits=49))
-    try:
-        to, P, ctx, sk_small, sk_big = _oracle(e)
-        rng = np.random.default_rng(8)
-        dl = e.delta_log()
-        table = rng.integers(-8, 8, 16)
-        msgs = rng.integers(-8, 8, 9)
-        ct = e.encrypt(msgs, dl)
-        lid = e.lut_register(table, 4, dl)
-        got = e.pbs_host(ct, np.full(9, lid, np.uint32))
-        assert list(e.decrypt(got, dl)) == [int(table[m + 8]) for m in msgs]
-        assert np.array_equal(got, ctx.pbs(ct, e.lut_get(lid)[None, :], np.zeros(9, np.uint32), unrolled=True))
-        _, _, bsk, ksk = e.export_keys(secret=False)
-        ev.import_keys(None, None, bsk, ksk)
-        ev.set_bsk_unroll(2)
-        with pytest.raises(tfhe.BmiError):      # unrolling selected, no unrolled key yet
-            ev.pbs_host(ct, np.full(9, ev.lut_register(table, 4, dl), np.uint32))
-        ev.import_bsk_unrolled(e.export_bsk_unrolled())
-        assert np.array_equal(ev.pbs_host(ct, np.full(9, ev.lut_register(table, 4, dl), np.uint32)), got)
-        ctx.close()
-    finally:
-        e.close()
-        ev.close()
+    pc.check_unrolled_csprng_key_and_evaluation_only_context(49, count=9)
 
 
 def test_key_files_carry_the_unrolled_key(eng, tmp_path):
@@ -186,7 +107,6 @@ def test_key_files_carry_the_unrolled_key(eng, tmp_path):
 def test_unrolled_output_noise_on_the_formula_and_timing(eng, capsys):
     """4,096 bootstraps: output variance = 3 x the key-noise term of the CGGI value (+ the unchanged decomposition term);
     prints the per-bootstrap latency of the unrolled kernel next to the plain latency kernel's"""
-    from bmi_amd import tfhe
     rng = np.random.default_rng(21)
     B = 4096
     dl = eng.delta_log()
@@ -196,34 +116,13 @@ def test_unrolled_output_noise_on_the_formula_and_timing(eng, capsys):
     ct = eng.encrypt(msgs, dl)
     out = eng.pbs_host(ct, np.full(B, lid, np.uint32))
     assert list(eng.decrypt(out, dl)) == list(msgs)
-    q = float(eng.modulus)
-    err = eng.phase(out).astype(np.int64) - (msgs.astype(np.int64) << dl)
-    err = np.where(err > q / 2, err - q, np.where(err < -q / 2, err + q, err)) / q
-    P = eng.P
-    N, l, Bg = 1024, P.bs_levels, 2.0 ** P.bs_base_log
-    key_term = P.n * l * 2 * N * (Bg * Bg + 2) / 12 * P.glwe_noise ** 2
-    dec_term = P.n * (1 + N / 2) / (12 * Bg ** (2 * l))
-    want = 3 * key_term + dec_term / 2
+    err = pc.centred_error(eng.phase(out), msgs, dl, eng.modulus)
+    want = pc.unrolled_field_variance(eng.P)
     ratio = float(np.mean(err ** 2)) / want
-    plain = tfhe.Engine(tfhe.default_params(q_bits=49))
-    plain.keygen(SEED)
-    t = {}
-    for name, e in (("unrolled", eng), ("plain latency kernel", plain)):
-        l2 = e.lut_register(ident, 4, dl)
-        for cnt in (1, 256):
-            c = e.encrypt(msgs[:cnt], dl)
-            ids = np.full(cnt, l2, np.uint32)
-            small = e.keyswitch_host(c)
-            e.blind_rotate_host(small, ids)
-            t0 = time.perf_counter()
-            for _ in range(3):
-                e.blind_rotate_host(small, ids)
-            t[(name, cnt)] = (time.perf_counter() - t0) / 3 * 1e3
-    plain.close()
+    timing = pc.time_blind_rotation_beside_plain(eng, SEED, ident, msgs, dl)
     with capsys.disabled():
         print(f"\nunrolled PBS: output log2 std {0.5 * np.log2(np.mean(err ** 2)):.2f} (3 x key term + dec/2: {0.5 * np.log2(want):.2f}, "
-              f"variance ratio {ratio:.3f}); blind rotation ms (host-buffer calls, copies included): "
-              + ", ".join(f"{k[0]} x{k[1]}: {v:.2f}" for k, v in t.items()))
+              f"variance ratio {ratio:.3f}); blind rotation ms (host-buffer calls, copies included): " + timing)
     assert 0.9 < ratio < 1.1
 
 
@@ -233,30 +132,18 @@ def test_encrypted_inverse_with_the_unrolled_key_matches_reference_golden(tag, c
     """BASELINE configs 2-5, the overflow-digit cases and the true-division / tensorize modes on ciphertexts with
     EncryptedMatrixInversion(unroll=True): decrypted digits == the reference's plaintext QFloat output
     (tests/golden/inverse.json, generated from the reference)."""
-    import json, os
     from bmi_amd.main import EncryptedMatrixInversion
-    with open(os.path.join(os.path.dirname(__file__), "golden", "inverse.json")) as f:
-        cases = json.load(f)
-    c = next(x for x in cases if x["tag"] == tag)
+    c = pc.golden_inverse(tag)
     emi = EncryptedMatrixInversion(c["n"], None, 2, c["len"], c["ints"], c["true_division"], c["tensorize"], unroll=True, q_bits=49)
     try:
         emi.keygen()                                # CSPRNG keys
         assert emi.engine.P.glwe_noise == 2.0 ** -41
-        M = np.array(c["M"]).reshape(c["n"], c["n"])
-        q, s = emi.quantize(M)
-        enc = emi.encrypt(q, s)
-        emi._executor()
-        if c["n"] < 8:
-            emi.evaluate(enc)                       # warm-up
-        t0 = time.time()
-        res = emi.evaluate(enc)
-        wall = time.time() - t0
-        out = emi.decrypt(res)
-        assert out.tolist() == c["out"], ("digits differ" + ("; the 8x8 runs 2.1 M look-ups at the 6.2 sigma decision margin the north star's (n 630, "
-                                          "N 1024, 4-bit messages) leave: about 1 run in 1,000 fails by noise alone - rerun once before "
-                                          "suspecting the kernels" if c["n"] == 8 else ""))
+        out, wall, depth = pc.timed_inverse(emi, c, warm_up=c["n"] < 8)
+        assert out == c["out"], ("digits differ" + ("; the 8x8 runs 2.1 M look-ups at the 6.2 sigma decision margin the north star's (n 630, "
+                                 "N 1024, 4-bit messages) leave: about 1 run in 1,000 fails by noise alone - rerun once before "
+                                 "suspecting the kernels" if c["n"] == 8 else ""))
         with capsys.disabled():
-            print(f"\nunrolled key, {tag}: evaluate {wall:.2f} s, {emi.circuit.summary()['depth']} levels, {wall / emi.circuit.summary()['depth'] * 1e3:.2f} ms per level")
+            print(f"\nunrolled key, {tag}: evaluate {wall:.2f} s, {depth} levels, {wall / depth * 1e3:.2f} ms per level")
     finally:
         emi.engine.close()
 
@@ -265,10 +152,8 @@ def test_secure128_preset_with_the_unrolled_key(capsys):
     """The 128-bit-secure preset (n 742, N 2048, l = 2) on the unrolled key: bit-exact against the oracle's unrolled mode under
     CSPRNG keys, output noise on the 3 x formula and still far below the keyswitch noise it feeds (the look-up margin is set by
     the latter), latency beside the plain kernel's, and the encrypted 2x2 inverse decrypting to the reference's digits."""
-    import json, os
     from bmi_amd import tfhe
     from bmi_amd.main import EncryptedMatrixInversion
-    from oracle import tfhe_oracle as to
     P = tfhe.preset_params("secure128")
     e = tfhe.Engine(P)
     plain = tfhe.Engine(P)
@@ -276,11 +161,6 @@ def test_secure128_preset_with_the_unrolled_key(capsys):
         e.set_bsk_unroll(2)
         e.keygen()
         plain.keygen()
-        to.set_field(49)
-        OP = to.Params(**{f: getattr(P, f) for f, _ in tfhe.Params._fields_})
-        sk_small, sk_big, bsk, ksk = e.export_keys()
-        ctx = to.Ctx(OP, bsk, ksk)
-        ctx.set_bsk_unrolled(e.export_bsk_unrolled())
         rng = np.random.default_rng(43)
         dl = e.delta_log()
         table = rng.integers(-8, 8, 16)
@@ -290,14 +170,10 @@ def test_secure128_preset_with_the_unrolled_key(capsys):
         out = e.pbs_host(ct, np.full(msgs.size, lid, np.uint32))
         assert np.array_equal(e.decrypt(out, dl), table[msgs + 8])
         pick = rng.choice(msgs.size, 5, replace=False)
-        assert np.array_equal(out[pick], ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(5, np.uint32), unrolled=True))
-        Q = e.modulus
-        want_m = table[msgs + 8]
-        oerr = np.array([((int(x) - (int(m) << dl)) + Q // 2) % Q - Q // 2 for x, m in zip(e.phase(out), want_m)], dtype=np.float64) / Q
-        Bg = 2.0 ** P.bs_base_log
-        key_term = P.n * P.bs_levels * 2 * P.N * (Bg * Bg + 2) / 12 * P.glwe_noise ** 2
-        dec_term = P.n * (1 + P.N / 2) / (12 * Bg ** (2 * P.bs_levels))
-        ratio = float(np.var(oerr)) / (3 * key_term + dec_term / 2)
+        with pc.oracle_for(e, unrolled=True) as o:
+            assert np.array_equal(out[pick], o.ctx.pbs(ct[pick], e.lut_get(lid)[None, :], np.zeros(5, np.uint32), unrolled=True))
+        oerr = pc.centred_error(e.phase(out), table[msgs + 8], dl, e.modulus)
+        ratio = float(np.var(oerr)) / pc.unrolled_field_variance(P)
         B = 2.0 ** P.ks_base_log
         ks_var = P.N * P.ks_levels * (B * B + 2) / 12.0 * P.lwe_noise ** 2      # keyswitch noise (measured at this value in test_gpu_parity)
         assert 0.8 < ratio < 1.25 and np.var(oerr) * 75 ** 2 < ks_var / 4        # x75: the widest linear combination of the circuits
@@ -313,8 +189,7 @@ def test_secure128_preset_with_the_unrolled_key(capsys):
                 for _ in range(3):
                     en.blind_rotate_host(small[:cnt], ids)
                 t[(name, cnt)] = (time.perf_counter() - t0) / 3 * 1e3
-        with open(os.path.join(os.path.dirname(__file__), "golden", "inverse.json")) as f:
-            c = next(x for x in json.load(f) if x["tag"] == "baseline_n2_len20_ints8")
+        c = pc.golden_inverse("baseline_n2_len20_ints8")
         emi = EncryptedMatrixInversion(2, None, 2, c["len"], c["ints"], False, False, engine=e)
         q, s = emi.quantize(np.array(c["M"]).reshape(2, 2))
         enc = emi.encrypt(q, s)
@@ -326,7 +201,6 @@ def test_secure128_preset_with_the_unrolled_key(capsys):
         with capsys.disabled():
             print(f"\nsecure128 + unrolled key: output log2 std {0.5 * np.log2(np.var(oerr)):.2f} (variance / formula {ratio:.3f}); blind rotation ms "
                   + ", ".join(f"{k[0]} x{k[1]}: {v:.2f}" for k, v in t.items()) + f"; encrypted 2x2 inverse {wall:.2f} s")
-        ctx.close()
     finally:
         e.close()
         plain.close()
