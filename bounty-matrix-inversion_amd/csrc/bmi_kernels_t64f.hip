@@ -13,9 +13,21 @@
 // polynomial c (decomposes it, transforms its L digit polynomials once, multiplies them with both key columns per limb),
 // publishes the partner's partial sum through its LDS tile, adds the partner's, and runs the inverse transform of output c.
 //
+// Roles of the eight wavefronts of a workgroup: ciphertext slot ctl = wave >> 1, polynomial c = wave & 1, partner = wave ^ 1.
+// Wavefronts w and w + 4 share a SIMD, so the two wavefronts of a ciphertext sit on different SIMDs and each SIMD holds one
+// wavefront of slots 0-1 (the older: it wins issue and leads) and one of slots 2-3 (it trails and sets the pace).  The four
+// wavefronts with the same c (0, 2, 4, 6 or 1, 3, 5, 7) read the same key rows (bsk_c depends on c only) and share them through
+// L1 - in part: the trailing wavefronts ask for a row two to five rows after the leaders, and measured a workgroup fetches 2.1 x
+// one copy of the key from L2 per CMUX (4,196 M 128-byte read requests per launch of 8,192 against 1,982 M).  That traffic is
+// not what holds the kernel: making the two wavefronts of a ciphertext SIMD-mates (ctl = wave % 4, c = wave / 4), which keeps the
+// four readers of a row together, brings it down to 1.3 x and is 1.2 - 1.7 ms per 8,192 SLOWER; a workgroup barrier at each limb's
+// first row is 8 ms slower (profiles/key_row_sharing_ab.txt, EXPERIMENTS A19).  These roles stay.
+// What a CMUX keeps in registers instead of re-reading from LDS: the forward transforms' table twiddles (ForwardTwiddles: loaded
+// once, used by the L transforms) and the lane's own 16 accumulator words across the back edge (`keep`).
+//
 // Who may touch a tile when (pair_sync.hpp; `hand` counts the hand-offs of the pair: 2 per CMUX, one per limb, strictly increasing;
 // pub[w] / ack[w] are written by wavefront w only).  Tile T_w of wavefront w is WRITTEN by w alone - the exchanges of its forward
-// transforms, the partial it publishes, the exchanges of its inverse transform - and READ by the partner w' only between w'
+// transforms, the partial it publishes, the exchanges of its inverse transform - and READ by the partner w' = w ^ 1 only between w'
 // seeing pub[w] = h and w' storing ack[w'] = h:
 //   w:  stores partial h into T_w; pub[w] = h (release: the stores are visible before the flag)
 //   w': sees pub[w] = h; reads T_w (8 reads per lane); waits until they have returned (lgkmcnt(0)); ack[w'] = h
@@ -127,6 +139,10 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     uint32_t hand = 0;   // handshake counter of the pair (one per inverse transform)
     double dev = 0.0;    // STATS: largest |value - nearest integer| this lane has rounded away
     PH_DECL();
+    // this lane's own 16 accumulator words, carried across the back edge: the recombination below stores them and the next CMUX
+    // would read the same words back (the rotated read still goes through LDS: those words are other lanes')
+    double keep[16];
+    static_for<0, 16>([&](auto J) { keep[J] = accf[lane + 64 * J]; });
     for (uint32_t i = 0; i < n; i++) {
         PH_MARK(7);
 #if BMI_T64F_RESYNC
@@ -140,10 +156,10 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         wave_sync();
         double r[16];
         {
-            double vr[16], vs[16];  // all 32 reads in flight before the first use
+            double vr[16], vs[16];  // all 16 reads in flight before the first use
             static_for<0, 16>([&](auto J) {
                 vr[J] = accf[((lane + 2 * N - a_t) + 64 * J) & (N - 1)];   // (= lane + 64 J + 2 N - a_t; in this association <3, 10> compiles to 28 B of scratch per lane, in the other to 36)
-                vs[J] = accf[lane + 64 * J];
+                vs[J] = keep[J];
             });
             sched_fence();
             static_for<0, 16>([&](auto J) {
@@ -164,6 +180,11 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         };
         double2 kb[2][8];
         auto fetch = [&](double2 (&dst)[8], int t) { static_for<0, 8>([&](auto P) { dst[P] = row_ptr(t)[P * 64 + lane]; }); };
+        // the forward transforms' 15 table twiddles per lane, read from LDS once per CMUX instead of once per transform (the
+        // wavefront fences inside a transform keep the compiler from doing this itself): 30 ds_read_b128 fewer per CMUX
+        ForwardTwiddles ftw;
+        load_forward_twiddles(ftw, lane, lds);
+        sched_fence();
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = L - 1 - LEV;  // least significant digit first
             pin();
@@ -181,7 +202,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                 fetch(kb[0], 0);
                 pin();
             }
-            forward(X[lev], lane, lds, tile);
+            forward(X[lev], lane, ftw, tile);
         });
         __builtin_amdgcn_s_setprio(0);
         PH_MARK(2);   // digits + L forward transforms
@@ -245,7 +266,8 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                         // x 2^(LB j) mod 2^AB: only the low AB - LB j bits of the limb's integer survive the shift
                         constexpr double W = (double)(1ull << (AB - LB * j));
                         x = __builtin_fma(-W, __builtin_rint(x * (1.0 / W)), x);
-                        accf[lane + 64 * J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
+                        keep[J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
+                        accf[lane + 64 * J] = keep[J];
                     } else {
                         accf[lane + 64 * J] += x;   // (reduced mod 2^AB with the last limb: 2^47 + 2^45 + 2^47 stays exact)
                     }

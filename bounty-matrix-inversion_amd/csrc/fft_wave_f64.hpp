@@ -158,6 +158,51 @@ __device__ __forceinline__ void forward(double (&x)[16], int lane, const double 
     });
 }
 
+// The forward transform's table twiddles of one lane, held in registers by a caller that runs several transforms in a row
+// (60 VGPRs): the 8 words of TW_T1 and the 7 of TW_T2 (t2[0] = 1 is never multiplied and never loaded).
+struct ForwardTwiddles {
+    double2 t1[8], t2[8];
+};
+__device__ __forceinline__ void load_forward_twiddles(ForwardTwiddles &f, int lane, const double *tw) {
+    const double2 *tw2 = reinterpret_cast<const double2 *>(tw);
+    static_for<0, 8>([&](auto K) { f.t1[K] = tw2[TW_T1 / 2 + K * 64 + lane]; });
+    static_for<1, 8>([&](auto D) { f.t2[D] = tw2[TW_T2 / 2 + D * 8 + (lane & 7)]; });
+}
+// The same transform with the twiddles preloaded: every value and every operation is forward()'s, only the 15 LDS reads are gone.
+template <class Mid = NoHook>
+__device__ __forceinline__ void forward(double (&x)[16], int lane, const ForwardTwiddles &f, double *scratch, Mid mid = Mid()) {
+    double2 *sc = reinterpret_cast<double2 *>(scratch);
+    C v[8];
+    v[0] = C{x[0], x[8]};
+    static_for<1, 8>([&](auto R) { v[R] = cmul<false>(C{x[R], x[R + 8]}, TWIST_C[R], TWIST_S[R]); });
+    dft8<false>(v);
+    static_for<0, 8>([&](auto K) { v[K] = cmul<false>(v[K], f.t1[K].x, f.t1[K].y); });
+    const int r1 = ex1_row(lane), a = lane & 7, base = ex2_base(lane);
+    wave_sync();
+    static_for<0, 8>([&](auto K) { sc[K * ROWC + lane] = double2{v[K].r, v[K].i}; });
+    wave_sync();
+    static_for<0, 8>([&](auto B) {
+        const double2 t = sc[r1 + 8 * B];
+        v[B] = C{t.x, t.y};
+    });
+    mid();
+    sched_fence();
+    dft8<false>(v);
+    static_for<1, 8>([&](auto D) { v[D] = cmul<false>(v[D], f.t2[D].x, f.t2[D].y); });
+    wave_sync();
+    static_for<0, 8>([&](auto D) { sc[base + D * 8 + ((a + D) & 7)] = double2{v[D].r, v[D].i}; });
+    wave_sync();
+    static_for<0, 8>([&](auto A) {
+        const double2 t = sc[base + a * 8 + ((A + a) & 7)];
+        v[A] = C{t.x, t.y};
+    });
+    dft8<false>(v);
+    static_for<0, 8>([&](auto Cc) {
+        x[Cc] = v[Cc].r;
+        x[Cc + 8] = v[Cc].i;
+    });
+}
+
 // Inverse transform (includes 1/512): evaluation layout in, x[J] = a[lane + 64 J] out (not yet rounded to integers).
 // pre() runs after the first DFT8 (registers only) and immediately before the first store to scratch: a caller whose scratch is
 // still being read by another wavefront waits for that reader there, under the DFT8, instead of before the transform.

@@ -23,7 +23,7 @@ for B in [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "8192").split("
     torch.cuda.synchronize()
     buf = (C.c_ulonglong * 128)(); assert tfhe.load_library().bmi_debug_phase_prof_t64f(buf) == 0
     a = np.array(buf[:64], dtype=np.float64).reshape(8, 8) / eng.P.n
-    print(f"B = {B}: shader-clock cycles (s_memtime) per CMUX, wavefronts 0-7 of workgroup 0")
+    print(f"B = {B}: shader-clock cycles (s_memtime) per CMUX, wavefronts 0-7 of workgroup 0 (partners w and w ^ 1; w and w + 4 share a SIMD and, with w + 2 and w + 6, a key row; 4-7 set the pace)")
     for k, nm in enumerate(NAMES):
         print(f"  {nm:48s} " + " ".join(f"{a[w, k]:8.1f}" for w in range(8)))
     print(f"  {'total':48s} " + " ".join(f"{a[w].sum():8.1f}" for w in range(8)))
