@@ -31,7 +31,16 @@
 // seeing pub[w] = h and w' storing ack[w'] = h:
 //   w:  stores partial h into T_w; pub[w] = h (release: the stores are visible before the flag)
 //   w': sees pub[w] = h; reads T_w (8 reads per lane); waits until they have returned (lgkmcnt(0)); ack[w'] = h
-//   w:  first DFT8 of inverse transform h (registers only); sees ack[w'] = h; only then the first store of the transform into T_w
+//   w:  first two butterfly stages of the first DFT8 of inverse transform h (registers only); sees ack[w'] = h; only then the
+//       first store of the transform into T_w
+// Where the stores of an exchange sit: the forward transforms and the partial issue their eight ds_write_b128 back to back after
+// the arithmetic; the two exchanges of the inverse transform issue them from inside the last butterfly stage of the DFT8 in front
+// (fftw::dft8_emit: two stores, then the next pair's four f64 instructions), so the VGPR-to-LDS transfer of a pair runs under
+// arithmetic of the same wavefront (-0.9 ms per 8,192; the same arrangement of the forward transforms' twiddle multiplications
+// and of the partial's last product row measured nothing and +0.3 ms: profiles/exchange_bubbles_ab.txt, EXPERIMENTS A20).  The
+// protocol does not see the difference: the wait for ack[w'] = h and the wavefront fence still precede the first store in program
+// order, every store of an exchange still precedes the fence in front of its reads, and an earlier read of T_w by w itself has
+// been consumed by the arithmetic the stores depend on.
 // Every later write of T_w follows that store in w's program order: the rest of inverse transform h; then partial h + 1 (second
 // limb: stored after inverse transform h has returned), guarded in turn by ack[w'] = h + 1; then, in the next CMUX, the forward
 // transforms (after inverse transform h + 1) and partial h + 2.  So no write of T_w can overtake a read of it by w', for both limbs
@@ -247,7 +256,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                 pin();
                 PH_MARK(5);   // adding the partner's partial, posting the acknowledgement (the WAIT for the partner's is in phase 6)
                 // the partner has read this tile once its acknowledgement is seen: the inverse transform waits for it just before its
-                // first store to the tile, with its first DFT8 (registers only) already done
+                // first store to the tile, between the second and the last butterfly stage of its first DFT8 (registers only)
                 inverse(acc, lane, lds, tile, [&]() {
                     pin();
                     pair_wait(f_ack_partner, hand);

@@ -113,6 +113,48 @@ struct NoHook {
     __device__ __forceinline__ void operator()() const {}
 };
 
+// dft8 for a caller that stores every output as soon as it exists: the operations of dft8 in the same order per output.  pre()
+// runs after the first two butterfly stages, before any output is final; emit(R) runs straight after output R.  The last stage
+// finishes the outputs in the pairs (0, 4), (2, 6), (1, 5), (3, 7): with a store in emit() each pair's two ds_write_b128 are
+// followed by the next pair's four f64 instructions instead of by six more stores (the scheduler is held to that per pair).
+template <bool INV, class Pre, class Emit>
+__device__ __forceinline__ void dft8_emit(C (&x)[8], Pre &&pre, Emit &&emit) {
+    constexpr double s = INV ? -1.0 : 1.0;
+    constexpr double h = 0.70710678118654752440;
+    const C a0 = x[0] + x[4], d0 = x[0] - x[4];
+    const C a1 = x[1] + x[5], t1 = x[1] - x[5];
+    const C a2 = x[2] + x[6], t2 = x[2] - x[6];
+    const C a3 = x[3] + x[7], t3 = x[3] - x[7];
+    const C d1 = C{t1.r - s * t1.i, t1.i + s * t1.r};        // t1 (1 + s i), times h later
+    const C d2 = mul_i<INV>(t2);
+    const C d3 = C{-t3.r - s * t3.i, s * t3.r - t3.i};       // t3 (-1 + s i), times h later
+    const C b0 = a0 + a2, b2 = a0 - a2;
+    const C b1 = a1 + a3, b3 = mul_i<INV>(a1 - a3);
+    const C e0 = d0 + d2, e2 = d0 - d2;
+    const C e1 = d1 + d3, e3 = mul_i<INV>(d1 - d3);
+    pre();
+    x[0] = b0 + b1;
+    emit(std::integral_constant<int, 0>{});
+    x[4] = b0 - b1;
+    emit(std::integral_constant<int, 4>{});
+    sched_fence();
+    x[2] = b2 + b3;
+    emit(std::integral_constant<int, 2>{});
+    x[6] = b2 - b3;
+    emit(std::integral_constant<int, 6>{});
+    sched_fence();
+    x[1] = fma_h(e0, e1, h);
+    emit(std::integral_constant<int, 1>{});
+    x[5] = fma_h(e0, e1, -h);
+    emit(std::integral_constant<int, 5>{});
+    sched_fence();
+    x[3] = fma_h(e2, e3, h);
+    emit(std::integral_constant<int, 3>{});
+    x[7] = fma_h(e2, e3, -h);
+    emit(std::integral_constant<int, 7>{});
+    sched_fence();
+}
+
 // scratch addresses (complex words) of the two exchanges
 __device__ __forceinline__ int ex1_row(int lane) { return (lane >> 3) * ROWC + (lane & 7); }          // + 8 b
 __device__ __forceinline__ int ex2_base(int lane) { return (lane >> 3) * ROWC; }
@@ -204,8 +246,11 @@ __device__ __forceinline__ void forward(double (&x)[16], int lane, const Forward
 }
 
 // Inverse transform (includes 1/512): evaluation layout in, x[J] = a[lane + 64 J] out (not yet rounded to integers).
-// pre() runs after the first DFT8 (registers only) and immediately before the first store to scratch: a caller whose scratch is
-// still being read by another wavefront waits for that reader there, under the DFT8, instead of before the transform.
+// pre() runs inside the first DFT8 (registers only), after its first two butterfly stages and before the first store to scratch:
+// a caller whose scratch is still being read by another wavefront waits for that reader there, under the DFT8, instead of before
+// the transform.  Both exchanges store from inside the last stage of the DFT8 in front of them (dft8_emit), a pair of outputs at
+// a time; in source order each exchange is still: every earlier read of the scratch, pre(), fence, the eight stores, fence, the
+// eight reads.
 template <class Pre = NoHook>
 __device__ __forceinline__ void inverse(double (&x)[16], int lane, const double *tw, double *scratch, Pre pre = Pre()) {
     const double2 *tw2 = reinterpret_cast<const double2 *>(tw);
@@ -216,10 +261,13 @@ __device__ __forceinline__ void inverse(double (&x)[16], int lane, const double 
     sched_fence();
     C v[8];
     static_for<0, 8>([&](auto Cc) { v[Cc] = C{x[Cc], x[Cc + 8]}; });
-    dft8<true>(v);   // over c -> a
-    pre();
-    wave_sync();
-    static_for<0, 8>([&](auto A) { sc[base + a * 8 + ((A + a) & 7)] = double2{v[A].r, v[A].i}; });
+    dft8_emit<true>(   // over c -> a
+        v,
+        [&]() {
+            pre();
+            wave_sync();
+        },
+        [&](auto A) { sc[base + a * 8 + ((A + a) & 7)] = double2{v[A].r, v[A].i}; });
     wave_sync();
     static_for<0, 8>([&](auto D) {
         const double2 t = sc[base + D * 8 + ((a + D) & 7)];
@@ -228,9 +276,7 @@ __device__ __forceinline__ void inverse(double (&x)[16], int lane, const double 
     static_for<1, 8>([&](auto D) { v[D] = cmul<true>(v[D], w[D].x, w[D].y); });
     static_for<0, 8>([&](auto K) { w[K] = tw2[TW_T1 / 2 + K * 64 + lane]; });
     sched_fence();
-    dft8<true>(v);   // over d -> b
-    wave_sync();
-    static_for<0, 8>([&](auto B) { sc[r1 + 8 * B] = double2{v[B].r, v[B].i}; });
+    dft8_emit<true>(v, [&]() { wave_sync(); }, [&](auto B) { sc[r1 + 8 * B] = double2{v[B].r, v[B].i}; });   // over d -> b
     wave_sync();
     static_for<0, 8>([&](auto K) {
         const double2 t = sc[K * ROWC + lane];

@@ -8,7 +8,7 @@
 //                                                       pair_wait(pub_P, h)
 //                                                       reads P's tile (eight ds_read_b128 per lane)
 //                                                       pair_ack(ack_Q, h)   ordered after those reads only
-//   first register DFT8 of P's inverse transform
+//   first two butterfly stages of the first register DFT8 of P's inverse transform
 //   pair_wait(ack_Q, h)      (the hook of fftw::inverse)
 //   first store of the inverse transform into P's tile
 // Both wavefronts of a pair play both roles in every hand-off.  No wait of hand-off h depends on anything the partner does after
