@@ -21,6 +21,17 @@ Decision boundary: a table over p bits has boxes of 2N / 2^(p+1) positions (narr
 scaled up by the tracer: wider boxes, and their coefficients carry the scale); a value fails when the noise exceeds half a box on
 either side: P = erfc(half_box / (sigma sqrt 2)).  Outputs fail at decryption when their noise exceeds Delta / 2.
 
+Shared rotations (share_rotations=True; shared_rotation.py): a look-up served from a rotation it shares with others is
+SampleExtract(ACC P_f), P_f its table's sparse factor (from the same shared_rotation.rotation_groups the executor runs).  v_pbs
+splits into a part that is white across the accumulator's coefficients and a part carried by the GLWE key, whose coefficients are
+correlated (pbs_output_variance_parts: v_pbs = v_white + hw(S) v_carried); the output carries
+
+    |P_f|^2 v_white  +  N (p (1 - p) |P_f|^2 + p^2 mean_j m_j^2) v_carried,        p = hw(S) / N
+
+(the expectation of |S P_f|^2 over keys of that weight; shared_rotation's docstring).  |P_f|^2 v_pbs, the white-noise model, was
+measured 3.1 x too low for the identity table and 1.7 x too high for a random one on the default set; this one within 3 %
+(tests/test_gpu_shared_rotation.py, EXPERIMENTS A21).  A group of one is an ordinary look-up.
+
 Key weights are random: hw(s) = n / 2, hw(S) = kN / 2 (their expectations) unless given."""
 from __future__ import annotations
 
@@ -61,6 +72,20 @@ def pbs_output_variance(P, bsk_precision=None, unroll=False, hw_small=None, hw_b
     return key + hs * rnd
 
 
+def pbs_output_variance_parts(P, bsk_precision=None, hw_small=None, hw_big=None):
+    """(v_white, v_carried) with pbs_output_variance = v_white + hw(S) v_carried (plain key): the noise that is white across the
+    accumulator's coefficients - the key's Gaussian noise, the rounding of the stored body words, the decomposition's rounding of
+    the body - and, per set bit of the GLWE key, the noise that key carries (the roundings of the mask words)"""
+    N, k, l, n = 1 << P.log_N, P.k, P.bs_levels, P.n
+    Bg = 2.0 ** P.bs_base_log
+    hs = n / 2.0 if hw_small is None else float(hw_small)
+    prec = default_bsk_precision(P) if bsk_precision is None else int(bsk_precision)
+    rho = 4.0 ** (64 - prec) / 12.0 / 2.0 ** 128 if (P.q_bits == TORUS64 and prec < 64) else 0.0
+    K = n * l * (k + 1) * N * (Bg * Bg + 2) / 12.0
+    rnd = hs / (12.0 * Bg ** (2 * l))
+    return K * (P.glwe_noise ** 2 + rho) + rnd, K * rho + rnd
+
+
 def keyswitch_variance(P, hw_big=None):
     N, k = 1 << P.log_N, P.k
     B = 2.0 ** P.ks_base_log
@@ -88,7 +113,7 @@ def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0):
     return sigma_pos, N / (2.0 ** (lut_bits + 1)) / sigma_pos
 
 
-def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None):
+def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None, share_rotations=False):
     """Error budget of `prog` (a program.Program) under the parameter set `P` (tfhe.Params or anything with its fields).
 
     Returns a dict: p_fail (probability that at least one look-up or output decodes wrong, union bound), log10_p_fail,
@@ -102,6 +127,18 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     hs = P.n / 2.0 if hw_small is None else float(hw_small)
     leaf_var = np.full(n_in + nn, v_pbs)
     leaf_var[:n_in] = v_enc
+    shared = 0
+    if share_rotations and nn:
+        from .shared_rotation import rotation_groups
+        if unroll:
+            raise ValueError("shared rotations run on the plain bootstrap key, not on an unrolled one")
+        rg = rotation_groups(prog)
+        in_shared = np.repeat(rg.sizes, rg.sizes) > 1
+        v_white, v_carried = pbs_output_variance_parts(P, bsk_precision, hw_small, hw_big)
+        dens = 0.5 if hw_big is None else float(hw_big) / (P.k * N)
+        carried2 = N * (dens * (1 - dens) * rg.norm2[in_shared] + dens * dens * rg.mean2[in_shared])      # E |S P_f|^2
+        leaf_var[n_in + rg.members[in_shared]] = rg.norm2[in_shared] * v_white + carried2 * v_carried
+        shared = int(in_shared.sum())
 
     def lincomb_var(ptr, leaf, coef):
         ln = np.diff(ptr)
@@ -113,6 +150,8 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     res = {"lookups": int(nn), "params": {"n": int(P.n), "N": int(N), "l": int(P.bs_levels), "log2_Bg": int(P.bs_base_log),
                                           "q_bits": int(P.q_bits), "log2_lwe_noise": round(math.log2(P.lwe_noise), 2)},
            "log2_std_pbs_output": 0.5 * math.log2(v_pbs), "log2_std_keyswitch": 0.5 * math.log2(v_ks)}
+    if share_rotations:
+        res.update(shared_lookups=shared, rotations=int(rg.groups) if nn else 0)
     log_terms = []
     if nn:
         v_in, amp = lincomb_var(prog.node_ptr, prog.term_leaf, prog.term_coef)
@@ -178,14 +217,14 @@ def candidate_sets(msg_bits, q_bits=None, secure=False):
     return out
 
 
-def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False):
+def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, share_rotations=False):
     """The first candidate set whose failure probability for `prog` is at most p_error (Concrete's `global_p_error`); the report of
     every set tried.  Raises when none qualifies."""
     from . import tfhe
     tried = []
     for label, spec in candidate_sets(prog.msg_bits, q_bits, secure):
         P = tfhe.preset_params(spec) if isinstance(spec, str) else tfhe.default_params(**spec)
-        rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10)
+        rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations)
         tried.append((label, rep["p_fail"]))
         if rep["p_fail"] <= p_error:
             return P, dict(rep, chosen=label, tried=tried, p_error=p_error)

@@ -21,6 +21,12 @@ Several INPUTS at once (`batch`): the same program evaluated on `batch` independ
 every level is `batch` times wider (replica b of a node reads replica b's rows: the store is `batch` stacked copies of the
 one-input store), so the levels of one latency-kernel round become throughput-kernel launches: the serving form (a 3x3 inverse
 is 319 rounds of <= 256 look-ups alone, 69 k look-ups at the throughput kernel's rate in a batch).
+
+Shared rotations (`share_rotations=True`, 2^64 torus): the look-ups of a level that read the same linear combination
+(shared_rotation.rotation_groups: carry and digit of one column sum, the comparison bits of one division step ...) cost ONE
+keyswitch and ONE blind rotation together.  Per level: one linear combination per GROUP -> bmi_pbs_shared_batch (keyswitch and
+rotation of the groups' base polynomials, then every member's table from its group's accumulator) -> the same scatter of every
+member's row.  Under `batch` every replica groups alike.  Not combined with several ranks.
 """
 from __future__ import annotations
 
@@ -84,13 +90,15 @@ def assign_rows(prog: Program, recycle=True):
 
 
 class Executor:
-    def __init__(self, circuit, engine, group=None, shard_threshold=None, recycle=True, batch=1):
+    def __init__(self, circuit, engine, group=None, shard_threshold=None, recycle=True, batch=1, share_rotations=False):
         """circuit: a program.Program (or a circuit.Circuit, frozen here); group: a torch.distributed process group (None:
         the default group when initialised with more than one rank, otherwise single-GPU execution); shard_threshold:
         narrowest level that is split across the ranks - None (default) = every level wider than one latency-kernel
         round (257 ciphertexts), and the program's levels are then re-packed for `world` x 256 ciphertexts per round
         (Program.rescheduled): G GPUs working on one level are one machine with G x 256 workgroup slots; recycle: reuse
-        store rows after a leaf's last consumer; batch: number of independent input vectors one run() evaluates (module docstring)."""
+        store rows after a leaf's last consumer; batch: number of independent input vectors one run() evaluates (module docstring);
+        share_rotations: one keyswitch and blind rotation per group of look-ups with the same input (module docstring; single rank).
+        After construction `lookups` is the number of table look-ups of one run() and `rotations` the number of blind rotations."""
         import torch
         self.torch = torch
         prog = Program.from_circuit(circuit) if isinstance(circuit, Circuit) else circuit
@@ -115,6 +123,9 @@ class Executor:
                 if int(lo.item()) != int(hi.item()):
                     raise RuntimeError("the ranks of this group hold different evaluation keys: generate one key set and share it "
                                        "(Engine.keygen_shared, or EncryptedMatrixInversion.keygen under torch.distributed)")
+        self.share_rotations = bool(share_rotations)
+        if self.share_rotations and self.world > 1:
+            raise ValueError("share_rotations is not combined with several ranks: a sharded level is split by look-ups, not by groups")
         if shard_threshold is None:
             shard_threshold = Program_ROUND + 1
             if self.world > 1:
@@ -144,6 +155,13 @@ class Executor:
                                                   int(prog.lut_p[j]), dl - 1 if prog.lut_half[j] else dl)
                               for j in range(prog.lut_p.size)], np.int32)
         to_dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.dev)  # noqa: E731
+        rg = None
+        if self.share_rotations:
+            # a level's nodes group by group (same widths, so the rows assigned above stand); the groups' first members carry
+            # the linear combinations
+            from .shared_rotation import rotation_groups
+            rg = rotation_groups(prog)
+            order = rg.members
 
         # every level's rows in level order: one set of flat arrays for the whole program, sliced per level
         consts = prog.half_unit_consts(prog.node_ptr, prog.term_leaf, prog.term_coef, prog.node_const)   # units of Delta / 2
@@ -156,18 +174,46 @@ class Executor:
                 if len(counts) else shift
             order = np.concatenate(tiled) if tiled else order
             counts = counts * B
-        lens = np.diff(prog.node_ptr)[order]
-        starts = prog.node_ptr[:-1][order]
-        tot = int(lens.sum())
-        off = np.arange(tot) - np.repeat(np.cumsum(lens) - lens, lens) + np.repeat(starts, lens)
-        self.d_idx = to_dev(self.row_of[prog.term_leaf[off]] + np.repeat(shift, lens) if tot else [0], np.int32)
-        self.d_coef = to_dev(prog.term_coef[off] if tot else [0], np.int64)
-        consts = consts[order]
-        uniq, inv = np.unique(consts, return_inverse=True)
-        self.d_const = to_dev(_torus(uniq, dl - 1, q)[inv] if consts.size else [0], np.int64)
         self.d_ids = to_dev(lut_ids[prog.node_lut[order]] if order.size else [0], np.int32)
         self.d_rows = to_dev(self.row_of[n_in + order] + shift if order.size else [0], np.int32)
-        # row_ptr of all nodes in level order, absolute term offsets: a level (or a rank's part of it) is a slice
+        self.lookups = int(order.size)
+        lin_order, lin_shift = order, shift         # the nodes whose linear combinations are formed: all of them ...
+        self.glevels = None
+        if rg is not None:
+            # ... or the first member of every group.  Per level: (groups, position of its first group, offset of its group_ptr
+            # segment); a segment starts at 0 and has groups + 1 entries (the B replicas' groups one after the other)
+            sizes = rg.sizes
+            first = np.concatenate([[0], np.cumsum(rg.level_groups)])
+            # a group's base: the base polynomial of its unit - or, for a group of one, the table itself (a plain bootstrap)
+            base_ids = np.asarray([engine.lut_register_base(dl - 1 if h else dl) for h in (False, True)], np.int32)
+            group_base = np.where(sizes == 1, lut_ids[prog.node_lut[rg.members[rg.group_ptr[:-1]]]], base_ids[rg.unit_half.astype(np.int64)])
+            leaders, lshift, gbase, gptr, self.glevels = [], [], [], [], []
+            gpos = poff = 0
+            for t in range(len(rg.level_groups)):
+                g0, g1 = int(first[t]), int(first[t + 1])
+                ng = (g1 - g0) * B
+                leaders.append(np.tile(rg.members[rg.group_ptr[g0:g1]], B))
+                lshift.append(np.repeat(np.arange(B, dtype=np.int64) * self.n_rows1, g1 - g0))
+                gbase.append(np.tile(group_base[g0:g1], B))
+                gptr.append(np.concatenate([[0], np.cumsum(np.tile(sizes[g0:g1], B))]))
+                self.glevels.append((ng, gpos, poff))
+                gpos += ng
+                poff += ng + 1
+            lin_order = np.concatenate(leaders) if leaders else order
+            lin_shift = np.concatenate(lshift) if lshift else shift
+            self.d_gbase = to_dev(np.concatenate(gbase) if gpos else [0], np.int32)
+            self.d_gptr = to_dev(np.concatenate(gptr) if gptr else [0], np.int32)
+        self.rotations = int(lin_order.size)
+        lens = np.diff(prog.node_ptr)[lin_order]
+        starts = prog.node_ptr[:-1][lin_order]
+        tot = int(lens.sum())
+        off = np.arange(tot) - np.repeat(np.cumsum(lens) - lens, lens) + np.repeat(starts, lens)
+        self.d_idx = to_dev(self.row_of[prog.term_leaf[off]] + np.repeat(lin_shift, lens) if tot else [0], np.int32)
+        self.d_coef = to_dev(prog.term_coef[off] if tot else [0], np.int64)
+        consts = consts[lin_order]
+        uniq, inv = np.unique(consts, return_inverse=True)
+        self.d_const = to_dev(_torus(uniq, dl - 1, q)[inv] if consts.size else [0], np.int64)
+        # row_ptr of all linear combinations in level order, absolute term offsets: a level (or a rank's part of it) is a slice
         self.d_rp = to_dev(np.concatenate([[0], np.cumsum(lens)]), np.int32)
         self.levels = []          # (width, position of the level's first node, padded width)
         pos = 0
@@ -226,7 +272,14 @@ class Executor:
             stream = torch.cuda.current_stream().cuda_stream if self.on_gpu else 0
             self.store.view(self.batch, -1, self.big)[:, :n_in].copy_(torch.from_numpy(ct.view(np.int64)), non_blocking=False)
             eng, tmp, lvl = self.eng, self.tmp, self.lvl
-            for width, pos, padded in self.levels:
+            for t, (width, pos, padded) in enumerate(self.levels):
+                if self.glevels is not None:     # one linear combination, keyswitch and rotation per group; every member's row as usual
+                    ng, gpos, poff = self.glevels[t]
+                    if width:
+                        eng.lincomb(self.store, self.d_rp[gpos:], self.d_idx, self.d_coef, self.d_const[gpos:], ng, tmp, stream)
+                        eng.pbs_shared(tmp, self.d_gptr[poff:], self.d_gbase[gpos:], self.d_ids[pos:], ng, width, lvl, stream)
+                        eng.scatter_rows(lvl, width, self.store, self.d_rows[pos:], stream)
+                    continue
                 lo, hi = 0, width
                 sharded = self.world > 1 and width >= self.shard_threshold
                 if sharded:

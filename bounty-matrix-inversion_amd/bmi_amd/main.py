@@ -26,7 +26,7 @@ class EncryptedMatrixInversion:
 
     def __init__(self, n, sampler=None, qfloat_base=2, qfloat_len=32, qfloat_ints=16, true_division=False,
                  tensorize=False, engine=None, device=0, shard_threshold=None, cache=True, unroll=False, q_bits=None,
-                 params=None, p_error=None):
+                 params=None, p_error=None, share_rotations=False):
         """The reference's seven arguments (main.py:17-36), then: engine / device (the GPU context to use) and
         shard_threshold (with torch.distributed initialised on several ranks, levels at least this wide are split
         across the ranks' GPUs; None = every level wider than one kernel round, levels re-packed for the rank count,
@@ -42,7 +42,9 @@ class EncryptedMatrixInversion:
         the probability that noise makes the whole evaluation wrong (Concrete's `global_p_error`, 1e-5 there) - the first
         parameter set of the chosen modulus whose error budget for THIS circuit meets it is taken (error_budget.choose_params:
         N = 1024 for small circuits, N = 2048 where the look-up count needs the wider margin, e.g. the 8x8 inverse); None keeps
-        the north-star set and reports its budget in `self.error_budget`."""
+        the north-star set and reports its budget in `self.error_budget`; share_rotations (2^64 torus, one rank): look-ups of a
+        level that read the same input share one keyswitch and blind rotation (executor.py, shared_rotation.py) - evaluate and
+        evaluate_many alike; the error budget and the p_error selection then count the larger noise of such look-ups."""
         self.shape = (n, n)
         self.qfloat_base, self.qfloat_len, self.qfloat_ints = qfloat_base, qfloat_len, qfloat_ints
         self.true_division, self.tensorize = true_division, tensorize
@@ -64,6 +66,7 @@ class EncryptedMatrixInversion:
         self.q_bits = q_bits
         self.params = params
         self.p_error = p_error
+        self.share_rotations = bool(share_rotations)
         self.error_budget = None      # filled when the engine exists: Program.failure_probability under its parameters
         if engine is not None and params is not None:
             raise ValueError("pass an engine or a parameter set, not both (the engine already has its parameters)")
@@ -84,7 +87,8 @@ class EncryptedMatrixInversion:
                 params = tfhe.preset_params(self.params) if isinstance(self.params, str) else self.params
             elif self.p_error is not None:  # the first set of this modulus whose error budget for this circuit meets p_error
                 from . import error_budget
-                params, self.error_budget = error_budget.choose_params(self.program, self.p_error, q_bits=qb, unroll=self.unroll)
+                params, self.error_budget = error_budget.choose_params(self.program, self.p_error, q_bits=qb, unroll=self.unroll,
+                                                                           share_rotations=self.share_rotations)
             elif self.msg_bits <= 4:
                 params = tfhe.default_params(q_bits=qb)
             elif self.msg_bits <= 6 and qb in (None, tfhe.TORUS64, 49):
@@ -109,6 +113,11 @@ class EncryptedMatrixInversion:
                              f"(this engine has N = {self.engine.P.N})")
         if self.error_budget is None:
             self.error_budget = self.program.failure_probability(self.engine)
+            if self.share_rotations:
+                from . import error_budget
+                eng = self.engine
+                self.error_budget = error_budget.failure_probability(self.program, eng.P, eng.bsk_precision if eng.q_bits == 65 else None,
+                                                                     getattr(eng, "unroll", 1) == 2, share_rotations=True)
             if self.p_error is not None and self.error_budget["p_fail"] > self.p_error:
                 raise ValueError(f"this circuit's failure probability under the engine's parameters is {self.error_budget['p_fail']:.2e} "
                                  f"> p_error = {self.p_error:g}: pass a wider parameter set (e.g. log_N=11) or let this object choose")
@@ -136,7 +145,8 @@ class EncryptedMatrixInversion:
             self._exec = {}
         if batch not in self._exec:
             from .executor import Executor
-            self._exec[batch] = Executor(self.circuit, self._engine(), shard_threshold=self.shard_threshold, batch=batch)
+            self._exec[batch] = Executor(self.circuit, self._engine(), shard_threshold=self.shard_threshold, batch=batch,
+                                         share_rotations=self.share_rotations)
         return self._exec[batch]
 
     # ---- the reference's six methods -----------------------------------------------------------------

@@ -56,6 +56,15 @@ _SIGS = {
     "bmi_phase": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
     "bmi_lut_register": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "bmi_lut_get": [C.c_void_p, C.c_uint32, C.c_void_p],
+    "bmi_lut_register_base": [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
+    "bmi_blind_rotate_glwe_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_glwe_lookup_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                              C.c_void_p],
+    "bmi_pbs_shared_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                             C.c_void_p],
+    "bmi_blind_rotate_glwe_batch_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "bmi_glwe_lookup_batch_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_pbs_shared_batch_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "bmi_pbs_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
     "bmi_keyswitch_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
     "bmi_blind_rotate_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
@@ -423,6 +432,13 @@ class Engine:
         self._luts[key] = lid.value
         return lid.value
 
+    def lut_register_base(self, unit_log):
+        """2^64 torus: the id of the base polynomial + 2^(unit_log - 1) sum_x X^x that the tables of a shared rotation with this
+        unit are factors of (one id per unit)"""
+        lid = C.c_uint32()
+        self._ck(self.lib.bmi_lut_register_base(self.h, int(unit_log), C.byref(lid)), "bmi_lut_register_base")
+        return lid.value
+
     def lut_get(self, lut_id):
         tv = np.zeros(self.P.N, np.uint64)
         self._ck(self.lib.bmi_lut_get(self.h, lut_id, _ptr(tv)), "bmi_lut_get")
@@ -495,6 +511,43 @@ class Engine:
                  "bmi_blind_rotate_batch_host")
         return out
 
+    def blind_rotate_glwe_host(self, small, lut_ids):
+        """blind_rotate_host returning the accumulators [count][2N] (mask polynomial, then body) instead of the extracted samples"""
+        small = np.ascontiguousarray(small, dtype=np.uint64).reshape(-1, self.P.small)
+        ids = np.ascontiguousarray(lut_ids, dtype=np.uint32).reshape(-1)
+        out = np.zeros((small.shape[0], 2 * self.P.N), np.uint64)
+        self._ck(self.lib.bmi_blind_rotate_glwe_batch_host(self.h, _ptr(small), _ptr(ids), small.shape[0], _ptr(out)),
+                 "bmi_blind_rotate_glwe_batch_host")
+        return out
+
+    def _groups(self, group_ptr, base_ids, lut_ids):
+        gp = np.ascontiguousarray(group_ptr, dtype=np.uint32).reshape(-1)
+        base = np.ascontiguousarray(base_ids, dtype=np.uint32).reshape(-1)
+        ids = np.ascontiguousarray(lut_ids, dtype=np.uint32).reshape(-1)
+        if gp.size != base.size + 1:
+            raise ValueError("group_ptr must have one entry more than there are groups")
+        return gp, base, ids
+
+    def glwe_lookup_host(self, glwe, group_ptr, base_ids, lut_ids):
+        """the look-ups lut_ids[group_ptr[g] : group_ptr[g+1]] of accumulator g (a rotation of the base polynomial base_ids[g])
+        -> [len(lut_ids)][N + 1] ciphertexts"""
+        gp, base, ids = self._groups(group_ptr, base_ids, lut_ids)
+        glwe = np.ascontiguousarray(glwe, dtype=np.uint64).reshape(base.size, 2 * self.P.N)
+        out = np.zeros((ids.size, self.P.big), np.uint64)
+        self._ck(self.lib.bmi_glwe_lookup_batch_host(self.h, _ptr(glwe), _ptr(gp), _ptr(base), _ptr(ids), base.size, ids.size,
+                                                     _ptr(out)), "bmi_glwe_lookup_batch_host")
+        return out
+
+    def pbs_shared_host(self, cts, group_ptr, base_ids, lut_ids):
+        """pbs_host with one keyswitch and one rotation per GROUP: ciphertext g is looked up in the tables
+        lut_ids[group_ptr[g] : group_ptr[g+1]] -> [len(lut_ids)][N + 1] ciphertexts"""
+        gp, base, ids = self._groups(group_ptr, base_ids, lut_ids)
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(base.size, self.P.big)
+        out = np.zeros((ids.size, self.P.big), np.uint64)
+        self._ck(self.lib.bmi_pbs_shared_batch_host(self.h, _ptr(cts), _ptr(gp), _ptr(base), _ptr(ids), base.size, ids.size, _ptr(out)),
+                 "bmi_pbs_shared_batch_host")
+        return out
+
     def fft_margin_host(self, small, lut_ids):
         """test hook (2^64 torus, 48-bit key in base 2^10): blind rotation by the floating-point-transform wave-pair kernel ->
         (outputs, largest distance of a limb sum from the integer it was rounded to)"""
@@ -525,6 +578,19 @@ class Engine:
     def blind_rotate(self, d_small, d_lut_ids, count, d_out, stream=0):
         self._ck(self.lib.bmi_blind_rotate_batch(self.h, _ptr(d_small), _ptr(d_lut_ids), count, _ptr(d_out),
                                                  C.c_void_p(stream)), "bmi_blind_rotate_batch")
+
+    def blind_rotate_glwe(self, d_small, d_lut_ids, count, d_glwe, stream=0):
+        self._ck(self.lib.bmi_blind_rotate_glwe_batch(self.h, _ptr(d_small), _ptr(d_lut_ids), count, _ptr(d_glwe),
+                                                      C.c_void_p(stream)), "bmi_blind_rotate_glwe_batch")
+
+    def glwe_lookup(self, d_glwe, d_group_ptr, d_base_ids, d_lut_ids, groups, total, d_out, stream=0):
+        self._ck(self.lib.bmi_glwe_lookup_batch(self.h, _ptr(d_glwe), _ptr(d_group_ptr), _ptr(d_base_ids), _ptr(d_lut_ids), groups,
+                                                total, _ptr(d_out), C.c_void_p(stream)), "bmi_glwe_lookup_batch")
+
+    def pbs_shared(self, d_in, d_group_ptr, d_base_ids, d_lut_ids, groups, total, d_out, stream=0):
+        """keyswitch + one rotation per group + the groups' look-ups (bmi_pbs_shared_batch)"""
+        self._ck(self.lib.bmi_pbs_shared_batch(self.h, _ptr(d_in), _ptr(d_group_ptr), _ptr(d_base_ids), _ptr(d_lut_ids), groups,
+                                               total, _ptr(d_out), C.c_void_p(stream)), "bmi_pbs_shared_batch")
 
     def lincomb(self, d_store, d_row_ptr, d_idx, d_coef, d_const, count, d_out, stream=0):
         self._ck(self.lib.bmi_lincomb_batch(self.h, _ptr(d_store), _ptr(d_row_ptr), _ptr(d_idx), _ptr(d_coef),

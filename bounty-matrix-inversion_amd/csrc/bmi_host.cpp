@@ -307,7 +307,17 @@ struct bmi_ctx {
                                        // dropped with the key set (drop_sk_mask) - lwe_phase
     uint32_t n_luts = 0, lut_cap = 0;
     std::vector<std::vector<u64>> luts_host;
+    // 2^64 torus, shared rotations (glwe_lookup.hip): per table the sparse factor P_f = (1 - X) TV_f / 2^scale as (position,
+    // difference) pairs, filled at registration.  head[id] = {entries, scale}; entries = NO_SPARSE where the table has more than
+    // BMI_SPARSE_CAP boxes (such a table cannot share a rotation); a base polynomial (bmi_lut_register_base) is {1, unit}: P = 1.
+    static constexpr uint32_t NO_SPARSE = 0xFFFFFFFFu;
+    DevBuf<uint2> sparse_head;         // [BMI_LUT_CAP]
+    DevBuf<int2> sparse;               // [BMI_LUT_CAP][BMI_SPARSE_CAP]
+    std::vector<uint2> sparse_head_host;
+    uint32_t base_id_of_unit[64] = {};   // id + 1 of the base polynomial registered for a unit, 0 = none yet
     // growable device scratch (grow)
+    DevBuf<u64> glwe;                  // accumulators of bmi_pbs_shared_batch and of the host-buffer forms ([groups][2 k N])
+    DevBuf<uint32_t> io_groups;        // host-buffer forms of the shared look-ups: group_ptr [groups + 1], then base ids [groups]
     DevBuf<u64> small;                 // keyswitched ciphertexts of bmi_pbs_batch and of the host-buffer forms
     DevBuf<u64> io_a, io_b;            // host-buffer forms: input and output ciphertexts, and look-up ids
     DevBuf<uint32_t> io_ids;
@@ -895,6 +905,55 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     return (int)hipErrorInvalidValue;
 }
 
+// The accumulator form of `rot` (bmi_blind_rotate_glwe_batch): the four plain floating-point-transform kernels of the torus have
+// one; *known = false for every other kernel (the exact-transform pair a pinned variant 1 / 3 / 4 selects, the N = 4096 kernel, the
+// unrolled ones, the prime fields).
+int launch_rotation_glwe(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *glwe, hipStream_t st, bool *known) {
+    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
+    const int p = c->bsk_prec;
+    const u64 *luts = c->luts.get();
+    const bmi_ctx::BskCopies &K = c->bsk;
+    *known = true;
+    switch (rot) {
+    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2_glwe(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), glwe, count, n, p, lv, bl, st);
+    case Rot::t64_wide: return bmit::launch_blind_rotate_wide_glwe(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), glwe, count, n, p, lv, bl, nullptr, st);
+    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft_glwe(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), glwe, count, n, p, lv, bl, nullptr, st);
+    case Rot::t64_fft: return bmit::launch_blind_rotate_fft_glwe(cts, ids, luts, K.fft.get(), c->tw_fft.get(), glwe, count, n, p, lv, bl, nullptr, st);
+    default: *known = false; return 0;
+    }
+}
+
+// accumulators of a batch (room for 256 at least)
+int ensure_glwe(bmi_ctx *c, size_t count) {
+    const size_t w = (size_t)2 * c->big_n * sizeof(u64);
+    return grow(c, c->glwe, count * w, 256 * w);
+}
+
+// What the device-pointer forms of the shared look-ups document as preconditions, checked on host arrays: the group ranges
+// partition [0, total), and every table is either its group's own base (a plain extraction) or a table with a sparse factor and a
+// scale not below the unit of the group's base, which is then a polynomial of bmi_lut_register_base.
+int check_groups(bmi_ctx *c, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids, uint32_t groups, uint32_t total) {
+    if (group_ptr[0] != 0 || group_ptr[groups] != total) return fail(c, -1, "group_ptr must run from 0 to the number of look-ups");
+    for (uint32_t g = 0; g < groups; g++) {
+        if (group_ptr[g + 1] < group_ptr[g]) return fail(c, -1, "group_ptr must not decrease");
+        const uint32_t b = base_ids[g];
+        if (b >= c->n_luts) return fail(c, -1, "look-up id " + std::to_string(b) + " is not registered");
+        const uint32_t unit = c->sparse_head_host[b].y;
+        const bool is_base = unit < 64 && c->base_id_of_unit[unit] == b + 1;
+        for (uint32_t t = group_ptr[g]; t < group_ptr[g + 1]; t++) {
+            const uint32_t id = lut_ids[t];
+            if (id >= c->n_luts) return fail(c, -1, "look-up id " + std::to_string(id) + " is not registered");
+            if (id == b) continue;   // the table is the group's own base: a plain extraction
+            if (!is_base)
+                return fail(c, -1, "id " + std::to_string(b) + " serves another table but is not a base polynomial (bmi_lut_register_base)");
+            const uint2 h = c->sparse_head_host[id];
+            if (h.x == bmi_ctx::NO_SPARSE) return fail(c, -1, "table " + std::to_string(id) + " has more than 64 boxes: it cannot share a rotation");
+            if (h.y < unit) return fail(c, -1, "table " + std::to_string(id) + " is encoded below its group's unit (2^" + std::to_string(unit) + ")");
+        }
+    }
+    return 0;
+}
+
 // a look-up id beyond the registered tables would make the kernels read past the table buffer: refused on the host
 // (the device-pointer entry points cannot look at their ids without a synchronisation; their contract is ids < count)
 int check_lut_ids(bmi_ctx *c, const uint32_t *lut_ids, uint32_t count) {
@@ -1035,6 +1094,12 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
     if (c->quad() && !c->t64()) put(c->tw_quad49, to_centred_doubles(build_twiddles_quad(c->f)));
     c->lut_cap = BMI_LUT_CAP;
     if (up == hipSuccess) up = c->luts.alloc((size_t)c->lut_cap * c->N * 8);
+    if (c->t64()) {   // the tables' sparse factors (shared rotations): no entries until a table is registered
+        if (up == hipSuccess) up = c->sparse_head.alloc((size_t)BMI_LUT_CAP * sizeof(uint2));
+        if (up == hipSuccess) up = c->sparse.alloc((size_t)BMI_LUT_CAP * bmit::BMI_SPARSE_CAP * sizeof(int2));
+        if (up == hipSuccess) up = hipMemset(c->sparse_head.get(), 0, c->sparse_head.bytes());
+        if (up == hipSuccess) up = hipMemset(c->sparse.get(), 0, c->sparse.bytes());
+    }
     if (up != hipSuccess) return bail(std::string("uploading the context's tables: ") + hipGetErrorString(up));
     *out = c;
     return 0;
@@ -1216,6 +1281,32 @@ int bmi_decrypt(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint32_
     return 0;
 }
 
+// the tail of a registration: the test polynomial and, on the torus, its sparse factor go to the device under the next free id
+static int add_table(bmi_ctx *c, std::vector<u64> tv, uint2 head, const std::vector<int2> &sparse, uint32_t *lut_id) {
+    const uint32_t N = c->N, id = c->n_luts;
+    HIP_OK(c, hipSetDevice(c->device));
+    {
+        const std::vector<double> tvd = c->f64() ? to_centred_doubles(tv) : std::vector<double>();
+        const void *src = c->f64() ? (const void *)tvd.data() : (const void *)tv.data();
+        HIP_OK(c, hipMemcpy(c->luts.get() + (size_t)id * N, src, N * 8, hipMemcpyHostToDevice));
+    }
+    if (c->t64()) {
+        if (!sparse.empty())
+            HIP_OK(c, hipMemcpy(c->sparse.get() + (size_t)id * bmit::BMI_SPARSE_CAP, sparse.data(), sparse.size() * sizeof(int2), hipMemcpyHostToDevice));
+        HIP_OK(c, hipMemcpy(c->sparse_head.get() + id, &head, sizeof(head), hipMemcpyHostToDevice));
+        c->sparse_head_host.push_back(head);
+    }
+    c->luts_host.push_back(std::move(tv));
+    *lut_id = c->n_luts++;
+    return 0;
+}
+
+// Shared rotations exist on the 2^64 torus through the plain floating-point-transform kernels: refused elsewhere
+static int shared_rotation_ok(const bmi_ctx *c) {
+    if (!c->t64()) return fail(c, -1, "shared rotations exist on the 2^64 torus only (not on the 49-bit field or Goldilocks)");
+    return 0;
+}
+
 int bmi_lut_register(bmi_ctx *c, const int64_t *table, uint32_t msg_bits, uint32_t out_delta_log, uint32_t *lut_id) {
     if (!c || !table || !lut_id) return -1;
     const uint32_t N = c->N;
@@ -1239,15 +1330,40 @@ int bmi_lut_register(bmi_ctx *c, const int64_t *table, uint32_t msg_bits, uint32
         const u64 v = c->f.mul(c->f.from_i64(f), (u64)1 << out_delta_log);
         tv[j] = negate ? c->f.neg(v) : v;
     }
-    HIP_OK(c, hipSetDevice(c->device));
-    {
-        const std::vector<double> tvd = c->f64() ? to_centred_doubles(tv) : std::vector<double>();
-        const void *src = c->f64() ? (const void *)tvd.data() : (const void *)tv.data();
-        HIP_OK(c, hipMemcpy(c->luts.get() + (size_t)c->n_luts * N, src, N * 8, hipMemcpyHostToDevice));
+    // 2^64 torus: the sparse factor P_f = (1 - X) TV_f / 2^out_delta_log (glwe_lookup.hip) - the differences of consecutive boxes
+    // s_0 .. s_M = f(0 .. M/2-1), -f(-M/2 .. -1), -f(0), at the box boundaries b w - w/2.  Taken from the table's INTEGERS: a
+    // difference of 2^p at full scale (f(M/2-1) = -M/2 next to -f(-M/2) = +M/2) has no sign once it is a torus word.
+    uint2 head{bmi_ctx::NO_SPARSE, out_delta_log};
+    std::vector<int2> sparse;
+    if (c->t64() && M <= bmit::BMI_SPARSE_CAP) {
+        auto box_value = [&](uint32_t b) -> i64 { return b < Mh ? table[b + Mh] : b < M ? -table[b - Mh] : -table[Mh]; };
+        bool fits = true;
+        for (uint32_t b = 1; b <= M; b++) {
+            const i64 d = box_value(b) - box_value(b - 1);
+            if (d > INT32_MAX || d < INT32_MIN) fits = false;
+            else if (d) sparse.push_back(int2{(int)(b * w - half), (int)d});
+        }
+        if (fits) head.x = (uint32_t)sparse.size();
     }
-    c->luts_host.push_back(std::move(tv));
-    *lut_id = c->n_luts++;
-    return 0;
+    return add_table(c, std::move(tv), head, sparse, lut_id);
+}
+
+int bmi_lut_register_base(bmi_ctx *c, uint32_t unit_log, uint32_t *lut_id) {
+    if (!c || !lut_id) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    if (unit_log == 0 || unit_log >= 63) return fail(c, -1, "unit_log out of range");
+    if (c->bsk_prec != 64 && unit_log < (uint32_t)(64 - c->bsk_prec) + 1)   // (the polynomial's words are 2^(unit_log - 1))
+        return fail(c, -1, "unit_log - 1 below 64 - (bootstrap-key precision) on the 2^64 torus: test polynomials must be multiples of the key's grid");
+    if (c->base_id_of_unit[unit_log]) {
+        *lut_id = c->base_id_of_unit[unit_log] - 1;
+        return 0;
+    }
+    if (c->n_luts == c->lut_cap) return fail(c, -1, "LUT table full");
+    // TV_0 = + 2^(unit_log - 1) sum_x X^x: (1 - X) TV_0 = 2^unit_log, so its own sparse factor is the constant 1
+    std::vector<u64> tv(c->N, (u64)1 << (unit_log - 1));
+    const int rc = add_table(c, std::move(tv), uint2{1, unit_log}, std::vector<int2>{int2{0, 1}}, lut_id);
+    if (!rc) c->base_id_of_unit[unit_log] = *lut_id + 1;
+    return rc;
 }
 
 int bmi_lut_get(const bmi_ctx *c, uint32_t lut_id, uint64_t *test_vector) {
@@ -1408,6 +1524,44 @@ int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, u
     return bmi_blind_rotate_batch(c, c->small.get(), d_lut_ids, count, d_out, stream);
 }
 
+int bmi_blind_rotate_glwe_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_glwe,
+                                void *stream) {
+    if (!c || (count && (!d_small || !d_lut_ids || !d_glwe))) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
+    HIP_OK(c, hipSetDevice(c->device));
+    Rot rot;
+    if (int rc = choose_rotation(c, count, &rot)) return rc;
+    bool known;
+    const int rc = launch_rotation_glwe(c, rot, d_small, d_lut_ids, count, d_glwe, (hipStream_t)stream, &known);
+    if (!known)
+        return fail(c, -1, "the accumulator form exists for the plain floating-point-transform kernels only (N = 1024 with the key at 48 bits, "
+                           "N = 2048): not for a pinned exact-transform variant (1 / 3 / 4), N = 4096, an unrolled key or another key precision");
+    return rc ? fail(c, -2, std::string("blind_rotate (accumulator form) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+int bmi_glwe_lookup_batch(bmi_ctx *c, const uint64_t *d_glwe, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
+                          const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream) {
+    if (!c || (groups && (!d_glwe || !d_group_ptr || !d_base_ids)) || (total && (!d_lut_ids || !d_out))) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    const int rc = bmit::launch_glwe_lookup(d_glwe, d_group_ptr, d_base_ids, d_lut_ids, c->sparse_head.get(), c->sparse.get(), d_out, groups,
+                                            total, c->N, (hipStream_t)stream);
+    return rc ? fail(c, -2, std::string("glwe_lookup launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+int bmi_pbs_shared_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
+                         const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream) {
+    if (!c) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    int rc = ensure_small(c, groups);
+    if (!rc) rc = ensure_glwe(c, groups);
+    if (!rc) rc = bmi_keyswitch_batch(c, d_in, groups, c->small.get(), stream);
+    if (!rc) rc = bmi_blind_rotate_glwe_batch(c, c->small.get(), d_base_ids, groups, c->glwe.get(), stream);
+    return rc ? rc : bmi_glwe_lookup_batch(c, c->glwe.get(), d_group_ptr, d_base_ids, d_lut_ids, groups, total, d_out, stream);
+}
+
 int bmi_lincomb_batch(bmi_ctx *c, const uint64_t *d_store, const uint32_t *d_row_ptr, const uint32_t *d_idx,
                       const int64_t *d_coef, const uint64_t *d_const_body, uint32_t count, uint64_t *d_out,
                       void *stream) {
@@ -1470,6 +1624,8 @@ int bmi_reserve(bmi_ctx *c, uint32_t max_count) {
         rc = ensure_ks_mfma(c, max_count);
         if (rc) return rc;
     }
+    if (c->t64())
+        if (int rc = ensure_glwe(c, max_count)) return rc;
     return ensure_small(c, max_count);
 }
 
@@ -1521,6 +1677,69 @@ int bmi_blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint
     rc = bmi_blind_rotate_batch(c, c->small.get(), c->io_ids.get(), count, c->io_b.get(), c->stream);
     if (rc) return rc;
     HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Host-buffer forms of the shared look-ups.  They refuse what the device-pointer forms state as preconditions (check_groups).
+int bmi_blind_rotate_glwe_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *glwe_out) {
+    if (!c || !small_in || !lut_ids || !glwe_out) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
+    HIP_OK(c, hipSetDevice(c->device));
+    int rc = ensure_io(c, count);
+    if (!rc) rc = ensure_glwe(c, count);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_blind_rotate_glwe_batch(c, c->small.get(), c->io_ids.get(), count, c->glwe.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(glwe_out, c->glwe.get(), (size_t)count * 2 * c->big_n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// uploads the group description of a host-buffer form: io_groups = group_ptr [groups + 1], base ids [groups]; io_ids = lut_ids [total]
+static int upload_groups(bmi_ctx *c, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids, uint32_t groups, uint32_t total) {
+    if (int bad = check_groups(c, group_ptr, base_ids, lut_ids, groups, total)) return bad;
+    int rc = ensure_io(c, std::max(groups, total));
+    if (!rc) rc = ensure_glwe(c, groups);
+    if (!rc) rc = grow(c, c->io_groups, ((size_t)2 * groups + 1) * 4, 4096);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->io_groups.get(), group_ptr, ((size_t)groups + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->io_groups.get() + groups + 1, base_ids, (size_t)groups * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+int bmi_glwe_lookup_batch_host(bmi_ctx *c, const uint64_t *glwe_in, const uint32_t *group_ptr, const uint32_t *base_ids,
+                               const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out) {
+    if (!c || !glwe_in || !group_ptr || !base_ids || !lut_ids || !out) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    int rc = upload_groups(c, group_ptr, base_ids, lut_ids, groups, total);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->glwe.get(), glwe_in, (size_t)groups * 2 * c->big_n * 8, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_glwe_lookup_batch(c, c->glwe.get(), c->io_groups.get(), c->io_groups.get() + groups + 1, c->io_ids.get(), groups, total,
+                               c->io_b.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)total * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bmi_pbs_shared_batch_host(bmi_ctx *c, const uint64_t *in, const uint32_t *group_ptr, const uint32_t *base_ids,
+                              const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out) {
+    if (!c || !in || !group_ptr || !base_ids || !lut_ids || !out) return -1;
+    if (int rc = shared_rotation_ok(c)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    int rc = upload_groups(c, group_ptr, base_ids, lut_ids, groups, total);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, (size_t)groups * (c->big_n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_pbs_shared_batch(c, c->io_a.get(), c->io_groups.get(), c->io_groups.get() + groups + 1, c->io_ids.get(), groups, total,
+                              c->io_b.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)total * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

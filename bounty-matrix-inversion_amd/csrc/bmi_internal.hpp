@@ -85,6 +85,20 @@ inline int with_levels_stats(uint32_t levels, bool stats, F f) {
     return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
+// The rotation kernels that return the accumulator (k_blind_rotate_*_glwe, bmi_blind_rotate_glwe_batch) are SECOND ENTRIES of the
+// plain torus FFT kernels, compiled from the same text in translation units of their own: bmi_kernels_t64{f,w,w2}_glwe.hip define
+// BMI_ROT_GLWE and include bmi_kernels_t64{f,w,w2}.hip, where BMI_ROT_ENTRY names the kernels and their launchers and ROT_GLWE
+// selects the epilogue (t64::store_glwe instead of t64::extract_sample) - everything up to the end of the CMUX loop is shared, and
+// the translation units of the existing entries see the same tokens as before.  The key conversions, their launchers and the shape
+// predicates of a kernel file are left out of its second compilation (#ifndef BMI_ROT_GLWE).
+#ifdef BMI_ROT_GLWE
+#define BMI_ROT_ENTRY(name) name##_glwe
+constexpr bool ROT_GLWE = true;
+#else
+#define BMI_ROT_ENTRY(name) name
+constexpr bool ROT_GLWE = false;
+#endif
+
 namespace bmi {
 using gl::i64;
 using gl::u64;
@@ -242,6 +256,27 @@ int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw
 int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
                              hipStream_t s);
+// The four plain FFT rotations above returning the ACCUMULATOR (bmi_kernels_t64{f,w,w2}_glwe.hip: the same kernels with the other
+// epilogue): glwe = [count][mask N][body N] words in natural order; every other argument as in the launcher of the same name.
+int launch_blind_rotate_fft_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
+                                 const double *g_tw_fft, u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels,
+                                 uint32_t base_log, unsigned long long *stat, hipStream_t s);
+int launch_blind_rotate_lat_fft_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
+                                     const double *g_tw_fft, u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels,
+                                     uint32_t base_log, unsigned long long *stat, hipStream_t s);
+int launch_blind_rotate_wide_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
+                                  u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
+                                  hipStream_t s);
+int launch_blind_rotate_wide2_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
+                                   u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, hipStream_t s);
+// glwe_lookup.hip: the look-ups of groups that share one rotation.  glwe = [groups][2N] accumulators of a rotation of the groups'
+// base polynomials; group g serves the tables lut_ids[group_ptr[g] .. group_ptr[g+1]) and writes their LWE rows out[t] (N + 1
+// words) = SampleExtract_0(ACC_g * P_t), P_t the table's sparse factor scaled by 2^(its scale - the scale of base_ids[g]).
+// sparse_head = [BMI_LUT_CAP] {entries, scale}, sparse = [BMI_LUT_CAP][BMI_SPARSE_CAP] {position, coefficient} (bmi_lut_register).
+constexpr uint32_t BMI_SPARSE_CAP = 64;   // entries of a table's sparse factor: 2^msg_bits, so msg_bits <= 6 share a rotation
+int launch_glwe_lookup(const u64 *glwe, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids,
+                       const uint2 *sparse_head, const int2 *sparse, u64 *out, uint32_t groups, uint32_t total, uint32_t N,
+                       hipStream_t s);
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
                      uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
                      hipStream_t s);

@@ -204,6 +204,18 @@ __device__ __forceinline__ void extract_sample(u64 *o, const T *acc, Slot slot, 
         o[N - nn] = (u64)0 - a0;
     }
 }
+// The accumulator itself (the rotation entries that return it, k_blind_rotate_*_glwe): g = [mask N][body N] words in natural order,
+// through the same conversion and slot map as the extraction.  One word of one polynomial (poly = its N elements) ...
+template <int PRE, int AB, typename T, typename Slot>
+__device__ __forceinline__ void store_glwe_word(u64 *g, const T *poly, Slot slot, uint32_t nn) {
+    g[nn] = acc_word<PRE, AB>(poly[slot(nn)]);
+}
+// ... and coefficient nn < N of both, by one thread
+template <int N, int PRE, int AB, typename T, typename Slot>
+__device__ __forceinline__ void store_glwe(u64 *g, const T *acc, Slot slot, uint32_t nn) {
+    store_glwe_word<PRE, AB>(g, acc, slot, nn);
+    store_glwe_word<PRE, AB>(g + N, acc + N, slot, nn);
+}
 #endif
 
 }  // namespace t64

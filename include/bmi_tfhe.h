@@ -161,6 +161,38 @@ int bmi_pbs_batch(bmi_ctx *ctx, const uint64_t *d_in, const uint32_t *d_lut_ids,
 int bmi_keyswitch_batch(bmi_ctx *ctx, const uint64_t *d_in, uint32_t count, uint64_t *d_small, void *stream);
 int bmi_blind_rotate_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
                            uint64_t *d_out, void *stream);
+/* ---- one blind rotation shared by the look-ups of the same ciphertext (2^64 torus; csrc/glwe_lookup.hip) ----
+ * A test polynomial of bmi_lut_register is a step function, so TV_f = TV_0 * P_f with TV_0 = 2^(unit_log - 1) * sum_x X^x and
+ * P_f = (1 - X) TV_f / 2^unit_log a sparse polynomial of at most 2^msg_bits small integers (the differences of neighbouring table
+ * values, times 2^(out_delta_log - unit_log)).  One rotation of TV_0 serves every table of a GROUP - tables that are looked up at
+ * the same input and whose out_delta_log is >= the group's unit_log: output t is SampleExtract_0(ACC * P_t), at most 2^msg_bits
+ * rotated additions per word instead of a keyswitch and a rotation.  The output's bootstrap noise variance grows by |P_t|^2 (the
+ * sum of squares of its coefficients).  Tables of msg_bits <= 6 can share (their sparse form is built at registration).
+ * Refused with a bmi_last_error text: the 49-bit field and Goldilocks; a pinned exact-transform kernel variant (1 / 3 / 4 at
+ * N = 1024), N = 4096, an unrolled key and every key precision the plain floating-point-transform kernels do not serve.
+ *
+ * bmi_lut_register_base: the id of TV_0 = + 2^(unit_log - 1) (every coefficient, PLUS sign; the existing table of -+1 at half
+ * scale yields the negative) as an ordinary table id; one per unit_log however often it is asked for.  unit_log - 1 >= 64 -
+ * (bootstrap-key precision), the grid bmi_lut_register holds its tables to. */
+int bmi_lut_register_base(bmi_ctx *ctx, uint32_t unit_log, uint32_t *lut_id);
+/* bmi_blind_rotate_batch returning the rotated ACCUMULATOR instead of its extracted sample: d_glwe [count][2N] words, the mask
+ * polynomial, then the body, coefficients in natural order (k = 1).  Any registered table; the same kernel choice by batch size,
+ * and o[0] = A[0], o[x] = -A[N - x], o[N] = B[0] are the words bmi_blind_rotate_batch writes. */
+int bmi_blind_rotate_glwe_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
+                                uint64_t *d_glwe, void *stream);
+/* The look-ups of `groups` accumulators: group g is the rotation of the base polynomial d_base_ids[g] and serves the tables
+ * d_lut_ids[d_group_ptr[g] .. d_group_ptr[g+1]) (CSR, d_group_ptr[groups] = total); d_out [total][N+1].  A table that IS its
+ * group's base (lut id = base id, any registered table: what a group of one is given) is the plain extraction, the words of
+ * bmi_blind_rotate_batch and no noise growth.  Preconditions (the *_host forms refuse a violation, the device forms stay inside
+ * their buffers but compute something else): registered ids; for every table other than its group's base, a base id from
+ * bmi_lut_register_base, msg_bits <= 6 and out_delta_log >= the base's unit_log; non-decreasing group ranges from 0 to total. */
+int bmi_glwe_lookup_batch(bmi_ctx *ctx, const uint64_t *d_glwe, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
+                          const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream);
+/* bmi_pbs_batch for grouped look-ups: keyswitch of the `groups` rows of d_in ([groups][N+1]), ONE rotation per group with its base
+ * polynomial, then the look-ups of bmi_glwe_lookup_batch into d_out [total][N+1] (d_in is consumed by the keyswitch before d_out is
+ * written).  The accumulators live in context scratch that bmi_reserve pre-sizes. */
+int bmi_pbs_shared_batch(bmi_ctx *ctx, const uint64_t *d_in, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
+                         const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream);
 /* Leveled (PBS-free) linear ops on big-key ciphertexts, CSR form:
  *   out[i] = const_body[i] + sum_{e in [row_ptr[i], row_ptr[i+1])} coef[e] * store[idx[e]]
  * replaces + - and constant * on Tracers and np.sum / slicing (qfloat.py:811-826, 901, 1015). */
@@ -188,6 +220,15 @@ int bmi_pbs_batch_host(bmi_ctx *ctx, const uint64_t *in, const uint32_t *lut_ids
 int bmi_keyswitch_batch_host(bmi_ctx *ctx, const uint64_t *in, uint32_t count, uint64_t *small_out);
 int bmi_blind_rotate_batch_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
                                 uint64_t *out);
+/* ... and of the shared look-ups (glwe_out / glwe_in: [count resp. groups][2N] words).  They refuse what the device forms state
+ * as preconditions: unknown ids, a base id that serves other tables and is no base polynomial, a table without a sparse form or encoded below its group's
+ * unit, group ranges that do not run from 0 to total without decreasing. */
+int bmi_blind_rotate_glwe_batch_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
+                                     uint64_t *glwe_out);
+int bmi_glwe_lookup_batch_host(bmi_ctx *ctx, const uint64_t *glwe_in, const uint32_t *group_ptr, const uint32_t *base_ids,
+                               const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out);
+int bmi_pbs_shared_batch_host(bmi_ctx *ctx, const uint64_t *in, const uint32_t *group_ptr, const uint32_t *base_ids,
+                              const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out);
 /* Test hook of the floating-point-transform kernels (2^64 torus; N = 1024: key at 48 bits, kernel variants 5 / 6; N = 2048: key at
  * 46 bits; N = 4096: key at 44 bits, k_blind_rotate_q_t64f): blind rotation of `count` small-key ciphertexts by the wave-pair kernel - by the latency form when kernel variant 6 or 2
  * is selected, by k_blind_rotate_w_t64f at N = 2048 -, which here also records how far every limb sum was from the integer it was
@@ -199,7 +240,7 @@ int bmi_fft_margin_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *
 int bmi_negacyclic_mul_host(bmi_ctx *ctx, const uint64_t *a, const uint64_t *b, uint32_t count, uint64_t *c);
 
 /* Pre-sizes the context's internal scratch (small-key ciphertexts of bmi_pbs_batch, digit matrix and limb sums of the
- * matrix-core keyswitch) for batches up to max_count, so that no allocation happens on the hot path afterwards. */
+ * matrix-core keyswitch, on the torus the accumulators of bmi_pbs_shared_batch) for batches up to max_count, so that no allocation happens on the hot path afterwards. */
 int bmi_reserve(bmi_ctx *ctx, uint32_t max_count);
 
 int bmi_sync(bmi_ctx *ctx, void *stream);
