@@ -309,8 +309,10 @@ struct bmi_ctx {
     std::vector<std::vector<u64>> luts_host;
     // 2^64 torus, shared rotations (glwe_lookup.hip): per table the sparse factor P_f = (1 - X) TV_f / 2^scale as (position,
     // difference) pairs, filled at registration.  head[id] = {entries, scale}; entries = NO_SPARSE where the table has more than
-    // BMI_SPARSE_CAP boxes (such a table cannot share a rotation); a base polynomial (bmi_lut_register_base) is {1, unit}: P = 1.
-    static constexpr uint32_t NO_SPARSE = 0xFFFFFFFFu;
+    // BMI_SPARSE_CAP boxes, WIDE_DIFFERENCE where two neighbouring boxes differ by more than an int32 holds (neither can share a
+    // rotation: the kernel counts any value above BMI_SPARSE_CAP as no entries); a base polynomial (bmi_lut_register_base) is
+    // {1, unit}: P = 1.
+    static constexpr uint32_t NO_SPARSE = 0xFFFFFFFFu, WIDE_DIFFERENCE = 0xFFFFFFFEu;
     DevBuf<uint2> sparse_head;         // [BMI_LUT_CAP]
     DevBuf<int2> sparse;               // [BMI_LUT_CAP][BMI_SPARSE_CAP]
     std::vector<uint2> sparse_head_host;
@@ -948,6 +950,8 @@ int check_groups(bmi_ctx *c, const uint32_t *group_ptr, const uint32_t *base_ids
                 return fail(c, -1, "id " + std::to_string(b) + " serves another table but is not a base polynomial (bmi_lut_register_base)");
             const uint2 h = c->sparse_head_host[id];
             if (h.x == bmi_ctx::NO_SPARSE) return fail(c, -1, "table " + std::to_string(id) + " has more than 64 boxes: it cannot share a rotation");
+            if (h.x == bmi_ctx::WIDE_DIFFERENCE)
+                return fail(c, -1, "table " + std::to_string(id) + " has neighbouring entries that differ by more than 2^31 - 1: it cannot share a rotation");
             if (h.y < unit) return fail(c, -1, "table " + std::to_string(id) + " is encoded below its group's unit (2^" + std::to_string(unit) + ")");
         }
     }
@@ -1343,7 +1347,7 @@ int bmi_lut_register(bmi_ctx *c, const int64_t *table, uint32_t msg_bits, uint32
             if (d > INT32_MAX || d < INT32_MIN) fits = false;
             else if (d) sparse.push_back(int2{(int)(b * w - half), (int)d});
         }
-        if (fits) head.x = (uint32_t)sparse.size();
+        head.x = fits ? (uint32_t)sparse.size() : bmi_ctx::WIDE_DIFFERENCE;
     }
     return add_table(c, std::move(tv), head, sparse, lut_id);
 }

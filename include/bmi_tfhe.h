@@ -167,7 +167,8 @@ int bmi_blind_rotate_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t
  * values, times 2^(out_delta_log - unit_log)).  One rotation of TV_0 serves every table of a GROUP - tables that are looked up at
  * the same input and whose out_delta_log is >= the group's unit_log: output t is SampleExtract_0(ACC * P_t), at most 2^msg_bits
  * rotated additions per word instead of a keyswitch and a rotation.  The output's bootstrap noise variance grows by |P_t|^2 (the
- * sum of squares of its coefficients).  Tables of msg_bits <= 6 can share (their sparse form is built at registration).
+ * sum of squares of its coefficients).  Tables of msg_bits <= 6 whose neighbouring entries differ by an int32 at most can share
+ * (their sparse form is built at registration; the others are refused as members of a base's group, each with its own text).
  * Refused with a bmi_last_error text: the 49-bit field and Goldilocks; a pinned exact-transform kernel variant (1 / 3 / 4 at
  * N = 1024), N = 4096, an unrolled key and every key precision the plain floating-point-transform kernels do not serve.
  *
@@ -185,7 +186,8 @@ int bmi_blind_rotate_glwe_batch(bmi_ctx *ctx, const uint64_t *d_small, const uin
  * group's base (lut id = base id, any registered table: what a group of one is given) is the plain extraction, the words of
  * bmi_blind_rotate_batch and no noise growth.  Preconditions (the *_host forms refuse a violation, the device forms stay inside
  * their buffers but compute something else): registered ids; for every table other than its group's base, a base id from
- * bmi_lut_register_base, msg_bits <= 6 and out_delta_log >= the base's unit_log; non-decreasing group ranges from 0 to total. */
+ * bmi_lut_register_base, msg_bits <= 6, int32 differences and out_delta_log >= the base's unit_log; non-decreasing group ranges
+ * from 0 to total. */
 int bmi_glwe_lookup_batch(bmi_ctx *ctx, const uint64_t *d_glwe, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
                           const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream);
 /* bmi_pbs_batch for grouped look-ups: keyswitch of the `groups` rows of d_in ([groups][N+1]), ONE rotation per group with its base

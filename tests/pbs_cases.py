@@ -225,6 +225,37 @@ def timed_inverse(emi, c, warm_up):
     return emi.decrypt(res).tolist(), wall, emi.circuit.summary()["depth"]
 
 
+# ---- shared rotations: the look-up kernel's edge tables and groups, one statement for the GPU test that runs them
+# ---- (tests/test_gpu_shared_rotation.py) and the CPU test that pins their reference to the oracle (tests/test_shared_rotation_model.py)
+
+# the finest unit a base polynomial can have, by ring size: 64 - (bits the default bootstrap key of that ring is stored at) + 1
+FLOOR_UNIT = {1024: 17, 2048: 19, 4096: 21}
+
+
+def edge_lookup_tables(rng):
+    """name -> (table, bits, scale): a 6-bit table whose 64 neighbouring differences are all non-zero (BMI_SPARSE_CAP entries;
+    (-1)^i (i mod 7 + 1) has 63: f(0) = -f(31), so f(-32) is changed), random 6-bit tables at their full scale and one above, 1-
+    and 2-bit tables of one to four entries, the all-zero table (no entry), a constant table (one entry, at N/2 - N/32), and
+    4-bit tables at full scale and at 2^22"""
+    six = np.array([(-1) ** i * (i % 7 + 1) for i in range(64)])
+    six[0] = 2
+    return {"six64": (six, 6, 57), "six_random": (rng.integers(-32, 32, 64), 6, 57), "six_at58": (rng.integers(-16, 16, 64), 6, 58),
+            "one": (np.array([-1, 0]), 1, 62), "one_const": (np.array([-1, -1]), 1, 62),
+            "two": (np.array([-2, 1, 0, 0]), 2, 61), "two_edge": (np.array([-2, 1, 0, -2]), 2, 61),
+            "zero": (np.zeros(16, np.int64), 4, 59), "const": (np.full(16, 5), 4, 59),
+            "four": (rng.integers(-8, 8, 16), 4, 59), "four_low": (rng.integers(-8, 8, 16), 4, 22)}
+
+
+def edge_lookup_groups(floor_unit):
+    """(unit of the group's base polynomial, members) of one block of four groups: the key's grid floor serving tables 2^42 / 2^40
+    / 2^38 and a few bits above it; the base polynomial of a coarser unit ("base59": P = 2) next to a 6-bit table; an empty
+    group; the narrow, empty and constant tables"""
+    return [(floor_unit, ["four", "six64", "six_random", "four_low"]),
+            (58, ["base59", "six_at58"]),
+            (59, []),
+            (59, ["zero", "const", "one", "one_const", "two", "two_edge"])]
+
+
 # ---- the unrolled blind rotation at three configurations: the 49-bit field, the torus with the 48-bit key (exact transform) and
 # ---- with the 42-bit key (floating-point transform)
 

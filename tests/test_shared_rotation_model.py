@@ -57,6 +57,35 @@ def test_sparse_factor_times_base_is_the_oracles_test_polynomial(log_N):
     assert coef[pos == 8 * (N >> 4) - (N >> 5)].tolist() == [2 * h]
 
 
+@pytest.mark.parametrize("log_N", [10, 11, 12])
+def test_sparse_factor_at_the_floor_units_and_edge_tables(log_N):
+    """the (table, scale, unit) triples the GPU test of k_glwe_lookup's edges runs (pbs_cases.edge_lookup_tables / _groups: units
+    down to the key's grid floor, 42 / 40 / 38 bits below the table's scale): sparse_table times the unit's base polynomial is the
+    oracle's test polynomial there too, so the dense product that test compares the kernel with is pinned at the shapes it uses"""
+    import pbs_cases as pc
+    from oracle import tfhe_oracle as to
+    to.set_field(65)
+    N = 1 << log_N
+    T = pc.edge_lookup_tables(np.random.default_rng(N + 1))
+    floor = pc.FLOOR_UNIT[N]
+    entries = {}
+    for unit, members in pc.edge_lookup_groups(floor):
+        for name in members:
+            if name == "base59":        # a base polynomial as a member of a finer group: P = 2^(59 - unit)
+                assert np.array_equal(base_polynomial(unit, N) * np.uint64(1 << (59 - unit)), base_polynomial(59, N))
+                continue
+            table, p, scale = T[name]
+            pos, coef = sparse_table(table, p, scale, unit, N)
+            entries[name] = pos.size
+            assert (pos > 0).all() and (pos < N).all() and (np.diff(pos) > 0).all() and (coef != 0).all(), name
+            assert np.array_equal(negacyclic_sparse(base_polynomial(unit, N), pos, coef), to.make_test_vector(log_N, p, table, scale)), (name, unit)
+            if name == "const":
+                assert pos.tolist() == [N // 2 - N // 32] and coef.tolist() == [-10]
+    edge = {"six64": 64, "zero": 0, "const": 1, "one": 2, "one_const": 1, "two": 3, "two_edge": 4}     # entries of the sparse factors
+    assert {k: entries[k] for k in edge} == edge and len(entries) == len(T)
+    assert 59 - pc.FLOOR_UNIT[1024] == 42 and 59 - pc.FLOOR_UNIT[2048] == 40
+
+
 def test_moments_of_a_sparse_factor():
     """sparse_moments against its definition, and E |S P|^2 = N (|P|^2 / 4 + mean m^2 / 4) against the exact |S P|^2 of random keys"""
     rng = np.random.default_rng(2)
