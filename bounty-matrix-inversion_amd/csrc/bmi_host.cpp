@@ -871,9 +871,17 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     return 0;
 }
 
+// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the four plain floating-point-transform kernels of the torus.
+// Not the exact-transform pair a pinned variant 1 / 3 / 4 selects, the N = 4096 kernel, the unrolled ones, the prime fields.
+bool has_accumulator_form(Rot rot) {
+    return rot == Rot::t64_wide2 || rot == Rot::t64_wide || rot == Rot::t64_lat_fft || rot == Rot::t64_fft;
+}
+
 // Launches `rot` on the context's key copies and tables.  stat: as in bmit::launch_blind_rotate_fft, for the kernels that take it.
+// glwe (has_accumulator_form(rot) only): out receives the accumulators [count][2N] instead of the extracted samples [count][N + 1].
 int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *out, unsigned long long *stat,
-                    hipStream_t st) {
+                    bool glwe, hipStream_t st) {
+    if (glwe && !has_accumulator_form(rot)) return (int)hipErrorInvalidValue;
     const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
     const int p = c->bsk_prec;
     const u64 *luts = c->luts.get();
@@ -881,8 +889,8 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     const bmi_ctx::BskCopies &K = c->bsk;
     const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
     switch (rot) {
-    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, st);
-    case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, glwe, st);
+    case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, st);
     case Rot::t64_tp2u_fft: return bmit::launch_blind_rotate_tp2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(), out,
                                                                       count, n, p, lv, bl, st);
@@ -890,9 +898,9 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
                                                                         out, count, n, p, lv, bl, stat, st);
     case Rot::t64_lat2u: return bmit::launch_blind_rotate_lat2u(cts, ids, luts, K3.exact_lat.get(), c->tw_half.get(), c->root_pow.get(), out, count,
                                                                 n, p, lv, bl, st);
-    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_lat: return bmit::launch_blind_rotate_lat(cts, ids, luts, K.exact_lat.get(), c->tw_half.get(), out, count, n, p, lv, bl, st);
-    case Rot::t64_fft: return bmit::launch_blind_rotate_fft(cts, ids, luts, K.fft.get(), c->tw_fft.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_fft: return bmit::launch_blind_rotate_fft(cts, ids, luts, K.fft.get(), c->tw_fft.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_exact: return bmit::launch_blind_rotate(cts, ids, luts, K.exact.get(), c->tw_wave.get(), out, count, n, p, lv, bl, st);
     case Rot::f49_wide_u: return bmi49::launch_blind_rotate_wide_u(cts, ids, luts49, K3.wide49.get(), c->tw_wave.get(), c->tw_wide49.get(),
                                                                    c->root_pow.get(), out, count, n, lv, bl, st);
@@ -905,24 +913,6 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     case Rot::gl_tp: return bmi::launch_blind_rotate_tp(cts, ids, luts, K.ntt_gl.get(), c->tw_gl.get(), out, count, n, st);
     }
     return (int)hipErrorInvalidValue;
-}
-
-// The accumulator form of `rot` (bmi_blind_rotate_glwe_batch): the four plain floating-point-transform kernels of the torus have
-// one; *known = false for every other kernel (the exact-transform pair a pinned variant 1 / 3 / 4 selects, the N = 4096 kernel, the
-// unrolled ones, the prime fields).
-int launch_rotation_glwe(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *glwe, hipStream_t st, bool *known) {
-    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
-    const int p = c->bsk_prec;
-    const u64 *luts = c->luts.get();
-    const bmi_ctx::BskCopies &K = c->bsk;
-    *known = true;
-    switch (rot) {
-    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2_glwe(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), glwe, count, n, p, lv, bl, st);
-    case Rot::t64_wide: return bmit::launch_blind_rotate_wide_glwe(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), glwe, count, n, p, lv, bl, nullptr, st);
-    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft_glwe(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), glwe, count, n, p, lv, bl, nullptr, st);
-    case Rot::t64_fft: return bmit::launch_blind_rotate_fft_glwe(cts, ids, luts, K.fft.get(), c->tw_fft.get(), glwe, count, n, p, lv, bl, nullptr, st);
-    default: *known = false; return 0;
-    }
 }
 
 // accumulators of a batch (room for 256 at least)
@@ -1504,17 +1494,29 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
     return rc ? fail(c, -2, std::string("keyswitch launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
 }
 
-int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
-                           uint64_t *d_out, void *stream) {
+// bmi_blind_rotate_batch (d_out = [count][N + 1] samples) and, with glwe, bmi_blind_rotate_glwe_batch (d_out = [count][2N] accumulators)
+static int blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_out, bool glwe,
+                              void *stream) {
     if (!c || (count && (!d_small || !d_lut_ids || !d_out))) return -1;
+    if (glwe)
+        if (int rc = shared_rotation_ok(c)) return rc;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     HIP_OK(c, hipSetDevice(c->device));
     Rot rot;
     if (int rc = choose_rotation(c, count, &rot)) return rc;
+    if (glwe && !has_accumulator_form(rot))
+        return fail(c, -1, "the accumulator form exists for the plain floating-point-transform kernels only (N = 1024 with the key at 48 bits, "
+                           "N = 2048): not for a pinned exact-transform variant (1 / 3 / 4), N = 4096, an unrolled key or another key precision");
     if (rot == Rot::t64_lat || rot == Rot::t64_exact)
         if (int rc = build_exact_torus_copies(c, nullptr)) return rc;   // (a no-op once built)
-    const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("blind_rotate launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, glwe, (hipStream_t)stream);
+    if (rc) return fail(c, -2, std::string(glwe ? "blind_rotate (accumulator form) launch: " : "blind_rotate launch: ") + hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
+                           uint64_t *d_out, void *stream) {
+    return blind_rotate_batch(c, d_small, d_lut_ids, count, d_out, false, stream);
 }
 
 int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_out,
@@ -1530,18 +1532,7 @@ int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, u
 
 int bmi_blind_rotate_glwe_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_glwe,
                                 void *stream) {
-    if (!c || (count && (!d_small || !d_lut_ids || !d_glwe))) return -1;
-    if (int rc = shared_rotation_ok(c)) return rc;
-    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    HIP_OK(c, hipSetDevice(c->device));
-    Rot rot;
-    if (int rc = choose_rotation(c, count, &rot)) return rc;
-    bool known;
-    const int rc = launch_rotation_glwe(c, rot, d_small, d_lut_ids, count, d_glwe, (hipStream_t)stream, &known);
-    if (!known)
-        return fail(c, -1, "the accumulator form exists for the plain floating-point-transform kernels only (N = 1024 with the key at 48 bits, "
-                           "N = 2048): not for a pinned exact-transform variant (1 / 3 / 4), N = 4096, an unrolled key or another key precision");
-    return rc ? fail(c, -2, std::string("blind_rotate (accumulator form) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return blind_rotate_batch(c, d_small, d_lut_ids, count, d_glwe, true, stream);
 }
 
 int bmi_glwe_lookup_batch(bmi_ctx *c, const uint64_t *d_glwe, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
@@ -1669,38 +1660,36 @@ int bmi_keyswitch_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uin
     return 0;
 }
 
-int bmi_blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
-                                uint64_t *out) {
+// bmi_blind_rotate_batch_host (rows of N + 1 words through io_b) and, with glwe, bmi_blind_rotate_glwe_batch_host (rows of 2N words
+// through the accumulator buffer)
+static int blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *out, bool glwe) {
     if (!c || !small_in || !lut_ids || !out) return -1;
+    if (glwe)
+        if (int rc = shared_rotation_ok(c)) return rc;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_io(c, count);
+    if (!rc && glwe) rc = ensure_glwe(c, count);
     if (rc) return rc;
+    u64 *d_out = glwe ? c->glwe.get() : c->io_b.get();
+    const size_t width = glwe ? (size_t)2 * c->big_n : (size_t)c->big_n + 1;
     HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_blind_rotate_batch(c, c->small.get(), c->io_ids.get(), count, c->io_b.get(), c->stream);
+    rc = blind_rotate_batch(c, c->small.get(), c->io_ids.get(), count, d_out, glwe, c->stream);
     if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipMemcpyAsync(out, d_out, count * width * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
+int bmi_blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
+                                uint64_t *out) {
+    return blind_rotate_batch_host(c, small_in, lut_ids, count, out, false);
+}
+
 // Host-buffer forms of the shared look-ups.  They refuse what the device-pointer forms state as preconditions (check_groups).
 int bmi_blind_rotate_glwe_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *glwe_out) {
-    if (!c || !small_in || !lut_ids || !glwe_out) return -1;
-    if (int rc = shared_rotation_ok(c)) return rc;
-    if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_io(c, count);
-    if (!rc) rc = ensure_glwe(c, count);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_blind_rotate_glwe_batch(c, c->small.get(), c->io_ids.get(), count, c->glwe.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(glwe_out, c->glwe.get(), (size_t)count * 2 * c->big_n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return blind_rotate_batch_host(c, small_in, lut_ids, count, glwe_out, true);
 }
 
 // uploads the group description of a host-buffer form: io_groups = group_ptr [groups + 1], base ids [groups]; io_ids = lut_ids [total]
@@ -1770,7 +1759,7 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
     hipError_t e = hipMemsetAsync(d_stat.get(), 0, 8, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)launch_rotation(c, rot, c->small.get(), c->io_ids.get(), count, c->io_b.get(), d_stat.get(), c->stream);
+    if (e == hipSuccess) e = (hipError_t)launch_rotation(c, rot, c->small.get(), c->io_ids.get(), count, c->io_b.get(), d_stat.get(), false, c->stream);
     unsigned long long bits = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&bits, d_stat.get(), 8, hipMemcpyDeviceToHost, c->stream);

@@ -85,19 +85,16 @@ inline int with_levels_stats(uint32_t levels, bool stats, F f) {
     return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
-// The rotation kernels that return the accumulator (k_blind_rotate_*_glwe, bmi_blind_rotate_glwe_batch) are SECOND ENTRIES of the
-// plain torus FFT kernels, compiled from the same text in translation units of their own: bmi_kernels_t64{f,w,w2}_glwe.hip define
-// BMI_ROT_GLWE and include bmi_kernels_t64{f,w,w2}.hip, where BMI_ROT_ENTRY names the kernels and their launchers and ROT_GLWE
-// selects the epilogue (t64::store_glwe instead of t64::extract_sample) - everything up to the end of the CMUX loop is shared, and
-// the translation units of the existing entries see the same tokens as before.  The key conversions, their launchers and the shape
-// predicates of a kernel file are left out of its second compilation (#ifndef BMI_ROT_GLWE).
-#ifdef BMI_ROT_GLWE
-#define BMI_ROT_ENTRY(name) name##_glwe
-constexpr bool ROT_GLWE = true;
-#else
-#define BMI_ROT_ENTRY(name) name
-constexpr bool ROT_GLWE = false;
-#endif
+// ... and the epilogue of the four plain torus FFT rotations (bmi_kernels_t64{f,w,w2}.hip), whose trailing template flag GLWE makes
+// them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
+// out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator
+// form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.
+template <typename F>
+inline int with_levels_stats_glwe(uint32_t levels, bool stats, bool glwe, F f) {
+    if (!glwe) return with_levels_stats(levels, stats, [&](auto L, auto STATS) { return f(L, STATS, std::false_type{}); });
+    if (stats) return (int)hipErrorInvalidValue;
+    return with_levels(levels, [&](auto L) { return f(L, std::false_type{}, std::true_type{}); });
+}
 
 namespace bmi {
 using gl::i64;
@@ -215,15 +212,17 @@ int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, con
 bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s);
 // stat (may be null): receives, as the bit pattern of a double, the largest distance of a limb sum from the integer it was rounded to
+// glwe (this launcher, launch_blind_rotate_lat_fft, launch_blind_rotate_wide and launch_blind_rotate_wide2): out receives the
+// ACCUMULATOR, [count][mask N][body N] words in natural order, instead of the extracted samples [count][N + 1]; stat must be null
 int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
                             const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, unsigned long long *stat, hipStream_t s);
+                            uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
 // latency form (one workgroup of 16 wavefronts per ciphertext, half transforms: fft_half_f64.hpp): own key copy, per (polynomial,
 // limb) 256 slots of [F_k, F_{k+256}]; tables ffth::HT_WORDS doubles
 int launch_bsk_to_latf(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
                                 const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                uint32_t base_log, unsigned long long *stat, hipStream_t s);
+                                uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
 // the unrolled step (two LWE coefficients) through the floating-point transform (bmi_kernels_t64fu.hip): key at 42 bits of precision
 // (two 21-bit limbs: the six-times larger limb sums stay inside the transform's certified range); bsk3_latf = launch_bsk_to_latf of
 // the unrolled key, g_zeta_pow = exp(i pi x / 1024) for x in [0, 1024) as (re, im); stat as in launch_blind_rotate_fft
@@ -247,7 +246,7 @@ int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, cons
 // per (polynomial, limb) [t 4][256 slots] complex words A_k / 2; tables and results as launch_blind_rotate_wide
 int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
-                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, hipStream_t s);
+                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s);
 // N = 2048 (bmi_kernels_t64w.hip, fft_quarter_f64.hpp): key at 46 bits of precision (two 23-bit limbs), one workgroup of 16
 // wavefronts per ciphertext (auto dispatch: up to 256 ciphertexts; launch_blind_rotate_wide2 beyond); key copy per (polynomial, limb) 1,024 complex words A_k / 2 in the order of the
 // multiplying threads; tables fftq::QT_WORDS doubles; stat as in launch_blind_rotate_fft
@@ -255,20 +254,7 @@ bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             hipStream_t s);
-// The four plain FFT rotations above returning the ACCUMULATOR (bmi_kernels_t64{f,w,w2}_glwe.hip: the same kernels with the other
-// epilogue): glwe = [count][mask N][body N] words in natural order; every other argument as in the launcher of the same name.
-int launch_blind_rotate_fft_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                                 const double *g_tw_fft, u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                 uint32_t base_log, unsigned long long *stat, hipStream_t s);
-int launch_blind_rotate_lat_fft_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                                     const double *g_tw_fft, u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                     uint32_t base_log, unsigned long long *stat, hipStream_t s);
-int launch_blind_rotate_wide_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
-                                  u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                                  hipStream_t s);
-int launch_blind_rotate_wide2_glwe(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
-                                   u64 *glwe, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, hipStream_t s);
+                             bool glwe, hipStream_t s);
 // glwe_lookup.hip: the look-ups of groups that share one rotation.  glwe = [groups][2N] accumulators of a rotation of the groups'
 // base polynomials; group g serves the tables lut_ids[group_ptr[g] .. group_ptr[g+1]) and writes their LWE rows out[t] (N + 1
 // words) = SampleExtract_0(ACC_g * P_t), P_t the table's sparse factor scaled by 2^(its scale - the scale of base_ids[g]).

@@ -81,7 +81,6 @@ constexpr int TF_LDS_WORDS = TW_WORDS + 2 * TF_CTS * (SCRATCH_WORDS + N) + TF_CT
 static_assert(TF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "TF_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(SCRATCH_WORDS >= N, "a tile carries 512 complex partial sums to the partner");
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per polynomial the two limb
 // polynomials in the evaluation layout of fft_wave_f64.hpp ([poly][limb][register c][lane] complex words)
 __global__ void __launch_bounds__(256) k_bsk_to_fft_t64(const u64 *__restrict__ std_polys, double *__restrict__ limb_polys,
@@ -102,12 +101,12 @@ __global__ void __launch_bounds__(256) k_bsk_to_fft_t64(const u64 *__restrict__ 
     double2 *dst = reinterpret_cast<double2 *>(limb_polys + (size_t)item * N);
     static_for<0, 8>([&](auto Cc) { dst[Cc * 64 + lane] = double2{x[Cc], x[Cc + 8]}; });
 }
-#endif
 
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
-template <int L, int BG, bool STATS = false>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, bool STATS, bool GLWE>
 __global__ void __launch_bounds__(128 * TF_CTS)
-    BMI_ROT_ENTRY(k_blind_rotate_t64f)(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
+    k_blind_rotate_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                         const double *__restrict__ bsk, const double *__restrict__ g_tw, u64 *__restrict__ out,
                         uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int CTS = TF_CTS;
@@ -293,7 +292,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
     if (!live) return;
     wave_sync();
-    if constexpr (ROT_GLWE) {   // the accumulator itself, out = [count][2N]: this wavefront's polynomial (c = 0: mask, 1: body)
+    if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]: this wavefront's polynomial (c = 0: mask, 1: body)
         u64 *g = out + (size_t)ct * (2 * N) + c * N;
         static_for<0, 16>([&](auto J) { t64::store_glwe_word<PRE, AB>(g, accf, t64::ResidueSlot<N, 0>{}, lane + 64 * J); });
         return;
@@ -334,7 +333,6 @@ static_assert(LF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "LF_LDS_WORDS exceeds the 160 K
 // accumulator words are kept split by parity (a lane's four points are 128 coefficients apart and of one parity)
 constexpr t64::ResidueSlot<N, 1> acc_slot{};
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // standard-domain GGSW polynomials -> per (polynomial, limb) 256 slots of [F_k, F_{k+256}] (k = ffth::slot_freq of the slot)
 __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__ std_polys, double *__restrict__ lat_polys,
                                                          const double *__restrict__ g_tw_h, uint32_t n_polys, int prec) {
@@ -373,13 +371,13 @@ __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__
         });
     }
 }
-#endif
 
 // STATS (the test hook bmi_fft_margin_host with the latency form selected): also records the largest distance of a limb sum from the
 // integer it is rounded to
-template <int L, int BG, bool STATS = false>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, bool STATS, bool GLWE>
 __global__ void __launch_bounds__(LF_THREADS)
-    BMI_ROT_ENTRY(k_blind_rotate_lat_t64f)(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
+    k_blind_rotate_lat_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                             const double *__restrict__ bsk_latf, const double *__restrict__ g_tw_h, u64 *__restrict__ out,
                             uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<48>::LIMBS, LB = Scheme<48>::BITS, PRE = Scheme<48>::PRE, AB = 64 - PRE;
@@ -489,19 +487,16 @@ __global__ void __launch_bounds__(LF_THREADS)
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    if constexpr (ROT_GLWE) t64::store_glwe<N, PRE, AB>(out + (size_t)ct * (2 * N), acc, acc_slot, tid);   // out = [count][2N]
+    if constexpr (GLWE) t64::store_glwe<N, PRE, AB>(out + (size_t)ct * (2 * N), acc, acc_slot, tid);   // out = [count][2N]
     else t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
 
 }  // namespace
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 PH_EXPORT(bmi_debug_phase_prof_t64f, g_phase_f)
-#endif
 
 namespace bmit {
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // (precision, levels, base log) combinations the transform's error bound was established for
 bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log) {
     return prec == 48 && base_log == 10 && (levels == 3 || levels == 2);
@@ -523,29 +518,26 @@ int launch_bsk_to_latf(const u64 *std_polys, double *lat_polys, const double *g_
     return 0;
 }
 
-#endif
-
-// (compiled a second time as launch_blind_rotate_lat_fft_glwe / launch_blind_rotate_fft_glwe: out = [count][2N] accumulator words)
-int BMI_ROT_ENTRY(launch_blind_rotate_lat_fft)(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
+int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
                                 const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                uint32_t base_log, unsigned long long *stat, hipStream_t s) {
+                                uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
-        return launch_with_lds<BMI_ROT_ENTRY(k_blind_rotate_lat_t64f)<L, 10, STATS>>(dim3(count), dim3(LF_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
-                                                                       small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS, GLWE>>(dim3(count), dim3(LF_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
+                                                                             small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
     });
 }
 
-int BMI_ROT_ENTRY(launch_blind_rotate_fft)(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
+int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
                             const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, unsigned long long *stat, hipStream_t s) {
+                            uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
-        return launch_with_lds<BMI_ROT_ENTRY(k_blind_rotate_t64f)<L, 10, STATS>>(dim3((count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS),
-                                                                   (size_t)TF_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_fft,
-                                                                   g_tw_fft, out, count, n, stat);
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_t64f<L, 10, STATS, GLWE>>(dim3((count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS),
+                                                                         (size_t)TF_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_fft,
+                                                                         g_tw_fft, out, count, n, stat);
     });
 }
 

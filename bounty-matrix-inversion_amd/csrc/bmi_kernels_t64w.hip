@@ -58,7 +58,6 @@ static_assert(2 * 2 * 4 * WQ <= WF_TILE_CPLX, "the sums S of both limbs and outp
 // accumulator words are kept split by residue mod 4 (a lane's points of a quarter are 256 coefficients apart and of one residue)
 constexpr t64::ResidueSlot<WN, 2> acc_slot{};
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per (polynomial, limb) 1,024
 // complex words A_k / 2 in the order the multiplying threads read them: thread (w8 = slot / 32, lane) of phase B owns slot
 // p = 32 w8 + (lane & 31) and, with tp = lane >> 5, the frequencies kappa(p) + 256 (tp + 2 f), f = 0, 1 - complex word
@@ -100,12 +99,12 @@ __global__ void __launch_bounds__(256) k_bsk_to_w_t64(const u64 *__restrict__ st
         });
     }
 }
-#endif
 
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
-template <int L, int BG, int PREC, bool STATS>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, int PREC, bool STATS, bool GLWE>
 __global__ void __launch_bounds__(WF_THREADS)
-    BMI_ROT_ENTRY(k_blind_rotate_w_t64f)(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
+    k_blind_rotate_w_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                           const double *__restrict__ bsk_w, const double *__restrict__ g_tw, u64 *__restrict__ out, uint32_t count,
                           uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
@@ -288,7 +287,7 @@ __global__ void __launch_bounds__(WF_THREADS)
     }
     PH_STORE(g_phase_w, wave, lane);
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    if constexpr (ROT_GLWE) {   // the accumulator itself, out = [count][2N]
+    if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
         u64 *g = out + (size_t)ct * (2 * WN);
         static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + WF_THREADS * Q); });
         return;
@@ -299,13 +298,10 @@ __global__ void __launch_bounds__(WF_THREADS)
 
 }  // namespace
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 PH_EXPORT(bmi_debug_phase_prof_t64w, g_phase_w)
-#endif
 
 namespace bmit {
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // (precision, levels, base log) combinations the N = 2048 transform's error bound was established for
 bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log) {
     return prec == 46 && base_log == 10 && (levels == 3 || levels == 2);
@@ -319,17 +315,14 @@ int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw
     return 0;
 }
 
-#endif
-
-// (compiled a second time as launch_blind_rotate_wide_glwe: out = [count][2N] accumulator words)
-int BMI_ROT_ENTRY(launch_blind_rotate_wide)(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
+int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             hipStream_t s) {
+                             bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
-        return launch_with_lds<BMI_ROT_ENTRY(k_blind_rotate_w_t64f)<L, 10, 46, STATS>>(dim3(count), dim3(WF_THREADS), (size_t)WF_LDS_WORDS * sizeof(double), s,
-                                                                         small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat);
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_w_t64f<L, 10, 46, STATS, GLWE>>(dim3(count), dim3(WF_THREADS), (size_t)WF_LDS_WORDS * sizeof(double), s,
+                                                                              small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat);
     });
 }
 

@@ -67,7 +67,6 @@ __device__ __forceinline__ void dft4(C (&q)[4]) {
     q[3] = INV ? p : m;
 }
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per (polynomial, limb) 1,024 complex
 // words A_k / 2 as [t 4][slot 256]: frequency kappa(slot) + 256 t.  One workgroup of four wavefronts (the quarters) per item.
 __global__ void __launch_bounds__(256) k_bsk_to_w2_t64(const u64 *__restrict__ std_polys, double *__restrict__ w2_polys,
@@ -105,11 +104,11 @@ __global__ void __launch_bounds__(256) k_bsk_to_w2_t64(const u64 *__restrict__ s
         static_for<0, 4>([&](auto T) { o[T * WS + p] = double2{0.5 * q[T].r, 0.5 * q[T].i}; });
     }
 }
-#endif
 
-template <int L, int BG, int PREC>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, int PREC, bool GLWE>
 __global__ void __launch_bounds__(W2_THREADS)
-    BMI_ROT_ENTRY(k_blind_rotate_w2_t64f)(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
+    k_blind_rotate_w2_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                            const double *__restrict__ bsk_w2, const double *__restrict__ g_tw, u64 *__restrict__ out, uint32_t count,
                            uint32_t n) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
@@ -250,7 +249,7 @@ __global__ void __launch_bounds__(W2_THREADS)
     }
     for (int b = 0; b < (live1 ? 2 : 1); b++) {
         const double *acc = accs + b * 2 * WN;
-        if constexpr (ROT_GLWE) {   // the accumulator itself, out = [count][2N]
+        if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
             u64 *g = out + (size_t)cts[b] * (2 * WN);
             static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W2_THREADS * Q); });
             continue;
@@ -264,7 +263,6 @@ __global__ void __launch_bounds__(W2_THREADS)
 
 namespace bmit {
 
-#ifndef BMI_ROT_GLWE   // (left out of the second compilation, bmi_internal.hpp BMI_ROT_ENTRY)
 int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s) {
     if (prec != 46) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
@@ -273,17 +271,15 @@ int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_
     return 0;
 }
 
-#endif
-
-// (compiled a second time as launch_blind_rotate_wide2_glwe: out = [count][2N] accumulator words)
-int BMI_ROT_ENTRY(launch_blind_rotate_wide2)(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
-                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, hipStream_t s) {
+int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
+                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels(levels, [&](auto L) {
-        return launch_with_lds<BMI_ROT_ENTRY(k_blind_rotate_w2_t64f)<L, 10, 46>>(dim3((count + 1) / 2), dim3(W2_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
-                                                                   small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
-    });
+    auto launch = [&](auto L, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((count + 1) / 2), dim3(W2_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
+                                                                        small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
+    };
+    return with_levels(levels, [&](auto L) { return glwe ? launch(L, std::true_type{}) : launch(L, std::false_type{}); });
 }
 
 }  // namespace bmit

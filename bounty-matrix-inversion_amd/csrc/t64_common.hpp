@@ -204,7 +204,7 @@ __device__ __forceinline__ void extract_sample(u64 *o, const T *acc, Slot slot, 
         o[N - nn] = (u64)0 - a0;
     }
 }
-// The accumulator itself (the rotation entries that return it, k_blind_rotate_*_glwe): g = [mask N][body N] words in natural order,
+// The accumulator itself (the rotation kernels instantiated with GLWE = true return it): g = [mask N][body N] words in natural order,
 // through the same conversion and slot map as the extraction.  One word of one polynomial (poly = its N elements) ...
 template <int PRE, int AB, typename T, typename Slot>
 __device__ __forceinline__ void store_glwe_word(u64 *g, const T *poly, Slot slot, uint32_t nn) {
