@@ -15,13 +15,14 @@
 //
 // Roles of the eight wavefronts of a workgroup: ciphertext slot ctl = wave >> 1, polynomial c = wave & 1, partner = wave ^ 1.
 // Wavefronts w and w + 4 share a SIMD, so the two wavefronts of a ciphertext sit on different SIMDs and each SIMD holds one
-// wavefront of slots 0-1 (the older: it wins issue and leads) and one of slots 2-3 (it trails and sets the pace).  The four
+// wavefront of slots 0-1 (group A, the older: it wins issue and leads by a forward phase, below) and one of slots 2-3 (group B).  The four
 // wavefronts with the same c (0, 2, 4, 6 or 1, 3, 5, 7) read the same key rows (bsk_c depends on c only) and share them through
-// L1 - in part: the trailing wavefronts ask for a row two to five rows after the leaders, and measured a workgroup fetches 2.1 x
-// one copy of the key from L2 per CMUX (4,196 M 128-byte read requests per launch of 8,192 against 1,982 M).  That traffic is
-// not what holds the kernel: making the two wavefronts of a ciphertext SIMD-mates (ctl = wave % 4, c = wave / 4), which keeps the
-// four readers of a row together, brings it down to 1.3 x and is 1.2 - 1.7 ms per 8,192 SLOWER; a workgroup barrier at each limb's
-// first row is 8 ms slower (profiles/key_row_sharing_ab.txt, EXPERIMENTS A19).  These roles stay.
+// L1 - in part.  With all eight wavefronts in phase (before the offset below) the trailing wavefronts asked for a row two to
+// five rows after the leaders and a workgroup fetched 2.1 x one copy of the key from L2 per CMUX (4,207 M 128-byte read requests
+// per launch of 8,192 against 1,982 M).  With the offset a row's four readers are two of each group, a forward phase apart by
+// design, and it is 2.4 x (4,778 M, same call) - in the faster kernel.  That traffic is not what holds the kernel: making the two wavefronts of a ciphertext SIMD-mates (ctl = wave % 4, c = wave / 4), which keeps the
+// four readers of a row together, brought it down to 1.3 x and was 1.2 - 1.7 ms per 8,192 SLOWER; a workgroup barrier at each limb's
+// first row was 8 ms slower (profiles/key_row_sharing_ab.txt, EXPERIMENTS A19).  These roles stay.
 // What a CMUX keeps in registers instead of re-reading from LDS: the forward transforms' table twiddles (ForwardTwiddles: loaded
 // once, used by the L transforms) and the lane's own 16 accumulator words across the back edge (`keep`).
 //
@@ -49,7 +50,25 @@
 // No deadlock: w waits for pub[w'] = h and for ack[w'] = h; w' stores pub[w'] = h before any of its waits of hand-off h (its last
 // wait before that is for ack[w] = h - 1, stored by w before w reached hand-off h), and stores ack[w'] = h after waiting for
 // pub[w] = h only, which w has stored before either of its waits.  Dead pairs (beyond `count`) run the whole protocol on a copy of
-// the last ciphertext.  The per-CMUX workgroup barrier is reached by every wavefront outside any hand-off.
+// the last ciphertext.  The per-CMUX workgroup barrier is reached by every wavefront outside any hand-off, at either site.
+//
+// Who is in which phase when (EXPERIMENTS A22, profiles/phase_offset_ab.txt).  Wavefronts 0 .. CTS-1 are group A, CTS .. 2 CTS-1
+// group B; each SIMD holds one wavefront of each group and both wavefronts of a pair are in the same group, so the pair protocol
+// never crosses groups (CTS is even; at CTS = 2 a SIMD holds one wavefront and the offset has no mate to serve).  Every wavefront executes ONE hardware barrier per CMUX (n in all, after the one of the prologue), at one
+// of two sites under a scalar branch (pair_sync.hpp: barrier_if): group B at the loop head, group A between its last forward
+// transform and its first product row.  The hardware counts arrivals: barrier i releases when B stands at the head of step i and A
+// has finished the forward transforms of step i.  From then on A leads its SIMD-mate by one forward phase - A multiplies key rows
+// (the compute unit's intake is the limit there, the f64 pipe idles) while B transforms (f64 and LDS stores, one prefetched row
+// on the memory path) - and eight wavefronts never enter the intake-bound product phase in step.  The lead cannot grow: A waits
+// at its site of step i + 1 until B has reached the head of step i + 1.  The barrier only paces: no wavefront reads another's
+// LDS words across it (tiles are guarded by the pair flags; at[] and the tables are read-only after the prologue), so it is bare
+// - no fence, no wait for outstanding loads - and a step count of 1, dead pairs and both level counts need no special case.
+// (One barrier per CMUX for all eight at the loop head, the form before: 1.3 ms per 8,192 slower; none at all: 83.2 ms against 68.9.)
+// Issue priority follows from mates being in different phases: 0 through the forward transforms, 1 from the first product row to
+// the end of the CMUX.  A product row is a few instructions whose loads should leave at once, the hand-offs and inverse transforms
+// are what the partner waits on, and the mate's transforms fill the rest.  With the in-phase ladder (3, 2, 1 / 0) the transforming
+// wavefront starves its mate's loads and the offset LOSES 1.5 - 4.4 ms; with no priorities it loses 3; the new priorities
+// without the offset lose 5.
 #include <hip/hip_runtime.h>
 
 #include "bmi_internal.hpp"
@@ -65,21 +84,19 @@ using namespace fftw;
 
 namespace {
 
-#ifndef BMI_T64F_RESYNC
-#define BMI_T64F_RESYNC 1   // workgroup barrier every so many CMUXes: keeps the four pairs on the same key rows, which they share through L1 (0: 83.2 ms, 4: 70.1, 1: 68.9 per 8,192)
-#endif
-
 PH_ARRAY(g_phase_f)   // make -C csrc prof; tools/phase_prof_t64f.py
 using t64::f64_to_word;
 using t64::mod_ab;
 using t64::Scheme;
 #ifndef BMI_T64F_CTS
-#define BMI_T64F_CTS 4      // ciphertexts (wavefront pairs) per workgroup: 4 fill the CU's LDS; 3 and 2 measured slower per ciphertext
+#define BMI_T64F_CTS 4      // ciphertexts (wavefront pairs) per workgroup, even: 4 fill the CU's LDS; 3 (before the barrier groups) and 2 measured slower per ciphertext
 #endif
 constexpr int TF_CTS = BMI_T64F_CTS;
 constexpr int TF_LDS_WORDS = TW_WORDS + 2 * TF_CTS * (SCRATCH_WORDS + N) + TF_CTS * BMI_AT_WORDS + 4 * TF_CTS;
 static_assert(TF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "TF_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(SCRATCH_WORDS >= N, "a tile carries 512 complex partial sums to the partner");
+// the two barrier groups are wavefronts 0 .. CTS-1 and CTS .. 2 CTS-1: with an odd CTS the pair (CTS-1, CTS) would straddle them
+static_assert(TF_CTS % 2 == 0, "both wavefronts of a pair must be in the same barrier group");
 
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per polynomial the two limb
 // polynomials in the evaluation layout of fft_wave_f64.hpp ([poly][limb][register c][lane] complex words)
@@ -155,14 +172,12 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     static_for<0, 16>([&](auto J) { keep[J] = accf[lane + 64 * J]; });
     for (uint32_t i = 0; i < n; i++) {
         PH_MARK(7);
-#if BMI_T64F_RESYNC
-        if (i % BMI_T64F_RESYNC == 0) __syncthreads();
-#endif
+        barrier_if(threadIdx.x >= 64 * CTS);   // barrier i of group B (the group flag is recomputed at each site, not carried)
         PH_MARK(0);   // resync barrier
         const uint32_t a_t = at[i];
         // this wavefront's L GGSW rows: [row = L c + lev][column][limb][N]
         const double *bsk_c = bsk + ((size_t)i * 4 * L + c * 2 * L) * LIMBS * N;
-        __builtin_amdgcn_s_setprio(3);   // issue priority steps down through the forward transforms (3, 2, 1), 0 in the limb loop
+        __builtin_amdgcn_s_setprio(0);   // issue priority: 0 through the forward transforms, 1 in the limb loop (header: SIMD-mates are in different phases)
         wave_sync();
         double r[16];
         {
@@ -198,7 +213,6 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = L - 1 - LEV;  // least significant digit first
             pin();
-            __builtin_amdgcn_s_setprio(lev + 1);
             static_for<0, 16>([&](auto J) {
                 if constexpr (lev == 0) {
                     X[0][J] = r[J];
@@ -214,8 +228,10 @@ __global__ void __launch_bounds__(128 * TF_CTS)
             }
             forward(X[lev], lane, ftw, tile);
         });
-        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(1);
         PH_MARK(2);   // digits + L forward transforms
+        barrier_if(threadIdx.x < 64 * CTS);   // barrier i of group A
+        PH_MARK(0);
         double acc[16];
         static_for<0, LIMBS * 2 * L>([&](auto T) {
             constexpr int t = T, j = t / (2 * L), q = t % (2 * L), lev = q % L, cur = t & 1;

@@ -54,6 +54,21 @@ __device__ __forceinline__ void pair_wait(uint32_t *flag, uint32_t v) {
         : "v"(pair_lds_addr(flag)), "s"(v)
         : "vcc", "memory");
 }
+// The workgroup's hardware barrier for the wavefronts whose `here` (wave-uniform, read from the first lane) is non-zero; the others
+// fall through.  Bare: no fence and no wait for outstanding memory operations in front of it - it paces wavefronts, it does not
+// order their LDS words.  The hardware counts arrivals, not sites: two groups of wavefronts may execute their barrier k at
+// different places of the same loop as long as every wavefront executes the same NUMBER of barriers.  One opaque block, as
+// pair_wait (the condition is a scalar, the branch never reaches the register allocator).
+__device__ __forceinline__ void barrier_if(bool here) {
+    asm volatile(
+        "s_cmp_eq_u32 %0, 0\n\t"
+        "s_cbranch_scc1 .Lbarrier_if_%=\n\t"
+        "s_barrier\n"
+        ".Lbarrier_if_%=:"
+        :
+        : "s"(__builtin_amdgcn_readfirstlane((uint32_t)here))
+        : "scc", "memory");
+}
 // nothing moves across this point (neither the compiler's memory operations nor the instruction scheduler's)
 __device__ __forceinline__ void pin() {
     asm volatile("" ::: "memory");
