@@ -30,7 +30,9 @@ correlated (pbs_output_variance_parts: v_pbs = v_white + hw(S) v_carried); the o
 
 (the expectation of |S P_f|^2 over keys of that weight; shared_rotation's docstring).  |P_f|^2 v_pbs, the white-noise model, was
 measured 3.1 x too low for the identity table and 1.7 x too high for a random one on the default set; this one within 3 %
-(tests/test_gpu_shared_rotation.py, EXPERIMENTS A21).  A group of one is an ordinary look-up.
+(tests/test_gpu_shared_rotation.py, EXPERIMENTS A21).  A group of one is an ordinary look-up.  On the unrolled key the parts
+are the same split of its own variance (3 x the key terms; rounding 2 x per pair of key bits not both zero, once white and once per
+set bit of S): measured within 2 % (tests/test_gpu_shared_rotation_wide_unrolled.py, EXPERIMENTS A23).
 
 Key weights are random: hw(s) = n / 2, hw(S) = kN / 2 (their expectations) unless given."""
 from __future__ import annotations
@@ -65,23 +67,33 @@ def pbs_output_variance(P, bsk_precision=None, unroll=False, hw_small=None, hw_b
     key = n * l * (k + 1) * N * (Bg * Bg + 2) / 12.0 * s2
     rnd = (1 + hb) / (12.0 * Bg ** (2 * l))
     if unroll:
-        live_pairs = (n + 1) // 2 * 0.75 if hw_small is None else None
-        if live_pairs is None:
-            live_pairs = min((n + 1) // 2, hs)          # upper bound from the weight alone
-        return 3 * key + 2 * live_pairs * rnd
+        return 3 * key + 2 * _live_pairs(n, hw_small) * rnd
     return key + hs * rnd
 
 
-def pbs_output_variance_parts(P, bsk_precision=None, hw_small=None, hw_big=None):
-    """(v_white, v_carried) with pbs_output_variance = v_white + hw(S) v_carried (plain key): the noise that is white across the
+def _live_pairs(n, hw_small):
+    """pairs of LWE key bits not both zero (the steps of an unrolled rotation whose rounding reaches the output): 3/4 of the
+    pairs at the average weight, else the upper bound the weight alone gives"""
+    return (n + 1) // 2 * 0.75 if hw_small is None else min((n + 1) // 2, float(hw_small))
+
+
+def pbs_output_variance_parts(P, bsk_precision=None, hw_small=None, hw_big=None, unroll=False, live_pairs=None):
+    """(v_white, v_carried) with pbs_output_variance = v_white + hw(S) v_carried: the noise that is white across the
     accumulator's coefficients - the key's Gaussian noise, the rounding of the stored body words, the decomposition's rounding of
-    the body - and, per set bit of the GLWE key, the noise that key carries (the roundings of the mask words)"""
+    the body - and, per set bit of the GLWE key, the noise that key carries (the roundings of the mask words).
+    unroll: the same split of the unrolled key's variance (3 x the key term; the rounding term 2 x per pair of LWE key bits not
+    both zero: `live_pairs`, else the count pbs_output_variance(unroll=True) assumes for the same hw_small).  Without a
+    bsk_precision both functions price default_bsk_precision(P); the unrolled floating-point-transform engine of the torus stores
+    its key at 42 bits, so a budget for a live engine passes engine.bsk_precision."""
     N, k, l, n = 1 << P.log_N, P.k, P.bs_levels, P.n
     Bg = 2.0 ** P.bs_base_log
     hs = n / 2.0 if hw_small is None else float(hw_small)
     prec = default_bsk_precision(P) if bsk_precision is None else int(bsk_precision)
     rho = 4.0 ** (64 - prec) / 12.0 / 2.0 ** 128 if (P.q_bits == TORUS64 and prec < 64) else 0.0
     K = n * l * (k + 1) * N * (Bg * Bg + 2) / 12.0
+    if unroll:
+        rnd = 2 * (_live_pairs(n, hw_small) if live_pairs is None else float(live_pairs)) / (12.0 * Bg ** (2 * l))
+        return 3 * K * (P.glwe_noise ** 2 + rho) + rnd, 3 * K * rho + rnd
     rnd = hs / (12.0 * Bg ** (2 * l))
     return K * (P.glwe_noise ** 2 + rho) + rnd, K * rho + rnd
 
@@ -130,11 +142,9 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     shared = 0
     if share_rotations and nn:
         from .shared_rotation import rotation_groups
-        if unroll:
-            raise ValueError("shared rotations run on the plain bootstrap key, not on an unrolled one")
         rg = rotation_groups(prog)
         in_shared = np.repeat(rg.sizes, rg.sizes) > 1
-        v_white, v_carried = pbs_output_variance_parts(P, bsk_precision, hw_small, hw_big)
+        v_white, v_carried = pbs_output_variance_parts(P, bsk_precision, hw_small, hw_big, unroll=unroll)
         dens = 0.5 if hw_big is None else float(hw_big) / (P.k * N)
         carried2 = N * (dens * (1 - dens) * rg.norm2[in_shared] + dens * dens * rg.mean2[in_shared])      # E |S P_f|^2
         leaf_var[n_in + rg.members[in_shared]] = rg.norm2[in_shared] * v_white + carried2 * v_carried

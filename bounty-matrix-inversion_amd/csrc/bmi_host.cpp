@@ -871,10 +871,14 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     return 0;
 }
 
-// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the four plain floating-point-transform kernels of the torus.
-// Not the exact-transform pair a pinned variant 1 / 3 / 4 selects, the N = 4096 kernel, the unrolled ones, the prime fields.
+// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the seven floating-point-transform kernels of the torus.
+// Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not the prime fields.
 bool has_accumulator_form(Rot rot) {
-    return rot == Rot::t64_wide2 || rot == Rot::t64_wide || rot == Rot::t64_lat_fft || rot == Rot::t64_fft;
+    switch (rot) {
+    case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft: case Rot::t64_lat_fft: case Rot::t64_fft:
+        return true;
+    default: return false;
+    }
 }
 
 // Launches `rot` on the context's key copies and tables.  stat: as in bmit::launch_blind_rotate_fft, for the kernels that take it.
@@ -891,11 +895,11 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     switch (rot) {
     case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, glwe, st);
     case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, st);
+    case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_tp2u_fft: return bmit::launch_blind_rotate_tp2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(), out,
-                                                                      count, n, p, lv, bl, st);
+                                                                      count, n, p, lv, bl, glwe, st);
     case Rot::t64_lat2u_fft: return bmit::launch_blind_rotate_lat2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(),
-                                                                        out, count, n, p, lv, bl, stat, st);
+                                                                        out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_lat2u: return bmit::launch_blind_rotate_lat2u(cts, ids, luts, K3.exact_lat.get(), c->tw_half.get(), c->root_pow.get(), out, count,
                                                                 n, p, lv, bl, st);
     case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), out, count, n, p, lv, bl, stat, glwe, st);
@@ -1295,7 +1299,7 @@ static int add_table(bmi_ctx *c, std::vector<u64> tv, uint2 head, const std::vec
     return 0;
 }
 
-// Shared rotations exist on the 2^64 torus through the plain floating-point-transform kernels: refused elsewhere
+// Shared rotations exist on the 2^64 torus through the floating-point-transform kernels: refused elsewhere
 static int shared_rotation_ok(const bmi_ctx *c) {
     if (!c->t64()) return fail(c, -1, "shared rotations exist on the 2^64 torus only (not on the 49-bit field or Goldilocks)");
     return 0;
@@ -1505,8 +1509,8 @@ static int blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_
     Rot rot;
     if (int rc = choose_rotation(c, count, &rot)) return rc;
     if (glwe && !has_accumulator_form(rot))
-        return fail(c, -1, "the accumulator form exists for the plain floating-point-transform kernels only (N = 1024 with the key at 48 bits, "
-                           "N = 2048): not for a pinned exact-transform variant (1 / 3 / 4), N = 4096, an unrolled key or another key precision");
+        return fail(c, -1, "the accumulator form exists for the floating-point-transform kernels only: not for a pinned exact-transform variant "
+                           "(1 / 3 / 4), nor for the unrolled key pinned at 48 bits of precision (the exact-transform unrolled kernel)");
     if (rot == Rot::t64_lat || rot == Rot::t64_exact)
         if (int rc = build_exact_torus_copies(c, nullptr)) return rc;   // (a no-op once built)
     const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, glwe, (hipStream_t)stream);

@@ -85,7 +85,7 @@ inline int with_levels_stats(uint32_t levels, bool stats, F f) {
     return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
-// ... and the epilogue of the four plain torus FFT rotations (bmi_kernels_t64{f,w,w2}.hip), whose trailing template flag GLWE makes
+// ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,w2,q}.hip), whose trailing template flag GLWE makes
 // them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
 // out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator
 // form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.
@@ -212,7 +212,7 @@ int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, con
 bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s);
 // stat (may be null): receives, as the bit pattern of a double, the largest distance of a limb sum from the integer it was rounded to
-// glwe (this launcher, launch_blind_rotate_lat_fft, launch_blind_rotate_wide and launch_blind_rotate_wide2): out receives the
+// glwe (every launcher below that takes it): out receives the
 // ACCUMULATOR, [count][mask N][body N] words in natural order, instead of the extracted samples [count][N + 1]; stat must be null
 int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
                             const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
@@ -229,11 +229,11 @@ int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, c
 bool shape_supported_unrolled_fft(int prec, uint32_t levels, uint32_t base_log);
 int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                   const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, hipStream_t s);
+                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
 // ... and its throughput form: two ciphertexts per workgroup, every key word a thread loads multiplied with both (same words)
 int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                 uint32_t levels, uint32_t base_log, hipStream_t s);
+                                 uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s);
 // N = 4096 (bmi_kernels_t64q.hip, fft_eighth_f64.hpp): key at 44 bits of precision (two 22-bit limbs), one workgroup per ciphertext,
 // one decomposition level of tiles in LDS at a time; key copy per (polynomial, limb) [t 8][256 slots] complex words A_k / 4; tables
 // ffte::ET_WORDS doubles
@@ -241,7 +241,7 @@ bool shape_supported_quad(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw_e, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             hipStream_t s);
+                             bool glwe, hipStream_t s);
 // N = 2048, throughput form (bmi_kernels_t64w2.hip): two ciphertexts per workgroup, every key word multiplied with both; its own key copy,
 // per (polynomial, limb) [t 4][256 slots] complex words A_k / 2; tables and results as launch_blind_rotate_wide
 int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);

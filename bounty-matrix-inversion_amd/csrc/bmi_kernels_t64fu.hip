@@ -54,7 +54,8 @@ static_assert(UF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "UF_LDS_WORDS exceeds the 160 K
 
 constexpr t64::ResidueSlot<N, 1> acc_slot{};   // accumulator words are kept split by parity
 
-template <int L, int BG, int PREC, bool STATS>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, int PREC, bool STATS, bool GLWE>
 __global__ void __launch_bounds__(UF_THREADS)
     k_blind_rotate_lat2u_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                               const double *__restrict__ bsk3_latf, const double *__restrict__ g_tw_h, const double *__restrict__ g_zeta_pow,
@@ -190,7 +191,8 @@ __global__ void __launch_bounds__(UF_THREADS)
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
+    if constexpr (GLWE) t64::store_glwe<N, PRE, AB>(out + (size_t)ct * (2 * N), acc, acc_slot, tid);   // out = [count][2N]
+    else t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
 
 
@@ -210,7 +212,8 @@ constexpr int U2_LDS_WORDS = ffth::HT_WORDS + U2_ZQ_WORDS + 2 * (2 * N) + 2 * (2
 static_assert(U2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "U2_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(2 * 2 * N <= 2 * UF_MAX_L * N, "a ciphertext's sums / differences fit over its tiles");
 
-template <int L, int BG, int PREC>
+// GLWE: as in the one-ciphertext kernel, each ciphertext of the workgroup its own [2N] row
+template <int L, int BG, int PREC, bool GLWE>
 __global__ void __launch_bounds__(UF_THREADS)
     k_blind_rotate_tp2u_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                              const double *__restrict__ bsk3_latf, const double *__restrict__ g_tw_h, const double *__restrict__ g_zeta_pow,
@@ -370,7 +373,8 @@ __global__ void __launch_bounds__(UF_THREADS)
     }
     static_for<0, 2>([&](auto Z) {
         if (Z == 1 && cts[1] == cts[0]) return;   // the padding copy of an odd batch
-        t64::extract_sample<N, PRE, AB>(out + (size_t)cts[Z] * (N + 1), acc_all + Z * 2 * N, acc_slot, tid);
+        if constexpr (GLWE) t64::store_glwe<N, PRE, AB>(out + (size_t)cts[Z] * (2 * N), acc_all + Z * 2 * N, acc_slot, tid);   // out = [count][2N]
+        else t64::extract_sample<N, PRE, AB>(out + (size_t)cts[Z] * (N + 1), acc_all + Z * 2 * N, acc_slot, tid);
     });
 }
 
@@ -386,23 +390,24 @@ bool shape_supported_unrolled_fft(int prec, uint32_t levels, uint32_t base_log) 
 // two ciphertexts per workgroup (key words shared in registers): the throughput form, same words as launch_blind_rotate_lat2u_fft
 int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                 uint32_t levels, uint32_t base_log, hipStream_t s) {
+                                 uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels(levels, [&](auto L) {
-        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42>>(dim3((count + 1) / 2), dim3(UF_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
-                                                                     small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
-    });
+    auto launch = [&](auto L, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42, GLWE>>(dim3((count + 1) / 2), dim3(UF_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
+                                                                           small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
+    };
+    return with_levels(levels, [&](auto L) { return glwe ? launch(L, std::true_type{}) : launch(L, std::false_type{}); });
 }
 
 int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                   const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, hipStream_t s) {
+                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
-        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS>>(dim3(count), dim3(UF_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
-                                                                             small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS, GLWE>>(dim3(count), dim3(UF_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
+                                                                                   small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
     });
 }
 

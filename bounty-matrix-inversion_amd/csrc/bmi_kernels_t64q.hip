@@ -91,7 +91,8 @@ __global__ void __launch_bounds__(512) k_bsk_to_q_t64(const u64 *__restrict__ st
 }
 
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
-template <int L, int BG, int PREC, bool STATS>
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, int PREC, bool STATS, bool GLWE>
 __global__ void __launch_bounds__(QF_THREADS)
     k_blind_rotate_q_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                           const double *__restrict__ bsk_q, const double *__restrict__ g_tw, u64 *__restrict__ out, uint32_t count,
@@ -222,8 +223,13 @@ __global__ void __launch_bounds__(QF_THREADS)
         }
     }
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
-    u64 *o = out + (size_t)ct * (QN + 1);
-    static_for<0, 4>([&](auto Q) { t64::extract_sample<QN, PRE, AB>(o, acc, acc_slot, tid + QF_THREADS * Q); });
+    if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
+        u64 *g = out + (size_t)ct * (2 * QN);
+        static_for<0, 4>([&](auto Q) { t64::store_glwe<QN, PRE, AB>(g, acc, acc_slot, tid + QF_THREADS * Q); });
+    } else {
+        u64 *o = out + (size_t)ct * (QN + 1);
+        static_for<0, 4>([&](auto Q) { t64::extract_sample<QN, PRE, AB>(o, acc, acc_slot, tid + QF_THREADS * Q); });
+    }
 }
 
 }  // namespace
@@ -245,12 +251,12 @@ int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw
 
 int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             hipStream_t s) {
+                             bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_quad(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats(levels, stat != nullptr, [&](auto L, auto STATS) {
-        return launch_with_lds<k_blind_rotate_q_t64f<L, 10, 44, STATS>>(dim3(count), dim3(QF_THREADS), (size_t)QF_LDS_WORDS * sizeof(double), s,
-                                                                         small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat);
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_q_t64f<L, 10, 44, STATS, GLWE>>(dim3(count), dim3(QF_THREADS), (size_t)QF_LDS_WORDS * sizeof(double), s,
+                                                                               small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat);
     });
 }
 

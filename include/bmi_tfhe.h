@@ -169,16 +169,20 @@ int bmi_blind_rotate_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t
  * rotated additions per word instead of a keyswitch and a rotation.  The output's bootstrap noise variance grows by |P_t|^2 (the
  * sum of squares of its coefficients).  Tables of msg_bits <= 6 whose neighbouring entries differ by an int32 at most can share
  * (their sparse form is built at registration; the others are refused as members of a base's group, each with its own text).
- * Refused with a bmi_last_error text: the 49-bit field and Goldilocks; a pinned exact-transform kernel variant (1 / 3 / 4 at
- * N = 1024), N = 4096, an unrolled key and every key precision the plain floating-point-transform kernels do not serve.
+ * Served by every floating-point-transform rotation of the torus: N = 1024 (key at 48 bits), N = 2048 (46 bits), N = 4096 (44 bits)
+ * and the unrolled key of bmi_set_bsk_unroll at its own 42 bits.  Refused with a bmi_last_error text: the 49-bit field and
+ * Goldilocks; a pinned exact-transform kernel variant (1 / 3 / 4 at N = 1024); the unrolled key pinned at 48 bits of precision
+ * (bmi_set_bsk_precision(ctx, 48) before bmi_set_bsk_unroll: the exact-transform unrolled kernel).
  *
  * bmi_lut_register_base: the id of TV_0 = + 2^(unit_log - 1) (every coefficient, PLUS sign; the existing table of -+1 at half
  * scale yields the negative) as an ordinary table id; one per unit_log however often it is asked for.  unit_log - 1 >= 64 -
- * (bootstrap-key precision), the grid bmi_lut_register holds its tables to. */
+ * (bootstrap-key precision), the grid bmi_lut_register holds its tables to: unit_log >= 17 at 48 bits, 19 at 46, 21 at 44
+ * (N = 4096) and 23 at 42 (the unrolled key). */
 int bmi_lut_register_base(bmi_ctx *ctx, uint32_t unit_log, uint32_t *lut_id);
 /* bmi_blind_rotate_batch returning the rotated ACCUMULATOR instead of its extracted sample: d_glwe [count][2N] words, the mask
- * polynomial, then the body, coefficients in natural order (k = 1).  Any registered table; the same kernel choice by batch size,
- * and o[0] = A[0], o[x] = -A[N - x], o[N] = B[0] are the words bmi_blind_rotate_batch writes. */
+ * polynomial, then the body, coefficients in natural order (k = 1).  Any registered table; the same kernel choice by batch size
+ * (at N = 4096 the one kernel of that ring; with the unrolled key one ciphertext per workgroup up to 256, two beyond), and
+ * o[0] = A[0], o[x] = -A[N - x], o[N] = B[0] are the words bmi_blind_rotate_batch writes. */
 int bmi_blind_rotate_glwe_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
                                 uint64_t *d_glwe, void *stream);
 /* The look-ups of `groups` accumulators: group g is the rotation of the base polynomial d_base_ids[g] and serves the tables
@@ -187,12 +191,13 @@ int bmi_blind_rotate_glwe_batch(bmi_ctx *ctx, const uint64_t *d_small, const uin
  * bmi_blind_rotate_batch and no noise growth.  Preconditions (the *_host forms refuse a violation, the device forms stay inside
  * their buffers but compute something else): registered ids; for every table other than its group's base, a base id from
  * bmi_lut_register_base, msg_bits <= 6, int32 differences and out_delta_log >= the base's unit_log; non-decreasing group ranges
- * from 0 to total. */
+ * from 0 to total.  Independent of the ring size and of the key that rotated: N = 1024 / 2048 / 4096, plain or unrolled. */
 int bmi_glwe_lookup_batch(bmi_ctx *ctx, const uint64_t *d_glwe, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
                           const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream);
 /* bmi_pbs_batch for grouped look-ups: keyswitch of the `groups` rows of d_in ([groups][N+1]), ONE rotation per group with its base
  * polynomial, then the look-ups of bmi_glwe_lookup_batch into d_out [total][N+1] (d_in is consumed by the keyswitch before d_out is
- * written).  The accumulators live in context scratch that bmi_reserve pre-sizes. */
+ * written).  The accumulators ([groups][2N] words: 64 KB each at N = 4096) live in context scratch that bmi_reserve pre-sizes.
+ * On every engine bmi_blind_rotate_glwe_batch serves. */
 int bmi_pbs_shared_batch(bmi_ctx *ctx, const uint64_t *d_in, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
                          const uint32_t *d_lut_ids, uint32_t groups, uint32_t total, uint64_t *d_out, void *stream);
 /* Leveled (PBS-free) linear ops on big-key ciphertexts, CSR form:
@@ -224,7 +229,8 @@ int bmi_blind_rotate_batch_host(bmi_ctx *ctx, const uint64_t *small_in, const ui
                                 uint64_t *out);
 /* ... and of the shared look-ups (glwe_out / glwe_in: [count resp. groups][2N] words).  They refuse what the device forms state
  * as preconditions: unknown ids, a base id that serves other tables and is no base polynomial, a table without a sparse form or encoded below its group's
- * unit, group ranges that do not run from 0 to total without decreasing. */
+ * unit, group ranges that do not run from 0 to total without decreasing; and, like the device forms, the engines without an
+ * accumulator form (above). */
 int bmi_blind_rotate_glwe_batch_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
                                      uint64_t *glwe_out);
 int bmi_glwe_lookup_batch_host(bmi_ctx *ctx, const uint64_t *glwe_in, const uint32_t *group_ptr, const uint32_t *base_ids,
