@@ -234,7 +234,11 @@ def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, s
     tried = []
     for label, spec in candidate_sets(prog.msg_bits, q_bits, secure):
         P = tfhe.preset_params(spec) if isinstance(spec, str) else tfhe.default_params(**spec)
-        rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations)
+        # unrolled kernels: N = 1024, and the 2^64 torus at N = 2048, whose unrolled key is stored at 40 bits (bmi_set_bsk_unroll)
+        if unroll and P.log_N == 11 and P.q_bits == TORUS64:
+            rep = failure_probability(prog, P, 40, unroll=True, share_rotations=share_rotations)
+        else:
+            rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations)
         tried.append((label, rep["p_fail"]))
         if rep["p_fail"] <= p_error:
             return P, dict(rep, chosen=label, tried=tried, p_error=p_error)

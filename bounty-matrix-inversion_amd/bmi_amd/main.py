@@ -99,8 +99,10 @@ class EncryptedMatrixInversion:
                 raise ValueError("look-ups wider than 4 bits need N >= 2048, which exists on the 2^64 torus and the 49-bit field; "
                                  "wider than 6 bits: no parameter set")
             if self.unroll:
-                if self.msg_bits > 4 or params.log_N != 10:
-                    raise ValueError("bootstrap-key unrolling exists at N = 1024 (4-bit look-ups) only")
+                # (the 2^64 torus also at N = 2048, e.g. secure128_torus: k_blind_rotate_wu_t64f on the key at 40 bits)
+                wide_torus = params.log_N == 11 and params.q_bits == tfhe.TORUS64
+                if self.msg_bits > 4 or (params.log_N != 10 and not wide_torus):
+                    raise ValueError("bootstrap-key unrolling exists at N = 1024 and, on the 2^64 torus, at N = 2048 (4-bit look-ups) only")
                 if params.q_bits == 49 and self.params is None:     # three products per step: key noise 2^-41 keeps the default set's output noise
                     params = tfhe.default_params(q_bits=49, glwe_noise=2.0 ** -41)
                 elif params.q_bits != tfhe.TORUS64:

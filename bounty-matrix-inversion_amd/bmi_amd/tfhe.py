@@ -452,7 +452,8 @@ class Engine:
 
     def set_bsk_precision(self, bits):
         """2^64 torus, before keygen: 64 = exact key (three limbs); 48 = key rounded to 48 bits (two limbs, 2/3 of the work; the
-        default at Bg = 2^10, the torus parameter set); 42 = rounded to 42 bits (two limbs at Bg = 2^15, noisier)"""
+        default at Bg = 2^10, the torus parameter set); 42 = rounded to 42 bits (two limbs at Bg = 2^15, noisier); N = 2048 / 4096 take 46 / 44 only, and N = 2048 in unrolled mode 40
+        (include/bmi_tfhe.h)"""
         self._ck(self.lib.bmi_set_bsk_precision(self.h, int(bits)), "bmi_set_bsk_precision")
 
     @property
@@ -463,7 +464,8 @@ class Engine:
         return v.value
 
     def set_bsk_unroll(self, factor):
-        """49-bit field, N = 1024 (or N = 2048 with l <= 2), or the 2^64 torus at its default set: 1 = CGGI's blind rotation (default), 2 = two LWE coefficients per step with an unrolled
+        """49-bit field, N = 1024 (or N = 2048 with l <= 2), or the 2^64 torus at its default set and at N = 2048 (secure128_torus: the key
+        is then stored at 40 bits): 1 = CGGI's blind rotation (default), 2 = two LWE coefficients per step with an unrolled
         bootstrap key (generated by the next keygen, or at once from the secret keys already held); include/bmi_tfhe.h"""
         self._ck(self.lib.bmi_set_bsk_unroll(self.h, int(factor)), "bmi_set_bsk_unroll")
         self.unroll = int(factor)

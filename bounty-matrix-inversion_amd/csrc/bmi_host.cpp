@@ -244,7 +244,7 @@ struct bmi_ctx {
     bool have_keys = false;
     bool have_secret = false;  // false for a context that imported evaluation keys only (no encrypt / decrypt)
     u64 seed = 0, enc_counter = 0;
-    int bsk_prec = 64;   // torus: bits of precision the bootstrap key is stored at (64 = exact, 48, 46, 42: t64_common.hpp; bmi_set_bsk_precision)
+    int bsk_prec = 64;   // torus: bits of precision the bootstrap key is stored at (64 = exact, 48, 46, 44, 42, 40: t64_common.hpp; bmi_set_bsk_precision)
     bool bsk_prec_explicit = false;   // set by bmi_set_bsk_precision: bmi_set_bsk_unroll then leaves the precision alone
     int bsk_limbs() const { return t64::limbs_of(bsk_prec); }
     bool secure_rng = false;       // true: keys / encryptions drawn from the CSPRNG below; false: test-only seeded streams
@@ -261,6 +261,7 @@ struct bmi_ctx {
     DevBuf<double> tw_fft;      // torus N = 1024: folded complex FFT (fft_wave_f64.hpp) - bsk_to_fft, blind_rotate_fft
     DevBuf<double> tw_fft_half; // torus N = 1024: half FFT (fft_half_f64.hpp) - bsk_to_latf, blind_rotate_lat_fft / _lat2u_fft / _tp2u_fft
     DevBuf<double> zeta_pow;    // torus N = 1024: exp(i pi x / 1024), x in [0, 1024) as (re, im) - blind_rotate_lat2u_fft / _tp2u_fft
+    DevBuf<double> zeta_oct;    // torus N = 2048: exp(i pi x / 2048), x in [0, 512] as (re, im), one octant - blind_rotate_wide_u
     DevBuf<double> tw_quarter;  // torus N = 2048: quarter transforms (fft_quarter_f64.hpp) - bsk_to_wide / _wide2, blind_rotate_wide / _wide2
     DevBuf<double> tw_eighth;   // torus N = 4096: eighth transforms (fft_eighth_f64.hpp) - bsk_to_quad, blind_rotate_quad
     DevBuf<u64> luts;           // BMI_LUT_CAP test polynomials of N words (49-bit field: centred doubles) - every blind rotation
@@ -294,7 +295,8 @@ struct bmi_ctx {
         DevBuf<double> wide49;     // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide_u
         DevBuf<double> exact_lat;  // torus, exact transform (bsk_to_lat): blind_rotate_lat2u
         DevBuf<double> fft_lat;    // torus, key at 42 bits: floating-point transform (bsk_to_latf): blind_rotate_lat2u_fft / _tp2u_fft
-        size_t bytes() const { return lat49.bytes() + wide49.bytes() + exact_lat.bytes() + fft_lat.bytes(); }
+        DevBuf<double> wide;       // torus N = 2048, key at 40 bits (bsk_to_wide): blind_rotate_wide_u
+        size_t bytes() const { return lat49.bytes() + wide49.bytes() + exact_lat.bytes() + fft_lat.bytes() + wide.bytes(); }
     } bsk3;
     bool have_bsk3 = false;
     uint32_t pairs() const { return (P.n + 1) / 2; }
@@ -629,6 +631,8 @@ int upload_bsk(bmi_ctx *c) {
     const hipStream_t st = c->stream;
     auto &K = c->bsk;
     if (c->t64() && c->wide()) {   // N = 2048: one ciphertext per workgroup, and two (batches beyond 256)
+        // (40 bits, the precision of the unrolled kernel only: no plain key copy)
+        if (!bmit::shape_supported_wide(prec, c->P.bs_levels, c->P.bs_base_log)) return 0;
         const int rc = build_copy(c, K.wide, bytes, "bsk_to_wide (torus)",
                                   [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
         return rc ? rc : build_copy(c, K.wide2, bytes, "bsk_to_wide2 (torus)",
@@ -726,7 +730,10 @@ int upload_bsk3(bmi_ctx *c) {
     const hipStream_t st = c->stream;
     const char *what = "bsk_to_lat (unrolled key)";
     int rc;
-    if (c->t64() && bmit::shape_supported_unrolled_fft(prec, c->P.bs_levels, c->P.bs_base_log))   // slot-pair order of the half FFT
+    if (c->t64() && c->wide())   // N = 2048: the per-polynomial layout of the plain kernel, over [pairs][3][2 l rows][2] polynomials
+        rc = build_copy(c, c->bsk3.wide, bytes, "bsk_to_wide (unrolled key)",
+                        [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    else if (c->t64() && bmit::shape_supported_unrolled_fft(prec, c->P.bs_levels, c->P.bs_base_log))   // slot-pair order of the half FFT
         rc = build_copy(c, c->bsk3.fft_lat, bytes, what,
                         [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
     else if (c->t64())
@@ -822,14 +829,14 @@ int ensure_ks_mfma(bmi_ctx *c, uint32_t count) {
 
 // The blind-rotation launchers (bmi_internal.hpp), one member each: choose_rotation picks one, launch_rotation runs it.
 enum class Rot {
-    t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
+    t64_wide_u, t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
     f49_wide_u, f49_wide, f49_quad, f49_lat2u, f49_lat2, f49_tpx,                                                   // 49-bit field
     gl_lat, gl_tp,                                                                                                  // Goldilocks
 };
 
 // The kernel of bmi_blind_rotate_batch for a batch of `count` on this context: 0 and *rot, or a refusal.
 int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
-    // unrolled key (49-bit field at N = 1024 / 2048, 2^64 torus at N = 1024: bmi_set_bsk_unroll refuses the rest): one kernel
+    // unrolled key (49-bit field and 2^64 torus at N = 1024 / 2048: bmi_set_bsk_unroll refuses the rest): one kernel
     // (one workgroup per ciphertext) for every batch size, so that a ciphertext's bits never depend on the batch it travelled in
     if (c->unroll == 2 && !c->have_bsk3)
         return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
@@ -843,7 +850,10 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     const int prec = c->bsk_prec;
     const uint32_t lv = c->P.bs_levels, bl = c->P.bs_base_log;
     if (c->t64()) {
-        if (c->wide() && !c->bsk.wide2.empty() && two_per_wg) *rot = Rot::t64_wide2;
+        if (c->wide() && c->unroll == 2) *rot = Rot::t64_wide_u;   // one workgroup per ciphertext at every count and variant
+        else if (c->wide() && c->bsk.wide.empty())
+            return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
+        else if (c->wide() && !c->bsk.wide2.empty() && two_per_wg) *rot = Rot::t64_wide2;
         else if (c->wide()) *rot = Rot::t64_wide;   // N = 2048 / 4096: one workgroup per ciphertext
         else if (c->quad()) *rot = Rot::t64_quad;
         else if (c->unroll == 2)   // the floating-point-transform route where the key is at 42 bits, else the exact transform
@@ -871,11 +881,12 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     return 0;
 }
 
-// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the seven floating-point-transform kernels of the torus.
+// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the eight floating-point-transform kernels of the torus.
 // Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not the prime fields.
 bool has_accumulator_form(Rot rot) {
     switch (rot) {
-    case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft: case Rot::t64_lat_fft: case Rot::t64_fft:
+    case Rot::t64_wide_u: case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft:
+    case Rot::t64_lat_fft: case Rot::t64_fft:
         return true;
     default: return false;
     }
@@ -893,6 +904,8 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     const bmi_ctx::BskCopies &K = c->bsk;
     const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
     switch (rot) {
+    case Rot::t64_wide_u: return bmit::launch_blind_rotate_wide_u(cts, ids, luts, K3.wide.get(), c->tw_quarter.get(), c->zeta_oct.get(), out, count, n,
+                                                                   p, lv, bl, stat, glwe, st);
     case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, glwe, st);
     case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, glwe, st);
@@ -1087,6 +1100,15 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
         if (c->quad()) ffte::build_tables(tq.data());
         else fftq::build_tables(tq.data());
         put(c->quad() ? c->tw_eighth : c->tw_quarter, tq);
+    }
+    if (c->t64() && c->wide()) {   // one octant of the powers of zeta = exp(i pi / 2048): the unrolled kernel folds the rest onto it
+        std::vector<double> zo(2 * 513);
+        for (uint32_t x = 0; x <= 512; x++) {
+            const long double ang = 3.14159265358979323846264338327950288L * (long double)x / 2048.0L;
+            zo[2 * x] = (double)cosl(ang);
+            zo[2 * x + 1] = (double)sinl(ang);
+        }
+        put(c->zeta_oct, zo);
     }
     if (c->wide() && !c->t64()) put(c->tw_wide49, to_centred_doubles(build_twiddles_wide(c->f)));
     if (c->quad() && !c->t64()) put(c->tw_quad49, to_centred_doubles(build_twiddles_quad(c->f)));
@@ -1311,7 +1333,7 @@ int bmi_lut_register(bmi_ctx *c, const int64_t *table, uint32_t msg_bits, uint32
     if (msg_bits == 0 || (1u << msg_bits) * 2 > N) return fail(c, -1, "msg_bits out of range for N");
     if (out_delta_log >= c->f.bits - 1) return fail(c, -1, "out_delta_log out of range");
     if (c->t64() && c->bsk_prec != 64 && out_delta_log < (uint32_t)(64 - c->bsk_prec))
-        // the torus kernels on a rounded key (48 / 46 / 42 bits) keep the accumulator as a multiple of 2^16 / 2^18 / 2^22: a table
+        // the torus kernels on a rounded key (48 / 46 / 42 / 40 bits) keep the accumulator as a multiple of 2^16 / 2^18 / 2^22 / 2^24: a table
         // encoded below that scale would lose its low bits - and sits ~2^40 below the noise anyway.  (The exact key has no such grid.)
         return fail(c, -1, "out_delta_log below 64 - (bootstrap-key precision) on the 2^64 torus: test polynomials must be multiples of the key's grid");
     if (c->n_luts == c->lut_cap) return fail(c, -1, "LUT table full");
@@ -1374,11 +1396,17 @@ int bmi_lut_get(const bmi_ctx *c, uint32_t lut_id, uint64_t *test_vector) {
 int bmi_set_bsk_precision(bmi_ctx *c, uint32_t bits) {
     if (!c) return -1;
     if (!c->t64()) return fail(c, -1, "the bootstrap-key precision option exists on the 2^64 torus only");
-    if (!t64::precision_ok((int)bits)) return fail(c, -1, "bootstrap-key precision must be 64 (exact), 48, 46, 44 or 42 bits");
+    if (!t64::precision_ok((int)bits)) return fail(c, -1, "bootstrap-key precision must be 64 (exact), 48, 46, 44, 42 or 40 bits");
     if (c->have_keys) return fail(c, -1, "set the bootstrap-key precision before generating or importing keys");
     if (c->wide() || c->quad()) {
-        if (!(c->quad() ? bmit::shape_supported_quad : bmit::shape_supported_wide)((int)bits, c->P.bs_levels, c->P.bs_base_log))
-            return fail(c, -1, "at N = 2048 the torus kernel takes the key at 46 bits of precision (two 23-bit limbs) only, at N = 4096 at 44 bits (two "
+        // N = 2048 in unrolled mode (bmi_set_bsk_unroll first - which selects it by itself when no precision was set): 40 bits only
+        if (c->wide() && c->unroll == 2) {
+            if (!bmit::shape_supported_wide_unrolled((int)bits, c->P.bs_levels, c->P.bs_base_log))
+                return fail(c, -1, "at N = 2048 the unrolled torus kernel takes the key at 40 bits of precision (two 20-bit limbs) only: the six-times "
+                                   "larger limb sums of the unrolled step must stay inside the transform's certified range (bmi_kernels_t64wu.hip)");
+        } else if (!(c->quad() ? bmit::shape_supported_quad : bmit::shape_supported_wide)((int)bits, c->P.bs_levels, c->P.bs_base_log))
+            return fail(c, -1, "at N = 2048 the torus kernel takes the key at 46 bits of precision (two 23-bit limbs) only - and at 40 bits (two 20-bit "
+                               "limbs) for the unrolled kernel (bmi_set_bsk_unroll) -, at N = 4096 at 44 bits (two "
                                "22-bit limbs): the lengths at which the floating-point transform's error bound certifies the rounding "
                                "(fft_quarter_f64.hpp, fft_eighth_f64.hpp)");
         c->bsk_prec = (int)bits;
@@ -1408,21 +1436,29 @@ int bmi_set_bsk_unroll(bmi_ctx *c, uint32_t factor) {
     if (!c) return -1;
     if (factor != 1 && factor != 2) return fail(c, -1, "the unrolling factor is 1 or 2");
     if (factor == 2 && !((c->f64() && !c->quad()) || c->t64()))
-        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field at N = 1024 and N = 2048 and for the 2^64 torus only");
-    if (factor == 2 && c->t64() && (c->wide() || c->quad()))
-        return fail(c, -1, "bootstrap-key unrolling has no HIP kernel on the 2^64 torus at N = 2048 / 4096");
+        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field and the 2^64 torus at N = 1024 and N = 2048 only");
+    if (factor == 2 && c->t64() && c->quad())
+        return fail(c, -1, "bootstrap-key unrolling has no HIP kernel on the 2^64 torus at N = 4096");
+    if (factor == 2 && c->t64() && c->wide() && !bmit::shape_supported_wide_unrolled(40, c->P.bs_levels, c->P.bs_base_log))
+        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled kernel exists for l = 2 or 3 levels in base 2^10");
     if (c->t64() && !c->bsk_prec_explicit && !c->have_keys) {
         // the precision nobody chose follows the mode: the unrolled step runs through the floating-point transform on a key stored
         // at 42 bits (k_blind_rotate_lat2u_t64f: 2.9 ms per bootstrap against 3.3 of the exact-transform kernel on the 48-bit key,
         // which bmi_set_bsk_precision(ctx, 48) still selects); back to the set's default when unrolling is switched off
-        if (factor == 2 && bmit::shape_supported_unrolled_fft(42, c->P.bs_levels, c->P.bs_base_log)) c->bsk_prec = 42;
+        // (N = 2048: 40 bits, the only precision of k_blind_rotate_wu_t64f)
+        if (factor == 2 && c->wide()) c->bsk_prec = 40;
+        else if (factor == 2 && bmit::shape_supported_unrolled_fft(42, c->P.bs_levels, c->P.bs_base_log)) c->bsk_prec = 42;
         if (factor == 1) c->bsk_prec = default_bsk_precision(c->P);
     }
-    if (factor == 2 && c->t64() && !bmit::shape_supported_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log) &&
+    if (factor == 2 && c->t64() && c->wide() && c->bsk_prec != 40)
+        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled kernel takes the key at 40 bits of precision only (chosen by itself when no "
+                           "precision was set, before keygen): the limb sums of its three scaled products must stay inside the transform's "
+                           "certified range");
+    if (factor == 2 && c->t64() && !c->wide() && !bmit::shape_supported_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log) &&
         !bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
         return fail(c, -1, "on the 2^64 torus the unrolled kernels take the key at 48 or 42 bits at base 2^10 (the default torus set): the limb sums of "
                            "its three scaled products must stay below p/2");
-    if (factor == 2 && c->wide() && c->P.bs_levels > 2)
+    if (factor == 2 && c->wide() && !c->t64() && c->P.bs_levels > 2)
         return fail(c, -1, "at N = 2048 the unrolled kernel exists for l <= 2 (at l = 3 it would not fit the registers: the plain kernel is faster)");
     c->unroll = factor;
     if (factor == 2 && c->have_keys && !c->have_bsk3) {
@@ -1436,8 +1472,10 @@ int bmi_set_bsk_unroll(bmi_ctx *c, uint32_t factor) {
 
 int bmi_import_bsk_unrolled(bmi_ctx *c, const uint64_t *bsk3) {
     if (!c || !bsk3) return -1;
-    if (!((c->f64() && !c->quad()) || (c->t64() && !c->wide() && !c->quad())))
-        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field at N = 1024 and N = 2048 and for the 2^64 torus at N = 1024 only");
+    if (!((c->f64() || c->t64()) && !c->quad()))
+        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field and the 2^64 torus at N = 1024 and N = 2048 only");
+    if (c->t64() && c->wide() && !bmit::shape_supported_wide_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
+        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled key is stored at 40 bits of precision: bmi_set_bsk_unroll(ctx, 2) before the key set");
     if (!c->have_keys) return fail(c, -1, "no keys: import or generate the key set first");
     const size_t words = c->bsk3_words();
     for (size_t i = 0; i < words; i++)
@@ -1748,11 +1786,12 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
     // its own kernel rule (batch size plays no part): the unrolled kernel where the unrolled 42-bit key is in use, else at N = 1024
     // the latency form when kernel variant 6 / 2 is selected, else the N = 2048 / 4096 kernel, else the wave-pair kernel
     const bool ufft = c->t64() && c->unroll == 2 && c->have_bsk3 && bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
+    const bool uwide = c->t64() && c->unroll == 2 && c->have_bsk3 && !c->bsk3.wide.empty();   // N = 2048, the unrolled 40-bit key
     const bool wide_key = !c->bsk.wide.empty() || !c->bsk.quad.empty();
-    if (c->bsk.fft.empty() && !wide_key && !ufft)
+    if (c->bsk.fft.empty() && !wide_key && !ufft && !uwide)
         return fail(c, -1, "the floating-point-transform kernels exist on the 2^64 torus with the bootstrap key at 48 bits (N = 1024), 46 bits "
                            "(N = 2048) or 44 bits (N = 4096) in base 2^10");
-    const Rot rot = ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
+    const Rot rot = uwide ? Rot::t64_wide_u : ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
                     : wide_key ? (c->quad() ? Rot::t64_quad : Rot::t64_wide) : Rot::t64_fft;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
     HIP_OK(c, hipSetDevice(c->device));

@@ -183,7 +183,7 @@ int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *
 
 // The 2^64 torus (bmi_kernels_t64*.hip): ciphertexts, test polynomials and keyswitch key are plain u64
 // words; the bootstrap key is LIMBS transform-domain f64 limb polynomials per key polynomial ([poly][limb][N]); the limb
-// scheme follows from the precision `prec` (64, 48 or 42 bits) the key is stored at (t64_common.hpp).
+// scheme follows from the precision `prec` (64, 48, 46, 44, 42 or 40 bits) the key is stored at (t64_common.hpp).
 namespace bmit {
 using gl::i64;
 using gl::u64;
@@ -255,6 +255,13 @@ int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw
 int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
                              bool glwe, hipStream_t s);
+// N = 2048 with the unrolled key (bmi_kernels_t64wu.hip): key at 40 bits of precision (two 20-bit limbs: the six-times larger limb sums
+// stay inside the transform's certified range), one workgroup per ciphertext for every batch size; bsk3_w = launch_bsk_to_wide of the
+// unrolled key [ceil(n/2)][3 keys][2 l rows][2] polynomials at prec = 40, g_zeta_oct = exp(i pi x / 2048) for x in [0, 512] as (re, im)
+bool shape_supported_wide_unrolled(int prec, uint32_t levels, uint32_t base_log);
+int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
+                               const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
+                               unsigned long long *stat, bool glwe, hipStream_t s);
 // glwe_lookup.hip: the look-ups of groups that share one rotation.  glwe = [groups][2N] accumulators of a rotation of the groups'
 // base polynomials; group g serves the tables lut_ids[group_ptr[g] .. group_ptr[g+1]) and writes their LWE rows out[t] (N + 1
 // words) = SampleExtract_0(ACC_g * P_t), P_t the table's sparse factor scaled by 2^(its scale - the scale of base_ids[g]).

@@ -308,7 +308,7 @@ bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log) {
 }
 
 int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s) {
-    if (prec != 46) return (int)hipErrorInvalidValue;
+    if (prec != 46 && prec != 40) return (int)hipErrorInvalidValue;   // 40: the unrolled key (bmi_kernels_t64wu.hip)
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
     hipLaunchKernelGGL(k_bsk_to_w_t64, dim3(items), dim3(256), 0, s, std_polys, w_polys, g_tw_q, n_polys, prec);
     BMI_LAUNCH_CHECK();

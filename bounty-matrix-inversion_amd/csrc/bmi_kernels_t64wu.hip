@@ -1,0 +1,288 @@
+// 2^64 TORUS at N = 2048 (the secure128_torus set: n 742, k 1, l 3, Bg 2^10), UNROLLED blind rotation (two LWE coefficients per
+// step) with the exact limb products carried by the floating-point transform of fft_quarter_f64.hpp (gfx950): the structure of
+// bmi_kernels_t64w.hip (one workgroup of 16 wavefronts per ciphertext, quarter transforms, phase B by lane pairs 32 apart, both
+// limbs in the inverse tasks, plain read-modify-write of the f64 accumulator) running the step of bmi_kernels_t64fu.hip
+// (oracle/tfhe_oracle.c ora_blind_rotate_extract_unrolled):
+//
+//     ACC <- ACC + sum_{j<3} (X^(c_j) - 1) (K3[i][j] [.] ACC),   c = (a + a', a, a'),
+//     K3[i] = GGSW(s s'), GGSW(s (1 - s')), GGSW((1 - s) s')   of the key bits (s, s') = (s_2i, s_2i+1),
+//
+// one decomposition of ACC itself and one set of forward transforms per PAIR of coefficients, three GGSW products scaled by
+// X^c - 1 in the transform domain: X^c at the root zeta^(4k+1) of frequency k is zeta^((4k+1) c), zeta = exp(i pi / 2048).
+//
+// Exactness.  A limb's inverse transform returns  sum_j (X^(c_j) - 1) sum_rows digit x limb : three keys, each scaled by a factor
+// of magnitude <= 2 - six times the plain step's sum.  The unrolled key is therefore stored at 40 bits of precision (two balanced
+// 20-bit limbs, words rounded to multiples of 2^24; the rounded key IS the key: exported, given to the oracle):
+// |sum| < 6 * 2 l N 2^9 2^19 = 2^44.2 < 2^45, and the a-priori bound of the transform's error is 0.38 < 1/2
+// (tools/fft_bound.py unrolled_limb_sum_bound: six times fft_quarter_f64.hpp's formula for a plain limb sum, 0.052 x 6 = 0.31,
+// with the scaling by zeta^(..c) - 1 counted as a multiplication stage of its own, n = 12, and its factor's error - a table
+// entry minus one - as beta = 1.5 e), so the nearest integer of the inverse transform is the exact sum and the words equal the
+// oracle's integer arithmetic on the same key (tests/test_gpu_torus_wide_unrolled.py).  21-bit limbs would give 0.76 (0.62
+// before the scaling stage is counted): not certified, hence 40 bits and not 42.
+//
+// The powers of zeta.  A full table of 2,048 complex powers is 32 KB and does not fit beside the tiles (the plain kernel uses 151
+// of the 160 KB).  The kernel keeps ONE OCTANT, zeta^x for x in [0, 512] (513 complex words, 8 KB + one entry), in LDS and folds
+// the exponent by the table's symmetries: zeta^(1024 - x) = i conj(zeta^x) (real and imaginary parts swapped), zeta^(x + 1024) =
+// i zeta^x.  The symmetries are exact, so every factor is a table entry rounded once from long double - no product of two
+// entries, nothing added to the `beta` of the bound.
+//
+// Per step (a pair with a = a' = 0 is skipped, uniformly over the workgroup; an odd n is completed by a' = 0):
+//   A  8 l forward tasks (input polynomial c, level, quarter h) over the 16 wavefronts: decompose 512 coefficients of the
+//      accumulator itself (no rotation), forward quarter -> tile (slot order, times W_h)
+//   B  all 1,024 threads = (output polynomial o, slot, tp), lanes 32 apart sharing a slot as in the plain kernel: for each of the
+//      three keys the 2 l rows' radix-4 butterfly (one 2 x 2 transpose on lane bit 5, v_permlane32_swap) and multiply-accumulates
+//      with both limbs' key words at the two frequencies kappa + 256 tp and kappa + 256 (tp + 2); the key's sums scaled by
+//      zeta^((4k+1) c_j) - 1 at those frequencies (the second is the first times (-1)^c) and added; the 6 l key rows of a step
+//      are one contiguous run, requested BMI_T64WU_KEY_ROWS_AHEAD rows ahead (the first during the step before); then the
+//      inverse butterfly, times conj W_h -> the sums S_h (over the tiles, after a barrier)
+//   C  8 inverse tasks (o, quarter) on wavefronts 8 .. 15: the inverse quarters of both limbs, nearest integers, limb 1 shifted
+//      into place, one plain read-modify-write per coefficient of the accumulator; re-centred mod 2^40 every 8 steps taken
+#include <hip/hip_runtime.h>
+
+#include "bmi_internal.hpp"
+#include "fft_quarter_f64.hpp"
+#include "pair_sync.hpp"
+#include "t64_common.hpp"
+
+using t64::i64;
+using t64::u64;
+
+namespace {
+
+using fftq::C;
+using fftq::static_for;
+using t64::mod_ab;
+using t64::Scheme;
+
+#ifndef BMI_T64WU_KEY_ROWS_AHEAD
+#define BMI_T64WU_KEY_ROWS_AHEAD 2   // key rows (of the 6 l of a step) a thread holds in registers
+#endif
+constexpr int WN = 2048, WLOG = 11;
+constexpr int WQ = fftq::QUARTER;
+constexpr int WU_THREADS = 1024;
+constexpr int WU_MAX_L = 3;
+constexpr int WU_RECENTRE = 8;
+constexpr int WU_RES = WN / 4;                                // accumulator words per residue class mod 4
+constexpr int WU_TILE_CPLX = 2 * WU_MAX_L * 4 * WQ;           // complex words of the forward tiles (the sums S overlay them)
+constexpr int WU_ZO = WN / 4;                                 // the octant: zeta^x for x in [0, WU_ZO]
+constexpr int WU_ZO_WORDS = 2 * (WU_ZO + 1);
+// LDS (doubles): tables | accumulator [2 components][4 residues][512] | tiles | mod-switched LWE words | octant of zeta powers
+constexpr int WU_LDS_WORDS = fftq::QT_WORDS + 2 * WN + 2 * WU_TILE_CPLX + BMI_AT_WORDS + WU_ZO_WORDS;
+static_assert(WU_LDS_WORDS <= BMI_LDS_WORDS_MAX, "WU_LDS_WORDS exceeds the 160 KB of LDS");
+static_assert(2 * 2 * 4 * WQ <= WU_TILE_CPLX, "the sums S of both limbs and outputs fit over the tiles");
+
+constexpr t64::ResidueSlot<WN, 2> acc_slot{};   // accumulator words are kept split by residue mod 4
+
+// STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
+// GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
+template <int L, int BG, int PREC, bool STATS, bool GLWE>
+__global__ void __launch_bounds__(WU_THREADS)
+    k_blind_rotate_wu_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
+                           const double *__restrict__ bsk3_w, const double *__restrict__ g_tw, const double *__restrict__ g_zeta_oct,
+                           u64 *__restrict__ out, uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
+    constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
+    // three keys, each scaled by |X^c - 1| <= 2: the limb sums are six times the plain step's
+    static_assert(6.0 * 2.0 * L * WN * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
+    static_assert(LIMBS == 2 && L <= WU_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    constexpr int ROWS = 3 * 2 * L;   // key rows of a step: [key 3][row 2L], contiguous in the key copy
+    constexpr int KD = BMI_T64WU_KEY_ROWS_AHEAD < ROWS ? BMI_T64WU_KEY_ROWS_AHEAD : ROWS;
+    extern __shared__ double lds[];
+    double *acc = lds + fftq::QT_WORDS;                                     // [2 components][4 residues][512]: word / 2^PRE, exact, |.| < 2^51
+    double2 *tiles = reinterpret_cast<double2 *>(acc + 2 * WN);             // [2L rows][4 quarters][256 slots] complex
+    double2 *SD = tiles;                                                    // [limb][output][4 quarters][256 slots], once the tiles are read
+    uint16_t *at = reinterpret_cast<uint16_t *>(tiles + WU_TILE_CPLX);
+    double *zo_w = reinterpret_cast<double *>(tiles + WU_TILE_CPLX) + BMI_AT_WORDS;
+    const double2 *ZO = reinterpret_cast<const double2 *>(zo_w);            // zeta^x, x in [0, 512]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int i = tid; i < fftq::QT_WORDS; i += WU_THREADS) lds[i] = g_tw[i];
+    for (int i = tid; i < WU_ZO_WORDS; i += WU_THREADS) zo_w[i] = g_zeta_oct[i];
+    const uint32_t ct = blockIdx.x;
+    const u64 *lwe = small_cts + (size_t)ct * (n + 1);
+    t64::stage_lwe<WLOG + 1>(at, lwe, n, tid, WU_THREADS);
+    __syncthreads();
+    {
+        const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * WN;
+        const uint32_t bt = at[n];
+        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + WU_THREADS * Q); });
+    }
+    __syncthreads();
+    // phase B: output polynomial, slot, and which half of the radix-4 butterfly this lane starts from
+    const int mo = wave >> 3, w8 = wave & 7, tp = lane >> 5, mq = w8 * 32 + (lane & 31);
+    // X^c at this thread's first frequency k0 = kappa + 256 tp is zeta^((4 k0 + 1) c); at k0 + 512 it is that times (-1)^c
+    const uint32_t root_e = 4 * ((uint32_t)fftq::slot_freq(mq >> 6, mq & 63) + 256 * (uint32_t)tp) + 1;
+    const uint32_t pairs = (n + 1) >> 1;
+    uint32_t since_centred = 0;   // steps taken since the accumulator was last reduced mod 2^AB
+    double dev = 0.0;             // STATS: largest |value - nearest integer| this lane has rounded away
+
+    auto a_first = [&](uint32_t ip) -> uint32_t { return at[2 * ip]; };
+    auto a_second = [&](uint32_t ip) -> uint32_t { return 2 * ip + 1 < n ? at[2 * ip + 1] : 0u; };   // (at[n] is the body)
+    // steps are the pairs with a non-zero coefficient (every factor X^0 - 1 vanishes: the oracle skips those too)
+    auto next_step = [&](uint32_t ip) {   // uniform over the workgroup
+        while (ip < pairs && (a_first(ip) | a_second(ip)) == 0) ip++;
+        return ip;
+    };
+    // zeta^x, x in [0, 4096), from the octant: r = x mod 1024 folded at 512 (swap), the quadrant a multiplication by i^q
+    auto zeta_pow = [&](uint32_t x) {
+        const uint32_t r = x & 1023, fold = r > (uint32_t)WU_ZO;
+        const double2 w = ZO[fold ? 1024 - r : r];
+        const double cr = fold ? w.y : w.x, ci = fold ? w.x : w.y;
+        const uint32_t quad = (x >> 10) & 3;
+        const double sr = (quad & 1) ? -ci : cr, si = (quad & 1) ? cr : ci;         // times i for odd quadrants
+        return double2{(quad & 2) ? -sr : sr, (quad & 2) ? -si : si};               // times -1 for quadrants 2, 3
+    };
+    // key words of this thread at pair ip: [key 3][row 2L][output 2][limb][f][64 w8 + lane] complex
+    auto key_ptr = [&](uint32_t ip) {
+        return reinterpret_cast<const double2 *>(bsk3_w + (size_t)ip * 3 * 4 * L * LIMBS * WN) + (size_t)mo * LIMBS * (WN / 2) + (w8 * 64 + lane);
+    };
+    double2 kk[KD][LIMBS][2];
+    auto request_row = [&](double2 (&dst)[LIMBS][2], const double2 *kth, const int row) {
+        static_for<0, LIMBS>([&](auto J) {
+            dst[J][0] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2)];
+            dst[J][1] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2) + WN / 4];
+        });
+    };
+    auto request_first_rows = [&](const double2 *kth) { static_for<0, KD>([&](auto R) { request_row(kk[R], kth, R); }); };
+    uint32_t ip = next_step(0);
+    if (ip < pairs) request_first_rows(key_ptr(ip));
+    while (ip < pairs) {
+        const uint32_t a1 = a_first(ip), a2 = a_second(ip);
+        const uint32_t cj[3] = {(a1 + a2) & (2 * WN - 1), a1, a2};
+        const double2 *kth = key_ptr(ip);
+        const uint32_t ip_next = next_step(ip + 1);
+        auto forward_task = [&](const int T) {
+            const int R = T >> 2, h = T & 3, c = R / L, lev = R % L;
+            const double *ac = acc + c * WN + h * WU_RES + lane;
+            double x[8];   // re[r] = x[r], im[r] = x[r + 4]
+            static_for<0, 8>([&](auto J) {
+                const double dd = mod_ab<AB>(ac[64 * (J & 3) + 256 * (J >> 2)]);   // coefficient 4 (lane + 64 (J & 3)) + h + 1024 (J >> 2)
+                x[J] = t64::digit<L, BG, AB>(dd, lev);
+            });
+            const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
+            C v[4];
+            fftq::forward_quarter(h, re, im, v, lane, lds);
+            double2 *tile = tiles + (size_t)T * WQ;
+            static_for<0, 4>([&](auto R4) { tile[R4 * 64 + lane] = double2{v[R4].r, v[R4].i}; });
+        };
+        if (wave < 8 * L) forward_task(wave);
+        if constexpr (8 * L > 16) {
+            pin();
+            if (wave < 8 * L - 16) forward_task(16 + wave);
+        }
+        __syncthreads();
+        C s_lo[LIMBS], s_hi[LIMBS];
+        {
+            C s[LIMBS][2], y[LIMBS][2];   // sums over the three keys, scaled; one key's sums over its 2L rows
+            static_for<0, LIMBS>([&](auto J) { s[J][0] = s[J][1] = y[J][0] = y[J][1] = C{0.0, 0.0}; });
+            static_for<0, ROWS>([&](auto T) {
+                constexpr int key = T / (2 * L), R = T % (2 * L);
+                const double2 lo = tiles[(size_t)(R * 4 + tp) * WQ + mq], hi = tiles[(size_t)(R * 4 + tp + 2) * WQ + mq];
+                // tp = 0: (q0 + q2, q0 - q2);  tp = 1: (q1 + q3, i (q1 - q3));  after the transpose  tp = 0: (a, cc),  tp = 1: (b, d)
+                C u{lo.x + hi.x, lo.y + hi.y};
+                const C dl{lo.x - hi.x, lo.y - hi.y};
+                C w = tp ? C{-dl.i, dl.r} : dl;
+                lanetr::tr_double<5>(u.r, w.r, lane);
+                lanetr::tr_double<5>(u.i, w.i, lane);
+                const C a0 = u + w, a1f = u - w;   // frequencies kappa + 256 tp and kappa + 256 (tp + 2)
+                static_for<0, LIMBS>([&](auto J) {
+                    const double2 k0 = kk[T % KD][J][0], k1 = kk[T % KD][J][1];
+                    y[J][0].r = __builtin_fma(a0.r, k0.x, __builtin_fma(-a0.i, k0.y, y[J][0].r));
+                    y[J][0].i = __builtin_fma(a0.r, k0.y, __builtin_fma(a0.i, k0.x, y[J][0].i));
+                    y[J][1].r = __builtin_fma(a1f.r, k1.x, __builtin_fma(-a1f.i, k1.y, y[J][1].r));
+                    y[J][1].i = __builtin_fma(a1f.r, k1.y, __builtin_fma(a1f.i, k1.x, y[J][1].i));
+                });
+                if constexpr (T + KD < ROWS) request_row(kk[T % KD], kth, T + KD);
+                if constexpr (R == 2 * L - 1) {   // the key is complete: scale by X^c - 1 at the thread's two frequencies, add
+                    const uint32_t cc = cj[key];
+                    const double2 z = zeta_pow((root_e * cc) & (2 * WN - 1));
+                    const double w0r = z.x - 1.0, w0i = z.y;
+                    const double w1r = ((cc & 1) ? -z.x : z.x) - 1.0, w1i = (cc & 1) ? -z.y : z.y;
+                    static_for<0, LIMBS>([&](auto J) {
+                        s[J][0].r += __builtin_fma(y[J][0].r, w0r, -(y[J][0].i * w0i));
+                        s[J][0].i += __builtin_fma(y[J][0].r, w0i, y[J][0].i * w0r);
+                        s[J][1].r += __builtin_fma(y[J][1].r, w1r, -(y[J][1].i * w1i));
+                        s[J][1].i += __builtin_fma(y[J][1].r, w1i, y[J][1].i * w1r);
+                        y[J][0] = y[J][1] = C{0.0, 0.0};
+                    });
+                }
+                pin();   // one row at a time: neither the next rows' tile reads nor their key requests move up (registers)
+            });
+            // inverse butterfly: tp = 0: (Y0 + Y2, Y0 - Y2);  tp = 1: (Y1 + Y3, -i (Y1 - Y3));  transpose;  S_tp = u + w, S_{tp+2} = u - w
+            // (branch-free; W_0 = 1 is the first word of the omega_64 table)
+            const double2 wl = reinterpret_cast<const double2 *>(lds)[tp ? fftq::QT_W1 / 2 + mq : ffth::HT_T2 / 2];
+            const double2 wh = reinterpret_cast<const double2 *>(lds)[(tp ? fftq::QT_W3 : fftq::QT_W2) / 2 + mq];
+            static_for<0, LIMBS>([&](auto J) {
+                C u = s[J][0] + s[J][1];
+                const C dl = s[J][0] - s[J][1];
+                C w = tp ? C{dl.i, -dl.r} : dl;
+                lanetr::tr_double<5>(u.r, w.r, lane);
+                lanetr::tr_double<5>(u.i, w.i, lane);
+                s_lo[J] = fftq::cmul<true>(u + w, wl.x, wl.y);
+                s_hi[J] = fftq::cmul<true>(u - w, wh.x, wh.y);
+            });
+        }
+        if (ip_next < pairs) request_first_rows(key_ptr(ip_next));   // (uniform) the next step's first rows
+        pin();
+        __syncthreads();   // every thread has read the tiles: the sums may overwrite them
+        static_for<0, LIMBS>([&](auto J) {
+            double2 *sd = SD + (size_t)((J * 2 + mo) * 4) * WQ + mq;
+            sd[tp * WQ] = double2{s_lo[J].r, s_lo[J].i};
+            sd[(tp + 2) * WQ] = double2{s_hi[J].r, s_hi[J].i};
+        });
+        __syncthreads();
+        if (wave >= 8) {   // (wavefronts 0 .. 7 ran two forward tasks where L = 3)
+            const int o = (wave >> 2) & 1, h = wave & 3;
+            double re[LIMBS][4], im[LIMBS][4];
+            static_for<0, LIMBS>([&](auto J) {
+                const double2 *sd = SD + (size_t)((J * 2 + o) * 4 + h) * WQ;
+                C v[4];
+                static_for<0, 4>([&](auto R) {
+                    const double2 t = sd[R * 64 + lane];
+                    v[R] = C{t.x, t.y};
+                });
+                fftq::inverse_quarter(v, re[J], im[J], lane, lds);
+            });
+            double *ao = acc + o * WN + h * WU_RES + lane;
+            static_for<0, 4>([&](auto R) {
+                ao[64 * R] += t64::place_limbs<AB, LB, STATS>(re[0][R], re[1][R], dev);              // coefficient 4 (lane + 64 R) + h
+                ao[64 * R + 256] += t64::place_limbs<AB, LB, STATS>(im[0][R], im[1][R], dev);        // ... + 1024
+            });
+        }
+        __syncthreads();
+        if (++since_centred == WU_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
+            since_centred = 0;
+            static_for<0, 4>([&](auto Q) { acc[tid + WU_THREADS * Q] = mod_ab<AB>(acc[tid + WU_THREADS * Q]); });
+            __syncthreads();
+        }
+        ip = ip_next;
+    }
+    if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
+    if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
+        u64 *g = out + (size_t)ct * (2 * WN);
+        static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + WU_THREADS * Q); });
+        return;
+    }
+    u64 *o = out + (size_t)ct * (WN + 1);
+    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + WU_THREADS * Q); });
+}
+
+}  // namespace
+
+namespace bmit {
+
+// (precision, levels, base log) of the N = 2048 unrolled kernel: the 40-bit key (two 20-bit limbs) in base 2^10
+bool shape_supported_wide_unrolled(int prec, uint32_t levels, uint32_t base_log) {
+    return prec == 40 && base_log == 10 && (levels == 3 || levels == 2);
+}
+
+int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
+                               const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
+                               unsigned long long *stat, bool glwe, hipStream_t s) {
+    if (count == 0) return 0;
+    if (!shape_supported_wide_unrolled(prec, levels, base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_wu_t64f<L, 10, 40, STATS, GLWE>>(dim3(count), dim3(WU_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s,
+                                                                               small_cts, lut_ids, luts, bsk3_w, g_tw_q, g_zeta_oct, out, count, n, stat);
+    });
+}
+
+}  // namespace bmit

@@ -23,6 +23,8 @@
 //   46 bits  2 limbs of 23 bits, PRE = 18  N = 2048 (the secure128_torus set, Bg = 2^10, l = 3) through the floating-point
 //                                          transform only (bmi_kernels_t64w.hip): a limb sum 2 l N 2^9 2^22 = 2^44.6 keeps the
 //                                          a-priori error bound of the 1,024-point transform below 1/2 (fft_quarter_f64.hpp)
+//   40 bits  2 limbs of 20 bits, PRE = 24  N = 2048 with the UNROLLED key only (bmi_kernels_t64wu.hip): the six-times larger limb
+//                                          sums, 6 * 2 l N 2^9 2^19 = 2^44.2, keep that bound at 0.31 (21-bit limbs: 0.62)
 #pragma once
 #include <stdint.h>
 
@@ -44,8 +46,9 @@ template <> struct Scheme<48> { static constexpr int LIMBS = 2, BITS = 24, PRE =
 template <> struct Scheme<42> { static constexpr int LIMBS = 2, BITS = 21, PRE = 22; };
 template <> struct Scheme<46> { static constexpr int LIMBS = 2, BITS = 23, PRE = 18; };
 template <> struct Scheme<44> { static constexpr int LIMBS = 2, BITS = 22, PRE = 20; };
+template <> struct Scheme<40> { static constexpr int LIMBS = 2, BITS = 20, PRE = 24; };
 
-T64_HD bool precision_ok(int prec) { return prec == 64 || prec == 48 || prec == 46 || prec == 44 || prec == 42; }
+T64_HD bool precision_ok(int prec) { return prec == 64 || prec == 48 || prec == 46 || prec == 44 || prec == 42 || prec == 40; }
 T64_HD int limbs_of(int prec) { return prec == 64 ? 3 : 2; }
 T64_HD int limb_bits(int prec) { return prec == 64 ? 22 : prec / 2; }
 T64_HD int limb_pre(int prec) { return 64 - prec; }

@@ -170,7 +170,7 @@ int bmi_blind_rotate_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t
  * sum of squares of its coefficients).  Tables of msg_bits <= 6 whose neighbouring entries differ by an int32 at most can share
  * (their sparse form is built at registration; the others are refused as members of a base's group, each with its own text).
  * Served by every floating-point-transform rotation of the torus: N = 1024 (key at 48 bits), N = 2048 (46 bits), N = 4096 (44 bits)
- * and the unrolled key of bmi_set_bsk_unroll at its own 42 bits.  Refused with a bmi_last_error text: the 49-bit field and
+ * and the unrolled key of bmi_set_bsk_unroll at its own 42 bits (N = 1024) or 40 bits (N = 2048).  Refused with a bmi_last_error text: the 49-bit field and
  * Goldilocks; a pinned exact-transform kernel variant (1 / 3 / 4 at N = 1024); the unrolled key pinned at 48 bits of precision
  * (bmi_set_bsk_precision(ctx, 48) before bmi_set_bsk_unroll: the exact-transform unrolled kernel).
  *
@@ -286,6 +286,12 @@ int bmi_set_kernel_variant(bmi_ctx *ctx, int variant);
  *       limbs keep them inside the range the floating-point transform is certified for (k_blind_rotate_lat2u_t64f; output noise
  *       2^-19.3).  At Bg = 2^15: round 2's throughput option for flat PBS batches (output noise 2^-15.15: too noisy for the
  *       encrypted inverse).
+ *   40  N = 2048 in UNROLLED mode only (Bg = 2^10, l = 3 or 2) - the precision bmi_set_bsk_unroll(ctx, 2) selects by itself there
+ *       when none was set, and the only one it takes: multiples of 2^24, two 20-bit limbs.  The six-times larger limb sums of the
+ *       unrolled step stay below 2^45 and the a-priori bound of the 1,024-point transform, with the scaling by zeta^(..c) - 1
+ *       counted as a stage, is 0.38 < 1/2 (tools/fft_bound.py; 21-bit limbs: 0.76) - k_blind_rotate_wu_t64f, output noise 2^-16.2
+ *       (std) against 2^-22.2 of the plain 46-bit key, far below the keyswitch noise it feeds (std 2^-9.8): DESIGN section 2.
+ *       Refused in plain mode; switching back to factor 1 restores 46.
  * The rounded key is the context's key from then on (bmi_export_keys / bmi_export_bsk_unrolled return it; results are
  * bit-exact against an oracle given that key; oracle/tfhe_oracle.c ora_round_key states the rule).  The rounding only ever
  * adds noise to valid LWE samples; generating the key on the grid directly would instead round its own noise away. */
@@ -295,7 +301,10 @@ int bmi_get_bsk_precision(const bmi_ctx *ctx, uint32_t *bits);
 
 /* 49-bit field at N = 1024, and at N = 2048 with l <= 2 (the secure128 shape), and the 2^64 torus at its default set (Bg = 2^10;
  * key at 42 bits: k_blind_rotate_lat2u_t64f, the floating-point-transform route, 2.9 ms per bootstrap - what this call selects when
- * no precision was set -, or pinned at 48 bits: k_blind_rotate_lat2u_t64, the exact transform, 3.3 ms): bootstrap-key unrolling (Zhou et al. 2018, Bourse et al. 2018; unrolling factor 2).
+ * no precision was set -, or pinned at 48 bits: k_blind_rotate_lat2u_t64, the exact transform, 3.3 ms), and the 2^64 torus at N = 2048
+ * (l = 3 or 2, Bg = 2^10, e.g. "secure128_torus"; key at 40 bits - selected by this call when no precision was set, any other explicit
+ * precision is refused -: k_blind_rotate_wu_t64f, one workgroup per ciphertext for every batch size and kernel variant; N = 4096 is
+ * refused): bootstrap-key unrolling (Zhou et al. 2018, Bourse et al. 2018; unrolling factor 2).
  * factor 1 (default): the blind rotation of CGGI, one LWE coefficient per step.  factor 2: a step absorbs two coefficients,
  *   ACC <- ACC + sum_{j<3} (X^(c_j) - 1) (K_j [.] ACC),  c = (a + a', a, a'),  K = GGSW(s s'), GGSW(s (1 - s')), GGSW((1 - s) s'),
  * with one decomposition and one set of forward transforms per step (half as many as the plain rotation; the factors X^c - 1

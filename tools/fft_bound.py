@@ -26,12 +26,26 @@ def percival_factor(n, beta=E):
     return math.expm1(3 * n * math.log1p(E) + (3 * n + 1) * math.log1p(E * math.sqrt(5)) + 3 * n * math.log1p(beta))
 
 
-def limb_sum_bound(log_n_poly, levels, base_log, limb_bits, extra=1):
+def limb_sum_bound(log_n_poly, levels, base_log, limb_bits, extra=1, beta=E):
     """bound on |computed - exact| of one limb sum; extra = multiplication stages counted on top of the log2(N) - 1 butterflies"""
     n_poly = 1 << log_n_poly
     norm = n_poly * 2.0 ** (base_log - 1) * 2.0 ** (limb_bits - 1)      # ||d|| ||k||, both at their largest in every coefficient
-    per_product = norm * percival_factor(log_n_poly - 1 + extra)
+    per_product = norm * percival_factor(log_n_poly - 1 + extra, beta)
     return 2 * levels * per_product, per_product
+
+
+# The UNROLLED step (csrc/bmi_kernels_t64fu.hip at N = 1024, csrc/bmi_kernels_t64wu.hip at N = 2048): a limb's inverse transform
+# returns sum_{j<3} (X^(c_j) - 1) sum_rows digit x limb - three keys, each scaled in the transform domain by a factor of
+# magnitude <= 2: six times the plain limb sum.  The scaling is one more multiplication stage (extra = 2).  Its factor
+# zeta^x - 1 is a table entry (rounded once from long double: the N = 2048 kernel folds one octant of the powers by exact
+# symmetries, never multiplying two entries) minus one: absolute error <= e (the entry) + 2 e (the subtraction's rounding, on a
+# result of magnitude <= 2) = 3 e on a factor bounded by 2, i.e. beta = 1.5 e, which the formula then charges to every stage.
+UNROLLED_BETA = 1.5 * E
+
+
+def unrolled_limb_sum_bound(log_n_poly, levels, base_log, limb_bits):
+    """bound on |computed - exact| of one limb sum of the unrolled step"""
+    return 6 * limb_sum_bound(log_n_poly, levels, base_log, limb_bits, extra=2, beta=UNROLLED_BETA)[0]
 
 
 SETS = {
@@ -42,10 +56,20 @@ SETS = {
     "N 4096 with 23-bit limbs (NOT used: bound fails)": (12, 3, 10, 23),
 }
 
+UNROLLED_SETS = {
+    "secure128_torus unrolled (N 2048, l 3, Bg 2^10, 20-bit limbs: key at 40 bits)": (11, 3, 10, 20),
+    "N 2048 unrolled with 21-bit limbs (NOT used: bound fails)": (11, 3, 10, 21),
+}
+
 if __name__ == "__main__":
     for name, (lg, l, bg, lb) in SETS.items():
         total, per = limb_sum_bound(lg, l, bg, lb)
         total0, _ = limb_sum_bound(lg, l, bg, lb, extra=0)
         print(f"{name}: per product {per:.4f}, limb sum {total:.3f} (twist counted as a stage; {total0:.3f} without)  "
+              f"{'< 1/2 ok' if total < 0.5 else '>= 1/2 NOT certified'}")
+    for name, (lg, l, bg, lb) in UNROLLED_SETS.items():
+        total = unrolled_limb_sum_bound(lg, l, bg, lb)
+        plain = 6 * limb_sum_bound(lg, l, bg, lb)[0]
+        print(f"{name}: limb sum {total:.3f} (scaling by zeta^x - 1 counted as a stage, beta 1.5 e; {plain:.3f} = 6 x the plain bound without)  "
               f"{'< 1/2 ok' if total < 0.5 else '>= 1/2 NOT certified'}")
     sys.exit(0)
