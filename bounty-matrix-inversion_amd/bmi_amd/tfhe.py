@@ -85,6 +85,7 @@ _SIGS = {
     "bmi_torus64_to_field": [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p],
     "bmi_field_to_torus64": [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p],
     "bmi_set_kernel_variant": [C.c_void_p, C.c_int],
+    "bmi_rotation_kernel": [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p)],
     "bmi_set_keyswitch_variant": [C.c_void_p, C.c_int],
     "bmi_set_bsk_precision": [C.c_void_p, C.c_uint32],
     "bmi_get_bsk_precision": [C.c_void_p, C.POINTER(C.c_uint32)],
@@ -449,6 +450,13 @@ class Engine:
         the 49-bit field), 3 pair kernel exchanging per CMUX, 4 latency kernel with one wavefront per transform, 5 (2^64 torus,
         48-bit key in base 2^10) pair kernel with the exact limb products carried by the f64 complex FFT, 6 its latency form"""
         self._ck(self.lib.bmi_set_kernel_variant(self.h, int(v)), "bmi_set_kernel_variant")
+
+    def rotation_kernel(self, count):
+        """name of the blind-rotation kernel the engine's current mode and kernel variant run for a batch of `count` ciphertexts
+        (answered by the library's dispatch itself: include/bmi_tfhe.h bmi_rotation_kernel)"""
+        name = C.c_char_p()
+        self._ck(self.lib.bmi_rotation_kernel(self.h, int(count), C.byref(name)), "bmi_rotation_kernel")
+        return name.value.decode()
 
     def set_bsk_precision(self, bits):
         """2^64 torus, before keygen: 64 = exact key (three limbs); 48 = key rounded to 48 bits (two limbs, 2/3 of the work; the

@@ -829,15 +829,15 @@ int ensure_ks_mfma(bmi_ctx *c, uint32_t count) {
 
 // The blind-rotation launchers (bmi_internal.hpp), one member each: choose_rotation picks one, launch_rotation runs it.
 enum class Rot {
-    t64_wide_u, t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
+    t64_wide_u, t64_wide_u2, t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
     f49_wide_u, f49_wide, f49_quad, f49_lat2u, f49_lat2, f49_tpx,                                                   // 49-bit field
     gl_lat, gl_tp,                                                                                                  // Goldilocks
 };
 
 // The kernel of bmi_blind_rotate_batch for a batch of `count` on this context: 0 and *rot, or a refusal.
 int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
-    // unrolled key (49-bit field and 2^64 torus at N = 1024 / 2048: bmi_set_bsk_unroll refuses the rest): one kernel
-    // (one workgroup per ciphertext) for every batch size, so that a ciphertext's bits never depend on the batch it travelled in
+    // unrolled key (49-bit field and 2^64 torus at N = 1024 / 2048: bmi_set_bsk_unroll refuses the rest): kernels that give the same
+    // words, so that a ciphertext's bits never depend on the batch it travelled in
     if (c->unroll == 2 && !c->have_bsk3)
         return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
     const int v = c->variant;
@@ -845,12 +845,16 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     // with wave-pair work, the throughput kernel beyond that (49-bit field: the exchange-once form).
     const bool latency = v == 2 || (v == 0 && count <= c->lat_threshold);
     // torus, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins
-    // the one-ciphertext form); the same words either way
+    // the one-ciphertext form); the same words either way.  The unrolled N = 2048 pair (wu / wu2) follows the plain pair's rule:
+    // one round of wu2 (up to 512 ciphertexts on 256 compute units) measures 11.35 ms against 7.6 ms for one round of wu (up to
+    // 256) and 15.25 ms for two (257 .. 512), so wu2 wins from 257 on and wu up to 256; at 1,024 / 2,048 / 8,192 wu2 takes 0.74 of
+    // wu's time (profiles/unrolled_wide2_ab.txt; 512 is the smallest batch measured - between 257 and 512 both kernels run the
+    // round counts they run at 512).
     const bool two_per_wg = v == 1 || v == 3 || (v == 0 && count > 256);
     const int prec = c->bsk_prec;
     const uint32_t lv = c->P.bs_levels, bl = c->P.bs_base_log;
     if (c->t64()) {
-        if (c->wide() && c->unroll == 2) *rot = Rot::t64_wide_u;   // one workgroup per ciphertext at every count and variant
+        if (c->wide() && c->unroll == 2) *rot = two_per_wg ? Rot::t64_wide_u2 : Rot::t64_wide_u;   // one key copy serves both
         else if (c->wide() && c->bsk.wide.empty())
             return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
         else if (c->wide() && !c->bsk.wide2.empty() && two_per_wg) *rot = Rot::t64_wide2;
@@ -881,11 +885,38 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     return 0;
 }
 
-// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the eight floating-point-transform kernels of the torus.
+// The __global__ function a member launches: bmi_rotation_kernel answers with it
+const char *rotation_name(Rot rot) {
+    switch (rot) {
+    case Rot::t64_wide_u: return "k_blind_rotate_wu_t64f";
+    case Rot::t64_wide_u2: return "k_blind_rotate_wu2_t64f";
+    case Rot::t64_wide2: return "k_blind_rotate_w2_t64f";
+    case Rot::t64_wide: return "k_blind_rotate_w_t64f";
+    case Rot::t64_quad: return "k_blind_rotate_q_t64f";
+    case Rot::t64_tp2u_fft: return "k_blind_rotate_tp2u_t64f";
+    case Rot::t64_lat2u_fft: return "k_blind_rotate_lat2u_t64f";
+    case Rot::t64_lat2u: return "k_blind_rotate_lat2u_t64";
+    case Rot::t64_lat_fft: return "k_blind_rotate_lat_t64f";
+    case Rot::t64_lat: return "k_blind_rotate_lat_t64";
+    case Rot::t64_fft: return "k_blind_rotate_t64f";
+    case Rot::t64_exact: return "k_blind_rotate_t64";
+    case Rot::f49_wide_u: return "k_blind_rotate_wide49u";
+    case Rot::f49_wide: return "k_blind_rotate_wide49";
+    case Rot::f49_quad: return "k_blind_rotate_quad49";
+    case Rot::f49_lat2u: return "k_blind_rotate_lat2u_49";
+    case Rot::f49_lat2: return "k_blind_rotate_lat2_49";
+    case Rot::f49_tpx: return "k_blind_rotate_tpx49";
+    case Rot::gl_lat: return "k_blind_rotate_lat";
+    case Rot::gl_tp: return "k_blind_rotate_tp";
+    }
+    return "";
+}
+
+// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the nine floating-point-transform kernels of the torus.
 // Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not the prime fields.
 bool has_accumulator_form(Rot rot) {
     switch (rot) {
-    case Rot::t64_wide_u: case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft:
+    case Rot::t64_wide_u: case Rot::t64_wide_u2: case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft:
     case Rot::t64_lat_fft: case Rot::t64_fft:
         return true;
     default: return false;
@@ -906,6 +937,8 @@ int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *i
     switch (rot) {
     case Rot::t64_wide_u: return bmit::launch_blind_rotate_wide_u(cts, ids, luts, K3.wide.get(), c->tw_quarter.get(), c->zeta_oct.get(), out, count, n,
                                                                    p, lv, bl, stat, glwe, st);
+    case Rot::t64_wide_u2: return bmit::launch_blind_rotate_wide_u2(cts, ids, luts, K3.wide.get(), c->tw_quarter.get(), c->zeta_oct.get(), out, count, n,
+                                                                     p, lv, bl, stat, glwe, st);
     case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, glwe, st);
     case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, glwe, st);
     case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, glwe, st);
@@ -1498,6 +1531,14 @@ int bmi_set_keyswitch_variant(bmi_ctx *c, int variant) {
     return 0;
 }
 
+int bmi_rotation_kernel(const bmi_ctx *c, uint32_t count, const char **name) {
+    if (!c || !name) return -1;
+    Rot rot;
+    if (int rc = choose_rotation(c, count, &rot)) return rc;
+    *name = rotation_name(rot);
+    return 0;
+}
+
 int bmi_set_kernel_variant(bmi_ctx *c, int variant) {
     if (!c) return -1;
     if (variant < 0 || variant > 6) return fail(c, -1, "variant must be 0..6");
@@ -1783,7 +1824,8 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
                         double *max_distance) {
     if (!c || !small_in || !lut_ids || !out || !max_distance) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    // its own kernel rule (batch size plays no part): the unrolled kernel where the unrolled 42-bit key is in use, else at N = 1024
+    // its own kernel rule (batch size plays a part for the unrolled 40-bit key at N = 2048 only, where choose_rotation decides: the
+    // kernel that would run that batch): the unrolled kernel where the unrolled 42-bit key is in use, else at N = 1024
     // the latency form when kernel variant 6 / 2 is selected, else the N = 2048 / 4096 kernel, else the wave-pair kernel
     const bool ufft = c->t64() && c->unroll == 2 && c->have_bsk3 && bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
     const bool uwide = c->t64() && c->unroll == 2 && c->have_bsk3 && !c->bsk3.wide.empty();   // N = 2048, the unrolled 40-bit key
@@ -1791,7 +1833,10 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
     if (c->bsk.fft.empty() && !wide_key && !ufft && !uwide)
         return fail(c, -1, "the floating-point-transform kernels exist on the 2^64 torus with the bootstrap key at 48 bits (N = 1024), 46 bits "
                            "(N = 2048) or 44 bits (N = 4096) in base 2^10");
-    const Rot rot = uwide ? Rot::t64_wide_u : ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
+    Rot rot_uwide = Rot::t64_wide_u;
+    if (uwide)
+        if (int rc = choose_rotation(c, count, &rot_uwide)) return rc;
+    const Rot rot = uwide ? rot_uwide : ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
                     : wide_key ? (c->quad() ? Rot::t64_quad : Rot::t64_wide) : Rot::t64_fft;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
     HIP_OK(c, hipSetDevice(c->device));

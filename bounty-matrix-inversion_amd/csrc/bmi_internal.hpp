@@ -85,7 +85,7 @@ inline int with_levels_stats(uint32_t levels, bool stats, F f) {
     return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
-// ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,w2,q}.hip), whose trailing template flag GLWE makes
+// ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,wu,wu2,w2,q}.hip), whose trailing template flag GLWE makes
 // them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
 // out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator
 // form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.
@@ -256,12 +256,18 @@ int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, cons
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
                              bool glwe, hipStream_t s);
 // N = 2048 with the unrolled key (bmi_kernels_t64wu.hip): key at 40 bits of precision (two 20-bit limbs: the six-times larger limb sums
-// stay inside the transform's certified range), one workgroup per ciphertext for every batch size; bsk3_w = launch_bsk_to_wide of the
+// stay inside the transform's certified range), one workgroup per ciphertext (auto dispatch: up to 256 ciphertexts;
+// launch_blind_rotate_wide_u2 beyond); bsk3_w = launch_bsk_to_wide of the
 // unrolled key [ceil(n/2)][3 keys][2 l rows][2] polynomials at prec = 40, g_zeta_oct = exp(i pi x / 2048) for x in [0, 512] as (re, im)
 bool shape_supported_wide_unrolled(int prec, uint32_t levels, uint32_t base_log);
 int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
                                unsigned long long *stat, bool glwe, hipStream_t s);
+// ... and its throughput form (bmi_kernels_t64wu2.hip): two ciphertexts per workgroup, every key word a thread loads multiplied with
+// both, one decomposition level of tiles in LDS at a time; the SAME key copy and tables, the same words
+int launch_blind_rotate_wide_u2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
+                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
+                                unsigned long long *stat, bool glwe, hipStream_t s);
 // glwe_lookup.hip: the look-ups of groups that share one rotation.  glwe = [groups][2N] accumulators of a rotation of the groups'
 // base polynomials; group g serves the tables lut_ids[group_ptr[g] .. group_ptr[g+1]) and writes their LWE rows out[t] (N + 1
 // words) = SampleExtract_0(ACC_g * P_t), P_t the table's sparse factor scaled by 2^(its scale - the scale of base_ids[g]).

@@ -1,4 +1,4 @@
-// Shared by all 2^64-torus kernel files (bmi_kernels_t64.hip, _t64u, _t64f, _t64fu, _t64w, _t64w2, _t64q) and the host
+// Shared by all 2^64-torus kernel files (bmi_kernels_t64.hip, _t64u, _t64f, _t64fu, _t64w, _t64wu, _t64wu2, _t64w2, _t64q) and the host
 // (bmi_host.cpp): the limb schemes of the bootstrap key and, for the kernels (__HIPCC__ part), the steps every blind rotation
 // states the same way - the word <-> exact-double conversions, the centred residue mod 2^AB, the oracle's rounding and digit
 // rule, the placement of a limb's integer, and the prologue (mod-switch, test polynomial) and epilogue (sample extraction).
@@ -23,7 +23,7 @@
 //   46 bits  2 limbs of 23 bits, PRE = 18  N = 2048 (the secure128_torus set, Bg = 2^10, l = 3) through the floating-point
 //                                          transform only (bmi_kernels_t64w.hip): a limb sum 2 l N 2^9 2^22 = 2^44.6 keeps the
 //                                          a-priori error bound of the 1,024-point transform below 1/2 (fft_quarter_f64.hpp)
-//   40 bits  2 limbs of 20 bits, PRE = 24  N = 2048 with the UNROLLED key only (bmi_kernels_t64wu.hip): the six-times larger limb
+//   40 bits  2 limbs of 20 bits, PRE = 24  N = 2048 with the UNROLLED key only (bmi_kernels_t64wu.hip, _t64wu2.hip): the six-times larger limb
 //                                          sums, 6 * 2 l N 2^9 2^19 = 2^44.2, keep that bound at 0.31 (21-bit limbs: 0.62)
 #pragma once
 #include <stdint.h>

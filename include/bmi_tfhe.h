@@ -239,7 +239,8 @@ int bmi_pbs_shared_batch_host(bmi_ctx *ctx, const uint64_t *in, const uint32_t *
                               const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out);
 /* Test hook of the floating-point-transform kernels (2^64 torus; N = 1024: key at 48 bits, kernel variants 5 / 6; N = 2048: key at
  * 46 bits; N = 4096: key at 44 bits, k_blind_rotate_q_t64f): blind rotation of `count` small-key ciphertexts by the wave-pair kernel - by the latency form when kernel variant 6 or 2
- * is selected, by k_blind_rotate_w_t64f at N = 2048 -, which here also records how far every limb sum was from the integer it was
+ * is selected, by k_blind_rotate_w_t64f at N = 2048, with the unrolled key there by the kernel that runs a batch of `count`
+ * (k_blind_rotate_wu_t64f or _wu2_t64f) -, which here also records how far every limb sum was from the integer it was
  * rounded to.  *max_distance must stay far below 1/2 (measured: below 2^-11) - that is what makes the
  * rounded results the exact integer sums, whatever the order of the floating-point operations. */
 int bmi_fft_margin_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *out,
@@ -263,8 +264,14 @@ int bmi_sync(bmi_ctx *ctx, void *stream);
  *     which pin the exact transform mod 2^49 - 720895; what auto picks for large batches on that key),
  * 6 = the same for the latency form (one workgroup per ciphertext; what auto and 2 pick on that key; 4 pins the exact transform).
  * 2^64 torus at N = 2048: auto = one workgroup per ciphertext up to 256 ciphertexts (2 pins it), two ciphertexts per workgroup sharing
- *     the key words beyond (1 / 3 pin it); the same words.  N = 4096: one kernel. */
+ *     the key words beyond (1 / 3 pin it); the same words - on the plain key (k_blind_rotate_w_t64f / _w2_t64f) and on the unrolled
+ *     key (k_blind_rotate_wu_t64f / _wu2_t64f, which share one key copy) alike.  N = 4096: one kernel. */
 int bmi_set_kernel_variant(bmi_ctx *ctx, int variant);
+/* *name = the name of the blind-rotation kernel (the __global__ function, a static string) that the context's current modulus,
+ * key mode, precision and kernel variant run for a batch of `count` ciphertexts: answered by the function that dispatches
+ * bmi_blind_rotate_batch, for every engine, so that tools can label timings and tests can tell kernels apart that give the same
+ * words by construction.  Fails where a rotation would be refused (e.g. unrolling selected without an unrolled key). */
+int bmi_rotation_kernel(const bmi_ctx *ctx, uint32_t count, const char **name);
 
 /* 2^64 torus only, before keygen / import: precision the bootstrap key is stored at.  No transform exists mod 2^64, so the
  * external product is computed exactly over the integers from limbs of every key word (csrc/t64_common.hpp); the number of
@@ -289,7 +296,9 @@ int bmi_set_kernel_variant(bmi_ctx *ctx, int variant);
  *   40  N = 2048 in UNROLLED mode only (Bg = 2^10, l = 3 or 2) - the precision bmi_set_bsk_unroll(ctx, 2) selects by itself there
  *       when none was set, and the only one it takes: multiples of 2^24, two 20-bit limbs.  The six-times larger limb sums of the
  *       unrolled step stay below 2^45 and the a-priori bound of the 1,024-point transform, with the scaling by zeta^(..c) - 1
- *       counted as a stage, is 0.38 < 1/2 (tools/fft_bound.py; 21-bit limbs: 0.76) - k_blind_rotate_wu_t64f, output noise 2^-16.2
+ *       counted as a stage, is 0.38 < 1/2 (tools/fft_bound.py; 21-bit limbs: 0.76) - k_blind_rotate_wu_t64f (one workgroup per ciphertext: up to 256
+ *       ciphertexts, kernel variant 2) and k_blind_rotate_wu2_t64f (two per workgroup sharing every key word: beyond 256, variants
+ *       1 / 3), the same words from one key copy; output noise 2^-16.2
  *       (std) against 2^-22.2 of the plain 46-bit key, far below the keyswitch noise it feeds (std 2^-9.8): DESIGN section 2.
  *       Refused in plain mode; switching back to factor 1 restores 46.
  * The rounded key is the context's key from then on (bmi_export_keys / bmi_export_bsk_unrolled return it; results are
@@ -303,15 +312,16 @@ int bmi_get_bsk_precision(const bmi_ctx *ctx, uint32_t *bits);
  * key at 42 bits: k_blind_rotate_lat2u_t64f, the floating-point-transform route, 2.9 ms per bootstrap - what this call selects when
  * no precision was set -, or pinned at 48 bits: k_blind_rotate_lat2u_t64, the exact transform, 3.3 ms), and the 2^64 torus at N = 2048
  * (l = 3 or 2, Bg = 2^10, e.g. "secure128_torus"; key at 40 bits - selected by this call when no precision was set, any other explicit
- * precision is refused -: k_blind_rotate_wu_t64f, one workgroup per ciphertext for every batch size and kernel variant; N = 4096 is
+ * precision is refused -: k_blind_rotate_wu_t64f, one workgroup per ciphertext, up to 256 ciphertexts and k_blind_rotate_wu2_t64f, two
+ * ciphertexts per workgroup sharing every key word, beyond, as bmi_set_kernel_variant states; N = 4096 is
  * refused): bootstrap-key unrolling (Zhou et al. 2018, Bourse et al. 2018; unrolling factor 2).
  * factor 1 (default): the blind rotation of CGGI, one LWE coefficient per step.  factor 2: a step absorbs two coefficients,
  *   ACC <- ACC + sum_{j<3} (X^(c_j) - 1) (K_j [.] ACC),  c = (a + a', a, a'),  K = GGSW(s s'), GGSW(s (1 - s')), GGSW((1 - s) s'),
  * with one decomposition and one set of forward transforms per step (half as many as the plain rotation; the factors X^c - 1
  * are applied in the transform domain).  Every batch size then runs k_blind_rotate_lat2u_49 (49-bit field, N = 1024),
- * k_blind_rotate_wide49u (N = 2048) or the torus kernel above, one workgroup per ciphertext; on the torus's floating-point route,
- * batches beyond 256 ciphertexts run k_blind_rotate_tp2u_t64f: two ciphertexts per workgroup sharing every key word in registers
- * (half the key bytes per bootstrap; the same words).
+ * k_blind_rotate_wide49u (N = 2048) or the torus kernel above, one workgroup per ciphertext; on the torus's floating-point routes,
+ * batches beyond 256 ciphertexts run k_blind_rotate_tp2u_t64f (N = 1024) or k_blind_rotate_wu2_t64f (N = 2048): two ciphertexts
+ * per workgroup sharing every key word in registers (half the key bytes per bootstrap; the same words).
  * The unrolled key (1.5 x the plain key's size) is generated by the next keygen call, or at once when the context already
  * holds secret keys; an evaluation-only context receives it through bmi_import_bsk_unrolled.  Layout:
  * [ceil(n/2)][3][(k+1) l][(k+1)][N] words, standard domain (an odd n is completed by a zero key bit).  Price: the key-noise

@@ -40,6 +40,10 @@ def limb_sum_bound(log_n_poly, levels, base_log, limb_bits, extra=1, beta=E):
 # zeta^x - 1 is a table entry (rounded once from long double: the N = 2048 kernel folds one octant of the powers by exact
 # symmetries, never multiplying two entries) minus one: absolute error <= e (the entry) + 2 e (the subtraction's rounding, on a
 # result of magnitude <= 2) = 3 e on a factor bounded by 2, i.e. beta = 1.5 e, which the formula then charges to every stage.
+# The bound does not depend on WHERE in a product's chain of multiplications the factor is applied: k_blind_rotate_wu_t64f scales
+# a key's sums after the products with its rows, k_blind_rotate_wu2_t64f (csrc/bmi_kernels_t64wu2.hip: two ciphertexts per
+# workgroup) scales the digit transform before them - the same stages on every product, one table entry per factor in both,
+# hence the same bound for both kernels.
 UNROLLED_BETA = 1.5 * E
 
 

@@ -11,6 +11,7 @@
 #                                libbmi_tfhe_x.so; "" = the product build), e.g.  ab "'' _kd3" tools/preset_timing.py secure128_torus 1,256
 #   timing <br_timing args>      tools/br_timing.py (batches, kernel variants, q_bits)
 #   preset <preset> [batches]    tools/preset_timing.py
+#   wu2ab [args]                 tools/unrolled_wide2_ab.py: the two unrolled N = 2048 kernels alternating -> profiles/unrolled_wide2_ab.txt (BMI_OUT=FILE: elsewhere)
 #   phase  <t64f|t64w> [batches] per-phase cycles of the debug build (make -C csrc prof)
 #   inverse [sizes]              encrypted-inverse wall-clocks on the default engine (bmi_amd/inverse_bench.py)
 #   calibrate [preset:bits:rounds ...]   failure-rate calibration of the error budget + phase-kernel time (tools/gpu_failure_rate.py)
@@ -39,6 +40,7 @@ case "$recipe" in
     done; done ;;
   timing) timeout -k 10 ${BMI_T:-500} python tools/br_timing.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/timing.log ;;
   preset) timeout -k 10 ${BMI_T:-300} python tools/preset_timing.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/preset_timing.log ;;
+  wu2ab) timeout -k 10 ${BMI_T:-420} python tools/unrolled_wide2_ab.py --out "${BMI_OUT:-profiles/unrolled_wide2_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -60 ;;
   phase)
     k=$1; shift
     timeout -k 10 ${BMI_T:-300} python tools/phase_prof_$k.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/phase_$k.log ;;
