@@ -88,7 +88,9 @@ inline int with_levels_stats(uint32_t levels, bool stats, F f) {
 // ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,wu,wu2,w2,q}.hip), whose trailing template flag GLWE makes
 // them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
 // out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator
-// form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.
+// form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.  (The four N = 2048
+// kernels share their steps through t64_wide_steps.hpp but each keeps this epilogue written out: behind a helper it renumbers the
+// step loop's registers, profiles/wide_steps_ab.txt.)
 template <typename F>
 inline int with_levels_stats_glwe(uint32_t levels, bool stats, bool glwe, F f) {
     if (!glwe) return with_levels_stats(levels, stats, [&](auto L, auto STATS) { return f(L, STATS, std::false_type{}); });

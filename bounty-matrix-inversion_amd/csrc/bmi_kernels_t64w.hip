@@ -28,35 +28,25 @@
 #include "pair_sync.hpp"
 #include "phase_prof.hpp"
 #include "t64_common.hpp"
+#include "t64_wide_steps.hpp"
 
 using t64::i64;
 using t64::u64;
 
 namespace {
 
-using fftq::C;
-using fftq::static_for;
-using t64::mod_ab;
+using namespace t64w;   // the N = 2048 family's constants (WN, WQ, W_*) and shared steps: t64_wide_steps.hpp
 using t64::Scheme;
 
 #ifndef BMI_T64W_KEY_ROWS_AHEAD
 #define BMI_T64W_KEY_ROWS_AHEAD 2   // key rows (of 2 l) a thread holds in registers: requested before phase A, then row r + this many when row r is done
 #endif
 PH_ARRAY(g_phase_w)   // make -C csrc prof; tools/phase_prof_t64w.py
-constexpr int WN = 2048, WLOG = 11;
-constexpr int WQ = fftq::QUARTER;
-constexpr int WF_THREADS = 1024;
-constexpr int WF_MAX_L = 3;
-constexpr int WF_RECENTRE = 8;
-constexpr int WF_RES = WN / 4;                                // accumulator words per residue class mod 4
-constexpr int WF_TILE_CPLX = 2 * WF_MAX_L * 4 * WQ;           // complex words of the forward tiles (the sums S overlay them)
+constexpr int WF_TILE_CPLX = 2 * W_MAX_L * 4 * WQ;            // complex words of the forward tiles (the sums S overlay them)
 // LDS (doubles): tables | accumulator [2 components][4 residues][512] | tiles | mod-switched LWE words
 constexpr int WF_LDS_WORDS = fftq::QT_WORDS + 2 * WN + 2 * WF_TILE_CPLX + BMI_AT_WORDS;
 static_assert(WF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "WF_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(2 * 2 * 4 * WQ <= WF_TILE_CPLX, "the sums S of both limbs and outputs fit over the tiles");
-
-// accumulator words are kept split by residue mod 4 (a lane's points of a quarter are 256 coefficients apart and of one residue)
-constexpr t64::ResidueSlot<WN, 2> acc_slot{};
 
 // standard-domain GGSW polynomials (u64 torus words, already rounded to the key precision) -> per (polynomial, limb) 1,024
 // complex words A_k / 2 in the order the multiplying threads read them: thread (w8 = slot / 32, lane) of phase B owns slot
@@ -73,17 +63,7 @@ __global__ void __launch_bounds__(256) k_bsk_to_w_t64(const u64 *__restrict__ st
     const uint32_t poly = item / limbs;
     const int j = (int)(item % limbs);
     double2 *tile = reinterpret_cast<double2 *>(lds + fftq::QT_WORDS);
-    {
-        double re[4], im[4];
-        static_for<0, 4>([&](auto R) {
-            const uint32_t m = 4 * (lane + 64 * R) + h;
-            re[R] = (double)t64::limb_of((i64)std_polys[(size_t)poly * WN + m], j, prec);
-            im[R] = (double)t64::limb_of((i64)std_polys[(size_t)poly * WN + m + WN / 2], j, prec);
-        });
-        C v[4];
-        fftq::forward_quarter(h, re, im, v, lane, lds);
-        static_for<0, 4>([&](auto R) { tile[h * WQ + R * 64 + lane] = double2{v[R].r, v[R].i}; });
-    }
+    key_limb_to_tile(tile, std_polys, poly, j, prec, h, lane, lds);
     __syncthreads();
     {
         const int p = threadIdx.x;
@@ -103,14 +83,14 @@ __global__ void __launch_bounds__(256) k_bsk_to_w_t64(const u64 *__restrict__ st
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, int PREC, bool STATS, bool GLWE>
-__global__ void __launch_bounds__(WF_THREADS)
+__global__ void __launch_bounds__(W_THREADS)
     k_blind_rotate_w_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                           const double *__restrict__ bsk_w, const double *__restrict__ g_tw, u64 *__restrict__ out, uint32_t count,
                           uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     // a limb's sum: 2 L N terms of |digit| <= 2^(BG-1) times |limb| <= 2^(LB-1) - the transform's error bound is stated for this size
     static_assert(2.0 * L * WN * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= WF_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= W_MAX_L && L * BG < AB, "two limbs, at most three levels");
     constexpr int KD = BMI_T64W_KEY_ROWS_AHEAD < 2 * L ? BMI_T64W_KEY_ROWS_AHEAD : 2 * L;
     extern __shared__ double lds[];
     double *acc = lds + fftq::QT_WORDS;                                     // [2 components][4 residues][512]: word / 2^PRE, exact, |.| < 2^51
@@ -118,16 +98,11 @@ __global__ void __launch_bounds__(WF_THREADS)
     double2 *SD = tiles;                                                    // [limb][output][4 quarters][256 slots], once the tiles are read
     uint16_t *at = reinterpret_cast<uint16_t *>(tiles + WF_TILE_CPLX);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < fftq::QT_WORDS; i += WF_THREADS) lds[i] = g_tw[i];
+    for (int i = tid; i < fftq::QT_WORDS; i += W_THREADS) lds[i] = g_tw[i];
     const uint32_t ct = blockIdx.x;
-    const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    t64::stage_lwe<WLOG + 1>(at, lwe, n, tid, WF_THREADS);
+    t64::stage_lwe<WLOG + 1>(at, small_cts + (size_t)ct * (n + 1), n, tid, W_THREADS);
     __syncthreads();
-    {
-        const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * WN;
-        const uint32_t bt = at[n];
-        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + WF_THREADS * Q); });
-    }
+    load_start_acc<PRE>(acc, luts, lut_ids, ct, at, n, tid);
     __syncthreads();
     // phase B: output polynomial, slot, and which half of the radix-4 butterfly this lane starts from
     const int mo = wave >> 3, w8 = wave & 7, tp = lane >> 5, mq = w8 * 32 + (lane & 31);
@@ -140,53 +115,29 @@ __global__ void __launch_bounds__(WF_THREADS)
         while (i < n && at[i] == 0) i++;
         return i;
     };
-    // key words of this thread at step i: [row 2L][output 2][limb][f][64 w8 + lane] complex
-    auto key_ptr = [&](uint32_t i) {
-        return reinterpret_cast<const double2 *>(bsk_w + (size_t)i * 4 * L * LIMBS * WN) + (size_t)mo * LIMBS * (WN / 2) + (w8 * 64 + lane);
-    };
+    // key words of this thread at step i: rows [2L] of the per-polynomial key copy
+    auto step_key = [&](uint32_t i) { return key_ptr<2 * L, LIMBS>(bsk_w, i, mo, w8, lane); };
     // rows 0 .. KD-1 of a step are requested during the step BEFORE (after its products: they land under its inverse quarters and
     // the next forward tasks), row r + KD when row r has been multiplied
     double2 kk[KD][LIMBS][2];
-    auto request_first_rows = [&](const double2 *kth) {
-        static_for<0, KD>([&](auto R) {
-            static_for<0, LIMBS>([&](auto J) {
-                kk[R][J][0] = kth[((size_t)R * 2 * LIMBS + J) * (WN / 2)];
-                kk[R][J][1] = kth[((size_t)R * 2 * LIMBS + J) * (WN / 2) + WN / 4];
-            });
-        });
-    };
+    auto request_first_rows = [&](const double2 *kth) { static_for<0, KD>([&](auto R) { request_row(kk[R], kth, R); }); };
     uint32_t i = next_step(0);
-    if (i < n) request_first_rows(key_ptr(i));
+    if (i < n) request_first_rows(step_key(i));
     while (i < n) {
         const uint32_t a_t = at[i];
-        const double2 *kth = key_ptr(i);
+        const double2 *kth = step_key(i);
         const uint32_t i_next = next_step(i + 1);
         PH_MARK(0);   // loop head, key requests
         auto forward_task = [&](const int T) {
             const int R = T >> 2, h = T & 3, c = R / L, lev = R % L;
             const double *ac = acc + c * WN;
             double x[8];   // re[r] = x[r], im[r] = x[r + 4]
-            // coefficient m_J = 4 (lane + 64 (J & 3)) + h + 1024 (J >> 2); its rotated source e_J = m_J - a_t mod 2N: a quarter of it is
-            // t0 + 64 (J & 3) + 256 (J >> 2) - the low 9 bits are the slot inside the residue block, bit 9 is the sign
-            const uint32_t e0 = (4 * lane + h + 2 * WN - a_t) & (2 * WN - 1);
-            const uint32_t t0 = e0 >> 2, pbase = (e0 & 3) * WF_RES;
             // (four coefficients at a time, fenced: the 32 key registers in flight leave this task ~90)
             static_for<0, 2>([&](auto G) {
-                double vr[4], vs[4];
-                static_for<0, 4>([&](auto J4) {
-                    constexpr int J = G * 4 + J4;
-                    const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                    vr[J4] = ac[pbase + (t & (WF_RES - 1))];
-                    vs[J4] = ac[h * WF_RES + lane + 64 * (J & 3) + 256 * (J >> 2)];
-                });
-                static_for<0, 4>([&](auto J4) {
-                    constexpr int J = G * 4 + J4;
-                    const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                    const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
-                    x[J] = t64::digit<L, BG, AB>(dd, lev);
-                });
+                rotated_diff_digits<L, BG, AB, G>(x, ac, h, lane, a_t, lev);
                 pin();
             });
+            // (written out in all four kernels: inlined through a helper, the transform's own instructions come in another order)
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             C v[4];
             fftq::forward_quarter(h, re, im, v, lane, lds);
@@ -209,52 +160,21 @@ __global__ void __launch_bounds__(WF_THREADS)
             static_for<0, LIMBS>([&](auto J) { y[J][0] = y[J][1] = C{0.0, 0.0}; });
             static_for<0, 2 * L>([&](auto R) {
                 const double2 lo = tiles[(size_t)(R * 4 + tp) * WQ + mq], hi = tiles[(size_t)(R * 4 + tp + 2) * WQ + mq];
-                // tp = 0: (q0 + q2, q0 - q2);  tp = 1: (q1 + q3, i (q1 - q3));  after the transpose  tp = 0: (a, cc),  tp = 1: (b, d)
-                C u{lo.x + hi.x, lo.y + hi.y};
-                const C dl{lo.x - hi.x, lo.y - hi.y};
-                C w = tp ? C{-dl.i, dl.r} : dl;
-                lanetr::tr_double<5>(u.r, w.r, lane);
-                lanetr::tr_double<5>(u.i, w.i, lane);
-                const C a0 = u + w, a1 = u - w;   // frequencies kappa + 256 tp and kappa + 256 (tp + 2)
-                static_for<0, LIMBS>([&](auto J) {
-                    const double2 k0 = kk[R % KD][J][0], k1 = kk[R % KD][J][1];
-                    y[J][0].r = __builtin_fma(a0.r, k0.x, __builtin_fma(-a0.i, k0.y, y[J][0].r));
-                    y[J][0].i = __builtin_fma(a0.r, k0.y, __builtin_fma(a0.i, k0.x, y[J][0].i));
-                    y[J][1].r = __builtin_fma(a1.r, k1.x, __builtin_fma(-a1.i, k1.y, y[J][1].r));
-                    y[J][1].i = __builtin_fma(a1.r, k1.y, __builtin_fma(a1.i, k1.x, y[J][1].i));
-                });
-                if constexpr (R + KD < 2 * L) {
-                    static_for<0, LIMBS>([&](auto J) {
-                        kk[R % KD][J][0] = kth[((size_t)(R + KD) * 2 * LIMBS + J) * (WN / 2)];
-                        kk[R % KD][J][1] = kth[((size_t)(R + KD) * 2 * LIMBS + J) * (WN / 2) + WN / 4];
-                    });
-                }
+                C a0, a1;   // the row at frequencies kappa + 256 tp and kappa + 256 (tp + 2)
+                forward_half_butterfly(lo, hi, tp, lane, a0, a1);
+                static_for<0, LIMBS>([&](auto J) { cmac2(y[J], a0, a1, kk[R % KD][J]); });
+                if constexpr (R + KD < 2 * L) request_row(kk[R % KD], kth, R + KD);
                 pin();   // one row at a time: neither the next rows' tile reads nor their key requests move up (registers)
             });
-            // inverse butterfly: tp = 0: (Y0 + Y2, Y0 - Y2);  tp = 1: (Y1 + Y3, -i (Y1 - Y3));  transpose;  S_tp = u + w, S_{tp+2} = u - w
-            // (branch-free: a conditional read would split the block and let the compiler sink every product below it. W_0 = 1 is the
-            // first word of the omega_64 table)
-            const double2 wl = reinterpret_cast<const double2 *>(lds)[tp ? fftq::QT_W1 / 2 + mq : ffth::HT_T2 / 2];
-            const double2 wh = reinterpret_cast<const double2 *>(lds)[(tp ? fftq::QT_W3 : fftq::QT_W2) / 2 + mq];
-            static_for<0, LIMBS>([&](auto J) {
-                C u = y[J][0] + y[J][1];
-                const C dl = y[J][0] - y[J][1];
-                C w = tp ? C{dl.i, -dl.r} : dl;
-                lanetr::tr_double<5>(u.r, w.r, lane);
-                lanetr::tr_double<5>(u.i, w.i, lane);
-                s_lo[J] = fftq::cmul<true>(u + w, wl.x, wl.y);
-                s_hi[J] = fftq::cmul<true>(u - w, wh.x, wh.y);
-            });
+            const double2 wl = reinterpret_cast<const double2 *>(lds)[conj_w_lo_index(tp, mq)];
+            const double2 wh = reinterpret_cast<const double2 *>(lds)[conj_w_hi_index(tp, mq)];
+            static_for<0, LIMBS>([&](auto J) { inverse_half_butterfly(y[J][0], y[J][1], tp, lane, wl, wh, s_lo[J], s_hi[J]); });
         }
-        if (i_next < n) request_first_rows(key_ptr(i_next));   // (uniform) the next step's first rows
+        if (i_next < n) request_first_rows(step_key(i_next));   // (uniform) the next step's first rows
         pin();
         PH_MARK(4);   // products of 2 L rows, inverse butterfly, next key requests
         __syncthreads();   // every thread has read the tiles: the sums may overwrite them
-        static_for<0, LIMBS>([&](auto J) {
-            double2 *sd = SD + (size_t)((J * 2 + mo) * 4) * WQ + mq;
-            sd[tp * WQ] = double2{s_lo[J].r, s_lo[J].i};
-            sd[(tp + 2) * WQ] = double2{s_hi[J].r, s_hi[J].i};
-        });
+        static_for<0, LIMBS>([&](auto J) { store_sums(SD + (size_t)((J * 2 + mo) * 4) * WQ + mq, tp, s_lo[J], s_hi[J]); });
         __syncthreads();
         PH_MARK(5);   // barrier, the sums to LDS, barrier
         if (wave >= 8) {   // (wavefronts 0 .. 7 ran two forward tasks where L = 3)
@@ -269,7 +189,7 @@ __global__ void __launch_bounds__(WF_THREADS)
                 });
                 fftq::inverse_quarter(v, re[J], im[J], lane, lds);
             });
-            double *ao = acc + o * WN + h * WF_RES + lane;
+            double *ao = acc + o * WN + h * W_RES + lane;
             static_for<0, 4>([&](auto R) {
                 ao[64 * R] += t64::place_limbs<AB, LB, STATS>(re[0][R], re[1][R], dev);              // coefficient 4 (lane + 64 R) + h
                 ao[64 * R + 256] += t64::place_limbs<AB, LB, STATS>(im[0][R], im[1][R], dev);        // ... + 1024
@@ -277,9 +197,9 @@ __global__ void __launch_bounds__(WF_THREADS)
         }
         PH_MARK(6);   // inverse quarters of both limbs, rounding, accumulation
         __syncthreads();
-        if (++since_centred == WF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
+        if (++since_centred == W_RECENTRE) {   // (uniform: counts the steps actually taken)
             since_centred = 0;
-            static_for<0, 4>([&](auto Q) { acc[tid + WF_THREADS * Q] = mod_ab<AB>(acc[tid + WF_THREADS * Q]); });
+            recentre<AB, 4>(acc, tid);
             __syncthreads();
         }
         PH_MARK(7);   // closing barrier (+ re-centring every eighth step)
@@ -287,13 +207,14 @@ __global__ void __launch_bounds__(WF_THREADS)
     }
     PH_STORE(g_phase_w, wave, lane);
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
+    // (the epilogue through a helper: the step loop's registers are numbered differently, 126 VGPRs for 127)
     if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
         u64 *g = out + (size_t)ct * (2 * WN);
-        static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + WF_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W_THREADS * Q); });
         return;
     }
     u64 *o = out + (size_t)ct * (WN + 1);
-    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + WF_THREADS * Q); });
+    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W_THREADS * Q); });
 }
 
 }  // namespace
@@ -321,7 +242,7 @@ int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, cons
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_w_t64f<L, 10, 46, STATS, GLWE>>(dim3(count), dim3(WF_THREADS), (size_t)WF_LDS_WORDS * sizeof(double), s,
+        return launch_with_lds<k_blind_rotate_w_t64f<L, 10, 46, STATS, GLWE>>(dim3(count), dim3(W_THREADS), (size_t)WF_LDS_WORDS * sizeof(double), s,
                                                                               small_cts, lut_ids, luts, bsk_w, g_tw_q, out, count, n, stat);
     });
 }

@@ -21,38 +21,20 @@
 #include "fft_quarter_f64.hpp"
 #include "pair_sync.hpp"
 #include "t64_common.hpp"
+#include "t64_wide_steps.hpp"
 
 using t64::i64;
 using t64::u64;
 
 namespace {
 
-using fftq::C;
-using fftq::static_for;
-using t64::mod_ab;
+using namespace t64w;   // the N = 2048 family's constants (WN, WQ, W_*) and shared steps: t64_wide_steps.hpp
 using t64::Scheme;
 
-constexpr int WN = 2048, WLOG = 11;
-constexpr int WS = fftq::QUARTER;                // slots per quarter
-constexpr int W2_THREADS = 1024;
-constexpr int W2_MAX_L = 3;
-constexpr int W2_RECENTRE = 8;
-constexpr int W2_RES = WN / 4;                   // accumulator words per residue class mod 4
-constexpr int W2_TILE_CPLX = 2 * 2 * 4 * WS;     // one level's tiles [ciphertext 2][component 2][quarter 4][256]; one limb's sums overlay them
+constexpr int W2_TILE_CPLX = 2 * 2 * 4 * WQ;     // one level's tiles [ciphertext 2][component 2][quarter 4][256]; one limb's sums overlay them
 // LDS (doubles): tables | accumulators [ciphertext 2][component 2][residue 4][512] | tiles | mod-switched LWE words of both
 constexpr int W2_LDS_WORDS = fftq::QT_WORDS + 2 * 2 * WN + 2 * W2_TILE_CPLX + 2 * BMI_AT_WORDS;
 static_assert(W2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "W2_LDS_WORDS exceeds the 160 KB of LDS");
-
-constexpr t64::ResidueSlot<WN, 2> acc_slot{};   // accumulator words are kept split by residue mod 4
-
-// an empty statement that reads and writes the sums: they must be in registers here (the branches of the next task would otherwise
-// let the compiler sink the multiply-adds below them: bmi_kernels_t64q.hip)
-__device__ __forceinline__ void keep(C (&y)[2][4]) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int t = 0; t < 4; t++) asm volatile("" : "+v"(y[b][t].r), "+v"(y[b][t].i));
-}
 
 // sum_h i^(h t) q_h in q[t]  (INV: i^(-h t))
 template <bool INV>
@@ -72,7 +54,7 @@ __device__ __forceinline__ void dft4(C (&q)[4]) {
 __global__ void __launch_bounds__(256) k_bsk_to_w2_t64(const u64 *__restrict__ std_polys, double *__restrict__ w2_polys,
                                                        const double *__restrict__ g_tw, uint32_t n_polys, int prec) {
     const int limbs = t64::limbs_of(prec);
-    __shared__ double lds[fftq::QT_WORDS + 4 * WS * 2];
+    __shared__ double lds[fftq::QT_WORDS + 4 * WQ * 2];
     for (int i = threadIdx.x; i < fftq::QT_WORDS; i += blockDim.x) lds[i] = g_tw[i];
     __syncthreads();
     const int h = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -80,40 +62,30 @@ __global__ void __launch_bounds__(256) k_bsk_to_w2_t64(const u64 *__restrict__ s
     const uint32_t poly = item / limbs;
     const int j = (int)(item % limbs);
     double2 *tile = reinterpret_cast<double2 *>(lds + fftq::QT_WORDS);
-    {
-        double re[4], im[4];
-        static_for<0, 4>([&](auto R) {
-            const uint32_t m = 4 * (lane + 64 * R) + h;
-            re[R] = (double)t64::limb_of((i64)std_polys[(size_t)poly * WN + m], j, prec);
-            im[R] = (double)t64::limb_of((i64)std_polys[(size_t)poly * WN + m + WN / 2], j, prec);
-        });
-        C v[4];
-        fftq::forward_quarter(h, re, im, v, lane, lds);
-        static_for<0, 4>([&](auto R) { tile[h * WS + R * 64 + lane] = double2{v[R].r, v[R].i}; });
-    }
+    key_limb_to_tile(tile, std_polys, poly, j, prec, h, lane, lds);
     __syncthreads();
     {
         const int p = threadIdx.x;
         C q[4];
         static_for<0, 4>([&](auto H) {
-            const double2 t = tile[H * WS + p];
+            const double2 t = tile[H * WQ + p];
             q[H] = C{t.x, t.y};
         });
         dft4<false>(q);
         double2 *o = reinterpret_cast<double2 *>(w2_polys + (size_t)item * WN);
-        static_for<0, 4>([&](auto T) { o[T * WS + p] = double2{0.5 * q[T].r, 0.5 * q[T].i}; });
+        static_for<0, 4>([&](auto T) { o[T * WQ + p] = double2{0.5 * q[T].r, 0.5 * q[T].i}; });
     }
 }
 
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, int PREC, bool GLWE>
-__global__ void __launch_bounds__(W2_THREADS)
+__global__ void __launch_bounds__(W_THREADS)
     k_blind_rotate_w2_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                            const double *__restrict__ bsk_w2, const double *__restrict__ g_tw, u64 *__restrict__ out, uint32_t count,
                            uint32_t n) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     static_assert(2.0 * L * WN * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= W2_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= W_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *accs = lds + fftq::QT_WORDS;                                    // [ciphertext][2 components][4 residues][512]: word / 2^PRE, exact
     double2 *tiles = reinterpret_cast<double2 *>(accs + 2 * 2 * WN);        // [ciphertext 2][component 2][quarter 4][256 slots] of the current level
@@ -121,22 +93,21 @@ __global__ void __launch_bounds__(W2_THREADS)
     uint16_t *at = reinterpret_cast<uint16_t *>(tiles + W2_TILE_CPLX);      // [ciphertext 2][BMI_AT_WORDS * 4]
     constexpr int AT_STRIDE = BMI_AT_WORDS * 4;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < fftq::QT_WORDS; i += W2_THREADS) lds[i] = g_tw[i];
+    for (int i = tid; i < fftq::QT_WORDS; i += W_THREADS) lds[i] = g_tw[i];
     // the two ciphertexts of this workgroup (an odd batch: the last workgroup runs its one ciphertext twice and writes it once)
-    const uint32_t ct0 = blockIdx.x * 2;
-    const bool live1 = ct0 + 1 < count;
-    const uint32_t cts[2] = {ct0, live1 ? ct0 + 1 : ct0};
+    uint32_t cts[2];
+    const bool live1 = ciphertext_pair(cts, blockIdx.x, count);
     for (int b = 0; b < 2; b++) {
         const u64 *lwe = small_cts + (size_t)cts[b] * (n + 1);
         // (t64::stage_lwe written out: handing it at + b * AT_STRIDE turns the guard of the step loop around in the generated code)
-        for (uint32_t i = tid; i <= n; i += W2_THREADS) at[b * AT_STRIDE + i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
+        for (uint32_t i = tid; i <= n; i += W_THREADS) at[b * AT_STRIDE + i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
     }
     __syncthreads();
-    for (int b = 0; b < 2; b++) {
+    for (int b = 0; b < 2; b++) {   // (t64w::load_start_acc per ciphertext: 12 B of scratch per lane)
         const u64 *tv = luts + (size_t)(lut_ids[cts[b]] & (BMI_LUT_CAP - 1)) * WN;
         const uint32_t bt = at[b * AT_STRIDE + n];
         double *acc = accs + b * 2 * WN;
-        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + W2_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + W_THREADS * Q); });
     }
     __syncthreads();
     // phase B: slot, output polynomial, limb (the four combinations of a slot sit 16 lanes apart: their tile reads coincide)
@@ -159,42 +130,27 @@ __global__ void __launch_bounds__(W2_THREADS)
             {   // phase A
                 const double *ac = accs + wb * 2 * WN + wc * WN;
                 double x[8];   // re[r] = x[r], im[r] = x[r + 4]
-                // coefficient m_J = 4 (lane + 64 (J & 3)) + h + 1024 (J >> 2); its rotated source e_J = m_J - a_t mod 2N: a quarter of it is
-                // t0 + 64 (J & 3) + 256 (J >> 2) - the low 9 bits are the slot inside the residue block, bit 9 is the sign
-                const uint32_t e0 = (4 * lane + wh + 2 * WN - a_own) & (2 * WN - 1);
-                const uint32_t t0 = e0 >> 2, pbase = (e0 & 3) * W2_RES;
-                static_for<0, 2>([&](auto G) {
-                    double vr[4], vs[4];
-                    static_for<0, 4>([&](auto J4) {
-                        constexpr int J = G * 4 + J4;
-                        const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                        vr[J4] = ac[pbase + (t & (W2_RES - 1))];
-                        vs[J4] = ac[wh * W2_RES + lane + 64 * (J & 3) + 256 * (J >> 2)];
-                    });
-                    static_for<0, 4>([&](auto J4) {
-                        constexpr int J = G * 4 + J4;
-                        const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                        const double dd = mod_ab<AB>(((t >> 9) & 1) ? -vr[J4] - vs[J4] : vr[J4] - vs[J4]);   // the centred lift of the u64 difference, / 2^PRE
-                        x[J] = t64::digit<L, BG, AB>(dd, lev);
-                    });
+                static_for<0, 2>([&](auto G) {   // four coefficients at a time, fenced
+                    rotated_diff_digits<L, BG, AB, G>(x, ac, wh, lane, a_own, lev);
                     pin();
                 });
+                // (written out in all four kernels: inlined through a helper, the transform's own instructions come in another order)
                 const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
                 C v[4];
                 fftq::forward_quarter(wh, re, im, v, lane, lds);
-                double2 *tile = tiles + (size_t)wave * WS;     // wave = (ciphertext 2, component 2, quarter 4)
+                double2 *tile = tiles + (size_t)wave * WQ;     // wave = (ciphertext 2, component 2, quarter 4)
                 static_for<0, 4>([&](auto R4) { tile[R4 * 64 + lane] = double2{v[R4].r, v[R4].i}; });
             }
             // this thread's key words of the level's two rows (component 0 / 1): they land under the barrier (requested during
             // the level before instead: 48 B of scratch per lane, 14.77 against 13.45 ms per 512)
-            static_for<0, 2>([&](auto CC) { static_for<0, 4>([&](auto T) { kw[CC][T] = row_ptr(CC * L + lev)[T * WS]; }); });
+            static_for<0, 2>([&](auto CC) { static_for<0, 4>([&](auto T) { kw[CC][T] = row_ptr(CC * L + lev)[T * WQ]; }); });
             pin();
             __syncthreads();
             static_for<0, 2>([&](auto CC) {   // rows (component CC, this level)
                 static_for<0, 2>([&](auto B) {
                     C q[4];
                     static_for<0, 4>([&](auto H) {
-                        const double2 t = tiles[(size_t)((B * 2 + CC) * 4 + H) * WS + slot];
+                        const double2 t = tiles[(size_t)((B * 2 + CC) * 4 + H) * WQ + slot];
                         q[H] = C{t.x, t.y};
                     });
                     dft4<false>(q);   // frequency kappa + 256 t in q[t]
@@ -212,12 +168,12 @@ __global__ void __launch_bounds__(W2_THREADS)
         static_for<0, LIMBS>([&](auto J) {
             if (mj == J) {
                 static_for<0, 2>([&](auto B) {
-                    static_for<0, 4>([&](auto H) { SD[(size_t)((B * 2 + mo) * 4 + H) * WS + slot] = double2{y[B][H].r, y[B][H].i}; });
+                    static_for<0, 4>([&](auto H) { SD[(size_t)((B * 2 + mo) * 4 + H) * WQ + slot] = double2{y[B][H].r, y[B][H].i}; });
                 });
             }
             __syncthreads();
             {
-                const double2 *sd = SD + (size_t)wave * WS;     // wave = (ciphertext, output, quarter)
+                const double2 *sd = SD + (size_t)wave * WQ;     // wave = (ciphertext, output, quarter)
                 C v[4];
                 static_for<0, 4>([&](auto R) {
                     const double2 t = sd[R * 64 + lane];
@@ -230,20 +186,14 @@ __global__ void __launch_bounds__(W2_THREADS)
                         v[R] = fftq::cmul<true>(v[R], t.x, t.y);
                     });
                 }
-                double re[4], im[4];
-                fftq::inverse_quarter(v, re, im, lane, lds);
-                double *ao = accs + wb * 2 * WN + wc * WN + wh * W2_RES + lane;
-                constexpr int j = J;
-                static_for<0, 4>([&](auto R) {
-                    ao[64 * R] += t64::place_limb<AB, LB>(re[R], j);              // coefficient 4 (lane + 64 R) + h
-                    ao[64 * R + 256] += t64::place_limb<AB, LB>(im[R], j);        // ... + 1024
-                });
+                double dev = 0.0;   // (no statistics in this kernel)
+                inverse_task_limb<AB, LB, false>(accs + wb * 2 * WN + wc * WN, wh, v, J, lane, lds, dev);
             }
             __syncthreads();
         });
-        if (++since_centred == W2_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulators' magnitude below 2^51
+        if (++since_centred == W_RECENTRE) {   // (uniform: counts the steps actually taken)
             since_centred = 0;
-            static_for<0, 8>([&](auto Q) { accs[tid + W2_THREADS * Q] = mod_ab<AB>(accs[tid + W2_THREADS * Q]); });
+            recentre<AB, 8>(accs, tid);
             __syncthreads();
         }
     }
@@ -251,11 +201,11 @@ __global__ void __launch_bounds__(W2_THREADS)
         const double *acc = accs + b * 2 * WN;
         if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
             u64 *g = out + (size_t)cts[b] * (2 * WN);
-            static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W2_THREADS * Q); });
+            static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W_THREADS * Q); });
             continue;
         }
         u64 *o = out + (size_t)cts[b] * (WN + 1);
-        static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W2_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W_THREADS * Q); });
     }
 }
 
@@ -276,7 +226,7 @@ int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, con
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     auto launch = [&](auto L, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((count + 1) / 2), dim3(W2_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
+        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((count + 1) / 2), dim3(W_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
                                                                         small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
     };
     return with_levels(levels, [&](auto L) { return glwe ? launch(L, std::true_type{}) : launch(L, std::false_type{}); });

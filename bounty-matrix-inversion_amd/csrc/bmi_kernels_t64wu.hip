@@ -43,47 +43,36 @@
 #include "fft_quarter_f64.hpp"
 #include "pair_sync.hpp"
 #include "t64_common.hpp"
+#include "t64_wide_steps.hpp"
 
 using t64::i64;
 using t64::u64;
 
 namespace {
 
-using fftq::C;
-using fftq::static_for;
-using t64::mod_ab;
+using namespace t64w;   // the N = 2048 family's constants (WN, WQ, W_*) and shared steps: t64_wide_steps.hpp
 using t64::Scheme;
 
 #ifndef BMI_T64WU_KEY_ROWS_AHEAD
 #define BMI_T64WU_KEY_ROWS_AHEAD 2   // key rows (of the 6 l of a step) a thread holds in registers
 #endif
-constexpr int WN = 2048, WLOG = 11;
-constexpr int WQ = fftq::QUARTER;
-constexpr int WU_THREADS = 1024;
-constexpr int WU_MAX_L = 3;
-constexpr int WU_RECENTRE = 8;
-constexpr int WU_RES = WN / 4;                                // accumulator words per residue class mod 4
-constexpr int WU_TILE_CPLX = 2 * WU_MAX_L * 4 * WQ;           // complex words of the forward tiles (the sums S overlay them)
-constexpr int WU_ZO = WN / 4;                                 // the octant: zeta^x for x in [0, WU_ZO]
-constexpr int WU_ZO_WORDS = 2 * (WU_ZO + 1);
+constexpr int WU_TILE_CPLX = 2 * W_MAX_L * 4 * WQ;            // complex words of the forward tiles (the sums S overlay them)
 // LDS (doubles): tables | accumulator [2 components][4 residues][512] | tiles | mod-switched LWE words | octant of zeta powers
-constexpr int WU_LDS_WORDS = fftq::QT_WORDS + 2 * WN + 2 * WU_TILE_CPLX + BMI_AT_WORDS + WU_ZO_WORDS;
+constexpr int WU_LDS_WORDS = fftq::QT_WORDS + 2 * WN + 2 * WU_TILE_CPLX + BMI_AT_WORDS + W_ZO_WORDS;
 static_assert(WU_LDS_WORDS <= BMI_LDS_WORDS_MAX, "WU_LDS_WORDS exceeds the 160 KB of LDS");
 static_assert(2 * 2 * 4 * WQ <= WU_TILE_CPLX, "the sums S of both limbs and outputs fit over the tiles");
-
-constexpr t64::ResidueSlot<WN, 2> acc_slot{};   // accumulator words are kept split by residue mod 4
 
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, int PREC, bool STATS, bool GLWE>
-__global__ void __launch_bounds__(WU_THREADS)
+__global__ void __launch_bounds__(W_THREADS)
     k_blind_rotate_wu_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                            const double *__restrict__ bsk3_w, const double *__restrict__ g_tw, const double *__restrict__ g_zeta_oct,
                            u64 *__restrict__ out, uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     // three keys, each scaled by |X^c - 1| <= 2: the limb sums are six times the plain step's
     static_assert(6.0 * 2.0 * L * WN * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= WU_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= W_MAX_L && L * BG < AB, "two limbs, at most three levels");
     constexpr int ROWS = 3 * 2 * L;   // key rows of a step: [key 3][row 2L], contiguous in the key copy
     constexpr int KD = BMI_T64WU_KEY_ROWS_AHEAD < ROWS ? BMI_T64WU_KEY_ROWS_AHEAD : ROWS;
     extern __shared__ double lds[];
@@ -94,17 +83,12 @@ __global__ void __launch_bounds__(WU_THREADS)
     double *zo_w = reinterpret_cast<double *>(tiles + WU_TILE_CPLX) + BMI_AT_WORDS;
     const double2 *ZO = reinterpret_cast<const double2 *>(zo_w);            // zeta^x, x in [0, 512]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < fftq::QT_WORDS; i += WU_THREADS) lds[i] = g_tw[i];
-    for (int i = tid; i < WU_ZO_WORDS; i += WU_THREADS) zo_w[i] = g_zeta_oct[i];
+    for (int i = tid; i < fftq::QT_WORDS; i += W_THREADS) lds[i] = g_tw[i];
+    for (int i = tid; i < W_ZO_WORDS; i += W_THREADS) zo_w[i] = g_zeta_oct[i];
     const uint32_t ct = blockIdx.x;
-    const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    t64::stage_lwe<WLOG + 1>(at, lwe, n, tid, WU_THREADS);
+    t64::stage_lwe<WLOG + 1>(at, small_cts + (size_t)ct * (n + 1), n, tid, W_THREADS);
     __syncthreads();
-    {
-        const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * WN;
-        const uint32_t bt = at[n];
-        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + WU_THREADS * Q); });
-    }
+    load_start_acc<PRE>(acc, luts, lut_ids, ct, at, n, tid);
     __syncthreads();
     // phase B: output polynomial, slot, and which half of the radix-4 butterfly this lane starts from
     const int mo = wave >> 3, w8 = wave & 7, tp = lane >> 5, mq = w8 * 32 + (lane & 31);
@@ -121,37 +105,20 @@ __global__ void __launch_bounds__(WU_THREADS)
         while (ip < pairs && (a_first(ip) | a_second(ip)) == 0) ip++;
         return ip;
     };
-    // zeta^x, x in [0, 4096), from the octant: r = x mod 1024 folded at 512 (swap), the quadrant a multiplication by i^q
-    auto zeta_pow = [&](uint32_t x) {
-        const uint32_t r = x & 1023, fold = r > (uint32_t)WU_ZO;
-        const double2 w = ZO[fold ? 1024 - r : r];
-        const double cr = fold ? w.y : w.x, ci = fold ? w.x : w.y;
-        const uint32_t quad = (x >> 10) & 3;
-        const double sr = (quad & 1) ? -ci : cr, si = (quad & 1) ? cr : ci;         // times i for odd quadrants
-        return double2{(quad & 2) ? -sr : sr, (quad & 2) ? -si : si};               // times -1 for quadrants 2, 3
-    };
-    // key words of this thread at pair ip: [key 3][row 2L][output 2][limb][f][64 w8 + lane] complex
-    auto key_ptr = [&](uint32_t ip) {
-        return reinterpret_cast<const double2 *>(bsk3_w + (size_t)ip * 3 * 4 * L * LIMBS * WN) + (size_t)mo * LIMBS * (WN / 2) + (w8 * 64 + lane);
-    };
+    // key words of this thread at pair ip: the step's rows [key 3][row 2L]
+    auto step_key = [&](uint32_t ip) { return key_ptr<ROWS, LIMBS>(bsk3_w, ip, mo, w8, lane); };
     double2 kk[KD][LIMBS][2];
-    auto request_row = [&](double2 (&dst)[LIMBS][2], const double2 *kth, const int row) {
-        static_for<0, LIMBS>([&](auto J) {
-            dst[J][0] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2)];
-            dst[J][1] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2) + WN / 4];
-        });
-    };
     auto request_first_rows = [&](const double2 *kth) { static_for<0, KD>([&](auto R) { request_row(kk[R], kth, R); }); };
     uint32_t ip = next_step(0);
-    if (ip < pairs) request_first_rows(key_ptr(ip));
+    if (ip < pairs) request_first_rows(step_key(ip));
     while (ip < pairs) {
         const uint32_t a1 = a_first(ip), a2 = a_second(ip);
         const uint32_t cj[3] = {(a1 + a2) & (2 * WN - 1), a1, a2};
-        const double2 *kth = key_ptr(ip);
+        const double2 *kth = step_key(ip);
         const uint32_t ip_next = next_step(ip + 1);
         auto forward_task = [&](const int T) {
             const int R = T >> 2, h = T & 3, c = R / L, lev = R % L;
-            const double *ac = acc + c * WN + h * WU_RES + lane;
+            const double *ac = acc + c * WN + h * W_RES + lane;
             double x[8];   // re[r] = x[r], im[r] = x[r + 4]
             static_for<0, 8>([&](auto J) {
                 const double dd = mod_ab<AB>(ac[64 * (J & 3) + 256 * (J >> 2)]);   // coefficient 4 (lane + 64 (J & 3)) + h + 1024 (J >> 2)
@@ -176,24 +143,13 @@ __global__ void __launch_bounds__(WU_THREADS)
             static_for<0, ROWS>([&](auto T) {
                 constexpr int key = T / (2 * L), R = T % (2 * L);
                 const double2 lo = tiles[(size_t)(R * 4 + tp) * WQ + mq], hi = tiles[(size_t)(R * 4 + tp + 2) * WQ + mq];
-                // tp = 0: (q0 + q2, q0 - q2);  tp = 1: (q1 + q3, i (q1 - q3));  after the transpose  tp = 0: (a, cc),  tp = 1: (b, d)
-                C u{lo.x + hi.x, lo.y + hi.y};
-                const C dl{lo.x - hi.x, lo.y - hi.y};
-                C w = tp ? C{-dl.i, dl.r} : dl;
-                lanetr::tr_double<5>(u.r, w.r, lane);
-                lanetr::tr_double<5>(u.i, w.i, lane);
-                const C a0 = u + w, a1f = u - w;   // frequencies kappa + 256 tp and kappa + 256 (tp + 2)
-                static_for<0, LIMBS>([&](auto J) {
-                    const double2 k0 = kk[T % KD][J][0], k1 = kk[T % KD][J][1];
-                    y[J][0].r = __builtin_fma(a0.r, k0.x, __builtin_fma(-a0.i, k0.y, y[J][0].r));
-                    y[J][0].i = __builtin_fma(a0.r, k0.y, __builtin_fma(a0.i, k0.x, y[J][0].i));
-                    y[J][1].r = __builtin_fma(a1f.r, k1.x, __builtin_fma(-a1f.i, k1.y, y[J][1].r));
-                    y[J][1].i = __builtin_fma(a1f.r, k1.y, __builtin_fma(a1f.i, k1.x, y[J][1].i));
-                });
+                C a0, a1f;   // the row at frequencies kappa + 256 tp and kappa + 256 (tp + 2)
+                forward_half_butterfly(lo, hi, tp, lane, a0, a1f);
+                static_for<0, LIMBS>([&](auto J) { cmac2(y[J], a0, a1f, kk[T % KD][J]); });
                 if constexpr (T + KD < ROWS) request_row(kk[T % KD], kth, T + KD);
                 if constexpr (R == 2 * L - 1) {   // the key is complete: scale by X^c - 1 at the thread's two frequencies, add
                     const uint32_t cc = cj[key];
-                    const double2 z = zeta_pow((root_e * cc) & (2 * WN - 1));
+                    const double2 z = zeta_pow(ZO, (root_e * cc) & (2 * WN - 1));
                     const double w0r = z.x - 1.0, w0i = z.y;
                     const double w1r = ((cc & 1) ? -z.x : z.x) - 1.0, w1i = (cc & 1) ? -z.y : z.y;
                     static_for<0, LIMBS>([&](auto J) {
@@ -206,28 +162,14 @@ __global__ void __launch_bounds__(WU_THREADS)
                 }
                 pin();   // one row at a time: neither the next rows' tile reads nor their key requests move up (registers)
             });
-            // inverse butterfly: tp = 0: (Y0 + Y2, Y0 - Y2);  tp = 1: (Y1 + Y3, -i (Y1 - Y3));  transpose;  S_tp = u + w, S_{tp+2} = u - w
-            // (branch-free; W_0 = 1 is the first word of the omega_64 table)
-            const double2 wl = reinterpret_cast<const double2 *>(lds)[tp ? fftq::QT_W1 / 2 + mq : ffth::HT_T2 / 2];
-            const double2 wh = reinterpret_cast<const double2 *>(lds)[(tp ? fftq::QT_W3 : fftq::QT_W2) / 2 + mq];
-            static_for<0, LIMBS>([&](auto J) {
-                C u = s[J][0] + s[J][1];
-                const C dl = s[J][0] - s[J][1];
-                C w = tp ? C{dl.i, -dl.r} : dl;
-                lanetr::tr_double<5>(u.r, w.r, lane);
-                lanetr::tr_double<5>(u.i, w.i, lane);
-                s_lo[J] = fftq::cmul<true>(u + w, wl.x, wl.y);
-                s_hi[J] = fftq::cmul<true>(u - w, wh.x, wh.y);
-            });
+            const double2 wl = reinterpret_cast<const double2 *>(lds)[conj_w_lo_index(tp, mq)];
+            const double2 wh = reinterpret_cast<const double2 *>(lds)[conj_w_hi_index(tp, mq)];
+            static_for<0, LIMBS>([&](auto J) { inverse_half_butterfly(s[J][0], s[J][1], tp, lane, wl, wh, s_lo[J], s_hi[J]); });
         }
-        if (ip_next < pairs) request_first_rows(key_ptr(ip_next));   // (uniform) the next step's first rows
+        if (ip_next < pairs) request_first_rows(step_key(ip_next));   // (uniform) the next step's first rows
         pin();
         __syncthreads();   // every thread has read the tiles: the sums may overwrite them
-        static_for<0, LIMBS>([&](auto J) {
-            double2 *sd = SD + (size_t)((J * 2 + mo) * 4) * WQ + mq;
-            sd[tp * WQ] = double2{s_lo[J].r, s_lo[J].i};
-            sd[(tp + 2) * WQ] = double2{s_hi[J].r, s_hi[J].i};
-        });
+        static_for<0, LIMBS>([&](auto J) { store_sums(SD + (size_t)((J * 2 + mo) * 4) * WQ + mq, tp, s_lo[J], s_hi[J]); });
         __syncthreads();
         if (wave >= 8) {   // (wavefronts 0 .. 7 ran two forward tasks where L = 3)
             const int o = (wave >> 2) & 1, h = wave & 3;
@@ -241,16 +183,16 @@ __global__ void __launch_bounds__(WU_THREADS)
                 });
                 fftq::inverse_quarter(v, re[J], im[J], lane, lds);
             });
-            double *ao = acc + o * WN + h * WU_RES + lane;
+            double *ao = acc + o * WN + h * W_RES + lane;
             static_for<0, 4>([&](auto R) {
                 ao[64 * R] += t64::place_limbs<AB, LB, STATS>(re[0][R], re[1][R], dev);              // coefficient 4 (lane + 64 R) + h
                 ao[64 * R + 256] += t64::place_limbs<AB, LB, STATS>(im[0][R], im[1][R], dev);        // ... + 1024
             });
         }
         __syncthreads();
-        if (++since_centred == WU_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
+        if (++since_centred == W_RECENTRE) {   // (uniform: counts the steps actually taken)
             since_centred = 0;
-            static_for<0, 4>([&](auto Q) { acc[tid + WU_THREADS * Q] = mod_ab<AB>(acc[tid + WU_THREADS * Q]); });
+            recentre<AB, 4>(acc, tid);
             __syncthreads();
         }
         ip = ip_next;
@@ -258,11 +200,11 @@ __global__ void __launch_bounds__(WU_THREADS)
     if constexpr (STATS) atomicMax(stat, (unsigned long long)__double_as_longlong(dev));   // non-negative doubles order like their bit patterns
     if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
         u64 *g = out + (size_t)ct * (2 * WN);
-        static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + WU_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W_THREADS * Q); });
         return;
     }
     u64 *o = out + (size_t)ct * (WN + 1);
-    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + WU_THREADS * Q); });
+    static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W_THREADS * Q); });
 }
 
 }  // namespace
@@ -280,7 +222,7 @@ int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, co
     if (count == 0) return 0;
     if (!shape_supported_wide_unrolled(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_wu_t64f<L, 10, 40, STATS, GLWE>>(dim3(count), dim3(WU_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s,
+        return launch_with_lds<k_blind_rotate_wu_t64f<L, 10, 40, STATS, GLWE>>(dim3(count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s,
                                                                                small_cts, lut_ids, luts, bsk3_w, g_tw_q, g_zeta_oct, out, count, n, stat);
     });
 }

@@ -56,57 +56,35 @@
 #include "fft_quarter_f64.hpp"
 #include "pair_sync.hpp"
 #include "t64_common.hpp"
+#include "t64_wide_steps.hpp"
 
 using t64::i64;
 using t64::u64;
 
 namespace {
 
-using fftq::C;
-using fftq::static_for;
-using t64::mod_ab;
+using namespace t64w;   // the N = 2048 family's constants (WN, WQ, W_*) and shared steps: t64_wide_steps.hpp
 using t64::Scheme;
 
 #ifndef BMI_T64WU2_KEY_ROWS_AHEAD
 #define BMI_T64WU2_KEY_ROWS_AHEAD 2   // key rows (of the 6 of a level) a thread holds in registers (3: 32 - 40 B of scratch per lane)
 #endif
-constexpr int WN = 2048, WLOG = 11;
-constexpr int WQ = fftq::QUARTER;
-constexpr int WU2_THREADS = 1024;
-constexpr int WU2_MAX_L = 3;
-constexpr int WU2_RECENTRE = 8;
-constexpr int WU2_RES = WN / 4;                                // accumulator words per residue class mod 4
 constexpr int WU2_TILE_CPLX = 2 * 2 * 4 * WQ;                  // one level's tiles [ciphertext 2][component 2][quarter 4][256]; one limb's sums overlay them
-constexpr int WU2_ZO = WN / 4;                                 // the octant: zeta^x for x in [0, WU2_ZO]
-constexpr int WU2_ZO_WORDS = 2 * (WU2_ZO + 1);
 // LDS (doubles): tables | accumulators [ciphertext 2][component 2][residue 4][512] | tiles | mod-switched LWE words of both | octant
-constexpr int WU2_LDS_WORDS = fftq::QT_WORDS + 2 * 2 * WN + 2 * WU2_TILE_CPLX + 2 * BMI_AT_WORDS + WU2_ZO_WORDS;
+constexpr int WU2_LDS_WORDS = fftq::QT_WORDS + 2 * 2 * WN + 2 * WU2_TILE_CPLX + 2 * BMI_AT_WORDS + W_ZO_WORDS;
 static_assert(WU2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "WU2_LDS_WORDS exceeds the 160 KB of LDS");
-
-constexpr t64::ResidueSlot<WN, 2> acc_slot{};   // accumulator words are kept split by residue mod 4
-
-// an empty statement that reads and writes the sums: they must be in registers here (the branches of the next level's forward task
-// would otherwise let the compiler sink the multiply-adds of all levels below them, their operands waiting in scratch)
-__device__ __forceinline__ void keep(C (&s)[2][2][2]) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int f = 0; f < 2; f++) asm volatile("" : "+v"(s[b][j][f].r), "+v"(s[b][j][f].i));
-}
 
 // STATS (the test hook bmi_fft_margin_host): also records the largest distance of a limb sum from the integer it is rounded to
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, int PREC, bool STATS, bool GLWE>
-__global__ void __launch_bounds__(WU2_THREADS)
+__global__ void __launch_bounds__(W_THREADS)
     k_blind_rotate_wu2_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                             const double *__restrict__ bsk3_w, const double *__restrict__ g_tw, const double *__restrict__ g_zeta_oct,
                             u64 *__restrict__ out, uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     // three keys, each scaled by |X^c - 1| <= 2: the limb sums are six times the plain step's
     static_assert(6.0 * 2.0 * L * WN * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= WU2_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= W_MAX_L && L * BG < AB, "two limbs, at most three levels");
     constexpr int LROWS = 3 * 2;   // key rows of a level: of the step's [key 3][row 2L] in the key copy, in the order (component, key)
     constexpr int KD = BMI_T64WU2_KEY_ROWS_AHEAD < LROWS ? BMI_T64WU2_KEY_ROWS_AHEAD : LROWS;
     extern __shared__ double lds[];
@@ -118,22 +96,21 @@ __global__ void __launch_bounds__(WU2_THREADS)
     double *zo_w = reinterpret_cast<double *>(tiles + WU2_TILE_CPLX) + 2 * BMI_AT_WORDS;
     const double2 *ZO = reinterpret_cast<const double2 *>(zo_w);            // zeta^x, x in [0, 512]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < fftq::QT_WORDS; i += WU2_THREADS) lds[i] = g_tw[i];
-    for (int i = tid; i < WU2_ZO_WORDS; i += WU2_THREADS) zo_w[i] = g_zeta_oct[i];
+    for (int i = tid; i < fftq::QT_WORDS; i += W_THREADS) lds[i] = g_tw[i];
+    for (int i = tid; i < W_ZO_WORDS; i += W_THREADS) zo_w[i] = g_zeta_oct[i];
     // the two ciphertexts of this workgroup (an odd batch: the last workgroup runs its one ciphertext twice and writes it once)
-    const uint32_t ct0 = blockIdx.x * 2;
-    const bool live1 = ct0 + 1 < count;
-    const uint32_t cts[2] = {ct0, live1 ? ct0 + 1 : ct0};
-    for (int b = 0; b < 2; b++) {
+    uint32_t cts[2];
+    const bool live1 = ciphertext_pair(cts, blockIdx.x, count);
+    for (int b = 0; b < 2; b++) {   // (written out, as is the loop below: see bmi_kernels_t64w2.hip)
         const u64 *lwe = small_cts + (size_t)cts[b] * (n + 1);
-        for (uint32_t i = tid; i <= n; i += WU2_THREADS) at[b * AT_STRIDE + i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
+        for (uint32_t i = tid; i <= n; i += W_THREADS) at[b * AT_STRIDE + i] = (uint16_t)t64::modswitch<WLOG + 1>(lwe[i]);
     }
     __syncthreads();
     for (int b = 0; b < 2; b++) {
         const u64 *tv = luts + (size_t)(lut_ids[cts[b]] & (BMI_LUT_CAP - 1)) * WN;
         const uint32_t bt = at[b * AT_STRIDE + n];
         double *acc = accs + b * 2 * WN;
-        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + WU2_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::load_test_poly<WN, PRE>(acc, acc_slot, tv, bt, tid + W_THREADS * Q); });
     }
     __syncthreads();
     // phase B: output polynomial, slot, and which half of the radix-4 butterfly this lane starts from
@@ -153,26 +130,12 @@ __global__ void __launch_bounds__(WU2_THREADS)
         while (ip < pairs && (a_first(0, ip) | a_second(0, ip) | a_first(1, ip) | a_second(1, ip)) == 0) ip++;
         return ip;
     };
-    // zeta^x, x in [0, 4096), from the octant: r = x mod 1024 folded at 512 (swap), the quadrant a multiplication by i^q
-    auto zeta_pow = [&](uint32_t x) {
-        const uint32_t r = x & 1023, fold = r > (uint32_t)WU2_ZO;
-        const double2 w = ZO[fold ? 1024 - r : r];
-        const double cr = fold ? w.y : w.x, ci = fold ? w.x : w.y;
-        const uint32_t quad = (x >> 10) & 3;
-        const double sr = (quad & 1) ? -ci : cr, si = (quad & 1) ? cr : ci;         // times i for odd quadrants
-        return double2{(quad & 2) ? -sr : sr, (quad & 2) ? -si : si};               // times -1 for quadrants 2, 3
-    };
     // key words of this thread at pair ip: [key 3][row 2L][output 2][limb][f][64 w8 + lane] complex
+    // (t64w::key_ptr called here: one vector instruction fewer)
     auto key_ptr = [&](uint32_t ip) {
         return reinterpret_cast<const double2 *>(bsk3_w + (size_t)ip * 3 * 4 * L * LIMBS * WN) + (size_t)mo * LIMBS * (WN / 2) + (w8 * 64 + lane);
     };
     double2 kk[KD][LIMBS][2];
-    auto request_row = [&](double2 (&dst)[LIMBS][2], const double2 *kth, const int row) {
-        static_for<0, LIMBS>([&](auto J) {
-            dst[J][0] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2)];
-            dst[J][1] = kth[((size_t)row * 2 * LIMBS + J) * (WN / 2) + WN / 4];
-        });
-    };
     // the T-th row a level uses, T = component * 3 + key, in the key copy's order [key][component][level]
     auto row_of = [](const int lev, const int T) constexpr { return (T % 3) * 2 * L + (T / 3) * L + lev; };
     uint32_t ip = next_step(0);
@@ -193,7 +156,7 @@ __global__ void __launch_bounds__(WU2_THREADS)
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = LEV;
             {   // phase A
-                const double *ac = accs + wb * 2 * WN + wc * WN + wh * WU2_RES + lane;
+                const double *ac = accs + wb * 2 * WN + wc * WN + wh * W_RES + lane;
                 double x[8];   // re[r] = x[r], im[r] = x[r + 4]
                 static_for<0, 8>([&](auto J) {
                     const double dd = mod_ab<AB>(ac[64 * (J & 3) + 256 * (J >> 2)]);   // coefficient 4 (lane + 64 (J & 3)) + h + 1024 (J >> 2)
@@ -213,7 +176,7 @@ __global__ void __launch_bounds__(WU2_THREADS)
                 C a[2][2];   // [ciphertext][frequency kappa + 256 tp, kappa + 256 (tp + 2)]
                 static_for<0, 2>([&](auto B) {
                     const double2 lo = tiles[(size_t)((B * 2 + CC) * 4 + tp) * WQ + mq], hi = tiles[(size_t)((B * 2 + CC) * 4 + tp + 2) * WQ + mq];
-                    // tp = 0: (q0 + q2, q0 - q2);  tp = 1: (q1 + q3, i (q1 - q3));  after the transpose  tp = 0: (a, cc),  tp = 1: (b, d)
+                    // t64w::forward_half_butterfly written out (through the helper the selects come in another order: 7 - 11 s_nop fewer)
                     C u{lo.x + hi.x, lo.y + hi.y};
                     const C dl{lo.x - hi.x, lo.y - hi.y};
                     C w = tp ? C{-dl.i, dl.r} : dl;
@@ -226,19 +189,13 @@ __global__ void __launch_bounds__(WU2_THREADS)
                     constexpr int T = CC * 3 + KEY;
                     static_for<0, 2>([&](auto B) {
                         // X^c - 1 at the thread's two frequencies (the second root is the first times (-1)^c), applied to the digits
-                        const double2 z = zeta_pow(fx[B][KEY]);
+                        const double2 z = zeta_pow(ZO, fx[B][KEY]);
                         const bool neg = fx[B][KEY] & 1;
                         const double w0r = z.x - 1.0, w0i = z.y;
                         const double w1r = (neg ? -z.x : z.x) - 1.0, w1i = neg ? -z.y : z.y;
                         const C p0{__builtin_fma(a[B][0].r, w0r, -(a[B][0].i * w0i)), __builtin_fma(a[B][0].r, w0i, a[B][0].i * w0r)};
                         const C p1{__builtin_fma(a[B][1].r, w1r, -(a[B][1].i * w1i)), __builtin_fma(a[B][1].r, w1i, a[B][1].i * w1r)};
-                        static_for<0, LIMBS>([&](auto J) {
-                            const double2 k0 = kk[T % KD][J][0], k1 = kk[T % KD][J][1];
-                            s[B][J][0].r = __builtin_fma(p0.r, k0.x, __builtin_fma(-p0.i, k0.y, s[B][J][0].r));
-                            s[B][J][0].i = __builtin_fma(p0.r, k0.y, __builtin_fma(p0.i, k0.x, s[B][J][0].i));
-                            s[B][J][1].r = __builtin_fma(p1.r, k1.x, __builtin_fma(-p1.i, k1.y, s[B][J][1].r));
-                            s[B][J][1].i = __builtin_fma(p1.r, k1.y, __builtin_fma(p1.i, k1.x, s[B][J][1].i));
-                        });
+                        static_for<0, LIMBS>([&](auto J) { cmac2(s[B][J], p0, p1, kk[T % KD][J]); });
                     });
                     if constexpr (T + KD < LROWS) request_row(kk[T % KD], kth, row_of(lev, T + KD));
                     keep(s);
@@ -247,29 +204,15 @@ __global__ void __launch_bounds__(WU2_THREADS)
             });
             __syncthreads();   // every thread has read this level's tiles: the next level (or the sums) may overwrite them
         });
-        // inverse butterfly: tp = 0: (Y0 + Y2, Y0 - Y2);  tp = 1: (Y1 + Y3, -i (Y1 - Y3));  transpose;  S_tp = u + w, S_{tp+2} = u - w,
-        // times conj W_h (branch-free; W_0 = 1 is the first word of the omega_64 table); s[b][j] = (S_tp, S_{tp+2}) afterwards
-        {
-            const double2 wl = reinterpret_cast<const double2 *>(lds)[tp ? fftq::QT_W1 / 2 + mq : ffth::HT_T2 / 2];
-            const double2 wh2 = reinterpret_cast<const double2 *>(lds)[(tp ? fftq::QT_W3 : fftq::QT_W2) / 2 + mq];
+        {   // inverse butterfly times conj W_h: s[b][j] = (S_tp, S_{tp+2}) afterwards
+            const double2 wl = reinterpret_cast<const double2 *>(lds)[conj_w_lo_index(tp, mq)];
+            const double2 wh2 = reinterpret_cast<const double2 *>(lds)[conj_w_hi_index(tp, mq)];
             static_for<0, 2>([&](auto B) {
-                static_for<0, LIMBS>([&](auto J) {
-                    C u = s[B][J][0] + s[B][J][1];
-                    const C dl = s[B][J][0] - s[B][J][1];
-                    C w = tp ? C{dl.i, -dl.r} : dl;
-                    lanetr::tr_double<5>(u.r, w.r, lane);
-                    lanetr::tr_double<5>(u.i, w.i, lane);
-                    s[B][J][0] = fftq::cmul<true>(u + w, wl.x, wl.y);
-                    s[B][J][1] = fftq::cmul<true>(u - w, wh2.x, wh2.y);
-                });
+                static_for<0, LIMBS>([&](auto J) { inverse_half_butterfly(s[B][J][0], s[B][J][1], tp, lane, wl, wh2, s[B][J][0], s[B][J][1]); });
             });
         }
         static_for<0, LIMBS>([&](auto J) {
-            static_for<0, 2>([&](auto B) {
-                double2 *sd = SD + (size_t)((B * 2 + mo) * 4) * WQ + mq;
-                sd[tp * WQ] = double2{s[B][J][0].r, s[B][J][0].i};
-                sd[(tp + 2) * WQ] = double2{s[B][J][1].r, s[B][J][1].i};
-            });
+            static_for<0, 2>([&](auto B) { store_sums(SD + (size_t)((B * 2 + mo) * 4) * WQ + mq, tp, s[B][J][0], s[B][J][1]); });
             __syncthreads();
             {
                 const double2 *sd = SD + (size_t)wave * WQ;     // wave = (ciphertext, output, quarter)
@@ -278,20 +221,13 @@ __global__ void __launch_bounds__(WU2_THREADS)
                     const double2 t = sd[R * 64 + lane];
                     v[R] = C{t.x, t.y};
                 });
-                double re[4], im[4];
-                fftq::inverse_quarter(v, re, im, lane, lds);
-                double *ao = accs + wb * 2 * WN + wc * WN + wh * WU2_RES + lane;
-                constexpr int j = J;
-                static_for<0, 4>([&](auto R) {
-                    ao[64 * R] += t64::place_limb<AB, LB, STATS>(re[R], j, dev);              // coefficient 4 (lane + 64 R) + h
-                    ao[64 * R + 256] += t64::place_limb<AB, LB, STATS>(im[R], j, dev);        // ... + 1024
-                });
+                inverse_task_limb<AB, LB, STATS>(accs + wb * 2 * WN + wc * WN, wh, v, J, lane, lds, dev);
             }
             __syncthreads();
         });
-        if (++since_centred == WU2_RECENTRE) {   // (uniform: counts the steps the workgroup takes) keep the accumulators' magnitude below 2^51
+        if (++since_centred == W_RECENTRE) {   // (uniform: counts the steps the workgroup takes)
             since_centred = 0;
-            static_for<0, 8>([&](auto Q) { accs[tid + WU2_THREADS * Q] = mod_ab<AB>(accs[tid + WU2_THREADS * Q]); });
+            recentre<AB, 8>(accs, tid);
             __syncthreads();
         }
         ip = ip_next;
@@ -301,11 +237,11 @@ __global__ void __launch_bounds__(WU2_THREADS)
         const double *acc = accs + b * 2 * WN;
         if constexpr (GLWE) {   // the accumulator itself, out = [count][2N]
             u64 *g = out + (size_t)cts[b] * (2 * WN);
-            static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + WU2_THREADS * Q); });
+            static_for<0, 2>([&](auto Q) { t64::store_glwe<WN, PRE, AB>(g, acc, acc_slot, tid + W_THREADS * Q); });
             continue;
         }
         u64 *o = out + (size_t)cts[b] * (WN + 1);
-        static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + WU2_THREADS * Q); });
+        static_for<0, 2>([&](auto Q) { t64::extract_sample<WN, PRE, AB>(o, acc, acc_slot, tid + W_THREADS * Q); });
     }
 }
 
@@ -319,7 +255,7 @@ int launch_blind_rotate_wide_u2(const u64 *small_cts, const uint32_t *lut_ids, c
     if (count == 0) return 0;
     if (!shape_supported_wide_unrolled(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_wu2_t64f<L, 10, 40, STATS, GLWE>>(dim3((count + 1) / 2), dim3(WU2_THREADS), (size_t)WU2_LDS_WORDS * sizeof(double),
+        return launch_with_lds<k_blind_rotate_wu2_t64f<L, 10, 40, STATS, GLWE>>(dim3((count + 1) / 2), dim3(W_THREADS), (size_t)WU2_LDS_WORDS * sizeof(double),
                                                                                 s, small_cts, lut_ids, luts, bsk3_w, g_tw_q, g_zeta_oct, out, count, n, stat);
     });
 }

@@ -1,7 +1,7 @@
 // 2 x 2 transposes between a pair of registers and one lane bit of a wavefront, without LDS: v_permlane32_swap / v_permlane16_swap
 // for lane bits 5 and 4 (one instruction per 32-bit register pair), bank-masked DPP row shifts for bits 3 and 2, v_cndmask_b32_dpp
 // for bits 1 and 0.  Used by the half transforms of the torus latency kernel (fft_half_f64.hpp)
-// and the N = 2048 torus kernel (bmi_kernels_t64w.hip).
+// and the N = 2048 torus kernels (the half butterflies of t64_wide_steps.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,7 +2,9 @@
 // (bmi_host.cpp): the limb schemes of the bootstrap key and, for the kernels (__HIPCC__ part), the steps every blind rotation
 // states the same way - the word <-> exact-double conversions, the centred residue mod 2^AB, the oracle's rounding and digit
 // rule, the placement of a limb's integer, and the prologue (mod-switch, test polynomial) and epilogue (sample extraction).
-// All of them are force-inlined templates on the compile-time constants of the calling kernel.
+// All of them are force-inlined templates on the compile-time constants of the calling kernel.  What the four N = 2048 kernels
+// (_t64w, _t64w2, _t64wu, _t64wu2) share beyond that, at the level of a transform - constants and accumulator layout, half
+// butterflies, multiply-accumulate, key rows, powers of zeta, inverse task, `keep` - is in t64_wide_steps.hpp, built on this file.
 //
 // No transform exists mod 2^64, so a torus external product is computed EXACTLY over the integers: the digit polynomials
 // (|d| <= 2^(Bg-1)) are transformed mod p = 2^49 - 720895 and multiplied with LIMBS balanced limb polynomials of every

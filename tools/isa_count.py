@@ -7,7 +7,7 @@ instructions are split by issue cost on a SIMD-32 (MI355X_MICROARCH.md: a wave64
     int64    v_mad_u64_u32 / v_mad_i64_i32, v_lshl*_b64, v_lshr*_b64, v_ashr*_i64, v_mul_hi_*, v_mul_lo_u32 (quarter-rate multiplies count here)
     other    every other v_* instruction (32-bit ALU, moves, compares, cndmask ...)
 usage: isa_count.py listing.s kernel_substring [kernel_substring ...]     -> one JSON object per kernel on stdout
-       isa_count.py --build <out.json>      compiles the four blind-rotation TUs and writes the counts of the shipped kernels"""
+       isa_count.py --build <out.json>      compiles the blind-rotation TUs and writes the counts of the shipped kernels"""
 import json, os, re, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,16 +74,18 @@ def count(body):
 def demangle(names):
     try:
         out = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
-        return [re.sub(r"^void \(anonymous namespace\)::", "", o).split("(")[0] for o in out[:len(names)]]
+        return [re.sub(r"^void ", "", o.replace("(anonymous namespace)::", "")).split("(")[0] for o in out[:len(names)]]
     except Exception:
         return names
 
 
 def build(out_path):
     srcs = {"bmi_kernels_f64.hip": True, "bmi_kernels_t64.hip": True, "bmi_kernels_t64f.hip": True, "bmi_kernels_t64fu.hip": True,
-            "bmi_kernels_t64w.hip": True, "bmi_kernels_t64w2.hip": True, "bmi_kernels_t64q.hip": True, "bmi_kernels_f64u.hip": False, "bmi_kernels_t64u.hip": False}   # True: max-ilp scheduler (csrc/Makefile)
+            "bmi_kernels_t64w.hip": True, "bmi_kernels_t64w2.hip": True, "bmi_kernels_t64wu.hip": True, "bmi_kernels_t64wu2.hip": True,
+            "bmi_kernels_t64q.hip": True, "bmi_kernels_f64u.hip": False, "bmi_kernels_t64u.hip": False}   # True: max-ilp scheduler (csrc/Makefile)
     want = ("k_blind_rotate_tpx49", "k_blind_rotate_t64", "k_blind_rotate_lat2_49", "k_blind_rotate_lat2u_49", "k_blind_rotate_lat_t64",
-            "k_blind_rotate_lat2u_t64", "k_blind_rotate_w_t64f", "k_blind_rotate_w2_t64f", "k_blind_rotate_q_t64f")   # (substring match: the t64f / t64fu kernels are picked up by the t64 entries)
+            "k_blind_rotate_lat2u_t64", "k_blind_rotate_w_t64f", "k_blind_rotate_w2_t64f", "k_blind_rotate_wu_t64f", "k_blind_rotate_wu2_t64f",
+            "k_blind_rotate_q_t64f")   # (substring match: the t64f / t64fu kernels are picked up by the t64 entries)
     res = {}
     with tempfile.TemporaryDirectory() as td:
         for src, ilp in srcs.items():
