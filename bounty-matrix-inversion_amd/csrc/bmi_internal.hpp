@@ -74,7 +74,8 @@ inline int launch_with_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t 
 
 // The runtime (levels, statistics wanted) of the floating-point-transform families -> their instantiations: calls
 // f(L, STATS) with L = std::integral_constant<int, 3 or 2> (the callers have checked the shape) and STATS = std::true_type
-// or std::false_type, usable as template arguments.  The kernels without a STATS form take with_levels alone.
+// or std::false_type, usable as template arguments.  The kernels without a STATS form take with_levels alone, or
+// with_levels_glwe: f(L, GLWE), GLWE the epilogue flag described below.
 template <typename F>
 inline int with_levels(uint32_t levels, F f) {
     if (levels == 3) return f(std::integral_constant<int, 3>{});
@@ -84,13 +85,18 @@ template <typename F>
 inline int with_levels_stats(uint32_t levels, bool stats, F f) {
     return with_levels(levels, [&](auto L) { return stats ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
+template <typename F>
+inline int with_levels_glwe(uint32_t levels, bool glwe, F f) {
+    return with_levels(levels, [&](auto L) { return glwe ? f(L, std::true_type{}) : f(L, std::false_type{}); });
+}
 
 // ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,wu,wu2,w2,q}.hip), whose trailing template flag GLWE makes
 // them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
 // out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator
-// form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.  (The four N = 2048
-// kernels share their steps through t64_wide_steps.hpp but each keeps this epilogue written out: behind a helper it renumbers the
-// step loop's registers, profiles/wide_steps_ab.txt.)
+// form is instantiated without statistics only: asked for both, the launcher returns hipErrorInvalidValue.  (Two families share
+// their steps through a header - the four N = 2048 kernels through t64_wide_steps.hpp, the three N = 1024 half-transform kernels
+// of bmi_kernels_t64{f,fu}.hip through t64_half_steps.hpp - but each kernel keeps this epilogue written out: behind a helper it
+// renumbers the step loop's registers of the N = 2048 kernels, profiles/wide_steps_ab.txt; at N = 1024 a helper was not tried.)
 template <typename F>
 inline int with_levels_stats_glwe(uint32_t levels, bool stats, bool glwe, F f) {
     if (!glwe) return with_levels_stats(levels, stats, [&](auto L, auto STATS) { return f(L, STATS, std::false_type{}); });

@@ -77,6 +77,7 @@
 #include "pair_sync.hpp"
 #include "phase_prof.hpp"
 #include "t64_common.hpp"
+#include "t64_half_steps.hpp"
 
 using t64::i64;
 using t64::u64;
@@ -338,22 +339,16 @@ __global__ void __launch_bounds__(128 * TF_CTS)
 //   C  wavefronts 0 .. 7 = (limb, o, parity): inverse half, nearest integer, shift into place and ONE LDS atomic add (f64) per
 //      coefficient into the accumulator (the two limbs of a coefficient meet there)
 // The accumulator is the exact integer word / 2^16 in a double, as in the wave-pair kernel, but only re-centred mod 2^48 every
-// LF_RECENTRE steps (the atomic adds cannot reduce): 2^47 + 8 (2^45 + 2^47) < 2^51 keeps every sum exact.
-constexpr int LF_THREADS = 1024;
-constexpr int LF_MAX_L = 3;
-constexpr int LF_HALF = N / 2;
-constexpr int LF_RECENTRE = 8;
-constexpr int LF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * LF_MAX_L * N + 2 * 2 * N + BMI_AT_WORDS;
+// H_RECENTRE steps (the atomic adds cannot reduce): 2^47 + 8 (2^45 + 2^47) < 2^51 keeps every sum exact.
+using namespace t64h;   // the family's constants (H_*), acc_slot and shared steps: t64_half_steps.hpp
+constexpr int LF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * H_MAX_L * N + 2 * 2 * N + BMI_AT_WORDS;
 static_assert(LF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "LF_LDS_WORDS exceeds the 160 KB of LDS");
-
-// accumulator words are kept split by parity (a lane's four points are 128 coefficients apart and of one parity)
-constexpr t64::ResidueSlot<N, 1> acc_slot{};
 
 // standard-domain GGSW polynomials -> per (polynomial, limb) 256 slots of [F_k, F_{k+256}] (k = ffth::slot_freq of the slot)
 __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__ std_polys, double *__restrict__ lat_polys,
                                                          const double *__restrict__ g_tw_h, uint32_t n_polys, int prec) {
     const int limbs = t64::limbs_of(prec);
-    __shared__ double lds[ffth::HT_WORDS + 4 * LF_HALF];
+    __shared__ double lds[ffth::HT_WORDS + 4 * H_HALF];
     for (int i = threadIdx.x; i < ffth::HT_WORDS; i += blockDim.x) lds[i] = g_tw_h[i];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -362,7 +357,7 @@ __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__
     const bool ok = item < n_polys * (uint32_t)limbs;
     const uint32_t poly = ok ? item / limbs : 0;
     const int j = ok ? (int)(item % limbs) : 0;
-    double2 *tile = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + wave * LF_HALF);   // 256 complex per wavefront
+    double2 *tile = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + wave * H_HALF);   // 256 complex per wavefront
     if (ok) {
         double re[4], im[4];
         static_for<0, 4>([&](auto R) {
@@ -371,13 +366,12 @@ __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__
             im[R] = (double)t64::limb_of((i64)std_polys[(size_t)poly * N + m + 512], j, prec);
         });
         ffth::C v[4];
-        if (h) ffth::forward_half<1>(re, im, v, lane, lds);
-        else ffth::forward_half<0>(re, im, v, lane, lds);
-        static_for<0, 4>([&](auto R) { tile[R * 64 + lane] = double2{v[R].r, v[R].i}; });
+        forward_half_of(h, re, im, v, lane, lds);
+        static_for<0, 4>([&](auto R) { tile[R * 64 + lane] = double2{v[R].r, v[R].i}; });   // (in the helper too: two s_nop fewer, not identical)
     }
     __syncthreads();
     if (ok) {
-        const double2 *te = reinterpret_cast<const double2 *>(lds + ffth::HT_WORDS + (wave & ~1) * LF_HALF), *to = te + LF_HALF / 2;
+        const double2 *te = reinterpret_cast<const double2 *>(lds + ffth::HT_WORDS + (wave & ~1) * H_HALF), *to = te + H_HALF / 2;
         double2 *o = reinterpret_cast<double2 *>(lat_polys + (size_t)item * N);
         static_for<0, 2>([&](auto Q2) {
             const int q = (h * 2 + Q2) * 64 + lane;
@@ -392,25 +386,25 @@ __global__ void __launch_bounds__(256) k_bsk_to_latf_t64(const u64 *__restrict__
 // integer it is rounded to
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, bool STATS, bool GLWE>
-__global__ void __launch_bounds__(LF_THREADS)
+__global__ void __launch_bounds__(H_THREADS)
     k_blind_rotate_lat_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                             const double *__restrict__ bsk_latf, const double *__restrict__ g_tw_h, u64 *__restrict__ out,
                             uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<48>::LIMBS, LB = Scheme<48>::BITS, PRE = Scheme<48>::PRE, AB = 64 - PRE;
     static_assert(2.0 * L * N * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= LF_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= H_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *acc = lds + ffth::HT_WORDS;                                     // [2 components][2 parities][512]: word / 2^16, exact, |.| < 2^51
     double2 *tiles = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + 2 * N);   // [2L rows][2 halves][256 slots] complex
-    double2 *SD = tiles + LF_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
+    double2 *SD = tiles + H_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
     uint16_t *at = reinterpret_cast<uint16_t *>(SD + 2 * N);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < ffth::HT_WORDS; i += LF_THREADS) lds[i] = g_tw_h[i];
+    for (int i = tid; i < ffth::HT_WORDS; i += H_THREADS) lds[i] = g_tw_h[i];
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, LF_THREADS);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, H_THREADS);
     __syncthreads();
-    {
+    {   // (written out in this family: a helper is identical here only, profiles/half_steps_ab.txt)
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
         t64::load_test_poly<N, PRE>(acc, acc_slot, tv, bt, tid);
@@ -439,11 +433,11 @@ __global__ void __launch_bounds__(LF_THREADS)
             // coefficient m_J = 2 (lane + 64 (J & 3)) + h + 512 (J >> 2); its rotated source e_J = m_J - a_t mod 2N: half of it is
             // t0 + 64 (J & 3) + 256 (J >> 2) - the low 9 bits are the slot inside the parity block, bit 9 is the sign
             const uint32_t e0 = (2 * lane + h + 2 * N - a_t) & (2 * N - 1);
-            const uint32_t t0 = e0 >> 1, pbase = (e0 & 1) * LF_HALF;
+            const uint32_t t0 = e0 >> 1, pbase = (e0 & 1) * H_HALF;
             static_for<0, 8>([&](auto J) {
                 const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
-                vr[J] = ac[pbase + (t & (LF_HALF - 1))];
-                vs[J] = ac[h * LF_HALF + lane + 64 * (J & 3) + 256 * (J >> 2)];
+                vr[J] = ac[pbase + (t & (H_HALF - 1))];
+                vs[J] = ac[h * H_HALF + lane + 64 * (J & 3) + 256 * (J >> 2)];
             });
             static_for<0, 8>([&](auto J) {
                 const uint32_t t = t0 + 64 * (J & 3) + 256 * (J >> 2);
@@ -452,53 +446,41 @@ __global__ void __launch_bounds__(LF_THREADS)
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
-            if (h) ffth::forward_half<1>(re, im, v, lane, lds);
-            else ffth::forward_half<0>(re, im, v, lane, lds);
-            double2 *tile = tiles + (size_t)(wave >> 1) * LF_HALF + h * (LF_HALF / 2);
+            forward_half_of(h, re, im, v, lane, lds);
+            double2 *tile = tiles + (size_t)(wave >> 1) * H_HALF + h * (H_HALF / 2);   // (the store stays here: in the helper it renumbers registers)
             static_for<0, 4>([&](auto R) { tile[R * 64 + lane] = double2{v[R].r, v[R].i}; });
         }
         __syncthreads();
         {
             ffth::C ylo{0.0, 0.0}, yhi{0.0, 0.0};
             static_for<0, 2 * L>([&](auto R) {
-                const double2 e = tiles[(size_t)R * LF_HALF + mq], od = tiles[(size_t)R * LF_HALF + LF_HALF / 2 + mq];
-                const double lr = e.x + od.x, li = e.y + od.y, hr = e.x - od.x, hi = e.y - od.y;
-                ylo.r = __builtin_fma(lr, klo[R].x, __builtin_fma(-li, klo[R].y, ylo.r));
-                ylo.i = __builtin_fma(lr, klo[R].y, __builtin_fma(li, klo[R].x, ylo.i));
-                yhi.r = __builtin_fma(hr, khi[R].x, __builtin_fma(-hi, khi[R].y, yhi.r));
-                yhi.i = __builtin_fma(hr, khi[R].y, __builtin_fma(hi, khi[R].x, yhi.i));
+                const double2 e = tiles[(size_t)R * H_HALF + mq], od = tiles[(size_t)R * H_HALF + H_HALF / 2 + mq];
+                mac_pair(ylo, yhi, e, od, klo[R], khi[R]);
             });
             const double2 w = reinterpret_cast<const double2 *>(lds + ffth::HT_W)[mq];
-            const ffth::C d = ffth::cmul<true>(ffth::C{ylo.r - yhi.r, ylo.i - yhi.i}, w.x, w.y);
-            double2 *sd = SD + (size_t)(mj * 2 + mo) * LF_HALF;
-            sd[mq] = double2{ylo.r + yhi.r, ylo.i + yhi.i};
-            sd[LF_HALF / 2 + mq] = double2{d.r, d.i};
+            sum_diff_store(SD + (size_t)(mj * 2 + mo) * H_HALF, mq, ylo, yhi, w);
         }
         __syncthreads();
         // phase C: eight tasks (limb, output, parity) meeting by LDS f64 atomics; four tasks running both limbs' inverse halves
         // with plain read-modify-writes measured 3.80 / 4.01 ms for 1 / 256 against 3.60 / 3.95 (four wavefronts leave the SIMDs idle)
         if (wave < 4 * LIMBS) {
             const int j = wave >> 2, o = (wave >> 1) & 1, h = wave & 1;
-            const double2 *sd = SD + (size_t)(j * 2 + o) * LF_HALF + h * (LF_HALF / 2);
+            const double2 *sd = SD + (size_t)(j * 2 + o) * H_HALF + h * (H_HALF / 2);
             ffth::C v[4];
-            static_for<0, 4>([&](auto R) {
-                const double2 t = sd[R * 64 + lane];
-                v[R] = ffth::C{t.x, t.y};
-            });
-            double re[4], im[4];
+            read_sums(v, sd, lane);
+            double re[4], im[4];   // (from here written out: a helper gives the same counts in another order and, timed, missed the rule at one bootstrap - profiles/half_steps_ab.txt)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
-            double *ao = acc + o * N + h * LF_HALF + lane;
+            double *ao = acc + o * N + h * H_HALF + lane;
             static_for<0, 4>([&](auto R) {
                 atomicAdd(ao + 64 * R, t64::place_limb<AB, LB, STATS>(re[R], j, dev));          // coefficient 2 (lane + 64 R) + h
                 atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB, STATS>(im[R], j, dev));    // ... + 512
             });
         }
         __syncthreads();
-        if (++since_centred == LF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
+        if (++since_centred == H_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            acc[tid] = mod_ab<AB>(acc[tid]);
-            acc[N + tid] = mod_ab<AB>(acc[N + tid]);
+            recentre<AB, 2>(acc, tid);
             __syncthreads();
         }
     }
@@ -540,7 +522,7 @@ int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, c
     if (count == 0) return 0;
     if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS, GLWE>>(dim3(count), dim3(LF_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
+        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS, GLWE>>(dim3(count), dim3(H_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
                                                                              small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
     });
 }

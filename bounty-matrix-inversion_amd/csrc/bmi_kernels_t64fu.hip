@@ -31,56 +31,49 @@
 #include "fft_half_f64.hpp"
 #include "pair_sync.hpp"
 #include "t64_common.hpp"
+#include "t64_half_steps.hpp"
 
 using t64::i64;
 using t64::u64;
 
 namespace {
 
-using fftw::static_for;
-using t64::mod_ab;
+using namespace t64h;   // the family's constants (HN, H_*), acc_slot and shared steps: t64_half_steps.hpp
 using t64::Scheme;
 
-constexpr int N = ffth::N;
-constexpr int LOG_N = 10;
-constexpr int UF_THREADS = 1024;
-constexpr int UF_MAX_L = 3;
-constexpr int UF_HALF = N / 2;
-constexpr int UF_RECENTRE = 8;
+constexpr int N = HN, LOG_N = HLOG;
 constexpr int UF_ZP_WORDS = 2 * N;   // zeta^x for x in [0, 1024) as (re, im); zeta^(x + 1024) = -zeta^x
 // tables | accumulator | tiles [2L rows][2 halves][256] complex | sums / differences [limb][output][S, D][256] complex | LWE words | zeta powers
-constexpr int UF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * UF_MAX_L * N + 2 * 2 * N + BMI_AT_WORDS + UF_ZP_WORDS;
+constexpr int UF_LDS_WORDS = ffth::HT_WORDS + 2 * N + 2 * H_MAX_L * N + 2 * 2 * N + BMI_AT_WORDS + UF_ZP_WORDS;
 static_assert(UF_LDS_WORDS <= BMI_LDS_WORDS_MAX, "UF_LDS_WORDS exceeds the 160 KB of LDS");
-
-constexpr t64::ResidueSlot<N, 1> acc_slot{};   // accumulator words are kept split by parity
 
 // GLWE: the kernel returns the accumulator itself, out = [count][2N], instead of the extracted sample, out = [count][N + 1]
 template <int L, int BG, int PREC, bool STATS, bool GLWE>
-__global__ void __launch_bounds__(UF_THREADS)
+__global__ void __launch_bounds__(H_THREADS)
     k_blind_rotate_lat2u_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                               const double *__restrict__ bsk3_latf, const double *__restrict__ g_tw_h, const double *__restrict__ g_zeta_pow,
                               u64 *__restrict__ out, uint32_t count, uint32_t n, unsigned long long *__restrict__ stat) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     // three keys, each scaled by |X^c - 1| <= 2: the limb sums are six times the plain step's
     static_assert(6.0 * 2.0 * L * N * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= UF_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    static_assert(LIMBS == 2 && L <= H_MAX_L && L * BG < AB, "two limbs, at most three levels");
     extern __shared__ double lds[];
     double *acc = lds + ffth::HT_WORDS;                                     // [2 components][2 parities][512]: word / 2^PRE, exact, |.| < 2^51
     double2 *tiles = reinterpret_cast<double2 *>(lds + ffth::HT_WORDS + 2 * N);   // [2L rows][2 halves][256 slots] complex
-    double2 *SD = tiles + UF_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
+    double2 *SD = tiles + H_MAX_L * N;                                     // [limb][output][S, D][256 slots] complex
     uint16_t *at = reinterpret_cast<uint16_t *>(SD + 2 * N);
     const double2 *ZP = reinterpret_cast<const double2 *>(reinterpret_cast<double *>(SD + 2 * N) + BMI_AT_WORDS);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < ffth::HT_WORDS; i += UF_THREADS) lds[i] = g_tw_h[i];
+    for (int i = tid; i < ffth::HT_WORDS; i += H_THREADS) lds[i] = g_tw_h[i];
     {
         double *zp = reinterpret_cast<double *>(SD + 2 * N) + BMI_AT_WORDS;
-        for (int i = tid; i < UF_ZP_WORDS; i += UF_THREADS) zp[i] = g_zeta_pow[i];
+        for (int i = tid; i < UF_ZP_WORDS; i += H_THREADS) zp[i] = g_zeta_pow[i];
     }
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
-    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, UF_THREADS);
+    t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, H_THREADS);
     __syncthreads();
-    {
+    {   // (written out in this family: behind a helper the accumulator form takes 5 more instructions in front of the loop, l = 3 a register)
         const u64 *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
         t64::load_test_poly<N, PRE>(acc, acc_slot, tv, bt, tid);
@@ -94,38 +87,26 @@ __global__ void __launch_bounds__(UF_THREADS)
     double dev = 0.0;             // STATS: largest |value - nearest integer| this lane has rounded away
     constexpr int CH = L;         // rows per chunk of key words (half a key): 2 CH double2 per chunk, two chunks in flight
     constexpr int NCH = 3 * 2;    // chunks per step
-    // this thread's key words: [pair][key 3][row 2L][output 2][limb][256 slots][F_k, F_{k+256}]
-    auto chunk_ptr = [&](uint32_t ip, int t) {   // chunk t = (key t / 2, rows (t & 1) CH .. + CH)
-        const int key = t >> 1, r0 = (t & 1) * CH;
-        return reinterpret_cast<const double2 *>(bsk3_latf + (((size_t)ip * 3 + key) * 2 * L + r0) * 2 * LIMBS * N) +
-               ((size_t)mo * LIMBS + mj) * (N / 2) + 2 * mq;
-    };
+    auto chunk = [&](uint32_t ip, int t) { return chunk_ptr<L, LIMBS>(bsk3_latf, ip, t, mo, mj, mq); };
     double2 kb[2][CH][2];
-    auto request = [&](double2 (&dst)[CH][2], const double2 *p) {
-        static_for<0, CH>([&](auto R) {
-            dst[R][0] = p[(size_t)R * 2 * LIMBS * (N / 2)];
-            dst[R][1] = p[(size_t)R * 2 * LIMBS * (N / 2) + 1];
-        });
-    };
 
     for (uint32_t ip = 0; ip < pairs; ip++) {
-        const uint32_t a1 = at[2 * ip], a2 = (2 * ip + 1 < n) ? at[2 * ip + 1] : 0u;
-        if ((a1 | a2) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes
-        const uint32_t cj[3] = {(a1 + a2) & (2 * N - 1), a1, a2};
-        request(kb[0], chunk_ptr(ip, 0));
+        uint32_t cj[3];
+        pair_exponents(cj, at, ip, n);
+        if ((cj[1] | cj[2]) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes
+        request<CH, LIMBS>(kb[0], chunk(ip, 0));
         if (wave < 4 * L) {
             const int c = wave / (2 * L), lev = (wave % (2 * L)) >> 1, h = wave & 1;
-            const double *ac = acc + c * N + h * UF_HALF;
-            double x[8];   // re[r] = x[r], im[r] = x[r + 4]
+            const double *ac = acc + c * N + h * H_HALF;
+            double x[8];   // re[r] = x[r], im[r] = x[r + 4]  (written out: as a helper identical here only, a wait more in tp2u, l = 2)
             static_for<0, 8>([&](auto J) {
                 const double dd = mod_ab<AB>(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);    // coefficient 2 (lane + 64 (J & 3)) + h + 512 (J >> 2)
                 x[J] = t64::digit<L, BG, AB>(dd, lev);
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
-            if (h) ffth::forward_half<1>(re, im, v, lane, lds);
-            else ffth::forward_half<0>(re, im, v, lane, lds);
-            double2 *tile = tiles + (size_t)(wave >> 1) * UF_HALF + h * (UF_HALF / 2);
+            forward_half_of(h, re, im, v, lane, lds);
+            double2 *tile = tiles + (size_t)(wave >> 1) * H_HALF + h * (H_HALF / 2);   // (the store stays here: in the helper it renumbers registers)
             static_for<0, 4>([&](auto R) { tile[R * 64 + lane] = double2{v[R].r, v[R].i}; });
         }
         __syncthreads();
@@ -134,59 +115,41 @@ __global__ void __launch_bounds__(UF_THREADS)
             ffth::C ylo{0.0, 0.0}, yhi{0.0, 0.0};   // one key's sums over its 2L rows
             static_for<0, NCH>([&](auto T) {
                 constexpr int t = T, key = t >> 1, r0 = (t & 1) * CH, cur = t & 1;
-                if constexpr (t + 1 < NCH) request(kb[cur ^ 1], chunk_ptr(ip, t + 1));
+                if constexpr (t + 1 < NCH) request<CH, LIMBS>(kb[cur ^ 1], chunk(ip, t + 1));
                 static_for<0, CH>([&](auto R) {
-                    const double2 e = tiles[(size_t)(r0 + R) * UF_HALF + mq], od = tiles[(size_t)(r0 + R) * UF_HALF + UF_HALF / 2 + mq];
-                    const double lr = e.x + od.x, li = e.y + od.y, hr = e.x - od.x, hi = e.y - od.y;
-                    const double2 klo = kb[cur][R][0], khi = kb[cur][R][1];
-                    ylo.r = __builtin_fma(lr, klo.x, __builtin_fma(-li, klo.y, ylo.r));
-                    ylo.i = __builtin_fma(lr, klo.y, __builtin_fma(li, klo.x, ylo.i));
-                    yhi.r = __builtin_fma(hr, khi.x, __builtin_fma(-hi, khi.y, yhi.r));
-                    yhi.i = __builtin_fma(hr, khi.y, __builtin_fma(hi, khi.x, yhi.i));
+                    const double2 e = tiles[(size_t)(r0 + R) * H_HALF + mq], od = tiles[(size_t)(r0 + R) * H_HALF + H_HALF / 2 + mq];
+                    mac_pair(ylo, yhi, e, od, kb[cur][R][0], kb[cur][R][1]);
                 });
                 if constexpr (t & 1) {   // the key is complete: scale by X^c - 1 at the slot's two roots, add
                     const uint32_t xe = (root_e * cj[key]) & (2 * N - 1);
                     double2 w = ZP[xe & (N - 1)];
                     if (xe & N) w = double2{-w.x, -w.y};
-                    const double wlr = w.x - 1.0, wli = w.y;
-                    const double whr = ((cj[key] & 1) ? -w.x : w.x) - 1.0, whi = (cj[key] & 1) ? -w.y : w.y;
-                    slo.r += __builtin_fma(ylo.r, wlr, -(ylo.i * wli));
-                    slo.i += __builtin_fma(ylo.r, wli, ylo.i * wlr);
-                    shi.r += __builtin_fma(yhi.r, whr, -(yhi.i * whi));
-                    shi.i += __builtin_fma(yhi.r, whi, yhi.i * whr);
-                    ylo = yhi = ffth::C{0.0, 0.0};
+                    scale_add(slo, shi, ylo, yhi, w, cj[key]);
                 }
                 pin();   // one chunk at a time: neither the next chunks' tile reads nor their key requests move up (registers)
             });
             const double2 w = reinterpret_cast<const double2 *>(lds + ffth::HT_W)[mq];
-            const ffth::C d = ffth::cmul<true>(ffth::C{slo.r - shi.r, slo.i - shi.i}, w.x, w.y);
-            double2 *sd = SD + (size_t)(mj * 2 + mo) * UF_HALF;
-            sd[mq] = double2{slo.r + shi.r, slo.i + shi.i};
-            sd[UF_HALF / 2 + mq] = double2{d.r, d.i};
+            sum_diff_store(SD + (size_t)(mj * 2 + mo) * H_HALF, mq, slo, shi, w);
         }
         __syncthreads();
         if (wave < 4 * LIMBS) {
             const int j = wave >> 2, o = (wave >> 1) & 1, h = wave & 1;
-            const double2 *sd = SD + (size_t)(j * 2 + o) * UF_HALF + h * (UF_HALF / 2);
+            const double2 *sd = SD + (size_t)(j * 2 + o) * H_HALF + h * (H_HALF / 2);
             ffth::C v[4];
-            static_for<0, 4>([&](auto R) {
-                const double2 t = sd[R * 64 + lane];
-                v[R] = ffth::C{t.x, t.y};
-            });
-            double re[4], im[4];
+            read_sums(v, sd, lane);
+            double re[4], im[4];   // (from here written out: a helper gives the same counts in another order and, timed, missed the rule at one bootstrap - profiles/half_steps_ab.txt)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
-            double *ao = acc + o * N + h * UF_HALF + lane;
+            double *ao = acc + o * N + h * H_HALF + lane;
             static_for<0, 4>([&](auto R) {
                 atomicAdd(ao + 64 * R, t64::place_limb<AB, LB, STATS>(re[R], j, dev));          // coefficient 2 (lane + 64 R) + h
                 atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB, STATS>(im[R], j, dev));    // ... + 512
             });
         }
         __syncthreads();
-        if (++since_centred == UF_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
+        if (++since_centred == H_RECENTRE) {   // (uniform: counts the steps actually taken) keep the accumulator's magnitude below 2^51
             since_centred = 0;
-            acc[tid] = mod_ab<AB>(acc[tid]);
-            acc[N + tid] = mod_ab<AB>(acc[N + tid]);
+            recentre<AB, 2>(acc, tid);
             __syncthreads();
         }
     }
@@ -194,7 +157,6 @@ __global__ void __launch_bounds__(UF_THREADS)
     if constexpr (GLWE) t64::store_glwe<N, PRE, AB>(out + (size_t)ct * (2 * N), acc, acc_slot, tid);   // out = [count][2N]
     else t64::extract_sample<N, PRE, AB>(out + (size_t)ct * (N + 1), acc, acc_slot, tid);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // THROUGHPUT form: TWO ciphertexts per workgroup sharing every key word in registers.  The one-ciphertext kernel above is bound
@@ -208,37 +170,37 @@ __global__ void __launch_bounds__(UF_THREADS)
 //      the sum and the twisted difference for the inverse halves
 //   C  16 inverse tasks (ciphertext, limb, output, parity), LDS f64 atomics into the accumulators
 constexpr int U2_ZQ_WORDS = N;   // zeta^x for x in [0, 512) as (re, im); zeta^(x + 512) = i zeta^x
-constexpr int U2_LDS_WORDS = ffth::HT_WORDS + U2_ZQ_WORDS + 2 * (2 * N) + 2 * (2 * UF_MAX_L * N) + 2 * BMI_AT_WORDS;
+constexpr int U2_LDS_WORDS = ffth::HT_WORDS + U2_ZQ_WORDS + 2 * (2 * N) + 2 * (2 * H_MAX_L * N) + 2 * BMI_AT_WORDS;
 static_assert(U2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "U2_LDS_WORDS exceeds the 160 KB of LDS");
-static_assert(2 * 2 * N <= 2 * UF_MAX_L * N, "a ciphertext's sums / differences fit over its tiles");
+static_assert(2 * 2 * N <= 2 * H_MAX_L * N, "a ciphertext's sums / differences fit over its tiles");
 
 // GLWE: as in the one-ciphertext kernel, each ciphertext of the workgroup its own [2N] row
 template <int L, int BG, int PREC, bool GLWE>
-__global__ void __launch_bounds__(UF_THREADS)
+__global__ void __launch_bounds__(H_THREADS)
     k_blind_rotate_tp2u_t64f(const u64 *__restrict__ small_cts, const uint32_t *__restrict__ lut_ids, const u64 *__restrict__ luts,
                              const double *__restrict__ bsk3_latf, const double *__restrict__ g_tw_h, const double *__restrict__ g_zeta_pow,
                              u64 *__restrict__ out, uint32_t count, uint32_t n) {
     constexpr int LIMBS = Scheme<PREC>::LIMBS, LB = Scheme<PREC>::BITS, PRE = Scheme<PREC>::PRE, AB = 64 - PRE;
     static_assert(6.0 * 2.0 * L * N * (double)(1ull << (BG - 1)) * (double)(1ull << (LB - 1)) <= 0x1p45, "limb sums must stay below 2^45");
-    static_assert(LIMBS == 2 && L <= UF_MAX_L && L * BG < AB, "two limbs, at most three levels");
-    constexpr int TILE_CPLX = UF_MAX_L * N;   // complex words of one ciphertext's tiles: [2L rows][2 halves][256]
+    static_assert(LIMBS == 2 && L <= H_MAX_L && L * BG < AB, "two limbs, at most three levels");
+    constexpr int TILE_CPLX = H_MAX_L * N;   // complex words of one ciphertext's tiles: [2L rows][2 halves][256]
     extern __shared__ double lds[];
     const double2 *ZQ = reinterpret_cast<const double2 *>(lds + ffth::HT_WORDS);
     double *acc_all = lds + ffth::HT_WORDS + U2_ZQ_WORDS;                 // [2 ciphertexts][2 components][2 parities][512]
     double2 *tiles_all = reinterpret_cast<double2 *>(acc_all + 2 * 2 * N);   // [2 ciphertexts][TILE_CPLX]; the sums overlay them
     uint16_t *at_all = reinterpret_cast<uint16_t *>(tiles_all + 2 * TILE_CPLX);   // [2][BMI_AT_WORDS * 4]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < ffth::HT_WORDS; i += UF_THREADS) lds[i] = g_tw_h[i];
-    for (int i = tid; i < U2_ZQ_WORDS; i += UF_THREADS) lds[ffth::HT_WORDS + i] = g_zeta_pow[i];   // the first 512 powers
+    for (int i = tid; i < ffth::HT_WORDS; i += H_THREADS) lds[i] = g_tw_h[i];
+    for (int i = tid; i < U2_ZQ_WORDS; i += H_THREADS) lds[ffth::HT_WORDS + i] = g_zeta_pow[i];   // the first 512 powers
     const uint32_t ct0 = 2 * blockIdx.x;
     const uint32_t cts[2] = {ct0, ct0 + 1 < count ? ct0 + 1 : ct0};      // an odd batch: the last workgroup runs its ciphertext twice
     static_for<0, 2>([&](auto Z) {
         const u64 *lwe = small_cts + (size_t)cts[Z] * (n + 1);
         uint16_t *at = at_all + Z * BMI_AT_WORDS * 4;
-        t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, UF_THREADS);
+        t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, H_THREADS);
     });
     __syncthreads();
-    static_for<0, 2>([&](auto Z) {
+    static_for<0, 2>([&](auto Z) {   // (written out: behind a helper two more instructions in front of the loop)
         const u64 *tv = luts + (size_t)(lut_ids[cts[Z]] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at_all[Z * BMI_AT_WORDS * 4 + n];
         t64::load_test_poly<N, PRE>(acc_all + Z * 2 * N, acc_slot, tv, bt, tid);
@@ -249,18 +211,8 @@ __global__ void __launch_bounds__(UF_THREADS)
     const uint32_t pairs = (n + 1) >> 1;
     uint32_t since_centred = 0;
     constexpr int CH = L, NCH = 3 * 2;
-    auto chunk_ptr = [&](uint32_t ip, int t) {
-        const int key = t >> 1, r0 = (t & 1) * CH;
-        return reinterpret_cast<const double2 *>(bsk3_latf + (((size_t)ip * 3 + key) * 2 * L + r0) * 2 * LIMBS * N) +
-               ((size_t)mo * LIMBS + mj) * (N / 2) + 2 * mq;
-    };
+    auto chunk = [&](uint32_t ip, int t) { return chunk_ptr<L, LIMBS>(bsk3_latf, ip, t, mo, mj, mq); };
     double2 kb[2][CH][2];
-    auto request = [&](double2 (&dst)[CH][2], const double2 *p) {
-        static_for<0, CH>([&](auto R) {
-            dst[R][0] = p[(size_t)R * 2 * LIMBS * (N / 2)];
-            dst[R][1] = p[(size_t)R * 2 * LIMBS * (N / 2) + 1];
-        });
-    };
     // zeta^x, x in [0, 2N): the table holds the first quadrant, the others are its multiples by i
     auto zeta_pow = [&](uint32_t xe) {
         const double2 w = ZQ[xe & 511];
@@ -271,29 +223,22 @@ __global__ void __launch_bounds__(UF_THREADS)
 
     for (uint32_t ip = 0; ip < pairs; ip++) {
         uint32_t cj[2][3];
-        static_for<0, 2>([&](auto Z) {
-            const uint16_t *at = at_all + Z * BMI_AT_WORDS * 4;
-            const uint32_t a1 = at[2 * ip], a2 = (2 * ip + 1 < n) ? at[2 * ip + 1] : 0u;
-            cj[Z][0] = (a1 + a2) & (2 * N - 1);
-            cj[Z][1] = a1;
-            cj[Z][2] = a2;
-        });
+        static_for<0, 2>([&](auto Z) { pair_exponents(cj[Z], at_all + Z * BMI_AT_WORDS * 4, ip, n); });
         if ((cj[0][1] | cj[0][2] | cj[1][1] | cj[1][2]) == 0) continue;  // uniform: every factor X^0 - 1 of both ciphertexts vanishes
-        request(kb[0], chunk_ptr(ip, 0));
+        request<CH, LIMBS>(kb[0], chunk(ip, 0));
         auto forward_task = [&](const int T) {
             const int z = T / (4 * L), w12 = T % (4 * L);
             const int c = w12 / (2 * L), lev = (w12 % (2 * L)) >> 1, h = w12 & 1;
-            const double *ac = acc_all + z * 2 * N + c * N + h * UF_HALF;
-            double x[8];
+            const double *ac = acc_all + z * 2 * N + c * N + h * H_HALF;
+            double x[8];   // (written out, as in the one-ciphertext kernel)
             static_for<0, 8>([&](auto J) {
                 const double dd = mod_ab<AB>(ac[lane + 64 * (J & 3) + 256 * (J >> 2)]);
                 x[J] = t64::digit<L, BG, AB>(dd, lev);
             });
             const double re[4] = {x[0], x[1], x[2], x[3]}, im[4] = {x[4], x[5], x[6], x[7]};
             ffth::C v[4];
-            if (h) ffth::forward_half<1>(re, im, v, lane, lds);
-            else ffth::forward_half<0>(re, im, v, lane, lds);
-            double2 *tile = tiles_all + (size_t)z * TILE_CPLX + (size_t)(w12 >> 1) * UF_HALF + h * (UF_HALF / 2);
+            forward_half_of(h, re, im, v, lane, lds);
+            double2 *tile = tiles_all + (size_t)z * TILE_CPLX + (size_t)(w12 >> 1) * H_HALF + h * (H_HALF / 2);   // (the store stays here: l = 2 gains a wait)
             static_for<0, 4>([&](auto R) { tile[R * 64 + lane] = double2{v[R].r, v[R].i}; });
         };
         if (wave < 8 * L) forward_task(wave);
@@ -308,66 +253,52 @@ __global__ void __launch_bounds__(UF_THREADS)
             static_for<0, 2>([&](auto Z) { slo[Z] = shi[Z] = ylo[Z] = yhi[Z] = ffth::C{0.0, 0.0}; });
             static_for<0, NCH>([&](auto T) {
                 constexpr int t = T, key = t >> 1, r0 = (t & 1) * CH, cur = t & 1;
-                if constexpr (t + 1 < NCH) request(kb[cur ^ 1], chunk_ptr(ip, t + 1));
+                if constexpr (t + 1 < NCH) request<CH, LIMBS>(kb[cur ^ 1], chunk(ip, t + 1));
                 static_for<0, 2>([&](auto Z) {
                     const double2 *tl = tiles_all + (size_t)Z * TILE_CPLX;
                     static_for<0, CH>([&](auto R) {
-                        const double2 e = tl[(size_t)(r0 + R) * UF_HALF + mq], od = tl[(size_t)(r0 + R) * UF_HALF + UF_HALF / 2 + mq];
-                        const double lr = e.x + od.x, li = e.y + od.y, hr = e.x - od.x, hi = e.y - od.y;
-                        const double2 klo = kb[cur][R][0], khi = kb[cur][R][1];
-                        ylo[Z].r = __builtin_fma(lr, klo.x, __builtin_fma(-li, klo.y, ylo[Z].r));
-                        ylo[Z].i = __builtin_fma(lr, klo.y, __builtin_fma(li, klo.x, ylo[Z].i));
-                        yhi[Z].r = __builtin_fma(hr, khi.x, __builtin_fma(-hi, khi.y, yhi[Z].r));
-                        yhi[Z].i = __builtin_fma(hr, khi.y, __builtin_fma(hi, khi.x, yhi[Z].i));
+                        const double2 e = tl[(size_t)(r0 + R) * H_HALF + mq], od = tl[(size_t)(r0 + R) * H_HALF + H_HALF / 2 + mq];
+                        mac_pair(ylo[Z], yhi[Z], e, od, kb[cur][R][0], kb[cur][R][1]);
                     });
                     if constexpr (t & 1) {   // the key is complete: scale by this ciphertext's X^c - 1 at the slot's two roots, add
                         const uint32_t c = cj[Z][key];
                         const double2 w = zeta_pow((root_e * c) & (2 * N - 1));
-                        const double wlr = w.x - 1.0, wli = w.y;
-                        const double whr = ((c & 1) ? -w.x : w.x) - 1.0, whi = (c & 1) ? -w.y : w.y;
-                        slo[Z].r += __builtin_fma(ylo[Z].r, wlr, -(ylo[Z].i * wli));
-                        slo[Z].i += __builtin_fma(ylo[Z].r, wli, ylo[Z].i * wlr);
-                        shi[Z].r += __builtin_fma(yhi[Z].r, whr, -(yhi[Z].i * whi));
-                        shi[Z].i += __builtin_fma(yhi[Z].r, whi, yhi[Z].i * whr);
-                        ylo[Z] = yhi[Z] = ffth::C{0.0, 0.0};
+                        scale_add(slo[Z], shi[Z], ylo[Z], yhi[Z], w, c);
                     }
                 });
                 pin();
             });
             const double2 w = reinterpret_cast<const double2 *>(lds + ffth::HT_W)[mq];
-            static_for<0, 2>([&](auto Z) {
+            static_for<0, 2>([&](auto Z) {   // (sum_diff_store in two pieces, the barrier between them: one kernel only)
                 sS[Z] = ffth::C{slo[Z].r + shi[Z].r, slo[Z].i + shi[Z].i};
                 sD[Z] = ffth::cmul<true>(ffth::C{slo[Z].r - shi[Z].r, slo[Z].i - shi[Z].i}, w.x, w.y);
             });
         }
         __syncthreads();   // every thread has read the tiles: the sums may overwrite them
         static_for<0, 2>([&](auto Z) {
-            double2 *sd = tiles_all + (size_t)Z * TILE_CPLX + (size_t)(mj * 2 + mo) * UF_HALF;
+            double2 *sd = tiles_all + (size_t)Z * TILE_CPLX + (size_t)(mj * 2 + mo) * H_HALF;
             sd[mq] = double2{sS[Z].r, sS[Z].i};
-            sd[UF_HALF / 2 + mq] = double2{sD[Z].r, sD[Z].i};
+            sd[H_HALF / 2 + mq] = double2{sD[Z].r, sD[Z].i};
         });
         __syncthreads();
         {
             const int z = wave >> 3, j = (wave >> 2) & 1, o = (wave >> 1) & 1, h = wave & 1;
-            const double2 *sd = tiles_all + (size_t)z * TILE_CPLX + (size_t)(j * 2 + o) * UF_HALF + h * (UF_HALF / 2);
+            const double2 *sd = tiles_all + (size_t)z * TILE_CPLX + (size_t)(j * 2 + o) * H_HALF + h * (H_HALF / 2);
             ffth::C v[4];
-            static_for<0, 4>([&](auto R) {
-                const double2 t = sd[R * 64 + lane];
-                v[R] = ffth::C{t.x, t.y};
-            });
-            double re[4], im[4];
+            read_sums(v, sd, lane);
+            double re[4], im[4];   // (from here written out: a helper passed its timing here only, and one kernel does not make a shared step)
             if (h) ffth::inverse_half<1>(v, re, im, lane, lds);
             else ffth::inverse_half<0>(v, re, im, lane, lds);
-            double *ao = acc_all + z * 2 * N + o * N + h * UF_HALF + lane;
+            double *ao = acc_all + z * 2 * N + o * N + h * H_HALF + lane;
             static_for<0, 4>([&](auto R) {
                 atomicAdd(ao + 64 * R, t64::place_limb<AB, LB>(re[R], j));
                 atomicAdd(ao + 64 * R + 256, t64::place_limb<AB, LB>(im[R], j));
             });
         }
         __syncthreads();
-        if (++since_centred == UF_RECENTRE) {
+        if (++since_centred == H_RECENTRE) {
             since_centred = 0;
-            static_for<0, 4>([&](auto Q) { acc_all[tid + UF_THREADS * Q] = mod_ab<AB>(acc_all[tid + UF_THREADS * Q]); });
+            recentre<AB, 4>(acc_all, tid);
             __syncthreads();
         }
     }
@@ -393,11 +324,10 @@ int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, 
                                  uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    auto launch = [&](auto L, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42, GLWE>>(dim3((count + 1) / 2), dim3(UF_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
+    return with_levels_glwe(levels, glwe, [&](auto L, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42, GLWE>>(dim3((count + 1) / 2), dim3(H_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
                                                                            small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
-    };
-    return with_levels(levels, [&](auto L) { return glwe ? launch(L, std::true_type{}) : launch(L, std::false_type{}); });
+    });
 }
 
 int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
@@ -406,7 +336,7 @@ int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids,
     if (count == 0) return 0;
     if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
     return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS, GLWE>>(dim3(count), dim3(UF_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
+        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS, GLWE>>(dim3(count), dim3(H_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
                                                                                    small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
     });
 }

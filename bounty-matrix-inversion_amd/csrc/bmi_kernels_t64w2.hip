@@ -225,11 +225,10 @@ int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, con
                               u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
     if (count == 0) return 0;
     if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    auto launch = [&](auto L, auto GLWE) {
+    return with_levels_glwe(levels, glwe, [&](auto L, auto GLWE) {
         return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((count + 1) / 2), dim3(W_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
                                                                         small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
-    };
-    return with_levels(levels, [&](auto L) { return glwe ? launch(L, std::true_type{}) : launch(L, std::false_type{}); });
+    });
 }
 
 }  // namespace bmit

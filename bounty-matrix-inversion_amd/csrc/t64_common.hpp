@@ -4,7 +4,8 @@
 // rule, the placement of a limb's integer, and the prologue (mod-switch, test polynomial) and epilogue (sample extraction).
 // All of them are force-inlined templates on the compile-time constants of the calling kernel.  What the four N = 2048 kernels
 // (_t64w, _t64w2, _t64wu, _t64wu2) share beyond that, at the level of a transform - constants and accumulator layout, half
-// butterflies, multiply-accumulate, key rows, powers of zeta, inverse task, `keep` - is in t64_wide_steps.hpp, built on this file.
+// butterflies, multiply-accumulate, key rows, powers of zeta, inverse task, `keep` - is in t64_wide_steps.hpp, built on this file;
+// the N = 1024 half-transform kernels (lat_t64f, lat2u_t64f, tp2u_t64f) have t64_half_steps.hpp the same way.
 //
 // No transform exists mod 2^64, so a torus external product is computed EXACTLY over the integers: the digit polynomials
 // (|d| <= 2^(Bg-1)) are transformed mod p = 2^49 - 720895 and multiplied with LIMBS balanced limb polynomials of every

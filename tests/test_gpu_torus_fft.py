@@ -145,3 +145,31 @@ def test_rounding_margin_of_the_limb_sums(kw):
         assert 0.0 < dist6 < 2.0 ** -9 and np.array_equal(out6, out[:256])
     finally:
         e.close()
+
+
+def test_two_level_latency_form_accumulator_bit_exact_at_an_odd_n_and_batch():
+    """k_blind_rotate_lat_t64f<2, 10, false, GLWE = true>: (l, Bg) = (2, 2^10) is otherwise bootstrapped in the extracted form only.
+    n = 3, a batch of 3, uniformly random words.  The extracted words against the oracle under auto dispatch and with variants 1
+    (exact transform) and 2 (latency form) pinned; all 2N words of the accumulator, auto and variant 2, against the exact numpy
+    rotation of tests/test_gpu_shared_rotation.py, itself pinned to the oracle through the extraction."""
+    from test_gpu_shared_rotation import extract, numpy_blind_rotation
+    e = _engine(seed=79, n=3, bs_levels=2)
+    try:
+        rng = np.random.default_rng(17)
+        lid = e.lut_register(rng.integers(-8, 8, 16), 4, e.delta_log())
+        tv = e.lut_get(lid)
+        small = pc.uniform_words(rng, (3, e.P.small))
+        ids = np.full(3, lid, np.uint32)
+        with pc.oracle_for(e) as o:
+            want = o.ctx.blind_rotate(small, tv[None, :], np.zeros(3, np.uint32))
+        ref = np.stack([numpy_blind_rotation(e.P, e.export_keys()[2], row, tv) for row in small])
+        assert np.array_equal(extract(ref, e.P.N), want)
+        for variant in (0, 1, 2):
+            with pc.pinned_variant(e, variant):
+                assert np.array_equal(e.blind_rotate_host(small, ids), want)
+        for variant in (0, 2):
+            with pc.pinned_variant(e, variant):
+                assert e.rotation_kernel(3) == "k_blind_rotate_lat_t64f"
+                assert np.array_equal(e.blind_rotate_glwe_host(small, ids), ref)
+    finally:
+        e.close()

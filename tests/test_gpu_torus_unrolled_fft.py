@@ -104,6 +104,38 @@ def test_unrolled_fft_other_shapes_bit_exact(kw):
         e.close()
 
 
+def test_two_level_forms_bit_exact_at_an_odd_n_and_batch():
+    """(l, Bg) = (2, 2^10) is otherwise bootstrapped by k_blind_rotate_lat2u_t64f in the extracted form only: here the other two-level
+    instantiations - tp2u plain and GLWE, lat2u STATS and GLWE - each named by the library's dispatch.  n = 3 (an odd n: the last
+    pair is half empty), a batch of 3 (an odd batch: tp2u's last workgroup runs the padding copy), uniformly random words, variant
+    1 (tp2u) and variant 2 (lat2u) pinned.  The extracted words against the oracle's unrolled mode; all 2N words of the accumulator
+    against the exact numpy rotation of tests/test_gpu_shared_rotation_wide_unrolled.py, itself pinned to the oracle through the
+    extraction; the rounding distance under the 2^-7 the l = 3 kernel is held to (its sums are larger)."""
+    from test_gpu_shared_rotation import extract
+    from test_gpu_shared_rotation_wide_unrolled import numpy_unrolled_blind_rotation
+    e = _engine(seed=78, n=3, bs_levels=2)
+    try:
+        rng = np.random.default_rng(19)
+        lid = e.lut_register(rng.integers(-8, 8, 16), 4, e.delta_log())
+        tv = e.lut_get(lid)
+        small = pc.uniform_words(rng, (3, e.P.small))
+        ids = np.full(3, lid, np.uint32)
+        with pc.oracle_for(e, unrolled=True) as o:
+            want = o.ctx.blind_rotate(small, tv[None, :], np.zeros(3, np.uint32), unrolled=True)
+        bsk3 = e.export_bsk_unrolled()
+        ref = np.stack([numpy_unrolled_blind_rotation(e.P, bsk3, row, tv) for row in small])
+        assert np.array_equal(extract(ref, e.P.N), want)
+        for variant, name in ((1, "k_blind_rotate_tp2u_t64f"), (2, "k_blind_rotate_lat2u_t64f")):
+            with pc.pinned_variant(e, variant):
+                assert e.rotation_kernel(3) == name
+                assert np.array_equal(e.blind_rotate_host(small, ids), want)
+                assert np.array_equal(e.blind_rotate_glwe_host(small, ids), ref)
+        out, dist = e.fft_margin_host(small, ids)      # the STATS form of lat2u, whatever the batch
+        assert np.array_equal(out, want) and 0.0 < dist < 2.0 ** -7, dist
+    finally:
+        e.close()
+
+
 def test_unrolled_fft_output_noise_on_the_formula_and_timing(eng, capsys):
     """2,048 bootstraps: the output variance against the unrolled CGGI formula with the 42-bit key's effective noise
     (bmi_amd/error_budget.pbs_output_variance with the exact key weights); latency of 1 and of a full round of 256"""
