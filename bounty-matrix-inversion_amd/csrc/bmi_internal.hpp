@@ -90,6 +90,16 @@ inline int with_levels_glwe(uint32_t levels, bool glwe, F f) {
     return with_levels(levels, [&](auto L) { return glwe ? f(L, std::true_type{}) : f(L, std::false_type{}); });
 }
 
+// The (levels, base log) of the 49-bit field's templated kernels -> their instantiations: calls f(L, BG) with
+// std::integral_constant<int, .> for (3, 15), (2, 15) and (1, 23); any other shape is refused.
+template <typename F>
+inline int with_shape49(uint32_t levels, uint32_t base_log, F f) {
+    if (levels == 3 && base_log == 15) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 15>{});
+    if (levels == 2 && base_log == 15) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 15>{});
+    if (levels == 1 && base_log == 23) return f(std::integral_constant<int, 1>{}, std::integral_constant<int, 23>{});
+    return (int)hipErrorInvalidValue;
+}
+
 // ... and the epilogue of the torus FFT rotations (bmi_kernels_t64{f,fu,w,wu,wu2,w2,q}.hip), whose trailing template flag GLWE makes
 // them return the accumulator itself (t64::store_glwe, out = [count][2N]) instead of the extracted sample (t64::extract_sample,
 // out = [count][N + 1]); everything up to the end of the CMUX loop is the same text.  Calls f(L, STATS, GLWE).  The accumulator

@@ -13,6 +13,7 @@
 
 #include "bmi_internal.hpp"
 #include "dec49.hpp"
+#include "exact_half_steps.hpp"
 #include "ks_lincomb.hpp"
 #include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
@@ -27,6 +28,7 @@ using namespace nttf;
 using dec49::Dec;
 using dec49::digit_of;
 using dec49::round_half_up;
+using exh::L2_THREADS;
 
 namespace {
 
@@ -244,8 +246,7 @@ __global__ void __launch_bounds__(128 * TPX_CTS)
 //      on the fly, multiply with the key (own copy in slot order, k_bsk_to_lat49), write S = Y_lo + Y_hi and Y_lo - Y_hi
 //   C  wavefronts 0..3   = (o, parity): inverse half transform, accumulator update
 // The accumulator is kept de-interleaved in LDS (acc[c][parity][512]) so that every access of a wavefront is contiguous.
-constexpr int L2_THREADS = 1024;
-constexpr int L2_LDS_WORDS = ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + 2 * N + BMI_AT_WORDS;   // 12 = 4 x (L = 3) tiles
+constexpr int L2_LDS_WORDS = exh::lds_words(1, false);
 static_assert(L2_LDS_WORDS <= BMI_LDS_WORDS_MAX, "L2_LDS_WORDS exceeds the 160 KB of LDS");
 
 // PAIRED: the two words of a slot, A_lo[p] and A_hi[p], are stored side by side ([512][2]) so that the consumer requests them
@@ -264,15 +265,12 @@ __global__ void __launch_bounds__(256) k_bsk_to_lat49(const u64 *__restrict__ st
     if (poly < n_polys) {
         double x[8];
         static_for<0, 8>([&](auto J) { x[J] = f49::to_f(std_polys[(size_t)poly * N + 2 * (lane + 64 * J) + h]); });
-        if (h) ntth::forward_half<true>(x, lane, lds, tile);
-        else ntth::forward_half<false>(x, lane, lds, tile);
-        wave_sync();
-        static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
+        exh::forward_to_tile(x, h, lane, lds, tile);
     }
     __syncthreads();
     if (poly < n_polys) {
         const double *te = lds + ntth::HT_WORDS + (wave & ~1) * ntth::HSCRATCH, *to = te + ntth::HSCRATCH;
-        double *o = lat_polys + (size_t)poly * N;
+        double *o = lat_polys + (size_t)poly * N;   // (store written out in both key conversions: a helper reorders it)
         static_for<0, 4>([&](auto Q4) {
             const int p = (h * 4 + Q4) * 64 + lane;   // the pair's 128 lanes cover the 512 slots in 4 steps
             const double e = te[p], od = to[p];
@@ -305,11 +303,7 @@ __global__ void __launch_bounds__(L2_THREADS)
     {
         const double *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const double v = tv[e & (N - 1)];
-        acc[(nn & 1) * ntth::HALF + (nn >> 1)] = 0.0;
-        acc[N + (nn & 1) * ntth::HALF + (nn >> 1)] = (e & N) ? -v : v;
+        exh::load_test_poly49<N, 1>(acc, tv, bt, tid);
     }
     __syncthreads();
     const int mo = tid >> 9, mp = tid & 511;  // phase B: output polynomial, slot
@@ -342,10 +336,7 @@ __global__ void __launch_bounds__(L2_THREADS)
                 x[J] = Dec<L, BG>::digit(round_half_up(f49::red(v - ac[h * ntth::HALF + m]), Dec<L, BG>::SC), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
-            if (h) ntth::forward_half<true>(x, lane, lds, tile);
-            else ntth::forward_half<false>(x, lane, lds, tile);
-            wave_sync();
-            static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
+            exh::forward_to_tile(x, h, lane, lds, tile);
             __builtin_amdgcn_s_setprio(0);
         }
         PH_MARK(0);
@@ -361,6 +352,7 @@ __global__ void __launch_bounds__(L2_THREADS)
             }
             ylo = f49::red(ylo);
             yhi = f49::red(yhi);
+            // (written out: exh::sum_diff_store changes this kernel's schedule and register count)
             SD[(mo * 2 + 0) * ntth::HALF + mp] = ylo + yhi;
             SD[(mo * 2 + 1) * ntth::HALF + mp] = ylo - yhi;
         }
@@ -369,7 +361,7 @@ __global__ void __launch_bounds__(L2_THREADS)
         PH_MARK(3);
         if (wave < 4) {
             const int o = wave >> 1, h = wave & 1;
-            double x[8];
+            double x[8];   // (read + inverse half written out: a helper reorders the task)
             static_for<0, 8>([&](auto R) { x[R] = SD[(o * 2 + h) * ntth::HALF + R * 64 + lane]; });
             double *tile = tiles + wave * ntth::HSCRATCH;
             if (h) ntth::inverse_half<true>(x, lane, lds, tile);
@@ -382,17 +374,7 @@ __global__ void __launch_bounds__(L2_THREADS)
         PH_MARK(5);
     }
     PH_STORE(g_phase, wave, lane);
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const double a0 = acc[(nn & 1) * ntth::HALF + (nn >> 1)];
-        if (nn == 0) {
-            o[0] = f49::to_u(a0);
-            o[N] = f49::to_u(acc[N]);
-        } else {
-            o[N - nn] = f49::to_u(-a0);
-        }
-    }
+    exh::extract_sample49<N, 1>(out + (size_t)ct * (N + 1), acc, tid);
 }
 
 
@@ -427,17 +409,30 @@ struct PrioStep0 {
     __device__ __forceinline__ void operator()() const { prio<0>(); }
 };
 
-template <bool PRIO = false>
-__device__ __forceinline__ void wide_forward_task(double (&x)[16], int h, int lane, const double *lds, double *tile) {
-    if constexpr (PRIO) {
-        prio<2>();
-        forward(x, lane, lds, tile, PrioStep1(), PrioStep0());
-    } else {
-        forward(x, lane, lds, tile);
-    }
+// What k_blind_rotate_wide49 and k_blind_rotate_wide49u (and, for the first, the key conversion) state the same way.  Their row
+// loads, sum store and extraction loop stay written out in both: behind a helper each changes the kernels' instruction order
+// (profiles/exact_steps_ab.txt).
+// The tail of a forward task at N = 2048: wave transform (mid / late: the two hooks of forward()), twist of the odd half by T,
+// reduced values into the tile
+template <typename Mid = NoHook, typename Late = NoHook>
+__device__ __forceinline__ void wide_forward_task(double (&x)[16], int h, int lane, const double *lds, double *tile, Mid mid = Mid(),
+                                                  Late late = Late()) {
+    forward(x, lane, lds, tile, mid, late);
     if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + V * 64 + lane]); });
     wave_sync();
     static_for<0, 16>([&](auto V) { tile[V * 64 + lane] = f49::red(x[V]); });
+}
+// inverse task of wavefront (o, h) = wave < 4: row (o, h) of the sums, untwisted (odd half), inverse wave transform, accumulator update
+__device__ __forceinline__ void wide_inverse_task(double *acc, double *tiles, int wave, int lane, const double *lds) {
+    const int o = wave >> 1, h = wave & 1;
+    double *tile = tiles + wave * SCRATCH_WORDS;   // row (o, h): read into registers, then the transpose scratch
+    double x[16];
+    static_for<0, 16>([&](auto V) { x[V] = tile[V * 64 + lane]; });
+    if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + N + V * 64 + lane]); });
+    wave_sync();
+    inverse(x, lane, lds, tile);
+    double *ao = acc + o * W_N + h * N;
+    static_for<0, 16>([&](auto J) { ao[lane + 64 * J] = f49::red(ao[lane + 64 * J] + x[J]); });
 }
 
 __global__ void __launch_bounds__(128) k_bsk_to_wide49(const u64 *__restrict__ std_polys, double *__restrict__ wide_polys,
@@ -483,12 +478,7 @@ __global__ void __launch_bounds__(W_THREADS)
     {
         const double *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * W_N;
         const uint32_t bt = at[n];
-        for (uint32_t nn = tid; nn < (uint32_t)W_N; nn += W_THREADS) {
-            const uint32_t e = (nn + bt) & (2 * W_N - 1);
-            const double v = tv[e & (W_N - 1)];
-            acc[(nn & 1) * N + (nn >> 1)] = 0.0;
-            acc[W_N + (nn & 1) * N + (nn >> 1)] = (e & W_N) ? -v : v;
-        }
+        for (uint32_t nn = tid; nn < (uint32_t)W_N; nn += W_THREADS) exh::load_test_poly49<W_N, 1>(acc, tv, bt, nn);
     }
     __syncthreads();
 
@@ -547,8 +537,8 @@ __global__ void __launch_bounds__(W_THREADS)
                 pin();
                 double *tile = tiles + wave * SCRATCH_WORDS;
                 prio<2>();
-                forward(
-                    x, lane, lds, tile,
+                wide_forward_task(
+                    x, h, lane, lds, tile,
                     [&]() {
                         prio<1>();
                         load_rows(std::integral_constant<int, S2>(), std::integral_constant<int, S3>());
@@ -557,9 +547,6 @@ __global__ void __launch_bounds__(W_THREADS)
                         prio<0>();
                         load_rows(std::integral_constant<int, S3>(), ICN());
                     });
-                if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + V * 64 + lane]); });
-                wave_sync();
-                static_for<0, 16>([&](auto V) { tile[V * 64 + lane] = f49::red(x[V]); });
             } else {
                 load_rows(IC0(), ICN());
             }
@@ -596,17 +583,7 @@ __global__ void __launch_bounds__(W_THREADS)
         }
         __syncthreads();
         PH_MARK(4);
-        if (wave < 4) {
-            const int o = wave >> 1, h = wave & 1;
-            double *tile = tiles + wave * SCRATCH_WORDS;   // row (o, h): read into registers, then the transpose scratch
-            double x[16];
-            static_for<0, 16>([&](auto V) { x[V] = tile[V * 64 + lane]; });
-            if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + N + V * 64 + lane]); });
-            wave_sync();
-            inverse(x, lane, lds, tile);
-            double *ao = acc + o * W_N + h * N;
-            static_for<0, 16>([&](auto J) { ao[lane + 64 * J] = f49::red(ao[lane + 64 * J] + x[J]); });
-        }
+        if (wave < 4) wide_inverse_task(acc, tiles, wave, lane, lds);
         PH_MARK(5);
         __syncthreads();
         PH_MARK(6);
@@ -657,12 +634,7 @@ __global__ void __launch_bounds__(W_THREADS)
     {
         const double *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * W_N;
         const uint32_t bt = at[n];
-        for (uint32_t nn = tid; nn < (uint32_t)W_N; nn += W_THREADS) {
-            const uint32_t e = (nn + bt) & (2 * W_N - 1);
-            const double v = tv[e & (W_N - 1)];
-            acc[(nn & 1) * N + (nn >> 1)] = 0.0;
-            acc[W_N + (nn & 1) * N + (nn >> 1)] = (e & W_N) ? -v : v;
-        }
+        for (uint32_t nn = tid; nn < (uint32_t)W_N; nn += W_THREADS) exh::load_test_poly49<W_N, 1>(acc, tv, bt, nn);
     }
     __syncthreads();
     // root exponents of this thread's four (output, slot) items: slot p = V * 64 + l of the wave transform holds the value at
@@ -715,8 +687,8 @@ __global__ void __launch_bounds__(W_THREADS)
                 pin();
                 double *tile = tiles + wave * SCRATCH_WORDS;
                 prio<2>();
-                forward(
-                    x, lane, lds, tile,
+                wide_forward_task(
+                    x, h, lane, lds, tile,
                     [&]() {
                         prio<1>();
                         load_rows(b, 0, std::integral_constant<int, S2>(), std::integral_constant<int, S3>());
@@ -725,9 +697,6 @@ __global__ void __launch_bounds__(W_THREADS)
                         prio<0>();
                         load_rows(b, 0, std::integral_constant<int, S3>(), ICN());
                     });
-                if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + V * 64 + lane]); });
-                wave_sync();
-                static_for<0, 16>([&](auto V) { tile[V * 64 + lane] = f49::red(x[V]); });
             } else {
                 load_rows(b, 0, IC0(), ICN());
             }
@@ -807,17 +776,7 @@ __global__ void __launch_bounds__(W_THREADS)
             tiles[(o * 2 + 1) * SCRATCH_WORDS + p] = lo - hi;             // reduced by the multiplication with T^-1
         }
         __syncthreads();
-        if (wave < 4) {
-            const int o = wave >> 1, h = wave & 1;
-            double *tile = tiles + wave * SCRATCH_WORDS;   // row (o, h): read into registers, then the transpose scratch
-            double x[16];
-            static_for<0, 16>([&](auto V) { x[V] = tile[V * 64 + lane]; });
-            if (h) static_for<0, 16>([&](auto V) { x[V] = f49::mul(x[V], lds[W_T + N + V * 64 + lane]); });
-            wave_sync();
-            inverse(x, lane, lds, tile);
-            double *ao = acc + o * W_N + h * N;
-            static_for<0, 16>([&](auto J) { ao[lane + 64 * J] = f49::red(ao[lane + 64 * J] + x[J]); });
-        }
+        if (wave < 4) wide_inverse_task(acc, tiles, wave, lane, lds);
         __syncthreads();
     }
     u64 *o = out + (size_t)ct * (W_N + 1);
@@ -918,12 +877,7 @@ __global__ void __launch_bounds__(Q_THREADS)
     {
         const double *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * Q_N;
         const uint32_t bt = at[n];
-        for (uint32_t nn = tid; nn < (uint32_t)Q_N; nn += Q_THREADS) {
-            const uint32_t e = (nn + bt) & (2 * Q_N - 1);
-            const double v = tv[e & (Q_N - 1)];
-            acc[(nn & 3) * N + (nn >> 2)] = 0.0;
-            acc[Q_N + (nn & 3) * N + (nn >> 2)] = (e & Q_N) ? -v : v;
-        }
+        for (uint32_t nn = tid; nn < (uint32_t)Q_N; nn += Q_THREADS) exh::load_test_poly49<Q_N, 2>(acc, tv, bt, nn);
     }
     __syncthreads();
 
@@ -1079,38 +1033,16 @@ int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw
     return 0;
 }
 
-// (levels, base log) pairs the templated kernels are instantiated for
-#define BMI49_FOR_LB(levels, base_log, F)                            \
-    do {                                                             \
-        if ((levels) == 3 && (base_log) == 15) return F<3, 15>::go;  \
-        if ((levels) == 2 && (base_log) == 15) return F<2, 15>::go;  \
-        if ((levels) == 1 && (base_log) == 23) return F<1, 23>::go;  \
-        return nullptr;                                              \
-    } while (0)
-
-template <int L, int BG>
-struct LaunchTpx {
-    static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk, const double *g_tw,
-                  u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        return launch_with_lds<k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>>(dim3((count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS),
-                                                                           (size_t)TPX_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
-                                                                           luts, bsk, g_tw, out, count, n);
-    }
-};
-typedef int (*launch9_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, u64 *, uint32_t, uint32_t,
-                         hipStream_t);
-static launch9_t pick_tpx(uint32_t levels, uint32_t base_log) { BMI49_FOR_LB(levels, base_log, LaunchTpx); }
-
 int launch_blind_rotate_tpx(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
                             const double *g_tw, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
                             hipStream_t s) {
     if (count == 0) return 0;
-    launch9_t f = pick_tpx(levels, base_log);
-    return f ? f(small_cts, lut_ids, luts, bsk, g_tw, out, count, n, s) : (int)hipErrorInvalidValue;
+    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>>(dim3((count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS),
+                                                                           (size_t)TPX_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
+                                                                           luts, bsk, g_tw, out, count, n);
+    });
 }
-
-
-
 
 int launch_bsk_to_quad(const u64 *std_polys, double *quad_polys, const double *g_tw, const double *g_t, uint32_t n_polys,
                        hipStream_t s) {
@@ -1133,48 +1065,27 @@ int launch_bsk_to_wide(const u64 *std_polys, double *wide_polys, const double *g
     return 0;
 }
 
-template <int L, int BG>
-struct LaunchWide {
-    static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_wide, const double *g_tw,
-                  const double *g_tw_wide, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        return launch_with_lds<k_blind_rotate_wide49<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)W_LDS_WORDS * sizeof(double), s, small_cts,
-                                                              lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out, count, n);
-    }
-};
-typedef int (*launch10_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *, u64 *,
-                          uint32_t, uint32_t, hipStream_t);
-static launch10_t pick_wide(uint32_t levels, uint32_t base_log) { BMI49_FOR_LB(levels, base_log, LaunchWide); }
-
 int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_wide,
                              const double *g_tw, const double *g_tw_wide, u64 *out, uint32_t count, uint32_t n,
                              uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
-    launch10_t f = pick_wide(levels, base_log);
-    return f ? f(small_cts, lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out, count, n, s) : (int)hipErrorInvalidValue;
-}
-
-template <int L, int BG>
-struct LaunchWideU {
-    static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_wide, const double *g_tw,
-                  const double *g_tw_wide, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        return launch_with_lds<k_blind_rotate_wide49u<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s, small_cts,
-                                                               lut_ids, luts, bsk3_wide, g_tw, g_tw_wide, g_root_pow, out, count, n);
-    }
-};
-typedef int (*launch11_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *,
-                          const double *, u64 *, uint32_t, uint32_t, hipStream_t);
-static launch11_t pick_wide_u(uint32_t levels, uint32_t base_log) {
-    if (levels == 2 && base_log == 15) return LaunchWideU<2, 15>::go;
-    if (levels == 1 && base_log == 23) return LaunchWideU<1, 23>::go;
-    return nullptr;
+    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_wide49<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)W_LDS_WORDS * sizeof(double), s, small_cts,
+                                                              lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out, count, n);
+    });
 }
 
 int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_wide,
                                const double *g_tw, const double *g_tw_wide, const double *g_root_pow, u64 *out, uint32_t count,
                                uint32_t n, uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
-    launch11_t f = pick_wide_u(levels, base_log);
-    return f ? f(small_cts, lut_ids, luts, bsk3_wide, g_tw, g_tw_wide, g_root_pow, out, count, n, s) : (int)hipErrorInvalidValue;
+    if (levels == 3) return (int)hipErrorInvalidValue;   // 2 l <= four GGSW rows: the kernel has one round
+    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+        if constexpr (L < 3)
+            return launch_with_lds<k_blind_rotate_wide49u<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s, small_cts,
+                                                                   lut_ids, luts, bsk3_wide, g_tw, g_tw_wide, g_root_pow, out, count, n);
+        else return (int)hipErrorInvalidValue;
+    });
 }
 
 int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, bool paired, hipStream_t s) {
@@ -1184,22 +1095,14 @@ int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_t
     return 0;
 }
 
-template <int L, int BG>
-struct LaunchLat2 {
-    static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat, const double *g_tw_h,
-                  u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        return launch_with_lds<k_blind_rotate_lat2_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2_LDS_WORDS * sizeof(double), s, small_cts,
-                                                               lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
-    }
-};
-static launch9_t pick_lat2(uint32_t levels, uint32_t base_log) { BMI49_FOR_LB(levels, base_log, LaunchLat2); }
-
 int launch_blind_rotate_lat2(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat,
                              const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
                              hipStream_t s) {
     if (count == 0) return 0;
-    launch9_t f = pick_lat2(levels, base_log);
-    return f ? f(small_cts, lut_ids, luts, bsk_lat, g_tw_h, out, count, n, s) : (int)hipErrorInvalidValue;
+    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_lat2_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2_LDS_WORDS * sizeof(double), s, small_cts,
+                                                               lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
+    });
 }
 
 int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,

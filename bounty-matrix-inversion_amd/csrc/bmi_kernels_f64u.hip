@@ -5,6 +5,7 @@
 
 #include "bmi_internal.hpp"
 #include "dec49.hpp"
+#include "exact_half_steps.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
 #include "phase_prof.hpp"
@@ -14,6 +15,7 @@ using f49::u64;
 using namespace nttf;
 using dec49::Dec;
 using dec49::round_half_up;
+using exh::L2_THREADS;
 
 namespace {
 
@@ -32,9 +34,7 @@ __device__ unsigned long long g_wg_times_u[1024][2];   // [workgroup][start, end
 // (e = 2 kk + 1 for A_lo, e + N for A_hi: a look-up in a 2N-entry table of root powers), so the rotation never touches the
 // coefficient domain; phase C is unchanged.  Per pair: 12 + 4 half transforms and 42 modular multiplications per thread,
 // against 24 + 8 and 24 of two plain steps.  The price is noise: the key-noise term of the output variance triples.
-constexpr int L2_THREADS = 1024;
-// twiddles, accumulator, twelve tiles, sums / differences, mod-switched ciphertext (the layout of k_blind_rotate_lat2_49), root powers
-constexpr int L2U_LDS_WORDS = ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + 2 * N + BMI_AT_WORDS + 2 * N;
+constexpr int L2U_LDS_WORDS = exh::lds_words(1, true);   // the layout of k_blind_rotate_lat2_49, then the root powers
 static_assert(L2U_LDS_WORDS <= BMI_LDS_WORDS_MAX, "L2U_LDS_WORDS exceeds the 160 KB of LDS");
 
 template <int L = 3, int BG = 15>
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(L2_THREADS)
     double *RP = SD + 2 * N + BMI_AT_WORDS;          // psi^x, x in [0, 2N)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i < ntth::HT_WORDS; i += L2_THREADS) lds[i] = g_tw_h[i];
-    for (int i = tid; i < 2 * N; i += L2_THREADS) RP[i ^ ((i >> 5) & 31)] = g_root_pow[i];
+    for (int i = tid; i < 2 * N; i += L2_THREADS) RP[i ^ ((i >> 5) & 31)] = g_root_pow[i];   // folded: exh::root_pow
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
     for (uint32_t i = tid; i <= n; i += L2_THREADS) at[i] = (uint16_t)f49::modswitch(lwe[i], LOG_N + 1);
@@ -62,11 +62,7 @@ __global__ void __launch_bounds__(L2_THREADS)
     {
         const double *tv = luts + (size_t)(lut_ids[ct] & (BMI_LUT_CAP - 1)) * N;
         const uint32_t bt = at[n];
-        const uint32_t nn = tid;  // coefficient index
-        const uint32_t e = (nn + bt) & (2 * N - 1);
-        const double v = tv[e & (N - 1)];
-        acc[(nn & 1) * ntth::HALF + (nn >> 1)] = 0.0;
-        acc[N + (nn & 1) * ntth::HALF + (nn >> 1)] = (e & N) ? -v : v;
+        exh::load_test_poly49<N, 1>(acc, tv, bt, tid);
     }
     __syncthreads();
     const int mo = tid >> 9, mp = tid & 511;  // phase B: output polynomial, slot
@@ -75,20 +71,14 @@ __global__ void __launch_bounds__(L2_THREADS)
     // this thread's 2 L x 2 words of GGSW key `key` (0..2) of pair `ip`: [2 L rows][2 outputs][512 slots][A_lo, A_hi], one
     // 16-byte request per row
     auto load_key = [&](double (&dst)[2 * L][2], uint32_t ip, int key) {
-        const double *bj = bsk3_lat + ((size_t)ip * 3 + key) * 4 * L * N;
-#pragma unroll
-        for (int r = 0; r < 2 * L; r++) {
-            const double2 w = reinterpret_cast<const double2 *>(bj + (size_t)(r * 2 + mo) * N)[mp];
-            dst[r][0] = w.x;
-            dst[r][1] = w.y;
-        }
+        exh::request_rows<1>(dst, bsk3_lat + ((size_t)ip * 3 + key) * 4 * L * N, mo, 0, mp);
     };
     double b[2 * L][2];
 
     PH_DECL();
     for (uint32_t ip = 0; ip < pairs; ip++) {
         const uint32_t a1 = at[2 * ip], a2 = (2 * ip + 1 < n) ? at[2 * ip + 1] : 0u;
-        if ((a1 | a2) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes
+        if ((a1 | a2) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes  (exponents written out: a helper adds a scalar instruction to the loop)
         const uint32_t cj[3] = {(a1 + a2) & (2 * N - 1), a1, a2};
         PH_MARK(7);
         load_key(b, ip, 0);
@@ -102,6 +92,8 @@ __global__ void __launch_bounds__(L2_THREADS)
                 x[J] = Dec<L, BG>::digit(round_half_up(ac[lane + 64 * J], Dec<L, BG>::SC), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
+            // (written out: exh::forward_to_tile renumbers this kernel's registers, and at one bootstrap that build fell outside the
+            // timing margin by less than a microsecond, twice: profiles/exact_steps_ab.txt)
             if (h) ntth::forward_half<true>(x, lane, lds, tile);
             else ntth::forward_half<false>(x, lane, lds, tile);
             wave_sync();
@@ -112,7 +104,7 @@ __global__ void __launch_bounds__(L2_THREADS)
         __syncthreads();
         PH_MARK(1);
         {
-            double alo[2 * L], ahi[2 * L];
+            double alo[2 * L], ahi[2 * L];   // (written out: behind a helper the multiply phase is scheduled in another order)
 #pragma unroll
             for (int r = 0; r < 2 * L; r++) {
                 const double e = tiles[(2 * r) * ntth::HSCRATCH + mp], od = tiles[(2 * r + 1) * ntth::HSCRATCH + mp];
@@ -122,16 +114,8 @@ __global__ void __launch_bounds__(L2_THREADS)
             double slo = 0.0, shi = 0.0;   // sums of three reduced products (<= 1.6 q)
             auto one_key = [&](const double (&kw)[2 * L][2], uint32_t c) {
                 double ylo = 0.0, yhi = 0.0;  // lazy sums of 2 L <= six reduced products (<= 3.1 q)
-#pragma unroll
-                for (int r = 0; r < 2 * L; r++) {
-                    ylo += f49::mul(alo[r], kw[r][0]);
-                    yhi += f49::mul(ahi[r], kw[r][1]);
-                }
-                // psi^(e c); at the root -psi^e: (-1)^c times it.  The table is stored at x ^ (bits 5..9 of x): the exponents of
-                // a wavefront, odd multiples of c, share their low bits when c is even - without the fold they would meet in a
-                // few LDS banks (SQ_LDS_BANK_CONFLICT: 30 % of this kernel's LDS cycles, rocprofv3 --pmc)
-                const uint32_t xe = (root_e * c) & (2 * N - 1);
-                const double w = RP[xe ^ ((xe >> 5) & 31)];
+                exh::mac_rows(ylo, yhi, alo, ahi, kw);
+                const double w = exh::root_pow(RP, root_e, c);   // psi^(e c); at the root -psi^e: (-1)^c times it
                 const double wh = (c & 1) ? -w : w;
                 slo += f49::mul(ylo, w - 1.0);   // the lazy sum goes into the product as it is (|.| <= 3.1 q: exact, like e + od above)
                 shi += f49::mul(yhi, wh - 1.0);
@@ -151,15 +135,14 @@ __global__ void __launch_bounds__(L2_THREADS)
             one_key(b, cj[2]);
             slo = f49::red(slo);
             shi = f49::red(shi);
-            SD[(mo * 2 + 0) * ntth::HALF + mp] = slo + shi;
-            SD[(mo * 2 + 1) * ntth::HALF + mp] = slo - shi;
+            exh::sum_diff_store(SD, mo, mp, slo, shi);
         }
         PH_MARK(2);
         __syncthreads();
         PH_MARK(3);
         if (wave < 4) {
             const int o = wave >> 1, h = wave & 1;
-            double x[8];
+            double x[8];   // (read + inverse half written out: a helper reorders the task)
             static_for<0, 8>([&](auto R) { x[R] = SD[(o * 2 + h) * ntth::HALF + R * 64 + lane]; });
             double *tile = tiles + wave * ntth::HSCRATCH;
             if (h) ntth::inverse_half<true>(x, lane, lds, tile);
@@ -175,17 +158,7 @@ __global__ void __launch_bounds__(L2_THREADS)
 #ifdef BMI_PHASE_PROF
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_wg_times_u[blockIdx.x][1] = wall_clock64();
 #endif
-    u64 *o = out + (size_t)ct * (N + 1);
-    {
-        const uint32_t nn = tid;
-        const double a0 = acc[(nn & 1) * ntth::HALF + (nn >> 1)];
-        if (nn == 0) {
-            o[0] = f49::to_u(a0);
-            o[N] = f49::to_u(acc[N]);
-        } else {
-            o[N - nn] = f49::to_u(-a0);
-        }
-    }
+    exh::extract_sample49<N, 1>(out + (size_t)ct * (N + 1), acc, tid);
 }
 
 }  // namespace
@@ -199,29 +172,14 @@ extern "C" int bmi_debug_wg_times_unrolled(unsigned long long *out2048) {
 
 namespace bmi49 {
 
-template <int L, int BG>
-struct LaunchLat2u {
-    static int go(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat, const double *g_tw_h,
-                  const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-        return launch_with_lds<k_blind_rotate_lat2u_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2U_LDS_WORDS * sizeof(double), s, small_cts,
-                                                                lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
-    }
-};
-typedef int (*launch10_t)(const u64 *, const uint32_t *, const double *, const double *, const double *, const double *, u64 *,
-                          uint32_t, uint32_t, hipStream_t);
-static launch10_t pick_lat2u(uint32_t levels, uint32_t base_log) {
-    if (levels == 3 && base_log == 15) return LaunchLat2u<3, 15>::go;
-    if (levels == 2 && base_log == 15) return LaunchLat2u<2, 15>::go;
-    if (levels == 1 && base_log == 23) return LaunchLat2u<1, 23>::go;
-    return nullptr;
-}
-
 int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat,
                               const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n,
                               uint32_t levels, uint32_t base_log, hipStream_t s) {
     if (count == 0) return 0;
-    launch10_t f = pick_lat2u(levels, base_log);
-    return f ? f(small_cts, lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n, s) : (int)hipErrorInvalidValue;
+    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_lat2u_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2U_LDS_WORDS * sizeof(double), s, small_cts,
+                                                                lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
+    });
 }
 
 }  // namespace bmi49

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bmi_internal.hpp"
+#include "exact_half_steps.hpp"
 #include "ks_lincomb.hpp"
 #include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
@@ -260,9 +261,9 @@ __global__ void __launch_bounds__(128 * T64_CTS)
 //      differences for the inverse halves; the next limb's key words are requested while this one is multiplied
 //   C  wavefronts 0 .. 11 = (limb, o, parity): inverse half transform, conversion of the exact integers to words,
 //      shift into place and ONE LDS atomic add per coefficient into the accumulator (the limbs of a coefficient meet in a slot)
-constexpr int LT_THREADS = 1024;
+constexpr int LT_THREADS = exh::L2_THREADS;
 constexpr t64::ResidueSlot<N, 1> lt_acc_slot{};   // accumulator words (u64) are kept split by parity
-constexpr int LT_LDS_WORDS = ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + 3 * 2 * N + BMI_AT_WORDS;   // sized for 3 limbs
+constexpr int LT_LDS_WORDS = exh::lds_words(3, false);   // sized for 3 limbs
 static_assert(LT_LDS_WORDS <= BMI_LDS_WORDS_MAX, "LT_LDS_WORDS exceeds the 160 KB of LDS");
 
 // standard-domain GGSW polynomials -> per limb, the slot-order pair (A_lo, A_hi) of the two-wave half transform:
@@ -285,15 +286,12 @@ __global__ void __launch_bounds__(256) k_bsk_to_lat_t64(const u64 *__restrict__ 
         static_for<0, 8>([&](auto J) {
             x[J] = (double)t64::limb_of((i64)std_polys[(size_t)poly * N + 2 * (lane + 64 * J) + h], j, prec);
         });
-        if (h) ntth::forward_half<true>(x, lane, lds, tile);
-        else ntth::forward_half<false>(x, lane, lds, tile);
-        wave_sync();
-        static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
+        exh::forward_to_tile(x, h, lane, lds, tile);
     }
     __syncthreads();
     if (ok) {
         const double *te = lds + ntth::HT_WORDS + (wave & ~1) * ntth::HSCRATCH, *to = te + ntth::HSCRATCH;
-        double *o = lat_polys + (size_t)item * N;
+        double *o = lat_polys + (size_t)item * N;   // (store written out, as in k_bsk_to_lat49: a helper reorders it)
         static_for<0, 4>([&](auto Q4) {
             const int p = (h * 4 + Q4) * 64 + lane;
             const double e = te[p], od = to[p];
@@ -337,12 +335,7 @@ __global__ void __launch_bounds__(LT_THREADS)
         // (row, limb)
         const double *bi = bsk_lat + (size_t)i * 4 * L * LIMBS * N;
         auto load_limb = [&](double (&dst)[2 * L][2], int j) {
-#pragma unroll
-            for (int r = 0; r < 2 * L; r++) {
-                const double2 w = reinterpret_cast<const double2 *>(bi + (((size_t)(r * 2 + mo)) * LIMBS + j) * N)[mp];
-                dst[r][0] = w.x;
-                dst[r][1] = w.y;
-            }
+            exh::request_rows<LIMBS>(dst, bi, mo, j, mp);
         };
         double b0[2 * L][2];
         load_limb(b0, 0);
@@ -361,15 +354,12 @@ __global__ void __launch_bounds__(LT_THREADS)
                 x[J] = t64::peel_digit<L, BG>(t64::rounded_top<L, BG>(v - ac[h * ntth::HALF + m]), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
-            if (h) ntth::forward_half<true>(x, lane, lds, tile);
-            else ntth::forward_half<false>(x, lane, lds, tile);
-            wave_sync();
-            static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
+            exh::forward_to_tile(x, h, lane, lds, tile);
             __builtin_amdgcn_s_setprio(0);
         }
         __syncthreads();
         {
-            double alo[2 * L], ahi[2 * L];
+            double alo[2 * L], ahi[2 * L];   // (written out: behind a helper the multiply phase is scheduled in another order)
 #pragma unroll
             for (int r = 0; r < 2 * L; r++) {
                 const double e = tiles[(2 * r) * ntth::HSCRATCH + mp], od = tiles[(2 * r + 1) * ntth::HSCRATCH + mp];
@@ -380,16 +370,8 @@ __global__ void __launch_bounds__(LT_THREADS)
             // (its registers are reused): a request is in flight during every multiplication
             auto one_limb = [&](const double (&kw)[2 * L][2], int j) {
                 double ylo = 0.0, yhi = 0.0;  // lazy sums of 2 L products (<= 10.3 p)
-#pragma unroll
-                for (int r = 0; r < 2 * L; r++) {
-                    ylo += f49::mul(alo[r], kw[r][0]);
-                    yhi += f49::mul(ahi[r], kw[r][1]);
-                }
-                ylo = f49::red(ylo);
-                yhi = f49::red(yhi);
-                double *sd = SD + (size_t)j * 2 * N;
-                sd[(mo * 2 + 0) * ntth::HALF + mp] = ylo + yhi;
-                sd[(mo * 2 + 1) * ntth::HALF + mp] = ylo - yhi;
+                exh::mac_rows(ylo, yhi, alo, ahi, kw);
+                exh::sum_diff_store(SD + (size_t)j * 2 * N, mo, mp, f49::red(ylo), f49::red(yhi));
             };
             double bn[2 * L][2];
             load_limb(bn, 1);
@@ -405,7 +387,7 @@ __global__ void __launch_bounds__(LT_THREADS)
         __syncthreads();
         if (wave < 4 * LIMBS) {
             const int j = wave >> 2, o = (wave >> 1) & 1, h = wave & 1;
-            double x[8];
+            double x[8];   // (read + inverse half written out: a helper reorders the task)
             const double *sd = SD + (size_t)j * 2 * N + (o * 2 + h) * ntth::HALF;
             static_for<0, 8>([&](auto R) { x[R] = sd[R * 64 + lane]; });
             double *tile = tiles + wave * ntth::HSCRATCH;
@@ -413,12 +395,7 @@ __global__ void __launch_bounds__(LT_THREADS)
             if (h) ntth::inverse_half<true>(x, lane, lds, tile);
             else ntth::inverse_half<false>(x, lane, lds, tile);
             __builtin_amdgcn_s_setprio(0);
-            unsigned long long *ao = reinterpret_cast<unsigned long long *>(acc + o * N + h * ntth::HALF);
-            const int sh = PRE + LB * j;
-            static_for<0, 8>([&](auto J) {
-                // the limb's exact integer (|.| < 2^47.6 < p/2), shifted into place; the three limbs of a slot add atomically
-                atomicAdd(ao + lane + 64 * J, (unsigned long long)(f64_to_word(f49::red(x[J])) << sh));
-            });
+            exh::place_limb(acc + o * N + h * ntth::HALF, x, lane, PRE + LB * j);
         }
         __syncthreads();
     }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bmi_internal.hpp"
+#include "exact_half_steps.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
 #include "phase_prof.hpp"
@@ -29,18 +30,16 @@
 using f49::i64;
 using f49::u64;
 using namespace nttf;
-using t64::f64_to_word;
 using t64::Scheme;
 
 namespace {
 
 PH_ARRAY(g_phase_tu)   // make -C csrc prof
 
-constexpr int LU_THREADS = 1024;
+constexpr int LU_THREADS = exh::L2_THREADS;
 constexpr t64::ResidueSlot<N, 1> acc_slot{};   // accumulator words (u64) are kept split by parity
-// twiddles, accumulator (u64), twelve tiles, sums / differences per limb, mod-switched ciphertext, root powers
 template <int LIMBS>
-constexpr int lu_lds_words() { return ntth::HT_WORDS + 2 * N + 12 * ntth::HSCRATCH + LIMBS * 2 * N + BMI_AT_WORDS + 2 * N; }
+constexpr int lu_lds_words() { return exh::lds_words(LIMBS, true); }   // the accumulator's words are u64
 
 template <int L, int BG, int PREC>
 __global__ void __launch_bounds__(LU_THREADS)
@@ -60,7 +59,7 @@ __global__ void __launch_bounds__(LU_THREADS)
     double *RP = SD + LIMBS * 2 * N + BMI_AT_WORDS;             // psi^x, x in [0, 2N), folded (see below)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i < ntth::HT_WORDS; i += LU_THREADS) lds[i] = g_tw_h[i];
-    for (int i = tid; i < 2 * N; i += LU_THREADS) RP[i ^ ((i >> 5) & 31)] = g_root_pow[i];
+    for (int i = tid; i < 2 * N; i += LU_THREADS) RP[i ^ ((i >> 5) & 31)] = g_root_pow[i];   // folded: exh::root_pow
     const uint32_t ct = blockIdx.x;
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
     t64::stage_lwe<LOG_N + 1>(at, lwe, n, tid, LU_THREADS);
@@ -77,20 +76,14 @@ __global__ void __launch_bounds__(LU_THREADS)
     // this thread's 2 L x 2 words of limb `j` of GGSW key `key` (0..2) of pair `ip`:
     // [2 L rows][2 outputs][limb][512 slots][A_lo, A_hi], one 16-byte request per row
     auto load_block = [&](double (&dst)[2 * L][2], uint32_t ip, int key, int j) {
-        const double *bj = bsk3_lat + ((size_t)ip * 3 + key) * 4 * L * LIMBS * N;
-#pragma unroll
-        for (int r = 0; r < 2 * L; r++) {
-            const double2 w = reinterpret_cast<const double2 *>(bj + ((size_t)(r * 2 + mo) * LIMBS + j) * N)[mp];
-            dst[r][0] = w.x;
-            dst[r][1] = w.y;
-        }
+        exh::request_rows<LIMBS>(dst, bsk3_lat + ((size_t)ip * 3 + key) * 4 * L * LIMBS * N, mo, j, mp);
     };
     double b[2 * L][2];
 
     PH_DECL();
     for (uint32_t ip = 0; ip < pairs; ip++) {
         const uint32_t a1 = at[2 * ip], a2 = (2 * ip + 1 < n) ? at[2 * ip + 1] : 0u;
-        if ((a1 | a2) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes
+        if ((a1 | a2) == 0) continue;  // uniform over the workgroup: every factor X^0 - 1 vanishes  (exponents written out: a helper adds a scalar instruction to the loop)
         const uint32_t cj[3] = {(a1 + a2) & (2 * N - 1), a1, a2};
         PH_MARK(7);
         load_block(b, ip, 0, 0);
@@ -104,17 +97,14 @@ __global__ void __launch_bounds__(LU_THREADS)
                 x[J] = t64::peel_digit<L, BG>(t64::rounded_top<L, BG>(ac[lane + 64 * J]), lev);
             });
             double *tile = tiles + (2 * pz + h) * ntth::HSCRATCH;
-            if (h) ntth::forward_half<true>(x, lane, lds, tile);
-            else ntth::forward_half<false>(x, lane, lds, tile);
-            wave_sync();
-            static_for<0, 8>([&](auto R) { tile[R * 64 + lane] = x[R]; });
+            exh::forward_to_tile(x, h, lane, lds, tile);
             __builtin_amdgcn_s_setprio(0);
         }
         PH_MARK(0);
         __syncthreads();
         PH_MARK(1);
         {
-            double alo[2 * L], ahi[2 * L];
+            double alo[2 * L], ahi[2 * L];   // (written out: behind a helper the multiply phase is scheduled in another order)
 #pragma unroll
             for (int r = 0; r < 2 * L; r++) {
                 const double e = tiles[(2 * r) * ntth::HSCRATCH + mp], od = tiles[(2 * r + 1) * ntth::HSCRATCH + mp];
@@ -126,20 +116,13 @@ __global__ void __launch_bounds__(LU_THREADS)
             for (int j = 0; j < LIMBS; j++) slo[j] = shi[j] = 0.0;
             double wlo = 0.0, whi = 0.0;     // psi^(e c_j) - 1 at the slot's two roots (psi^e and -psi^e), for the key being multiplied
             auto root_factor = [&](uint32_t c) {
-                // the table is stored at x ^ (bits 5..9 of x): the exponents of a wavefront, odd multiples of c, share their low
-                // bits when c is even - without the fold they would meet in a few LDS banks (bmi_kernels_f64u.hip)
-                const uint32_t xe = (root_e * c) & (2 * N - 1);
-                const double w = RP[xe ^ ((xe >> 5) & 31)];
+                const double w = exh::root_pow(RP, root_e, c);
                 wlo = w - 1.0;
                 whi = ((c & 1) ? -w : w) - 1.0;
             };
             auto one_block = [&](const double (&kw)[2 * L][2], int key, int j) {
                 double ylo = 0.0, yhi = 0.0;  // lazy sums of 2 L <= six reduced products (<= 3.1 q)
-#pragma unroll
-                for (int r = 0; r < 2 * L; r++) {
-                    ylo += f49::mul(alo[r], kw[r][0]);
-                    yhi += f49::mul(ahi[r], kw[r][1]);
-                }
+                exh::mac_rows(ylo, yhi, alo, ahi, kw);
                 slo[j] += f49::mul(ylo, wlo);   // the lazy sum goes into the product as it is (exact: |.| < 2^53)
                 shi[j] += f49::mul(yhi, whi);
             };
@@ -160,9 +143,7 @@ __global__ void __launch_bounds__(LU_THREADS)
 #pragma unroll
             for (int j = 0; j < LIMBS; j++) {
                 const double lo = f49::red(slo[j]), hi = f49::red(shi[j]);
-                double *sd = SD + (size_t)j * 2 * N;
-                sd[(mo * 2 + 0) * ntth::HALF + mp] = lo + hi;
-                sd[(mo * 2 + 1) * ntth::HALF + mp] = lo - hi;
+                exh::sum_diff_store(SD + (size_t)j * 2 * N, mo, mp, lo, hi);
             }
         }
         PH_MARK(2);
@@ -170,18 +151,13 @@ __global__ void __launch_bounds__(LU_THREADS)
         PH_MARK(3);
         if (wave < 4 * LIMBS) {
             const int j = wave >> 2, o = (wave >> 1) & 1, h = wave & 1;
-            double x[8];
+            double x[8];   // (read + inverse half written out: a helper reorders the task)
             const double *sd = SD + (size_t)j * 2 * N + (o * 2 + h) * ntth::HALF;
             static_for<0, 8>([&](auto R) { x[R] = sd[R * 64 + lane]; });
             double *tile = tiles + wave * ntth::HSCRATCH;
             if (h) ntth::inverse_half<true>(x, lane, lds, tile);
             else ntth::inverse_half<false>(x, lane, lds, tile);
-            unsigned long long *ao = reinterpret_cast<unsigned long long *>(acc + o * N + h * ntth::HALF);
-            const int sh = PRE + LB * j;
-            static_for<0, 8>([&](auto J) {
-                // the limb's exact integer (|.| < p/2), shifted into place; the limbs of a slot add atomically
-                atomicAdd(ao + lane + 64 * J, (unsigned long long)(f64_to_word(f49::red(x[J])) << sh));
-            });
+            exh::place_limb(acc + o * N + h * ntth::HALF, x, lane, PRE + LB * j);
         }
         PH_MARK(4);
         __syncthreads();

@@ -429,9 +429,11 @@ def test_secure128_preset_bit_exact_noise_and_margin():
                                        (65, dict(n=211, bs_base_log=15)),
                                        (65, dict(n=211, bs_levels=2)),
                                        (65, dict(n=211, _precision=64)),
-                                       (65, dict(n=211, bs_base_log=15, _precision=42))],
+                                       (65, dict(n=211, bs_base_log=15, _precision=42)),
+                                       (65, dict(n=211, bs_levels=2, bs_base_log=15, _precision=42))],
                          ids=["goldilocks64-n97", "p49-n97", "p49-n639", "p49-n1024-max", "p49-l2", "p49-l1-Bg23", "torus64-l2-Bg15",
-                              "torus64-n1024-max", "torus64-Bg15-exact-key", "torus64-l2", "torus64-Bg10-exact-key", "torus64-Bg15-key42"])
+                              "torus64-n1024-max", "torus64-Bg15-exact-key", "torus64-l2", "torus64-Bg10-exact-key", "torus64-Bg15-key42",
+                              "torus64-l2-Bg15-key42"])
 def test_other_parameter_shape_bit_exact(q_bits, kw):
     """n = 97 (98 output columns: a ragged column block in the matrix-core keyswitch) with a 5 x 6-bit keyswitch
     decomposition, n = 639 (640 columns exactly) with 4 x 7-bit digits (|d| <= 64, the int8 limit of the matrix-core
@@ -481,6 +483,25 @@ def test_other_parameter_shape_bit_exact(q_bits, kw):
         assert e.pbs_host(empty, np.zeros(0, np.uint32)).shape == (0, e.P.big)
         assert e.keyswitch_host(empty).shape == (0, e.P.small)
         assert e.blind_rotate_host(np.zeros((0, e.P.small), np.uint64), np.zeros(0, np.uint32)).shape == (0, e.P.big)
+    finally:
+        e.close()
+
+
+def test_one_level_decomposition_at_N2048_with_the_plain_key_bit_exact_at_an_odd_n_and_batch():
+    """k_blind_rotate_wide49<1, 23>: (l, Bg) = (1, 2^23) on the 49-bit field at N = 2048 is otherwise bootstrapped with the unrolled
+    key only (tests/test_gpu_unrolled.py).  The blind rotation alone: n = 3, a batch of 3, uniformly random words of Z_q, every word
+    against the oracle."""
+    from bmi_amd import tfhe
+    e = tfhe.Engine(tfhe.default_params(q_bits=49, n=3, log_N=11, bs_levels=1, bs_base_log=23))
+    try:
+        e.keygen(SEED + 2)
+        rng = np.random.default_rng(23)
+        lid = e.lut_register(rng.integers(-8, 8, 16), 4, e.delta_log())
+        small = pc.rand_q(rng, (3, e.P.small), e.modulus)
+        with pc.oracle_for(e) as o:
+            want = o.ctx.blind_rotate(small, e.lut_get(lid)[None, :], np.zeros(3, np.uint32))
+        assert e.rotation_kernel(3) == "k_blind_rotate_wide49"
+        assert np.array_equal(e.blind_rotate_host(small, np.full(3, lid, np.uint32)), want)
     finally:
         e.close()
 

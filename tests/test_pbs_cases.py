@@ -103,7 +103,7 @@ PARAMETER_SETS = [(qb, kw) for qb in (49, 64, 65) for kw in (dict(), dict(n=629)
 PARAMETER_SETS += [(64, dict(n=97, ks_levels=5, ks_base_log=6)), (49, dict(n=97, ks_levels=5, ks_base_log=6)), (49, dict(n=639, ks_levels=4, ks_base_log=7)),
                    (49, dict(n=1024, ks_levels=8, ks_base_log=4)), (49, dict(n=211, bs_levels=2, bs_base_log=15)), (49, dict(n=211, bs_levels=1, bs_base_log=23)),
                    (65, dict(n=211, bs_levels=2, bs_base_log=15)), (65, dict(n=211, bs_base_log=15)), (65, dict(n=211, bs_levels=2)), (65, dict(n=211)),
-                   (65, dict(bs_base_log=15)), (49, dict(log_N=11)), (49, dict(log_N=12))]
+                   (65, dict(bs_base_log=15)), (49, dict(log_N=11)), (49, dict(log_N=12)), (49, dict(n=3, log_N=11, bs_levels=1, bs_base_log=23))]
 
 
 def test_field_copy_of_the_library_parameters_equals_the_oracle_defaults():

@@ -2,12 +2,14 @@
 """Compares the gfx950 machine code of two source trees, kernel by kernel (CPU only: it compiles, it runs nothing).
 Every .hip translation unit of csrc/ is compiled to a listing with the product flags of that tree's csrc/Makefile (the per-TU
 scheduler choice included); a listing is split per kernel, and comments, directives, the per-compilation __hip_cuid symbol and the
-function index inside local labels (.LBB<n>_) are stripped.  Per kernel: "identical", or the per-class instruction counts of
-both sides (classes of isa_count.py; whole kernel and main loop); VGPR / AGPR / SGPR / scratch / LDS / occupancy of both sides.
+function index inside local labels (.LBB<n>_) are stripped.  Per kernel: "identical"; "registers only (k lines)" when the k
+differing lines all vanish once register numbers are erased (the same instruction sequence, numbered differently); else "DIFFERENT
+(k lines, m after erasing register numbers)" and the per-class instruction counts of both sides (classes of isa_count.py; whole
+kernel and main loop); VGPR / AGPR / SGPR / scratch / LDS / occupancy of both sides.
 usage: isa_diff.py <tree A> <tree B> [--only SUBSTR] [--defs "-DX -DY"] [--jobs N]
        --only: translation units whose file name contains SUBSTR;  --defs: extra defines (-DBMI_PHASE_PROF: the `make prof` build)
 exit status 1 when any kernel differs (or exists on one side only)"""
-import argparse, os, re, subprocess, sys, tempfile
+import argparse, difflib, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -65,6 +67,21 @@ def counts(stream):
     return len(ins), tally(ins), (tally(ins[span[0]:span[1] + 1]) if span else None)
 
 
+def erased(stream):
+    """the stream with register NUMBERS erased: v12 -> v, s[4:5] -> s[2], a3 -> a (one token per register class and width); opcodes,
+    modifiers, immediates, labels and order are kept"""
+    def one(s):
+        s = re.sub(r"\b([vsa]|ttmp)\[(\d+):(\d+)\]", lambda m: f"{m.group(1)}[{int(m.group(3)) - int(m.group(2)) + 1}]", s)
+        return re.sub(r"\b([vsa]|ttmp)\d+\b", r"\1", s)
+    return [one(s) for s in stream]
+
+
+def differing_lines(a, b):
+    """lines outside the longest matching blocks of the two streams (per differing block the longer side counts)"""
+    ops = difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes()
+    return sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")
+
+
 def fmt(c):
     return "-" if c is None else " ".join(f"{k} {v}" for k, v in c.items())
 
@@ -96,9 +113,13 @@ def main():
                 nb, cb, lb = counts(sb)
                 same = sa == sb
                 differing += not same
-                res = " ".join(f"{k} {ra[k]}" for k in ra) + ("  resources equal" if ra == rb else "  |  " + " ".join(f"{k} {rb[k]}" for k in rb) + "  RESOURCES DIFFER")
-                print(f"{f[len('bmi_kernels_'):-4] if f.startswith('bmi_kernels_') else f[:-4]:6} {d:50} {na:6d} {nb:6d}  {'identical' if same else 'DIFFERENT'}  {res}")
+                verdict = "identical"
                 if not same:
+                    k, m = differing_lines(sa, sb), differing_lines(erased(sa), erased(sb))
+                    verdict = f"registers only ({k} lines)" if m == 0 else f"DIFFERENT ({k} lines, {m} after erasing register numbers)"
+                res = " ".join(f"{k} {ra[k]}" for k in ra) + ("  resources equal" if ra == rb else "  |  " + " ".join(f"{k} {rb[k]}" for k in rb) + "  RESOURCES DIFFER")
+                print(f"{f[len('bmi_kernels_'):-4] if f.startswith('bmi_kernels_') else f[:-4]:6} {d:50} {na:6d} {nb:6d}  {verdict}  {res}")
+                if verdict.startswith("DIFFERENT"):
                     print(f"         kernel    A: {fmt(ca)}\n         kernel    B: {fmt(cb)}\n         main loop A: {fmt(la)}\n         main loop B: {fmt(lb)}")
     print(f"{differing} kernel(s) differ")
     return 1 if differing else 0
