@@ -485,10 +485,13 @@ class Configuration:
     """fhe.Configuration: `p_error` / `global_p_error` bound the probability that noise makes a result wrong (global: the whole
     circuit, which is what this front end budgets - a per-look-up `p_error` is turned into a global one by the look-up count);
     `security_level=128` restricts the parameter choice to the 128-bit-secure set.  Concrete's other options (key cache, dataflow,
-    graph printing, precision strategy: qfloat_matrix_inversion.py:995-1002) are accepted and have no counterpart here."""
+    graph printing, precision strategy: qfloat_matrix_inversion.py:995-1002) are accepted and have no counterpart here.
+    `centred_modswitch=True` (this front end's own, default off): the engine's centred modulus switch (bmi_set_modswitch), priced
+    by the parameter choice."""
 
-    def __init__(self, p_error=None, global_p_error=None, security_level=None, **options):
+    def __init__(self, p_error=None, global_p_error=None, security_level=None, centred_modswitch=False, **options):
         self.p_error, self.global_p_error, self.security_level = p_error, global_p_error, security_level
+        self.centred_modswitch = bool(centred_modswitch)
         self.options = options
 
 
@@ -569,16 +572,20 @@ class Circuit:
         secure = self.configuration.security_level is not None
         if secure and int(self.configuration.security_level) != 128:
             raise ValueError("security_level: only 128 has a parameter set (secure128_torus / secure128)")
-        return error_budget.choose_params(prog, self._p_error_target(), q_bits=qb, secure=secure)
+        return error_budget.choose_params(prog, self._p_error_target(), q_bits=qb, secure=secure,
+                                          centred_modswitch=getattr(self.configuration, "centred_modswitch", False))
 
     def _gpu(self):
         if getattr(self, "_ex", None) is None:
             from bmi_amd import tfhe
             from bmi_amd.executor import Executor
             P, self.error_budget = self.choose_parameters()
-            key = (int(P.q_bits), int(P.log_N), int(P.n), float(P.lwe_noise))
+            centred = bool(getattr(self.configuration, "centred_modswitch", False))
+            key = (int(P.q_bits), int(P.log_N), int(P.n), float(P.lwe_noise), centred)     # an engine per modulus-switch mode
             if key not in _ENGINES:
                 eng = tfhe.Engine(P)
+                if centred:
+                    eng.set_modswitch(1)
                 seed = os.environ.get("BMI_COMPAT_KEY_SEED") or os.environ.get("ENCSHIM_KEY_SEED")
                 eng.keygen(int(seed) if seed else None)        # CSPRNG keys unless the test-only seed is given
                 _ENGINES[key] = eng

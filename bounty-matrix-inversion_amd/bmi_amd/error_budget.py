@@ -16,6 +16,9 @@ tests/test_gpu_parity.py, tests/test_gpu_torus_wide.py):
   a look-up's input is a linear combination sum_t c_t leaf_t: v_in = sum_t c_t^2 v(leaf_t)   (independent leaves)
   keyswitch       v_ks = kN l_ks (B^2 + 2) / 12 * lwe_noise^2 + hw(S) / (12 B^(2 l_ks))
   mod-switch      (v_in + v_ks) (2N)^2 + (1 + hw(s)) / 12    positions^2 on the circle of 2N positions
+  ... centred     (v_in + v_ks) (2N)^2 + (1 + n / 4) / 12    (centred_modswitch=True: bmi_set_modswitch(ctx, 1) subtracts the public
+                  mean sum e_i / 2 of the mask words' rounding errors from the body; what is left, sum (s_i - 1/2) e_i - e_b, does
+                  not depend on the key's weight)
 
 Decision boundary: a table over p bits has boxes of 2N / 2^(p+1) positions (narrower tables than the circuit's message space are
 scaled up by the tracer: wider boxes, and their coefficients carry the scale); a value fails when the noise exceeds half a box on
@@ -118,15 +121,18 @@ def _log_erfc(x):
     return out
 
 
-def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0):
+def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0, centred_modswitch=False):
     """(sigma in positions of the 2N circle, half box / sigma) of look-ups through tables of `lut_bits` bits (scalars or arrays)"""
     N = 1 << P.log_N
-    sigma_pos = np.sqrt(((input_variance + v_ks) * (2.0 * N) ** 2 + (1 + hs) / 12.0) * variance_scale)
+    rounding = (1 + P.n / 4.0) / 12.0 if centred_modswitch else (1 + hs) / 12.0
+    sigma_pos = np.sqrt(((input_variance + v_ks) * (2.0 * N) ** 2 + rounding) * variance_scale)
     return sigma_pos, N / (2.0 ** (lut_bits + 1)) / sigma_pos
 
 
-def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None, share_rotations=False):
+def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None, share_rotations=False,
+                        centred_modswitch=False):
     """Error budget of `prog` (a program.Program) under the parameter set `P` (tfhe.Params or anything with its fields).
+    centred_modswitch: the budget of an engine in modulus-switch mode 1 (only the rounding term of the mod-switch changes).
 
     Returns a dict: p_fail (probability that at least one look-up or output decodes wrong, union bound), log10_p_fail,
     lookups, worst_margin_sigma (smallest half-box / sigma over the look-ups), p_fail_worst_lookup, widest_amplification
@@ -168,7 +174,7 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
         p_node = prog.lut_p[prog.node_lut].astype(np.int64)
         if (1 << (int(p_node.max()) + 1)) > N:
             raise ValueError(f"a {int(p_node.max())}-bit look-up does not fit N = {N}")
-        sigma_pos, margin = _lookup_margin(P, p_node, v_in, v_ks, hs)
+        sigma_pos, margin = _lookup_margin(P, p_node, v_in, v_ks, hs, centred_modswitch=centred_modswitch)
         lp = _log_erfc(margin / math.sqrt(2.0))
         log_terms.append(lp)
         res.update(worst_margin_sigma=float(margin.min()), log10_p_fail_worst_lookup=float(lp.max()),
@@ -189,19 +195,30 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     return res
 
 
+def engine_failure_probability(prog, eng, hw_small=None, hw_big=None, share_rotations=False):
+    """failure_probability of `prog` on a live tfhe.Engine as it is configured: its parameters, the precision its bootstrap key is
+    stored at, its unrolling and its modulus-switch mode (Engine.modswitch; a stand-in without that attribute counts as mode 0).
+    Program.failure_probability(engine) prices the standard switch whatever the engine's mode: program.py is part of the tracer
+    fingerprint that names the shipped programs, so the mode is read here instead."""
+    return failure_probability(prog, eng.P, eng.bsk_precision if eng.q_bits == TORUS64 else None, getattr(eng, "unroll", 1) == 2,
+                               hw_small, hw_big, share_rotations=share_rotations,
+                               centred_modswitch=getattr(eng, "modswitch", 0) == 1)
+
+
 def lookup_failure_probability(P, lut_bits, input_variance=0.0, bsk_precision=None, unroll=False, hw_small=None, hw_big=None,
-                               variance_scale=1.0):
+                               variance_scale=1.0, centred_modswitch=False):
     """The per-look-up term of failure_probability on its own: the probability that one look-up through a table of `lut_bits`
     bits decodes a neighbouring box, for an input of variance `input_variance` (relative to q^2: 2 glwe_noise^2 for the sum of
     two fresh encryptions, pbs_output_variance(P, bsk_precision, unroll, ...) times the squared coefficients for bootstrapped
     leaves - the only place the key's precision and unrolling enter, so those two arguments are accepted and unused here).
     `variance_scale` multiplies the variance in positions^2 (the +-15 % the variance terms are held to give the band a measured
-    failure count is accepted in: tests/test_gpu_decrypt_device.py)."""
+    failure count is accepted in: tests/test_gpu_decrypt_device.py).  centred_modswitch: as in failure_probability."""
     N = 1 << P.log_N
     if (1 << (int(lut_bits) + 1)) > N:
         raise ValueError(f"a {int(lut_bits)}-bit look-up does not fit N = {N}")
     hs = P.n / 2.0 if hw_small is None else float(hw_small)
-    _, margin = _lookup_margin(P, int(lut_bits), float(input_variance), keyswitch_variance(P, hw_big), hs, float(variance_scale))
+    _, margin = _lookup_margin(P, int(lut_bits), float(input_variance), keyswitch_variance(P, hw_big), hs, float(variance_scale),
+                               centred_modswitch)
     return float(10.0 ** _log_erfc(np.array([margin / math.sqrt(2.0)]))[0])
 
 
@@ -227,18 +244,19 @@ def candidate_sets(msg_bits, q_bits=None, secure=False):
     return out
 
 
-def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, share_rotations=False):
+def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, share_rotations=False, centred_modswitch=False):
     """The first candidate set whose failure probability for `prog` is at most p_error (Concrete's `global_p_error`); the report of
-    every set tried.  Raises when none qualifies."""
+    every set tried.  Raises when none qualifies.  centred_modswitch is passed through to failure_probability."""
     from . import tfhe
     tried = []
     for label, spec in candidate_sets(prog.msg_bits, q_bits, secure):
         P = tfhe.preset_params(spec) if isinstance(spec, str) else tfhe.default_params(**spec)
         # unrolled kernels: N = 1024, and the 2^64 torus at N = 2048, whose unrolled key is stored at 40 bits (bmi_set_bsk_unroll)
         if unroll and P.log_N == 11 and P.q_bits == TORUS64:
-            rep = failure_probability(prog, P, 40, unroll=True, share_rotations=share_rotations)
+            rep = failure_probability(prog, P, 40, unroll=True, share_rotations=share_rotations, centred_modswitch=centred_modswitch)
         else:
-            rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations)
+            rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations,
+                                      centred_modswitch=centred_modswitch)
         tried.append((label, rep["p_fail"]))
         if rep["p_fail"] <= p_error:
             return P, dict(rep, chosen=label, tried=tried, p_error=p_error)

@@ -123,6 +123,14 @@ class Executor:
                 if int(lo.item()) != int(hi.item()):
                     raise RuntimeError("the ranks of this group hold different evaluation keys: generate one key set and share it "
                                        "(Engine.keygen_shared, or EncryptedMatrixInversion.keygen under torch.distributed)")
+            # ... and with one modulus switch (Engine.set_modswitch): a level split between a rank that centres and one that does not
+            # would decrypt, at two different noise levels that no error budget describes
+            mode = int(getattr(engine, "modswitch", 0))
+            modes = torch.tensor([mode, -mode], dtype=torch.int64, device=self.dev if dist.get_backend(group) == "nccl" else "cpu")
+            dist.all_reduce(modes, op=dist.ReduceOp.MIN, group=group)
+            if int(modes[0].item()) != -int(modes[1].item()):
+                raise RuntimeError("the ranks of this group report different modulus-switch modes: call set_modswitch with the same "
+                                   "mode on every rank's engine (EncryptedMatrixInversion(centred_modswitch=...) does)")
         self.share_rotations = bool(share_rotations)
         if self.share_rotations and self.world > 1:
             raise ValueError("share_rotations is not combined with several ranks: a sharded level is split by look-ups, not by groups")

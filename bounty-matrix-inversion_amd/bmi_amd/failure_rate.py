@@ -26,11 +26,12 @@ def key_weights(eng):
     return int(sk_small.sum()), int(sk_big.sum())
 
 
-def prediction(P, lut_bits, n, hw_small, hw_big):
+def prediction(P, lut_bits, n, hw_small, hw_big, modswitch=0):
     """per-look-up probabilities at variance_scale 0.85 / 1 / 1.15 for the sum of two fresh encryptions, the expected count and
-    the accepted band [n p(0.85) - 3 sqrt(n p(0.85)), n p(1.15) + 3 sqrt(n p(1.15))] (model tolerance + Poisson sampling noise)"""
+    the accepted band [n p(0.85) - 3 sqrt(n p(0.85)), n p(1.15) + 3 sqrt(n p(1.15))] (model tolerance + Poisson sampling noise);
+    modswitch: the engine's modulus-switch mode (Engine.modswitch: 1 = centred)"""
     p = [eb.lookup_failure_probability(P, lut_bits, input_variance=2.0 * P.glwe_noise ** 2, hw_small=hw_small, hw_big=hw_big,
-                                       variance_scale=s) for s in SCALES]
+                                       variance_scale=s, centred_modswitch=modswitch == 1) for s in SCALES]
     return {"p": dict(zip(("0.85", "1.0", "1.15"), p)), "expected": n * p[1],
             "band": [n * p[0] - 3.0 * math.sqrt(n * p[0]), n * p[2] + 3.0 * math.sqrt(n * p[2])]}
 
@@ -47,7 +48,8 @@ def _pool_stats(parts):
 
 
 def measure(eng, lut_bits, rounds, pool=8192, seed=2024):
-    """`rounds` x `pool` look-ups of uniform messages through the `lut_bits`-bit identity table on `eng` (keys generated).
+    """`rounds` x `pool` look-ups of uniform messages through the `lut_bits`-bit identity table on `eng` (keys generated), in the
+    modulus-switch mode the engine is in (the prediction follows it).
     Returns {n, wrong, off_by_one (every wrong result is expected +-1 modulo 2^lut_bits), right / wrong_stats (Engine.noise_stats of
     the look-ups that decoded right / wrong, pooled over the rounds), hw_small, hw_big, delta_log} and the prediction()."""
     import torch
@@ -91,7 +93,8 @@ def measure(eng, lut_bits, rounds, pool=8192, seed=2024):
     n = rounds * B
     res = {"n": n, "lut_bits": lut_bits, "delta_log": dl, "rounds": rounds, "pool": B, "wrong": wrong, "off_by_one": off_by_one,
            "right": _pool_stats(right), "wrong_stats": _pool_stats(wrong_stats), "hw_small": hs, "hw_big": hb}
-    res.update(prediction(P, lut_bits, n, hs, hb))
+    res["modswitch"] = eng.modswitch
+    res.update(prediction(P, lut_bits, n, hs, hb, res["modswitch"]))
     res["ratio"] = wrong / res["expected"] if res["expected"] > 0 else None
     res["pbs_output_std_model"] = math.sqrt(eb.pbs_output_variance(P, bsk_precision=eng.bsk_precision, hw_small=hs, hw_big=hb))
     return res

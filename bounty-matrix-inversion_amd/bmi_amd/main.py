@@ -26,7 +26,7 @@ class EncryptedMatrixInversion:
 
     def __init__(self, n, sampler=None, qfloat_base=2, qfloat_len=32, qfloat_ints=16, true_division=False,
                  tensorize=False, engine=None, device=0, shard_threshold=None, cache=True, unroll=False, q_bits=None,
-                 params=None, p_error=None, share_rotations=False):
+                 params=None, p_error=None, share_rotations=False, centred_modswitch=False):
         """The reference's seven arguments (main.py:17-36), then: engine / device (the GPU context to use) and
         shard_threshold (with torch.distributed initialised on several ranks, levels at least this wide are split
         across the ranks' GPUs; None = every level wider than one kernel round, levels re-packed for the rank count,
@@ -44,7 +44,12 @@ class EncryptedMatrixInversion:
         N = 1024 for small circuits, N = 2048 where the look-up count needs the wider margin, e.g. the 8x8 inverse); None keeps
         the north-star set and reports its budget in `self.error_budget`; share_rotations (2^64 torus, one rank): look-ups of a
         level that read the same input share one keyswitch and blind rotation (executor.py, shared_rotation.py) - evaluate and
-        evaluate_many alike; the error budget and the p_error selection then count the larger noise of such look-ups."""
+        evaluate_many alike; the error budget and the p_error selection then count the larger noise of such look-ups;
+        centred_modswitch (2^64 torus and 49-bit field): the centred modulus switch (bmi_set_modswitch(ctx, 1): the rounding
+        variance of a look-up (1 + n/4) / 12 instead of (1 + hw(s)) / 12 positions^2; 6.2 -> 8.8 sigma for a 4-bit look-up of the
+        default set) - set on the engine this object creates AND on an engine passed in (whose mode this changes); the p_error
+        selection and `self.error_budget` price it.  Works with unroll, share_rotations, evaluate_many and several ranks (every
+        rank's engine must be in the same mode: executor.py)."""
         self.shape = (n, n)
         self.qfloat_base, self.qfloat_len, self.qfloat_ints = qfloat_base, qfloat_len, qfloat_ints
         self.true_division, self.tensorize = true_division, tensorize
@@ -67,6 +72,7 @@ class EncryptedMatrixInversion:
         self.params = params
         self.p_error = p_error
         self.share_rotations = bool(share_rotations)
+        self.centred_modswitch = bool(centred_modswitch)
         self.error_budget = None      # filled when the engine exists: Program.failure_probability under its parameters
         if engine is not None and params is not None:
             raise ValueError("pass an engine or a parameter set, not both (the engine already has its parameters)")
@@ -88,7 +94,8 @@ class EncryptedMatrixInversion:
             elif self.p_error is not None:  # the first set of this modulus whose error budget for this circuit meets p_error
                 from . import error_budget
                 params, self.error_budget = error_budget.choose_params(self.program, self.p_error, q_bits=qb, unroll=self.unroll,
-                                                                           share_rotations=self.share_rotations)
+                                                                           share_rotations=self.share_rotations,
+                                                                           centred_modswitch=self.centred_modswitch)
             elif self.msg_bits <= 4:
                 params = tfhe.default_params(q_bits=qb)
             elif self.msg_bits <= 6 and qb in (None, tfhe.TORUS64, 49):
@@ -110,16 +117,14 @@ class EncryptedMatrixInversion:
             self.engine = tfhe.Engine(params, device=self.device)
             if self.unroll:
                 self.engine.set_bsk_unroll(2)
+        if self.centred_modswitch and self.engine.modswitch != 1:
+            self.engine.set_modswitch(1)
         if self.engine.P.N < (1 << (self.msg_bits + 6)):
             raise ValueError(f"{self.msg_bits}-bit look-ups need a parameter set with N >= {1 << (self.msg_bits + 6)} "
                              f"(this engine has N = {self.engine.P.N})")
         if self.error_budget is None:
-            self.error_budget = self.program.failure_probability(self.engine)
-            if self.share_rotations:
-                from . import error_budget
-                eng = self.engine
-                self.error_budget = error_budget.failure_probability(self.program, eng.P, eng.bsk_precision if eng.q_bits == 65 else None,
-                                                                     getattr(eng, "unroll", 1) == 2, share_rotations=True)
+            from . import error_budget
+            self.error_budget = error_budget.engine_failure_probability(self.program, self.engine, share_rotations=self.share_rotations)
             if self.p_error is not None and self.error_budget["p_fail"] > self.p_error:
                 raise ValueError(f"this circuit's failure probability under the engine's parameters is {self.error_budget['p_fail']:.2e} "
                                  f"> p_error = {self.p_error:g}: pass a wider parameter set (e.g. log_N=11) or let this object choose")

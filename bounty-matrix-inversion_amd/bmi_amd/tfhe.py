@@ -87,6 +87,10 @@ _SIGS = {
     "bmi_set_kernel_variant": [C.c_void_p, C.c_int],
     "bmi_rotation_kernel": [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p)],
     "bmi_set_keyswitch_variant": [C.c_void_p, C.c_int],
+    "bmi_set_modswitch": [C.c_void_p, C.c_uint32],
+    "bmi_get_modswitch": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "bmi_modswitch_centre_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_modswitch_centre_batch_host": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
     "bmi_set_bsk_precision": [C.c_void_p, C.c_uint32],
     "bmi_get_bsk_precision": [C.c_void_p, C.POINTER(C.c_uint32)],
     "bmi_set_bsk_unroll": [C.c_void_p, C.c_uint32],
@@ -498,6 +502,28 @@ class Engine:
         """keyswitch: 0 auto (int8 matrix-core product), 1 scalar kernel"""
         self._ck(self.lib.bmi_set_keyswitch_variant(self.h, int(v)), "bmi_set_keyswitch_variant")
 
+    def set_modswitch(self, mode):
+        """modulus switch of pbs / pbs_shared and their host forms: 0 = standard (default), 1 = centred - the bodies of the
+        keyswitched ciphertexts minus half the sum of the mask words' rounding errors, which takes the rounding variance from
+        (1 + hw(s)) / 12 to (1 + n/4) / 12 positions^2 (2^64 torus and 49-bit field; include/bmi_tfhe.h).  keyswitch and
+        blind_rotate are the same in both modes."""
+        self._ck(self.lib.bmi_set_modswitch(self.h, int(mode)), "bmi_set_modswitch")
+
+    @property
+    def modswitch(self):
+        """the modulus-switch mode in force (0 standard, 1 centred)"""
+        v = C.c_uint32()
+        self._ck(self.lib.bmi_get_modswitch(self.h, C.byref(v)), "bmi_get_modswitch")
+        return v.value
+
+    def modswitch_centre_host(self, small):
+        """the centred bodies of small-key ciphertexts [count][n + 1] (mask words unchanged); whatever the mode"""
+        small = np.ascontiguousarray(small, dtype=np.uint64).reshape(-1, self.P.small)
+        out = np.zeros_like(small)
+        self._ck(self.lib.bmi_modswitch_centre_batch_host(self.h, _ptr(small), small.shape[0], _ptr(out)),
+                 "bmi_modswitch_centre_batch_host")
+        return out
+
     # ---- hot path, host buffers (numpy in / numpy out)
     def pbs_host(self, cts, lut_ids):
         cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, self.P.big)
@@ -584,6 +610,11 @@ class Engine:
     def keyswitch(self, d_in, count, d_small, stream=0):
         self._ck(self.lib.bmi_keyswitch_batch(self.h, _ptr(d_in), count, _ptr(d_small), C.c_void_p(stream)),
                  "bmi_keyswitch_batch")
+
+    def modswitch_centre(self, d_in, count, d_out, stream=0):
+        """d_out = the small ciphertexts d_in [count][n + 1] with centred bodies (bmi_modswitch_centre_batch; d_out may be d_in)"""
+        self._ck(self.lib.bmi_modswitch_centre_batch(self.h, _ptr(d_in), count, _ptr(d_out), C.c_void_p(stream)),
+                 "bmi_modswitch_centre_batch")
 
     def blind_rotate(self, d_small, d_lut_ids, count, d_out, stream=0):
         self._ck(self.lib.bmi_blind_rotate_batch(self.h, _ptr(d_small), _ptr(d_lut_ids), count, _ptr(d_out),

@@ -331,6 +331,8 @@ struct bmi_ctx {
     int variant = 0;
     uint32_t lat_threshold = 512;  // 2 rounds of 256 one-workgroup PBS (11.2 ms) tie with one round of the wave-pair kernel (11.3 ms)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
+    uint32_t modswitch = 0;   // 0 = the rotation kernels' own rounding, 1 = centred (bmi_set_modswitch): bmi_pbs_batch / _shared_batch run
+                              // k_modswitch_centre on the scratch small ciphertexts between the keyswitch and the rotation
     bool ks_mfma_ok = false;
     mutable std::string err;
     bool f64() const { return f.bits == 49; }
@@ -1531,6 +1533,22 @@ int bmi_set_keyswitch_variant(bmi_ctx *c, int variant) {
     return 0;
 }
 
+int bmi_set_modswitch(bmi_ctx *c, uint32_t mode) {
+    if (!c) return -1;
+    if (mode > 1) return fail(c, -1, "modulus-switch mode must be 0 (standard) or 1 (centred)");
+    if (mode == 1 && !c->t64() && !c->f64())
+        return fail(c, -1, "the centred modulus switch exists on the 2^64 torus and the 49-bit field only (Goldilocks is a cross-check engine)");
+    c->modswitch = mode;
+    return 0;
+}
+
+int bmi_get_modswitch(const bmi_ctx *c, uint32_t *mode) {
+    if (!c) return -1;
+    if (!mode) return fail(c, -1, "bmi_get_modswitch: null result pointer");
+    *mode = c->modswitch;
+    return 0;
+}
+
 int bmi_rotation_kernel(const bmi_ctx *c, uint32_t count, const char **name) {
     if (!c || !name) return -1;
     Rot rot;
@@ -1602,6 +1620,19 @@ int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *
     return blind_rotate_batch(c, d_small, d_lut_ids, count, d_out, false, stream);
 }
 
+// The centred modulus switch of `count` small ciphertexts (modswitch_centre.hip): their bodies minus half the sum of the mask words'
+// rounding errors.  Needs no keys; whatever the context's mode.
+int bmi_modswitch_centre_batch(bmi_ctx *c, const uint64_t *d_small_in, uint32_t count, uint64_t *d_small_out, void *stream) {
+    if (!c) return -1;
+    if (count && (!d_small_in || !d_small_out)) return fail(c, -1, "bmi_modswitch_centre_batch: null ciphertext pointer");
+    if (!c->t64() && !c->f64())
+        return fail(c, -1, "the centred modulus switch exists on the 2^64 torus and the 49-bit field only (Goldilocks is a cross-check engine)");
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    const int rc = bmi::launch_modswitch_centre(d_small_in, d_small_out, count, c->P.n, c->P.log_N, c->t64(), (hipStream_t)stream);
+    return rc ? fail(c, -2, std::string("modswitch_centre launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
 int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_out,
                   void *stream) {
     if (!c) return -1;
@@ -1609,6 +1640,7 @@ int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, u
     int rc = ensure_small(c, count);
     if (rc) return rc;
     rc = bmi_keyswitch_batch(c, d_in, count, c->small.get(), stream);
+    if (!rc && c->modswitch == 1) rc = bmi_modswitch_centre_batch(c, c->small.get(), count, c->small.get(), stream);
     if (rc) return rc;
     return bmi_blind_rotate_batch(c, c->small.get(), d_lut_ids, count, d_out, stream);
 }
@@ -1636,6 +1668,7 @@ int bmi_pbs_shared_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_gro
     int rc = ensure_small(c, groups);
     if (!rc) rc = ensure_glwe(c, groups);
     if (!rc) rc = bmi_keyswitch_batch(c, d_in, groups, c->small.get(), stream);
+    if (!rc && c->modswitch == 1) rc = bmi_modswitch_centre_batch(c, c->small.get(), groups, c->small.get(), stream);
     if (!rc) rc = bmi_blind_rotate_glwe_batch(c, c->small.get(), d_base_ids, groups, c->glwe.get(), stream);
     return rc ? rc : bmi_glwe_lookup_batch(c, c->glwe.get(), d_group_ptr, d_base_ids, d_lut_ids, groups, total, d_out, stream);
 }
@@ -1739,6 +1772,21 @@ int bmi_keyswitch_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uin
     rc = bmi_keyswitch_batch(c, c->io_a.get(), count, c->small.get(), c->stream);
     if (rc) return rc;
     HIP_OK(c, hipMemcpyAsync(small_out, c->small.get(), (size_t)count * (c->P.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bmi_modswitch_centre_batch_host(bmi_ctx *c, const uint64_t *small_in, uint32_t count, uint64_t *small_out) {
+    if (!c) return -1;
+    if (!small_in || !small_out) return fail(c, -1, "bmi_modswitch_centre_batch_host: null ciphertext pointer");
+    HIP_OK(c, hipSetDevice(c->device));
+    int rc = ensure_small(c, count);
+    if (rc) return rc;
+    const size_t bytes = (size_t)count * (c->P.n + 1) * 8;
+    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_modswitch_centre_batch(c, c->small.get(), count, c->small.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(small_out, c->small.get(), bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -144,6 +144,9 @@ int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32
 // secret key as big_n / 64 words of bits
 int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
                      uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
+// modswitch_centre.hip: out = the `count` small ciphertexts in ([count][n + 1], may be the same buffer) with the body minus half the
+// sum of the mask words' rounding errors to the 2N positions; torus: q = 2^64, else the 49-bit field (Goldilocks has no such kernel)
+int launch_modswitch_centre(const u64 *in, u64 *out, uint32_t count, uint32_t n, uint32_t log_N, bool torus, hipStream_t s);
 }  // namespace bmi
 
 // The same launchers for the 49-bit field (bmi_kernels_f64.hip): NTT-domain key, twiddles and test polynomials are f64.

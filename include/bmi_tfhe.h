@@ -161,6 +161,30 @@ int bmi_pbs_batch(bmi_ctx *ctx, const uint64_t *d_in, const uint32_t *d_lut_ids,
 int bmi_keyswitch_batch(bmi_ctx *ctx, const uint64_t *d_in, uint32_t count, uint64_t *d_small, void *stream);
 int bmi_blind_rotate_batch(bmi_ctx *ctx, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
                            uint64_t *d_out, void *stream);
+/* ---- centred modulus switch (2^64 torus and 49-bit field; csrc/modswitch_centre.hip; TFHE-rs' "centred mean" variant) ----
+ * The rotation rounds the n mask words and the body of a small ciphertext to the 2N positions of the circle.  For a BINARY key s -
+ * which every key path of this library presumes - the rounding error of the switched phase is
+ *      sum_i s_i e_i - e_b  =  sum_i e_i / 2  +  sum_i (s_i - 1/2) e_i  -  e_b,
+ * e_i the rounding error of mask word i and e_b the body's.  The first sum is public: subtracted from the body BEFORE the body is
+ * rounded, it leaves sum (s_i - 1/2) e_i - e_b, of variance (1 + n/4) / 12 positions^2 whatever the key's weight, against
+ * (1 + hw(s)) / 12 ~ (1 + n/2) / 12 of the standard switch.  No key material, no change to a rotation kernel: the rotation's own
+ * rounding of the new body yields the compensated switch.  Under the unrolled key (bmi_set_bsk_unroll) the exponents
+ * (a^ + a^', a^, a^') of a step are sums of the same rounded words, so the same compensation applies.
+ * Exactly:  torus, S = 64 - log2(2N):  e_i = ((a_i + 2^(S-1)) mod 2^S) - 2^(S-1),  b' = b - (sum_i e_i >> 1) mod 2^64 (arithmetic shift);
+ *           field, q = 2^49 - 720895:  A_i = floor((a_i 2N + (q >> 1)) / q),  E_i = a_i 2N - A_i q,  b' = b - floor(sum_i E_i / 4N) mod q.
+ *
+ * bmi_set_modswitch: mode 0 (default) = the standard switch, every word as before; mode 1 = centred: bmi_pbs_batch,
+ * bmi_pbs_shared_batch and their *_host forms rewrite the bodies of their scratch small ciphertexts between the keyswitch and the
+ * rotation, on the caller's stream.  Other values are refused, and mode 1 on Goldilocks (a cross-check engine).  Independent of the
+ * key set, the unrolling, the kernel variant and the ring size; may be switched at any time.
+ * bmi_keyswitch_batch, bmi_blind_rotate_batch and bmi_blind_rotate_glwe_batch (and their *_host forms) are UNCHANGED IN BOTH
+ * MODES: they return, resp. rotate, exactly the words they are given.  A caller of the split stages applies
+ * bmi_modswitch_centre_batch between them itself: d_small_in / d_small_out [count][n+1] (may alias; mask words are copied
+ * unchanged, the body is replaced by b').  It needs no keys, works whatever the mode, and count == 0 launches nothing. */
+int bmi_set_modswitch(bmi_ctx *ctx, uint32_t mode);
+int bmi_get_modswitch(const bmi_ctx *ctx, uint32_t *mode);
+int bmi_modswitch_centre_batch(bmi_ctx *ctx, const uint64_t *d_small_in, uint32_t count, uint64_t *d_small_out, void *stream);
+int bmi_modswitch_centre_batch_host(bmi_ctx *ctx, const uint64_t *small_in, uint32_t count, uint64_t *small_out);
 /* ---- one blind rotation shared by the look-ups of the same ciphertext (2^64 torus; csrc/glwe_lookup.hip) ----
  * A test polynomial of bmi_lut_register is a step function, so TV_f = TV_0 * P_f with TV_0 = 2^(unit_log - 1) * sum_x X^x and
  * P_f = (1 - X) TV_f / 2^unit_log a sparse polynomial of at most 2^msg_bits small integers (the differences of neighbouring table

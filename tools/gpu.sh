@@ -12,6 +12,8 @@
 #   timing <br_timing args>      tools/br_timing.py (batches, kernel variants, q_bits)
 #   preset <preset> [batches]    tools/preset_timing.py
 #   wu2ab [args]                 tools/unrolled_wide2_ab.py: the two unrolled N = 2048 kernels alternating -> profiles/unrolled_wide2_ab.txt (BMI_OUT=FILE: elsewhere)
+#   msab [args]                  tools/modswitch_ab.py: the standard and the centred modulus switch alternating in one process
+#                                (BMI_OUT=FILE: its lines also written there)                         -> section 2 of profiles/centred_modswitch_ab.txt
 #   phase  <t64f|t64w> [batches] per-phase cycles of the debug build (make -C csrc prof)
 #   inverse [sizes]              encrypted-inverse wall-clocks on the default engine (bmi_amd/inverse_bench.py)
 #   calibrate [preset:bits:rounds ...]   failure-rate calibration of the error budget + phase-kernel time (tools/gpu_failure_rate.py)
@@ -41,6 +43,7 @@ case "$recipe" in
   timing) timeout -k 10 ${BMI_T:-500} python tools/br_timing.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/timing.log ;;
   preset) timeout -k 10 ${BMI_T:-300} python tools/preset_timing.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/preset_timing.log ;;
   wu2ab) timeout -k 10 ${BMI_T:-420} python tools/unrolled_wide2_ab.py --out "${BMI_OUT:-profiles/unrolled_wide2_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -60 ;;
+  msab) timeout -k 10 ${BMI_T:-420} python tools/modswitch_ab.py ${BMI_OUT:+--out "$BMI_OUT"} "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
   phase)
     k=$1; shift
     timeout -k 10 ${BMI_T:-300} python tools/phase_prof_$k.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/phase_$k.log ;;
@@ -77,5 +80,5 @@ PY
     python3 tools/summarize_prof.py $TAG $B $F/prof $F/summary $F/prof_trace.log > $F/summary/summary.log 2>&1 || { tail -20 $F/summary/summary.log; exit 1; }
     rm -rf $F/prof
     tail -c 1500 $F/bench_default.json; echo; cat $F/summary/summary.log ;;
-  *) sed -n 2,22p "$0"; exit 2 ;;
+  *) sed -n 2,24p "$0"; exit 2 ;;
 esac

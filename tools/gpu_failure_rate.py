@@ -2,7 +2,8 @@
 """Failure-rate calibration of the error budget on the GPU box (bmi_amd/failure_rate.py): observed wrong look-ups through an
 identity table too wide for the parameter set against error_budget.lookup_failure_probability, plus the time of the device
 phase kernel beside a one-term bmi_lincomb_batch over the same rows (same bytes read).
-usage: gpu_failure_rate.py [PRESET:LUT_BITS:ROUNDS ...] [--out FILE] [--commit ID]
+usage: gpu_failure_rate.py [PRESET:LUT_BITS:ROUNDS ...] [--out FILE] [--commit ID] [--centred]
+  --centred: the engines in modulus-switch mode 1 (bmi_set_modswitch; measure() and its prediction follow the engine's mode)
   default cases: north_star_torus64:5:32 secure128_torus:6:8 north_star_torus64:4:1 ; default FILE profiles/failure_rate_calibration.json"""
 import json, os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,17 +48,22 @@ def kernel_times(eng, B=8192, reps=20):
 
 def main():
     args = sys.argv[1:]
+    centred = "--centred" in args
+    if centred:
+        args.remove("--centred")
     opt = {"--out": os.path.join(REPO, "profiles", "failure_rate_calibration.json"), "--commit": None}
     for k in list(opt):
         if k in args:
             i = args.index(k); opt[k] = args[i + 1]; del args[i: i + 2]
     cases = args or DEFAULT_CASES
-    engines, report = {}, {"head_commit": opt["--commit"] or head_commit(), "key_seed": "0x5EED", "cases": [], "kernel_times": []}
+    engines, report = {}, {"head_commit": opt["--commit"] or head_commit(), "key_seed": "0x5EED", "modswitch": int(centred), "cases": [], "kernel_times": []}
     for case in cases:
         preset, bits, rounds = case.split(":")
         if preset not in engines:
             engines[preset] = tfhe.Engine(tfhe.preset_params(preset))
             engines[preset].keygen(0x5EED)
+            if centred:
+                engines[preset].set_modswitch(1)
             report["kernel_times"].append(dict(preset=preset, **kernel_times(engines[preset])))
         res = failure_rate.measure(engines[preset], int(bits), int(rounds))
         report["cases"].append(dict(preset=preset, **res))
