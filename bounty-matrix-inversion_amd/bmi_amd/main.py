@@ -174,18 +174,26 @@ class EncryptedMatrixInversion:
                                  "was traced for (matrix entry too large for qfloat_ints?)")
         return flat
 
-    def encrypt(self, quantized_matrix: np.ndarray, qfloats_signs: np.ndarray) -> np.ndarray:
+    def encrypt(self, quantized_matrix: np.ndarray, qfloats_signs: np.ndarray, seeded=False):
+        """seeded=True (2^64 torus, CSPRNG keys): tfhe.SeededCiphertexts - 8 bytes per input instead of (N + 1) * 8; evaluate and
+        evaluate_many of a server that loaded this client's seeded keys (Engine.import_keys_seeded / load_keys) take them"""
         flat = self._flat_inputs(quantized_matrix, qfloats_signs)
-        return self._engine().encrypt(flat, self._engine().delta_log(self.msg_bits))
+        eng = self._engine()
+        return (eng.encrypt_seeded if seeded else eng.encrypt)(flat, eng.delta_log(self.msg_bits))
 
-    def evaluate(self, encrypted_quantized_matrix: np.ndarray) -> np.ndarray:
-        return self._executor().run(encrypted_quantized_matrix)
+    def _expanded(self, enc):
+        """an input of evaluate: seeded ciphertexts are expanded on the GPU, full ones pass as they are"""
+        from .tfhe import SeededCiphertexts
+        return self._engine().expand_seeded(enc) if isinstance(enc, SeededCiphertexts) else enc
+
+    def evaluate(self, encrypted_quantized_matrix) -> np.ndarray:
+        return self._executor().run(self._expanded(encrypted_quantized_matrix))
 
     def evaluate_many(self, encrypted_quantized_matrices) -> np.ndarray:
         """B encrypted matrices (a sequence of encrypt() results, or one (B, inputs, words) array) through the circuit in ONE walk of
         its levels: every level is B times wider, so the look-ups run on the throughput kernel instead of B x depth rounds of the
         latency kernel (executor.py, `batch`) - the serving form.  Returns (B, outputs, words); decrypt() each."""
-        enc = np.ascontiguousarray(np.stack([np.asarray(e) for e in encrypted_quantized_matrices]), dtype=np.uint64)
+        enc = np.ascontiguousarray(np.stack([np.asarray(self._expanded(e)) for e in encrypted_quantized_matrices]), dtype=np.uint64)
         if enc.ndim != 3:
             raise ValueError("expected B encrypted matrices of shape (inputs, words)")
         return self._executor(enc.shape[0]).run(enc).reshape(enc.shape[0], -1, enc.shape[2])

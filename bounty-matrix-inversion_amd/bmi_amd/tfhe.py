@@ -100,7 +100,44 @@ _SIGS = {
     "bmi_circuit_schedule": [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                              C.POINTER(C.c_int32)],
     "bmi_key_bytes": [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "bmi_seeded_mask_words": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p],
+    "bmi_export_keys_seeded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bmi_import_keys_seeded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bmi_export_bsk_unrolled_seeded": [C.c_void_p, C.c_void_p],
+    "bmi_import_bsk_unrolled_seeded": [C.c_void_p, C.c_void_p],
+    "bmi_encrypt_seeded": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p],
+    "bmi_expand_seeded_batch": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_expand_seeded_batch_host": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p],
 }
+
+# domains of the public mask streams (include/bmi_tfhe.h BMI_SEED_DOMAIN_*): part of the seeded key / ciphertext format
+SEED_DOMAIN_BSK_MASK, SEED_DOMAIN_KSK_MASK, SEED_DOMAIN_ENC_MASK, SEED_DOMAIN_BSK3_MASK = 3, 5, 7, 9
+
+
+def seeded_mask_words(pub_key, nonce, first_word, count):
+    """words first_word .. first_word + count of the ChaCha20 stream (pub_key, nonce) that seeded keys and ciphertexts take their
+    masks from (bmi_seeded_mask_words; context-free, CPU)"""
+    key = np.ascontiguousarray(pub_key, dtype=np.uint32).reshape(-1)
+    if key.size != 8:
+        raise ValueError("the public key has 8 32-bit words")
+    out = np.zeros(int(count), np.uint64)
+    if load_library().bmi_seeded_mask_words(_ptr(key), C.c_uint64(int(nonce)), C.c_uint64(int(first_word)), C.c_uint64(int(count)),
+                                            _ptr(out)):
+        raise BmiError("bmi_seeded_mask_words failed")
+    return out
+
+
+class SeededCiphertexts:
+    """Fresh big-key ciphertexts in seeded form: ciphertext i is (encryption counter first_counter + i, body word bodies[i]); its
+    masks are words of the encrypting context's public stream, which Engine.expand_seeded regenerates on the GPU."""
+
+    def __init__(self, first_counter, bodies):
+        self.first_counter = int(first_counter)
+        # host words, or (for the device form of expand_seeded) a device tensor of int64 words, kept as it is
+        self.bodies = bodies if hasattr(bodies, "data_ptr") else np.ascontiguousarray(bodies, dtype=np.uint64).reshape(-1)
+
+    def __len__(self):
+        return int(self.bodies.numel()) if hasattr(self.bodies, "numel") else self.bodies.size
 
 
 def circuit_prune(n_in, node_ptr, term_leaf, out_leaf):
@@ -273,20 +310,37 @@ class Engine:
         else:
             self._ck(self.lib.bmi_keygen_insecure_deterministic(self.h, C.c_uint64(seed)), "bmi_keygen_insecure_deterministic")
 
-    def keygen_shared(self, seed=None, group=None, src=0, share_secret=False):
+    def keygen_shared(self, seed=None, group=None, src=0, share_secret=False, seeded=False):
         """One set of EVALUATION keys on every rank of a torch.distributed group WITHOUT the seeded (test-only) generator: rank
         `src` generates the key set (CSPRNG when seed is None) and broadcasts the bootstrap and keyswitch keys (about 100 MB at
         the north-star set; the unrolled key too in unrolled mode); the other ranks import them as evaluation-only contexts -
         the secret keys stay on `src`, the only rank that can encrypt / decrypt (share_secret=True replicates them as well, over
         whatever transport the group uses: only for tests and trusted single-node groups).  With a single process this is
-        keygen(seed).  The sharded executor needs the same evaluation keys on every GPU and checks it (executor.py)."""
-        import torch
+        keygen(seed).  The sharded executor needs the same evaluation keys on every GPU and checks it (executor.py).
+        seeded=True (opt-in): the public key and the body words travel (0.3 of the bytes at the default set) and every rank expands
+        the masks on its own GPU; where the seeded export is refused (a deterministic seed, a prime field, share_secret) the full
+        form travels as before."""
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
             return self.keygen(seed)
         rank = dist.get_rank(group)
         unrolled = getattr(self, "unroll", 1) == 2     # the unrolled bootstrap key travels with the set
         P, rows = self.P, (self.P.k + 1) * self.P.bs_levels
+        if seeded and seed is None and not share_secret and self.q_bits == TORUS64:   # what the seeded export takes, known on every rank
+            if rank == src:
+                self.keygen()
+                pub, bsk_body, ksk_body = self.export_keys_seeded()
+                parts = [pub.astype(np.uint64), bsk_body, ksk_body] + ([self.export_bsk_unrolled_seeded()] if unrolled else [])
+            else:
+                parts = [np.zeros(8, np.uint64), np.zeros((P.n, rows, P.N), np.uint64), np.zeros((P.k * P.N, P.ks_levels), np.uint64)]
+                if unrolled:
+                    parts.append(np.zeros(self.unrolled_key_shape()[:3] + (P.N,), np.uint64))
+            self._broadcast_parts(parts, group, src)
+            if rank != src:
+                self.import_keys_seeded(parts[0].astype(np.uint32), parts[1], parts[2])
+                if unrolled:
+                    self.import_bsk_unrolled_seeded(parts[3])
+            return
         if rank == src:
             self.keygen(seed)
             sk_small, sk_big, bsk, ksk = self.export_keys()
@@ -296,6 +350,18 @@ class Engine:
                     [np.zeros((P.n, rows, P.k + 1, P.N), np.uint64), np.zeros((P.k * P.N, P.ks_levels, P.n + 1), np.uint64)]
             if unrolled:
                 parts.append(np.zeros(self.unrolled_key_shape(), np.uint64))
+        self._broadcast_parts(parts, group, src)
+        if rank != src:
+            sec = parts[:2] if share_secret else [None, None]
+            ev = parts[2:] if share_secret else parts
+            self.import_keys(sec[0], sec[1], ev[0], ev[1])
+            if unrolled:
+                self.import_bsk_unrolled(ev[2])
+
+    def _broadcast_parts(self, parts, group, src):
+        """the uint64 arrays `parts` from rank `src` into the same arrays on every rank (through the GPU when the backend is RCCL)"""
+        import torch
+        import torch.distributed as dist
         on_gpu = dist.get_backend(group) == "nccl"
         for a in parts:
             t = torch.from_numpy(a.view(np.int64))
@@ -304,12 +370,6 @@ class Engine:
             dist.broadcast(t, src=src, group=group)
             if on_gpu:
                 a.view(np.int64)[...] = t.cpu().numpy()
-        if rank != src:
-            sec = parts[:2] if share_secret else [None, None]
-            ev = parts[2:] if share_secret else parts
-            self.import_keys(sec[0], sec[1], ev[0], ev[1])
-            if unrolled:
-                self.import_bsk_unrolled(ev[2])
 
     def eval_key_fingerprint(self):
         """64-bit fingerprint of the evaluation keys this context holds (bootstrap, keyswitch and, in unrolled mode, the unrolled
@@ -350,6 +410,40 @@ class Engine:
                 raise BmiError("secret key arrays do not match this context's parameters")
         self._ck(self.lib.bmi_import_keys(self.h, _ptr(sk_small), _ptr(sk_big), _ptr(bsk), _ptr(ksk)), "bmi_import_keys")
 
+    def export_keys_seeded(self):
+        """(pub_key[8] uint32, bsk_body (n, rows, N), ksk_body (k N, ks_levels)): the evaluation keys without their masks, which
+        are words of the ChaCha20 stream of pub_key (include/bmi_tfhe.h).  2^64 torus, CSPRNG keys generated by this context."""
+        P = self.P
+        pub = np.zeros(8, np.uint32)
+        bsk_body = np.zeros((P.n, (P.k + 1) * P.bs_levels, P.N), np.uint64)
+        ksk_body = np.zeros((P.k * P.N, P.ks_levels), np.uint64)
+        self._ck(self.lib.bmi_export_keys_seeded(self.h, _ptr(pub), _ptr(bsk_body), _ptr(ksk_body)), "bmi_export_keys_seeded")
+        return pub, bsk_body, ksk_body
+
+    def import_keys_seeded(self, pub_key, bsk_body, ksk_body):
+        """loads the key set of export_keys_seeded: the masks are expanded on the GPU; this context becomes evaluation-only.  For
+        the exporter's key word for word, store the key at the exporter's precision (in unrolled mode: set_bsk_unroll(2) first)."""
+        P = self.P
+        pub = np.ascontiguousarray(pub_key, dtype=np.uint32).reshape(-1)
+        bsk_body = np.ascontiguousarray(bsk_body, dtype=np.uint64)
+        ksk_body = np.ascontiguousarray(ksk_body, dtype=np.uint64)
+        if pub.size != 8 or bsk_body.size != P.n * (P.k + 1) * P.bs_levels * P.N or ksk_body.size != P.k * P.N * P.ks_levels:
+            raise BmiError("seeded key arrays do not match this context's parameters")
+        self._ck(self.lib.bmi_import_keys_seeded(self.h, _ptr(pub), _ptr(bsk_body), _ptr(ksk_body)), "bmi_import_keys_seeded")
+
+    def export_bsk_unrolled_seeded(self):
+        """the body polynomials (pairs, 3, rows, N) of the unrolled bootstrap key; its masks come from export_keys_seeded's pub_key"""
+        body = np.zeros(self.unrolled_key_shape()[:3] + (self.P.N,), np.uint64)
+        self._ck(self.lib.bmi_export_bsk_unrolled_seeded(self.h, _ptr(body)), "bmi_export_bsk_unrolled_seeded")
+        return body
+
+    def import_bsk_unrolled_seeded(self, bsk3_body):
+        """the unrolled key of export_bsk_unrolled_seeded, after import_keys_seeded (whose public key expands its masks)"""
+        body = np.ascontiguousarray(bsk3_body, dtype=np.uint64)
+        if body.size != int(np.prod(self.unrolled_key_shape()[:3])) * self.P.N:
+            raise BmiError("unrolled key bodies do not match this context's parameters")
+        self._ck(self.lib.bmi_import_bsk_unrolled_seeded(self.h, _ptr(body)), "bmi_import_bsk_unrolled_seeded")
+
     def keygen_from_secret(self, sk_small, sk_big, seed=0):
         """evaluation keys for binary secret keys made elsewhere (e.g. by a Concrete client); seed=0: CSPRNG masks and
         noise, seed != 0: deterministic test vectors (not cryptographic)"""
@@ -369,9 +463,23 @@ class Engine:
 
     _PARAM_FIELDS = ("n", "log_N", "k", "bs_levels", "bs_base_log", "ks_levels", "ks_base_log", "q_bits", "lwe_noise", "glwe_noise")
 
-    def save_keys(self, path, secret=True):
+    def save_keys(self, path, secret=True, seeded=False):
         """Key file (numpy .npz): the parameter set and the standard-domain keys.  secret=False writes the evaluation
-        keys only - what a server needs (the reference's analogue: Concrete's key cache, qfloat_matrix_inversion.py:997)."""
+        keys only - what a server needs (the reference's analogue: Concrete's key cache, qfloat_matrix_inversion.py:997).
+        seeded=True (evaluation keys only: refused with secret=True): the seeded form - pub_key, bsk_body, ksk_body, in unrolled
+        mode bsk_unrolled_body, params, and bsk_precision (the precision the bodies were rounded at, which the loading context
+        must store the key at) - 0.3 of the full file at the default set; load_keys expands the masks on the GPU."""
+        if seeded:
+            if secret:
+                raise BmiError("a seeded key file holds evaluation keys only: save_keys(path, secret=False, seeded=True)")
+            pub, bsk_body, ksk_body = self.export_keys_seeded()
+            arrays = {"pub_key": pub, "bsk_body": bsk_body, "ksk_body": ksk_body, "bsk_precision": np.array([self.bsk_precision]),
+                      "params": np.array([float(getattr(self.P, f)) for f in self._PARAM_FIELDS])}
+            if getattr(self, "unroll", 1) == 2:
+                arrays["bsk_unrolled_body"] = self.export_bsk_unrolled_seeded()
+            with open(path, "wb") as f:
+                np.savez(f, **arrays)
+            return
         sk_small, sk_big, bsk, ksk = self.export_keys(secret=secret)
         arrays = {"bsk": bsk, "ksk": ksk, "params": np.array([float(getattr(self.P, f)) for f in self._PARAM_FIELDS])}
         if secret:
@@ -391,6 +499,17 @@ class Engine:
                 theirs[7] = 64.0
             if mine != theirs:
                 raise BmiError(f"key file parameters {theirs} differ from this context's {mine}")
+            if "pub_key" in z.files:                 # the seeded form (save_keys(..., seeded=True)): evaluation keys only
+                unrolled = "bsk_unrolled_body" in z.files
+                if unrolled:                         # before the keys: the mode decides the precision they are stored at
+                    self.set_bsk_unroll(2)
+                prec = int(z["bsk_precision"][0])
+                if self.bsk_precision != prec:       # the masks must be rounded the way the writer's were
+                    self.set_bsk_precision(prec)
+                self.import_keys_seeded(z["pub_key"], z["bsk_body"], z["ksk_body"])
+                if unrolled:
+                    self.import_bsk_unrolled_seeded(z["bsk_unrolled_body"])
+                return False
             has_secret = "sk_small" in z.files
             self.import_keys(z["sk_small"] if has_secret else None, z["sk_big"] if has_secret else None, z["bsk"], z["ksk"])
             if "bsk_unrolled" in z.files:            # written by a context in unrolled mode: this one switches to it too
@@ -410,6 +529,39 @@ class Engine:
         msgs = np.ascontiguousarray(msgs, dtype=np.int64).reshape(-1)
         out = np.zeros((msgs.size, self.P.big), np.uint64)
         self._ck(self.lib.bmi_encrypt(self.h, _ptr(msgs), msgs.size, delta_log, _ptr(out)), "bmi_encrypt")
+        return out
+
+    def encrypt_seeded(self, msgs, delta_log):
+        """encrypt() in seeded form: SeededCiphertexts(first_counter, bodies), 8 bytes per ciphertext - the ciphertexts encrypt()
+        would have returned at this context's encryption counter, without their masks (bmi_encrypt_seeded)"""
+        msgs = np.ascontiguousarray(msgs, dtype=np.int64).reshape(-1)
+        bodies = np.zeros(msgs.size, np.uint64)
+        first = C.c_uint64(0)
+        self._ck(self.lib.bmi_encrypt_seeded(self.h, _ptr(msgs), msgs.size, delta_log, C.byref(first), _ptr(bodies)),
+                 "bmi_encrypt_seeded")
+        return SeededCiphertexts(first.value, bodies)
+
+    def expand_seeded(self, seeded, d_out=None, stream=0):
+        """SeededCiphertexts -> the full ciphertexts (count, k N + 1), masks regenerated on the GPU from this context's public key
+        (a server: the one of import_keys_seeded).  Host form (d_out None): numpy in, numpy out.  Device form: seeded.bodies may
+        be a device tensor of int64 words, d_out is a device tensor of count x (k N + 1) words, filled on `stream`."""
+        if d_out is not None:
+            bodies = seeded.bodies
+            count = int(bodies.numel()) if hasattr(bodies, "numel") else int(bodies.size)
+            if isinstance(bodies, np.ndarray):       # host bodies into a device tensor beside d_out
+                import torch
+                bodies = torch.from_numpy(bodies.view(np.int64)).to(d_out.device)
+            self._ck(self.lib.bmi_expand_seeded_batch(self.h, C.c_uint64(seeded.first_counter), _ptr(bodies), count, _ptr(d_out),
+                                                      C.c_void_p(stream)), "bmi_expand_seeded_batch")
+            return d_out
+        return self.expand_seeded_host(seeded.first_counter, seeded.bodies)
+
+    def expand_seeded_host(self, first_counter, bodies):
+        """the ciphertexts (first_counter + i, bodies[i]) in full: (count, k N + 1) uint64 (bmi_expand_seeded_batch_host)"""
+        bodies = np.ascontiguousarray(bodies, dtype=np.uint64).reshape(-1)
+        out = np.zeros((bodies.size, self.P.big), np.uint64)
+        self._ck(self.lib.bmi_expand_seeded_batch_host(self.h, C.c_uint64(int(first_counter)), _ptr(bodies), bodies.size, _ptr(out)),
+                 "bmi_expand_seeded_batch_host")
         return out
 
     def decrypt(self, cts, delta_log):

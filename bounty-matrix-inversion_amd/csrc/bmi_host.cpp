@@ -89,6 +89,10 @@ struct Stream {
     }
 };
 enum : u64 { S_SK_SMALL = 1, S_SK_BIG, S_BSK_MASK, S_BSK_NOISE, S_KSK_MASK, S_KSK_NOISE, S_ENC_MASK, S_ENC_NOISE, S_BSK3_MASK, S_BSK3_NOISE };
+// the mask domains are part of the seeded key / ciphertext format (include/bmi_tfhe.h)
+static_assert(S_BSK_MASK == BMI_SEED_DOMAIN_BSK_MASK && S_KSK_MASK == BMI_SEED_DOMAIN_KSK_MASK && S_ENC_MASK == BMI_SEED_DOMAIN_ENC_MASK &&
+                  S_BSK3_MASK == BMI_SEED_DOMAIN_BSK3_MASK,
+              "the published stream domains are the ones key generation uses");
 
 // --------------------------------------------------------------------------- CSPRNG (production keys and encryptions)
 // ChaCha20 (D. J. Bernstein's original variant: 256-bit key, 64-bit nonce, 64-bit block counter) keyed from the
@@ -136,6 +140,10 @@ struct ChaStream {
     uint32_t buf[16];
     int pos = 16;
     ChaStream(const ChaKey &k, u64 domain, u64 row) : key(&k), nonce((domain << 56) | (row & ((1ULL << 56) - 1))) {}
+    // the stream of a whole nonce, positioned at its 64-bit word `first_word` (bmi_seeded_mask_words)
+    ChaStream(const ChaKey &k, u64 whole_nonce, u64 first_word, int) : key(&k), nonce(whole_nonce), counter(first_word / 8) {
+        for (u64 skip = first_word % 8; skip; skip--) (void)next64();
+    }
     u64 next64() {
         if (pos > 14) {
             chacha_block(*key, nonce, counter++, buf);
@@ -249,6 +257,12 @@ struct bmi_ctx {
     int bsk_limbs() const { return t64::limbs_of(bsk_prec); }
     bool secure_rng = false;       // true: keys / encryptions drawn from the CSPRNG below; false: test-only seeded streams
     ChaKey rng_secret, rng_public; // independent ChaCha20 keys from getrandom(): secrets + noise / public masks
+    // Where the mask words of the evaluation keys held came from (beside have_keys; the seeded forms of chacha_expand.hip):
+    // OWN_STREAM = drawn by this context from rng_public (CSPRNG key generation), SEEDED_IMPORT = expanded from the public key of
+    // bmi_import_keys_seeded, which rng_public then holds; OTHER = anything else (bmi_import_keys, the deterministic test streams):
+    // such masks are no function of a public key that may be told.
+    enum class MaskSource { OTHER, OWN_STREAM, SEEDED_IMPORT } mask_src = MaskSource::OTHER;
+    bool bsk3_from_stream = false; // ... and the same for the unrolled key held: its masks are words of rng_public's S_BSK3_MASK streams
     std::vector<u64> sk_small, sk_big, bsk_std, ksk;
     // Tables (bmi_ctx_create), with the kernels that read them; empty where the context's modulus and N have no such kernel.
     DevBuf<u64> tw_gl;          // Goldilocks: wave-NTT twiddles (ntt_wave.hpp) - bsk_to_ntt, negacyclic_mul, blind_rotate_lat / _tp
@@ -569,7 +583,18 @@ void gen_ggsw_rows(bmi_ctx *c, uint64_t seed, u64 mask_stream, u64 noise_stream,
             for (uint32_t t = 0; t < N; t++)
                 if (skb[(size_t)j * N + t]) add_shifted(f, B, A, t, N);
         }
-        if (bits[i]) row[(size_t)comp * N] = f.add(row[(size_t)comp * N], (u64)1 << (f.bits - bl * (lev + 1)));
+        if (!bits[i]) return;
+        const u64 g = (u64)1 << (f.bits - bl * (lev + 1));
+        if (secure && comp < k) {
+            // CSPRNG keys: a row of component comp < k encrypts -g S_comp in its BODY (the form of TFHE-rs and Concrete; the same
+            // phase, the same noise), so that every mask word stays a word of the public stream - what the seeded form of the key
+            // rests on.  Adding g to the mask polynomial instead, as below, would make that word tell the key bit to whoever
+            // knows the stream.
+            for (uint32_t x = 0; x < N; x++)
+                if (skb[(size_t)comp * N + x]) B[x] = f.sub(B[x], g);
+        } else {
+            row[(size_t)comp * N] = f.add(row[(size_t)comp * N], g);   // deterministic test keys: as oracle/tfhe_oracle.c ggsw_rows
+        }
     });
 }
 
@@ -586,6 +611,7 @@ void gen_bsk3(bmi_ctx *c, uint64_t seed) {
     }
     c->bsk3_std.assign(c->bsk3_words(), 0);
     gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, msg, c->bsk3_std.data());
+    c->bsk3_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
 }
 
 // Builds one key copy of `bytes` bytes into a fresh buffer (launch(buffer) converts into it on the context's stream) and moves
@@ -780,6 +806,7 @@ int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
     // body's noise, std 2^20, is then rounded to the grid too and vanishes in 95 % of the words: not an LWE sample any more.)
     gen_ggsw_rows(c, seed, S_BSK_MASK, S_BSK_NOISE, c->sk_small, c->bsk_std.data());
     c->have_bsk3 = false;
+    c->mask_src = c->secure_rng ? bmi_ctx::MaskSource::OWN_STREAM : bmi_ctx::MaskSource::OTHER;
     if (c->unroll == 2) gen_bsk3(c, seed);
     // --- keyswitch key
     c->ksk.assign((size_t)k * N * lk * (n + 1), 0);
@@ -1241,6 +1268,7 @@ int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big
     c->have_keys = false;
     drop_sk_mask(c);
     c->have_bsk3 = false;   // an unrolled key belongs to the key set it was generated with: import it again (bmi_import_bsk_unrolled)
+    c->mask_src = bmi_ctx::MaskSource::OTHER;
     c->bsk_std.assign(bsk, bsk + bsk_words);
     c->ksk.assign(ksk, ksk + ksk_words);
     c->have_secret = sk_small != nullptr;
@@ -1278,8 +1306,9 @@ int bmi_key_bytes(const bmi_ctx *c, uint64_t *bsk_bytes, uint64_t *ksk_bytes) {
     return 0;
 }
 
-int bmi_encrypt(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *ct_out) {
-    if (!c || !msgs || !ct_out) return -1;
+// bmi_encrypt (ct_out: [count][k N + 1] words) and bmi_encrypt_seeded (bodies_out: [count] body words; the masks are not kept) are
+// this one routine: ciphertext i takes the encryption counter first + i, its masks from the public stream, its noise from the secret one
+static int encrypt_rows(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *ct_out, uint64_t *bodies_out) {
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
     if (delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
@@ -1294,17 +1323,24 @@ int bmi_encrypt(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_
     const double sigma = c->P.glwe_noise;
     parallel_for(count, [=](size_t i) {
         RowRng sm(smp, *kpub, S_ENC_MASK, first + i, secure), se(sep, *ksec, S_ENC_NOISE, first + i, secure);
-        u64 *ct = ct_out + i * (dim + 1);
+        u64 *ct = ct_out ? ct_out + i * (dim + 1) : nullptr;
         const u64 torus = f.mul(f.from_i64(msgs[i]), (u64)1 << delta_log);
         u64 b = f.add(torus, se.gauss(first + i, sigma));
         for (uint32_t x = 0; x < dim; x++) {
-            ct[x] = sm.uniform((first + i) * (u64)(dim + 1) + x);
-            if (key[x]) b = f.add(b, ct[x]);
+            const u64 a = sm.uniform((first + i) * (u64)(dim + 1) + x);
+            if (ct) ct[x] = a;
+            if (key[x]) b = f.add(b, a);
         }
-        ct[dim] = b;
+        if (ct) ct[dim] = b;
+        else bodies_out[i] = b;
     });
     c->enc_counter += count;
     return 0;
+}
+
+int bmi_encrypt(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *ct_out) {
+    if (!c || !msgs || !ct_out) return -1;
+    return encrypt_rows(c, msgs, count, delta_log, ct_out, nullptr);
 }
 
 int bmi_phase(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint64_t *phase) {
@@ -1516,6 +1552,7 @@ int bmi_import_bsk_unrolled(bmi_ctx *c, const uint64_t *bsk3) {
     for (size_t i = 0; i < words; i++)
         if (!c->f.canonical(bsk3[i])) return fail(c, -1, "unrolled bootstrap key word not reduced mod q");
     c->bsk3_std.assign(bsk3, bsk3 + words);
+    c->bsk3_from_stream = false;
     return upload_bsk3(c);
 }
 
@@ -1918,6 +1955,147 @@ int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, ui
     if (c->ops->negacyclic_mul(c, da.get(), db.get(), dc.get(), count)) return fail(c, -2, "negacyclic_mul launch failed");
     HIP_OK(c, hipStreamSynchronize(c->stream));
     HIP_OK(c, hipMemcpy(out, dc.get(), words * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------- seeded keys and ciphertexts (chacha_expand.hip)
+// The specification of the seeded forms: words first_word .. first_word + count of the ChaCha20 stream (pub_key, nonce), drawn the
+// way key generation draws a row's masks on the 2^64 torus (ChaStream::next64).  Context-free, host only.
+int bmi_seeded_mask_words(const uint32_t pub_key[8], uint64_t nonce, uint64_t first_word, uint64_t count, uint64_t *out) {
+    if (!pub_key || (count && !out)) return -1;
+    ChaKey key;
+    std::memcpy(key.k, pub_key, sizeof(key.k));
+    ChaStream s(key, nonce, first_word, 0);
+    for (u64 i = 0; i < count; i++) out[i] = s.next64();
+    return 0;
+}
+
+// What the seeded forms need of a context: masks that are words of a public stream whose key may be told.  `what` names the caller.
+static int seeded_ok(const bmi_ctx *c, const char *what) {
+    if (!c->t64())
+        return fail(c, -1, std::string(what) + ": seeded forms exist on the 2^64 torus only - on the 49-bit field and Goldilocks the masks are "
+                           "rejection-sampled, so a mask word's position in the stream depends on the words before it");
+    if (!c->have_keys) return fail(c, -1, std::string(what) + ": no keys: call bmi_keygen first");
+    if (c->mask_src == bmi_ctx::MaskSource::OTHER)
+        return fail(c, -1, std::string(what) + ": the masks of this key set did not come from the context's own public stream (keys loaded by "
+                           "bmi_import_keys, or deterministic test keys, whose stream key is an invertible function of the seed and would "
+                           "reveal the secrets): no seeded form");
+    return 0;
+}
+
+// One seeded array -> its full standard-domain form in `full` ([rows][mask_w + body_w] host words): the compact bodies are uploaded
+// and placed behind the masks (k_place_bodies), the masks are expanded on the device (k_chacha_expand, rows numbered from 0 in
+// `domain`), and the host copy is filled from the device buffer.
+static int expand_seeded_key(bmi_ctx *c, u64 domain, size_t rows, uint32_t mask_w, uint32_t body_w, const u64 *bodies, std::vector<u64> &full) {
+    const size_t pitch = (size_t)mask_w + body_w;
+    DevBuf<u64> d_bodies, d_full;
+    HIP_OK(c, d_bodies.alloc(rows * body_w * 8));
+    HIP_OK(c, d_full.alloc(rows * pitch * 8));
+    HIP_OK(c, hipMemcpyAsync(d_bodies.get(), bodies, rows * body_w * 8, hipMemcpyHostToDevice, c->stream));
+    int rc = bmi::launch_place_bodies(d_bodies.get(), d_full.get() + mask_w, pitch, body_w, rows, c->stream);
+    if (!rc) rc = bmi::launch_chacha_expand(d_full.get(), pitch, mask_w, rows, c->rng_public.k, domain, 0, c->stream);
+    if (rc) return fail(c, -2, std::string("chacha_expand launch: ") + hipGetErrorString((hipError_t)rc));
+    full.resize(rows * pitch);
+    HIP_OK(c, hipMemcpyAsync(full.data(), d_full.get(), rows * pitch * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the body words ([rows][body_w]) of a standard-domain array [rows][mask_w + body_w]
+static void copy_bodies(const std::vector<u64> &full, size_t rows, uint32_t mask_w, uint32_t body_w, u64 *bodies) {
+    const size_t pitch = (size_t)mask_w + body_w;
+    for (size_t r = 0; r < rows; r++) std::memcpy(bodies + r * body_w, full.data() + r * pitch + mask_w, (size_t)body_w * 8);
+}
+
+int bmi_export_keys_seeded(const bmi_ctx *c, uint32_t pub_key[8], uint64_t *bsk_bodies, uint64_t *ksk_bodies) {
+    if (!c || !pub_key || !bsk_bodies || !ksk_bodies) return -1;
+    if (int rc = seeded_ok(c, "bmi_export_keys_seeded")) return rc;
+    std::memcpy(pub_key, c->rng_public.k, sizeof(c->rng_public.k));
+    copy_bodies(c->bsk_std, (size_t)c->P.n * c->rows, c->big_n, c->N, bsk_bodies);
+    copy_bodies(c->ksk, (size_t)c->big_n * c->P.ks_levels, c->P.n, 1, ksk_bodies);
+    return 0;
+}
+
+int bmi_import_keys_seeded(bmi_ctx *c, const uint32_t pub_key[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies) {
+    if (!c || !pub_key || !bsk_bodies || !ksk_bodies) return -1;
+    if (!c->t64())
+        return fail(c, -1, "bmi_import_keys_seeded: seeded forms exist on the 2^64 torus only - on the 49-bit field and Goldilocks the masks "
+                           "are rejection-sampled, so a mask word's position in the stream depends on the words before it");
+    HIP_OK(c, hipSetDevice(c->device));
+    c->have_keys = false;
+    drop_sk_mask(c);
+    c->have_bsk3 = false;
+    c->bsk3_from_stream = false;
+    c->have_secret = false;   // evaluation-only: the secrets stay with the client
+    c->sk_small.clear();
+    c->sk_big.clear();
+    c->mask_src = bmi_ctx::MaskSource::OTHER;   // until both arrays are expanded
+    std::memcpy(c->rng_public.k, pub_key, sizeof(c->rng_public.k));
+    c->secure_rng = true;
+    if (int rc = expand_seeded_key(c, S_BSK_MASK, (size_t)c->P.n * c->rows, c->big_n, c->N, bsk_bodies, c->bsk_std)) return rc;
+    if (int rc = expand_seeded_key(c, S_KSK_MASK, (size_t)c->big_n * c->P.ks_levels, c->P.n, 1, ksk_bodies, c->ksk)) return rc;
+    // from here on the path of every key set: rounding to the key's precision, key conversions, keyswitch bias and limb form
+    if (int rc = upload_eval_keys(c)) return rc;
+    c->mask_src = bmi_ctx::MaskSource::SEEDED_IMPORT;
+    return 0;
+}
+
+int bmi_export_bsk_unrolled_seeded(const bmi_ctx *c, uint64_t *bsk3_bodies) {
+    if (!c || !bsk3_bodies) return -1;
+    if (int rc = seeded_ok(c, "bmi_export_bsk_unrolled_seeded")) return rc;
+    if (!c->have_bsk3) return fail(c, -1, "no unrolled bootstrap key: bmi_set_bsk_unroll(ctx, 2) before keygen, or import one");
+    if (!c->bsk3_from_stream)
+        return fail(c, -1, "bmi_export_bsk_unrolled_seeded: the masks of this unrolled key did not come from the context's own public stream "
+                           "(a key loaded by bmi_import_bsk_unrolled): no seeded form");
+    copy_bodies(c->bsk3_std, (size_t)c->pairs() * 3 * c->rows, c->big_n, c->N, bsk3_bodies);
+    return 0;
+}
+
+int bmi_import_bsk_unrolled_seeded(bmi_ctx *c, const uint64_t *bsk3_bodies) {
+    if (!c || !bsk3_bodies) return -1;
+    if (!c->have_keys || c->mask_src != bmi_ctx::MaskSource::SEEDED_IMPORT)
+        return fail(c, -1, "bmi_import_bsk_unrolled_seeded: the unrolled key's masks are expanded from the public key of a preceding "
+                           "bmi_import_keys_seeded, and this context has none");
+    if (c->quad()) return fail(c, -1, "bootstrap-key unrolling has no HIP kernel on the 2^64 torus at N = 4096");
+    if (c->wide() && !bmit::shape_supported_wide_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
+        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled key is stored at 40 bits of precision: bmi_set_bsk_unroll(ctx, 2) before the key set");
+    HIP_OK(c, hipSetDevice(c->device));
+    if (int rc = expand_seeded_key(c, S_BSK3_MASK, (size_t)c->pairs() * 3 * c->rows, c->big_n, c->N, bsk3_bodies, c->bsk3_std)) return rc;
+    if (int rc = upload_bsk3(c)) return rc;
+    c->bsk3_from_stream = true;
+    return 0;
+}
+
+int bmi_encrypt_seeded(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *first_counter, uint64_t *bodies) {
+    if (!c || !first_counter || (count && (!msgs || !bodies))) return -1;
+    if (int rc = seeded_ok(c, "bmi_encrypt_seeded")) return rc;
+    const u64 first = c->enc_counter;
+    if (int rc = encrypt_rows(c, msgs, count, delta_log, nullptr, bodies)) return rc;
+    *first_counter = first;
+    return 0;
+}
+
+int bmi_expand_seeded_batch(bmi_ctx *c, uint64_t first_counter, const uint64_t *d_bodies, uint32_t count, uint64_t *d_out, void *stream) {
+    if (!c || (count && (!d_bodies || !d_out))) return -1;
+    if (int rc = seeded_ok(c, "bmi_expand_seeded_batch")) return rc;
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    const size_t pitch = (size_t)c->big_n + 1;
+    int rc = bmi::launch_place_bodies(d_bodies, d_out + c->big_n, pitch, 1, count, (hipStream_t)stream);
+    if (!rc) rc = bmi::launch_chacha_expand(d_out, pitch, c->big_n, count, c->rng_public.k, S_ENC_MASK, first_counter, (hipStream_t)stream);
+    return rc ? fail(c, -2, std::string("chacha_expand launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+int bmi_expand_seeded_batch_host(bmi_ctx *c, uint64_t first_counter, const uint64_t *bodies, uint32_t count, uint64_t *out) {
+    if (!c || (count && (!bodies || !out))) return -1;
+    if (int rc = seeded_ok(c, "bmi_expand_seeded_batch_host")) return rc;
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    if (int rc = ensure_io(c, count)) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->io_b.get(), bodies, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = bmi_expand_seeded_batch(c, first_counter, c->io_b.get(), count, c->io_a.get(), c->stream)) return rc;
+    HIP_OK(c, hipMemcpyAsync(out, c->io_a.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

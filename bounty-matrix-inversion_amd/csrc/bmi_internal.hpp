@@ -147,6 +147,13 @@ int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *
 // modswitch_centre.hip: out = the `count` small ciphertexts in ([count][n + 1], may be the same buffer) with the body minus half the
 // sum of the mask words' rounding errors to the 2N positions; torus: q = 2^64, else the 49-bit field (Goldilocks has no such kernel)
 int launch_modswitch_centre(const u64 *in, u64 *out, uint32_t count, uint32_t n, uint32_t log_N, bool torus, hipStream_t s);
+// chacha_expand.hip (2^64 torus: seeded keys and ciphertexts): row r < rows receives, at base + r * pitch, the first words_per_row
+// words of the ChaCha20 stream (key, nonce (domain << 56) | (first_row + r)) - what bmi_seeded_mask_words returns for that nonce;
+// pitch >= words_per_row, domain < 256, rows of any 8-byte alignment; rows == 0 launches nothing
+int launch_chacha_expand(u64 *base, u64 pitch, uint32_t words_per_row, u64 rows, const uint32_t key[8], u64 domain, u64 first_row,
+                         hipStream_t s);
+// ... and base[r * pitch + j] = bodies[r * w + j] for j < w: the compact body words into their slots behind the masks
+int launch_place_bodies(const u64 *bodies, u64 *base, u64 pitch, uint32_t w, u64 rows, hipStream_t s);
 }  // namespace bmi
 
 // The same launchers for the 49-bit field (bmi_kernels_f64.hip): NTT-domain key, twiddles and test polynomials are f64.

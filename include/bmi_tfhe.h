@@ -374,6 +374,58 @@ int bmi_circuit_prune(uint32_t n_in, uint32_t n_nodes, const int64_t *node_ptr, 
 int bmi_circuit_schedule(uint32_t n_in, uint32_t n_nodes, const int64_t *node_ptr, const int32_t *term_leaf,
                          uint32_t round_, uint32_t wide_round, int32_t *level_out, int32_t *depth_out);
 
+/* ---- seeded evaluation keys and ciphertexts (2^64 torus; csrc/chacha_expand.hip) ---------------------------------------------
+ * More than two thirds of the words of an evaluation key, and all but one word of a fresh ciphertext, are public masks drawn from
+ * the ChaCha20 stream of the context's PUBLIC key (bmi_keygen: one key for secrets and noise, an independent one for the masks).
+ * The seeded forms carry that 32-byte key and the body words only; the receiver regenerates the masks on its GPU.
+ *
+ * The format.  Every row has its own nonce (domain << 56) | row (56 bits of row), domain one of the four below, and its masks
+ * are the first words of the stream (pub_key, nonce): ChaCha20 in D. J. Bernstein's variant (256-bit key, 64-bit block counter
+ * starting at 0, 64-bit nonce), word j = output words (2 (j mod 8), 2 (j mod 8) + 1) of block j / 8, low word first.
+ *   BSK_MASK   row = (i * (k+1) l + r) of GGSW(s_i) row r: k N mask words, then N body words
+ *   BSK3_MASK  the same numbering over the rows of the unrolled key [ceil(n/2)][3][(k+1) l]
+ *   KSK_MASK   row = j * ks_levels + level: n mask words, then one body word
+ *   ENC_MASK   row = the encryption counter of the ciphertext: k N mask words, then the body
+ * (So that every mask word of a bootstrap key IS a stream word, CSPRNG key generation puts the message of a GGSW row of component
+ * < k, -g S, into the row's body - the form of TFHE-rs and Concrete; the deterministic test keys add g to the mask polynomial, as
+ * oracle/tfhe_oracle.c does.  Same phase, same noise; every consumer takes either.)
+ * Bodies are the words bmi_export_keys returns, i.e. rounded to the precision the key is stored at (bmi_set_bsk_precision); the
+ * masks are rounded by the importer the same way, so AN IMPORTER AT THE EXPORTER'S PRECISION holds, in every device-resident copy,
+ * byte for byte the key that bmi_import_keys of the full export gives.  Sizes against the full forms: 0.300 for the default and
+ * the secure128_torus sets, 0.215 for secure128_torus_wide, 0.5 for an unrolled key, 8 bytes instead of (k N + 1) * 8 per ciphertext.
+ *
+ * Refused, with a bmi_last_error text that says why: contexts on the 49-bit field or Goldilocks (their masks are rejection-sampled:
+ * a word's position in the stream depends on the words before it); contexts without keys; and contexts whose masks did not come from
+ * their own public stream - keys loaded by bmi_import_keys, and the deterministic test keys (bmi_keygen_insecure_deterministic,
+ * bmi_keygen_from_secret with seed != 0), whose stream key is an invertible function of the seed and would reveal the secrets. */
+#define BMI_SEED_DOMAIN_BSK_MASK 3u
+#define BMI_SEED_DOMAIN_KSK_MASK 5u
+#define BMI_SEED_DOMAIN_ENC_MASK 7u
+#define BMI_SEED_DOMAIN_BSK3_MASK 9u
+/* out[i] = word first_word + i of the stream (pub_key, nonce), i < count: the specification the device kernel is held to.
+ * Context-free, host only (like bmi_torus64_to_field). */
+int bmi_seeded_mask_words(const uint32_t pub_key[8], uint64_t nonce, uint64_t first_word, uint64_t count, uint64_t *out);
+/* The key set as (public key, bodies): bsk_bodies[n * (k+1) l * N], ksk_bodies[k N * ks_levels]. */
+int bmi_export_keys_seeded(const bmi_ctx *ctx, uint32_t pub_key[8], uint64_t *bsk_bodies, uint64_t *ksk_bodies);
+/* Makes the context evaluation-only with the key set of a bmi_export_keys_seeded: the bodies are uploaded, the masks expanded on
+ * the device, then the path of every key set (rounding, key conversions, keyswitch bias and limb form).  bmi_export_keys then
+ * returns the full key.  The context keeps pub_key: bmi_import_bsk_unrolled_seeded and bmi_expand_seeded_batch use it. */
+int bmi_import_keys_seeded(bmi_ctx *ctx, const uint32_t pub_key[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
+/* The same for the unrolled key (bmi_set_bsk_unroll; N = 1024 at 42 bits, N = 2048 at 40 bits): bsk3_bodies[ceil(n/2) * 3 *
+ * (k+1) l * N].  The import is refused unless a bmi_import_keys_seeded came before it (whose public key it uses); select the
+ * unrolled mode before that call, as the exporter did before its keygen, so that both store the keys at the same precision. */
+int bmi_export_bsk_unrolled_seeded(const bmi_ctx *ctx, uint64_t *bsk3_bodies);
+int bmi_import_bsk_unrolled_seeded(bmi_ctx *ctx, const uint64_t *bsk3_bodies);
+/* bmi_encrypt in seeded form: the ciphertexts bmi_encrypt would have produced at the context's encryption counter, as
+ * (*first_counter, bodies[count]); the counter advances by count.  One routine serves both entry points. */
+int bmi_encrypt_seeded(bmi_ctx *ctx, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *first_counter,
+                       uint64_t *bodies);
+/* d_out [count][k N + 1] = the ciphertexts (first_counter + i, d_bodies[i]) in full, on the caller's stream: masks from the
+ * context's own public key, or from the one imported by bmi_import_keys_seeded on a server.  count == 0 launches nothing. */
+int bmi_expand_seeded_batch(bmi_ctx *ctx, uint64_t first_counter, const uint64_t *d_bodies, uint32_t count, uint64_t *d_out,
+                            void *stream);
+int bmi_expand_seeded_batch_host(bmi_ctx *ctx, uint64_t first_counter, const uint64_t *bodies, uint32_t count, uint64_t *out);
+
 /* bytes of device memory held by the keys: every resident transform-domain copy of the bootstrap key (one per selectable kernel
  * family, plus the unrolled key when present), and the keyswitch key in word form */
 int bmi_key_bytes(const bmi_ctx *ctx, uint64_t *bsk_bytes, uint64_t *ksk_bytes);
