@@ -37,6 +37,15 @@ measured 3.1 x too low for the identity table and 1.7 x too high for a random on
 are the same split of its own variance (3 x the key terms; rounding 2 x per pair of key bits not both zero, once white and once per
 set bit of S): measured within 2 % (tests/test_gpu_shared_rotation_wide_unrolled.py, EXPERIMENTS A23).
 
+Compressed outputs (compressed_outputs=(levels L, base_log b, log_modulus c); include/bmi_tfhe.h, csrc/lwe_pack.hip): an output packed
+with `count` others into a GLWE ciphertext and cut to c bits per word carries, on top of its own variance, compression_variance =
+
+    min(count, N) N L (4^b + 2) / 12 glwe_noise^2   (the key's noise: N L digits of each of the block's ciphertexts)
+  + hw(S) 4^(-L b) / 12                              (the rounding of the mask words to the top L b bits)
+  + (1 + N / 4) / 12 4^(-c)                          (the centred switch of the 2N GLWE words to c bits)
+
+each term held alone to +-15 % (tests/test_compress_model.py, tests/test_gpu_compress.py).
+
 Key weights are random: hw(s) = n / 2, hw(S) = kN / 2 (their expectations) unless given."""
 from __future__ import annotations
 
@@ -108,6 +117,18 @@ def keyswitch_variance(P, hw_big=None):
     return k * N * P.ks_levels * (B * B + 2) / 12.0 * P.lwe_noise ** 2 + hb / (12.0 * B ** (2 * P.ks_levels))
 
 
+def compression_variance(P, levels, base_log, log_modulus, count, hw_big=None):
+    """variance (torus^2, the units of pbs_output_variance) that compression adds to each of `count` ciphertexts packed together
+    (per block of N) at the key shape (levels, base_log) and cut to log_modulus bits: key noise + decomposition rounding + centred
+    modulus switch (module docstring)"""
+    N = 1 << P.log_N
+    hb = P.k * N / 2.0 if hw_big is None else float(hw_big)
+    key = min(int(count), N) * N * levels * (4.0 ** base_log + 2) / 12.0 * P.glwe_noise ** 2
+    rounding = hb * 4.0 ** (-levels * base_log) / 12.0
+    switch = (1 + N / 4.0) / 12.0 * 4.0 ** (-log_modulus)
+    return key + rounding + switch
+
+
 def _log_erfc(x):
     """log10 of erfc(x), finite for large x (erfc underflows beyond x ~ 26)"""
     x = np.asarray(x, np.float64)
@@ -130,9 +151,11 @@ def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0, ce
 
 
 def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None, share_rotations=False,
-                        centred_modswitch=False):
+                        centred_modswitch=False, compressed_outputs=None):
     """Error budget of `prog` (a program.Program) under the parameter set `P` (tfhe.Params or anything with its fields).
     centred_modswitch: the budget of an engine in modulus-switch mode 1 (only the rounding term of the mod-switch changes).
+    compressed_outputs: None, or (levels, base_log, log_modulus) of outputs that come home compressed (Executor.run_compressed):
+    compression_variance of the program's outputs packed together is added to every output's own variance.
 
     Returns a dict: p_fail (probability that at least one look-up or output decodes wrong, union bound), log10_p_fail,
     lookups, worst_margin_sigma (smallest half-box / sigma over the look-ups), p_fail_worst_lookup, widest_amplification
@@ -181,6 +204,8 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
                    widest_amplification=float(amp.max()), sigma_positions_typical=float(np.median(sigma_pos)))
     if prog.n_outputs:
         v_out, _ = lincomb_var(prog.out_ptr, prog.out_leaf, prog.out_coef)
+        if compressed_outputs is not None:
+            v_out = v_out + compression_variance(P, *compressed_outputs, count=prog.n_outputs, hw_big=hw_big)
         m_out = 2.0 ** -(prog.msg_bits + 2) / np.sqrt(np.maximum(v_out, 1e-300))     # Delta / 2 over sigma, Delta = q / 2^(msg_bits + 1)
         log_terms.append(_log_erfc(m_out / math.sqrt(2.0)))
         res["output_margin_sigma"] = float(m_out.min())
@@ -195,14 +220,14 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     return res
 
 
-def engine_failure_probability(prog, eng, hw_small=None, hw_big=None, share_rotations=False):
+def engine_failure_probability(prog, eng, hw_small=None, hw_big=None, share_rotations=False, compressed_outputs=None):
     """failure_probability of `prog` on a live tfhe.Engine as it is configured: its parameters, the precision its bootstrap key is
     stored at, its unrolling and its modulus-switch mode (Engine.modswitch; a stand-in without that attribute counts as mode 0).
     Program.failure_probability(engine) prices the standard switch whatever the engine's mode: program.py is part of the tracer
     fingerprint that names the shipped programs, so the mode is read here instead."""
     return failure_probability(prog, eng.P, eng.bsk_precision if eng.q_bits == TORUS64 else None, getattr(eng, "unroll", 1) == 2,
                                hw_small, hw_big, share_rotations=share_rotations,
-                               centred_modswitch=getattr(eng, "modswitch", 0) == 1)
+                               centred_modswitch=getattr(eng, "modswitch", 0) == 1, compressed_outputs=compressed_outputs)
 
 
 def lookup_failure_probability(P, lut_bits, input_variance=0.0, bsk_precision=None, unroll=False, hw_small=None, hw_big=None,
@@ -244,19 +269,22 @@ def candidate_sets(msg_bits, q_bits=None, secure=False):
     return out
 
 
-def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, share_rotations=False, centred_modswitch=False):
+def choose_params(prog, p_error=1e-5, q_bits=None, secure=False, unroll=False, share_rotations=False, centred_modswitch=False,
+                  compressed_outputs=None):
     """The first candidate set whose failure probability for `prog` is at most p_error (Concrete's `global_p_error`); the report of
-    every set tried.  Raises when none qualifies.  centred_modswitch is passed through to failure_probability."""
+    every set tried.  Raises when none qualifies.  centred_modswitch and compressed_outputs are passed through to
+    failure_probability."""
     from . import tfhe
     tried = []
     for label, spec in candidate_sets(prog.msg_bits, q_bits, secure):
         P = tfhe.preset_params(spec) if isinstance(spec, str) else tfhe.default_params(**spec)
         # unrolled kernels: N = 1024, and the 2^64 torus at N = 2048, whose unrolled key is stored at 40 bits (bmi_set_bsk_unroll)
         if unroll and P.log_N == 11 and P.q_bits == TORUS64:
-            rep = failure_probability(prog, P, 40, unroll=True, share_rotations=share_rotations, centred_modswitch=centred_modswitch)
+            rep = failure_probability(prog, P, 40, unroll=True, share_rotations=share_rotations, centred_modswitch=centred_modswitch,
+                                      compressed_outputs=compressed_outputs)
         else:
             rep = failure_probability(prog, P, unroll=unroll and P.log_N == 10, share_rotations=share_rotations,
-                                      centred_modswitch=centred_modswitch)
+                                      centred_modswitch=centred_modswitch, compressed_outputs=compressed_outputs)
         tried.append((label, rep["p_fail"]))
         if rep["p_fail"] <= p_error:
             return P, dict(rep, chosen=label, tried=tried, p_error=p_error)

@@ -270,6 +270,27 @@ class Executor:
         res = msgs[: self.n_out].cpu().numpy()
         return res if self.batch == 1 else res.reshape(self.batch, -1)
 
+    def run_compressed(self, ct_inputs, log_modulus=16):
+        """run() with the outputs compressed where they are (Engine.compress on the output rows, on the walk's stream: the context
+        must hold a compression key): a tfhe.CompressedCiphertexts - about 4 bytes per output of a full block at 16 bits come home
+        instead of a ciphertext.  With batch > 1 every matrix is compressed separately and a list is returned, so that every client
+        receives its own blocks."""
+        from .tfhe import CompressedCiphertexts, compressed_words
+        torch = self.torch
+        if self.world > 1:
+            raise NotImplementedError("run_compressed is a one-rank form: under torch.distributed call run()")
+        stream = self._walk(ct_inputs)
+        per, N = self.n_out // self.batch, self.eng.P.N
+        words = compressed_words(per, N)
+        with torch.cuda.device(self.dev):
+            packed = torch.empty((self.batch, max(words, 1)), dtype=torch.int32, device=self.dev)
+            for b in range(self.batch):
+                self.eng.compress(self.out[b * per:], per, packed[b], log_modulus, stream=stream)
+            torch.cuda.synchronize(self.dev)
+        host = packed.cpu().numpy().view(np.uint32)
+        res = [CompressedCiphertexts(per, N, log_modulus, host[b, :words]) for b in range(self.batch)]
+        return res[0] if self.batch == 1 else res
+
     def _walk(self, ct_inputs):
         """the level walk of run(): leaves the output ciphertexts in self.out, queued on the stream it returns"""
         torch = self.torch

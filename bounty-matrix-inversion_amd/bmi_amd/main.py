@@ -26,7 +26,7 @@ class EncryptedMatrixInversion:
 
     def __init__(self, n, sampler=None, qfloat_base=2, qfloat_len=32, qfloat_ints=16, true_division=False,
                  tensorize=False, engine=None, device=0, shard_threshold=None, cache=True, unroll=False, q_bits=None,
-                 params=None, p_error=None, share_rotations=False, centred_modswitch=False):
+                 params=None, p_error=None, share_rotations=False, centred_modswitch=False, compress_outputs=False):
         """The reference's seven arguments (main.py:17-36), then: engine / device (the GPU context to use) and
         shard_threshold (with torch.distributed initialised on several ranks, levels at least this wide are split
         across the ranks' GPUs; None = every level wider than one kernel round, levels re-packed for the rank count,
@@ -49,7 +49,11 @@ class EncryptedMatrixInversion:
         variance of a look-up (1 + n/4) / 12 instead of (1 + hw(s)) / 12 positions^2; 6.2 -> 8.8 sigma for a 4-bit look-up of the
         default set) - set on the engine this object creates AND on an engine passed in (whose mode this changes); the p_error
         selection and `self.error_budget` price it.  Works with unroll, share_rotations, evaluate_many and several ranks (every
-        rank's engine must be in the same mode: executor.py)."""
+        rank's engine must be in the same mode: executor.py); compress_outputs (2^64 torus, one rank; True = 16 bits, or a
+        log_modulus in [2, 32]): keygen also makes the compression key (levels 1, base 2^16), evaluate / evaluate_many return
+        tfhe.CompressedCiphertexts - the outputs packed into GLWE ciphertexts and cut to log_modulus bits per word, about 4 bytes
+        per output instead of (N + 1) * 8 - and decrypt takes either form; the error budget and the p_error selection add
+        error_budget.compression_variance to every output.  Under torch.distributed: NotImplementedError."""
         self.shape = (n, n)
         self.qfloat_base, self.qfloat_len, self.qfloat_ints = qfloat_base, qfloat_len, qfloat_ints
         self.true_division, self.tensorize = true_division, tensorize
@@ -73,6 +77,13 @@ class EncryptedMatrixInversion:
         self.p_error = p_error
         self.share_rotations = bool(share_rotations)
         self.centred_modswitch = bool(centred_modswitch)
+        # 0 = outputs come home as full ciphertexts, else the log_modulus they are compressed to
+        self.compress_log_modulus = 16 if compress_outputs is True else int(compress_outputs or 0)
+        if self.compress_log_modulus and not 2 <= self.compress_log_modulus <= 32:
+            raise ValueError("compress_outputs: True (16 bits) or a log_modulus in [2, 32]")
+        if self.compress_log_modulus and self._dist() is not None:
+            raise NotImplementedError("compress_outputs is a one-rank option: under torch.distributed the outputs come home as full "
+                                      "ciphertexts")
         self.error_budget = None      # filled when the engine exists: Program.failure_probability under its parameters
         if engine is not None and params is not None:
             raise ValueError("pass an engine or a parameter set, not both (the engine already has its parameters)")
@@ -95,7 +106,8 @@ class EncryptedMatrixInversion:
                 from . import error_budget
                 params, self.error_budget = error_budget.choose_params(self.program, self.p_error, q_bits=qb, unroll=self.unroll,
                                                                            share_rotations=self.share_rotations,
-                                                                           centred_modswitch=self.centred_modswitch)
+                                                                           centred_modswitch=self.centred_modswitch,
+                                                                           compressed_outputs=self._compressed_outputs())
             elif self.msg_bits <= 4:
                 params = tfhe.default_params(q_bits=qb)
             elif self.msg_bits <= 6 and qb in (None, tfhe.TORUS64, 49):
@@ -124,11 +136,18 @@ class EncryptedMatrixInversion:
                              f"(this engine has N = {self.engine.P.N})")
         if self.error_budget is None:
             from . import error_budget
-            self.error_budget = error_budget.engine_failure_probability(self.program, self.engine, share_rotations=self.share_rotations)
+            self.error_budget = error_budget.engine_failure_probability(self.program, self.engine, share_rotations=self.share_rotations,
+                                                                        compressed_outputs=self._compressed_outputs())
             if self.p_error is not None and self.error_budget["p_fail"] > self.p_error:
                 raise ValueError(f"this circuit's failure probability under the engine's parameters is {self.error_budget['p_fail']:.2e} "
                                  f"> p_error = {self.p_error:g}: pass a wider parameter set (e.g. log_N=11) or let this object choose")
         return self.engine
+
+    COMPRESSION_SHAPE = (1, 16)      # (levels, base_log) of the compression key keygen makes
+
+    def _compressed_outputs(self):
+        """the error budget's `compressed_outputs` argument: (levels, base_log, log_modulus), or None"""
+        return self.COMPRESSION_SHAPE + (self.compress_log_modulus,) if self.compress_log_modulus else None
 
     def keygen(self, seed=None):
         """circuit.keygen() (main.py:177).  seed=None: CSPRNG keys; an integer: the test-only deterministic key set.
@@ -142,9 +161,14 @@ class EncryptedMatrixInversion:
         except Exception:
             shared = False
         if shared:
+            if self.compress_log_modulus:
+                raise NotImplementedError("compress_outputs is a one-rank option: under torch.distributed the outputs come home as "
+                                          "full ciphertexts")
             eng.keygen_shared(seed)
         else:
             eng.keygen(seed)
+            if self.compress_log_modulus:
+                eng.compression_keygen(*self.COMPRESSION_SHAPE)
 
     def _executor(self, batch=1):
         """the executor of this circuit for `batch` input matrices per run (one per batch size, built on first use)"""
@@ -187,15 +211,22 @@ class EncryptedMatrixInversion:
         return self._engine().expand_seeded(enc) if isinstance(enc, SeededCiphertexts) else enc
 
     def evaluate(self, encrypted_quantized_matrix) -> np.ndarray:
+        """the encrypted inverse: (outputs, words) ciphertexts, or with compress_outputs a tfhe.CompressedCiphertexts"""
+        if self.compress_log_modulus:
+            return self._executor().run_compressed(self._expanded(encrypted_quantized_matrix), self.compress_log_modulus)
         return self._executor().run(self._expanded(encrypted_quantized_matrix))
 
     def evaluate_many(self, encrypted_quantized_matrices) -> np.ndarray:
         """B encrypted matrices (a sequence of encrypt() results, or one (B, inputs, words) array) through the circuit in ONE walk of
         its levels: every level is B times wider, so the look-ups run on the throughput kernel instead of B x depth rounds of the
-        latency kernel (executor.py, `batch`) - the serving form.  Returns (B, outputs, words); decrypt() each."""
+        latency kernel (executor.py, `batch`) - the serving form.  Returns (B, outputs, words); decrypt() each.  With
+        compress_outputs: a list of B tfhe.CompressedCiphertexts, every matrix in blocks of its own."""
         enc = np.ascontiguousarray(np.stack([np.asarray(self._expanded(e)) for e in encrypted_quantized_matrices]), dtype=np.uint64)
         if enc.ndim != 3:
             raise ValueError("expected B encrypted matrices of shape (inputs, words)")
+        if self.compress_log_modulus:
+            res = self._executor(enc.shape[0]).run_compressed(enc, self.compress_log_modulus)
+            return res if isinstance(res, list) else [res]
         return self._executor(enc.shape[0]).run(enc).reshape(enc.shape[0], -1, enc.shape[2])
 
     def run_many(self, matrices, validate=True):
@@ -215,7 +246,12 @@ class EncryptedMatrixInversion:
 
     def decrypt(self, encrypted_quantized_inverted_matrix: np.ndarray) -> np.ndarray:
         n2 = self.shape[0] * self.shape[1]
-        m = self._engine().decrypt(encrypted_quantized_inverted_matrix, self._engine().delta_log(self.msg_bits))
+        eng = self._engine()
+        from .tfhe import CompressedCiphertexts
+        if isinstance(encrypted_quantized_inverted_matrix, CompressedCiphertexts):
+            m = eng.decrypt_compressed(encrypted_quantized_inverted_matrix, eng.delta_log(self.msg_bits))
+        else:
+            m = eng.decrypt(encrypted_quantized_inverted_matrix, eng.delta_log(self.msg_bits))
         return m.reshape(n2, self.qfloat_len + 1)
 
     def dequantize(self, quantized_inverted_matrix: np.ndarray) -> np.ndarray:

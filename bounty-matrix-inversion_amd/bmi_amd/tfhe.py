@@ -108,10 +108,22 @@ _SIGS = {
     "bmi_encrypt_seeded": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p],
     "bmi_expand_seeded_batch": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
     "bmi_expand_seeded_batch_host": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p],
+    "bmi_compression_keygen": [C.c_void_p, C.c_uint32, C.c_uint32],
+    "bmi_compression_key_info": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+    "bmi_export_compression_key": [C.c_void_p, C.c_void_p],
+    "bmi_import_compression_key": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_export_compression_key_seeded": [C.c_void_p, C.c_void_p],
+    "bmi_import_compression_key_seeded": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_compressed_words": [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)],
+    "bmi_compress_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_compress_batch_host": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_phase_compressed": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_decrypt_compressed": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
 }
 
 # domains of the public mask streams (include/bmi_tfhe.h BMI_SEED_DOMAIN_*): part of the seeded key / ciphertext format
 SEED_DOMAIN_BSK_MASK, SEED_DOMAIN_KSK_MASK, SEED_DOMAIN_ENC_MASK, SEED_DOMAIN_BSK3_MASK = 3, 5, 7, 9
+SEED_DOMAIN_PKSK_MASK = 11      # the compression key's masks
 
 
 def seeded_mask_words(pub_key, nonce, first_word, count):
@@ -138,6 +150,55 @@ class SeededCiphertexts:
 
     def __len__(self):
         return int(self.bodies.numel()) if hasattr(self.bodies, "numel") else self.bodies.size
+
+
+def compressed_words(count, N):
+    """values of the compressed form of `count` ciphertexts: per block of N its N mask values, then its body values"""
+    return -(-int(count) // int(N)) * int(N) + int(count)
+
+
+class CompressedCiphertexts:
+    """`count` big-key ciphertexts in compressed form (Engine.compress_host; include/bmi_tfhe.h): per block of N ciphertexts one
+    GLWE ciphertext whose 2N words are cut to log_modulus bits - words = uint32 values below 2^log_modulus, per block N mask values
+    then the block's body values.  The wire form (tobytes / frombytes) is a 16-byte header - the magic b"BMIC", count, N and
+    log_modulus as little-endian uint32 - then the values as uint16 for log_modulus <= 16 and uint32 otherwise."""
+    MAGIC = b"BMIC"
+    HEADER_BYTES = 16
+
+    def __init__(self, count, N, log_modulus, words):
+        self.count, self.N, self.log_modulus = int(count), int(N), int(log_modulus)
+        self.words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        if not 2 <= self.log_modulus <= 32:
+            raise ValueError("log_modulus must be in [2, 32]")
+        if self.words.size != compressed_words(self.count, self.N):
+            raise ValueError(f"{self.count} ciphertexts at N = {self.N} compress to {compressed_words(self.count, self.N)} values, "
+                             f"not {self.words.size}")
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def nbytes(self):
+        """bytes of the wire form"""
+        return self.HEADER_BYTES + self.words.size * (2 if self.log_modulus <= 16 else 4)
+
+    def tobytes(self):
+        head = self.MAGIC + np.array([self.count, self.N, self.log_modulus], "<u4").tobytes()
+        return head + self.words.astype("<u2" if self.log_modulus <= 16 else "<u4").tobytes()
+
+    @classmethod
+    def frombytes(cls, data):
+        data = bytes(data)
+        if len(data) < cls.HEADER_BYTES or data[:4] != cls.MAGIC:
+            raise ValueError("not a compressed ciphertext list")
+        count, N, log_modulus = (int(v) for v in np.frombuffer(data, "<u4", 3, 4))
+        if N not in (1024, 2048, 4096) or not 2 <= log_modulus <= 32:
+            raise ValueError("compressed ciphertext list with an impossible header")
+        dt = "<u2" if log_modulus <= 16 else "<u4"
+        want = compressed_words(count, N)
+        if len(data) != cls.HEADER_BYTES + want * np.dtype(dt).itemsize:
+            raise ValueError("compressed ciphertext list of the wrong length")
+        return cls(count, N, log_modulus, np.frombuffer(data, dt, want, cls.HEADER_BYTES).astype(np.uint32))
 
 
 def circuit_prune(n_in, node_ptr, term_leaf, out_leaf):
@@ -444,6 +505,84 @@ class Engine:
             raise BmiError("unrolled key bodies do not match this context's parameters")
         self._ck(self.lib.bmi_import_bsk_unrolled_seeded(self.h, _ptr(body)), "bmi_import_bsk_unrolled_seeded")
 
+    # ---- compression of output ciphertexts (2^64 torus; include/bmi_tfhe.h, csrc/lwe_pack.hip)
+    def compression_keygen(self, levels=1, base_log=16):
+        """the packing keyswitch key of the key set held (needs the secret keys): N * levels GLWE rows under the context's own GLWE
+        key; 16.8 MB at the defaults and N = 1024.  A new key set (keygen, import_keys, load_keys) drops it.  One shape per key
+        set: a second call with another (levels, base_log) is refused until the next key set (it would reuse the rows' mask and
+        noise streams under other messages, which reveals the secret key; include/bmi_tfhe.h)."""
+        self._ck(self.lib.bmi_compression_keygen(self.h, int(levels), int(base_log)), "bmi_compression_keygen")
+
+    def compression_key_info(self):
+        """(levels, base_log, bytes on the device); levels == 0: no compression key"""
+        lv, bl, by = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._ck(self.lib.bmi_compression_key_info(self.h, C.byref(lv), C.byref(bl), C.byref(by)), "bmi_compression_key_info")
+        return lv.value, bl.value, by.value
+
+    def export_compression_key(self):
+        """(N, levels, 2, N) uint64, standard domain: row (j, l) = [mask polynomial, body polynomial]"""
+        levels = self.compression_key_info()[0]
+        key = np.zeros((self.P.N, max(levels, 1), 2, self.P.N), np.uint64)
+        self._ck(self.lib.bmi_export_compression_key(self.h, _ptr(key)), "bmi_export_compression_key")
+        return key
+
+    def import_compression_key(self, key, levels, base_log):
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        if key.size != self.P.N * int(levels) * 2 * self.P.N:
+            raise BmiError("compression key array does not match this context's parameters and levels")
+        self._ck(self.lib.bmi_import_compression_key(self.h, int(levels), int(base_log), _ptr(key)), "bmi_import_compression_key")
+
+    def export_compression_key_seeded(self):
+        """the body polynomials (N, levels, N); the masks are words of export_keys_seeded's pub_key (domain SEED_DOMAIN_PKSK_MASK)"""
+        levels = self.compression_key_info()[0]
+        body = np.zeros((self.P.N, max(levels, 1), self.P.N), np.uint64)
+        self._ck(self.lib.bmi_export_compression_key_seeded(self.h, _ptr(body)), "bmi_export_compression_key_seeded")
+        return body
+
+    def import_compression_key_seeded(self, bodies, levels, base_log):
+        """the compression key of export_compression_key_seeded, after import_keys_seeded (whose public key expands its masks)"""
+        bodies = np.ascontiguousarray(bodies, dtype=np.uint64)
+        if bodies.size != self.P.N * int(levels) * self.P.N:
+            raise BmiError("compression key bodies do not match this context's parameters and levels")
+        self._ck(self.lib.bmi_import_compression_key_seeded(self.h, int(levels), int(base_log), _ptr(bodies)),
+                 "bmi_import_compression_key_seeded")
+
+    def compressed_words(self, count):
+        w = C.c_uint64()
+        self._ck(self.lib.bmi_compressed_words(self.h, int(count), C.byref(w)), "bmi_compressed_words")
+        return w.value
+
+    def compress(self, d_in, count, d_out, log_modulus=16, stream=0):
+        """d_out (device tensor of compressed_words(count) 32-bit values) = the compressed form of the `count` big-key ciphertexts
+        d_in [count][N + 1] (device words), on `stream` (bmi_compress_batch)"""
+        self._ck(self.lib.bmi_compress_batch(self.h, _ptr(d_in), int(count), int(log_modulus), _ptr(d_out), C.c_void_p(stream)),
+                 "bmi_compress_batch")
+
+    def compress_host(self, cts, log_modulus=16):
+        """numpy ciphertexts (count, N + 1) -> CompressedCiphertexts"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, self.P.big)
+        out = np.zeros(compressed_words(cts.shape[0], self.P.N), np.uint32)
+        self._ck(self.lib.bmi_compress_batch_host(self.h, _ptr(cts), cts.shape[0], int(log_modulus), _ptr(out)),
+                 "bmi_compress_batch_host")
+        return CompressedCiphertexts(cts.shape[0], self.P.N, log_modulus, out)
+
+    def _compressed(self, cc):
+        if cc.N != self.P.N:
+            raise BmiError(f"ciphertexts compressed at N = {cc.N} on a context with N = {self.P.N}")
+        return cc
+
+    def phase_compressed(self, cc):
+        """phases (uint64) of a CompressedCiphertexts under this context's secret key (host)"""
+        out = np.zeros(self._compressed(cc).count, np.uint64)
+        self._ck(self.lib.bmi_phase_compressed(self.h, _ptr(cc.words), cc.count, cc.log_modulus, _ptr(out)), "bmi_phase_compressed")
+        return out
+
+    def decrypt_compressed(self, cc, delta_log):
+        out = np.zeros(self._compressed(cc).count, np.int64)
+        self._ck(self.lib.bmi_decrypt_compressed(self.h, _ptr(cc.words), cc.count, cc.log_modulus, int(delta_log), _ptr(out)),
+                 "bmi_decrypt_compressed")
+        return out
+
     def keygen_from_secret(self, sk_small, sk_big, seed=0):
         """evaluation keys for binary secret keys made elsewhere (e.g. by a Concrete client); seed=0: CSPRNG masks and
         noise, seed != 0: deterministic test vectors (not cryptographic)"""
@@ -468,7 +607,9 @@ class Engine:
         keys only - what a server needs (the reference's analogue: Concrete's key cache, qfloat_matrix_inversion.py:997).
         seeded=True (evaluation keys only: refused with secret=True): the seeded form - pub_key, bsk_body, ksk_body, in unrolled
         mode bsk_unrolled_body, params, and bsk_precision (the precision the bodies were rounded at, which the loading context
-        must store the key at) - 0.3 of the full file at the default set; load_keys expands the masks on the GPU."""
+        must store the key at) - 0.3 of the full file at the default set; load_keys expands the masks on the GPU.
+        Either form carries the compression key, if the engine holds one, and its (levels, base_log): in full, or in a seeded file
+        as its bodies (a compression key that was loaded by import_compression_key has no seeded form and travels in full there)."""
         if seeded:
             if secret:
                 raise BmiError("a seeded key file holds evaluation keys only: save_keys(path, secret=False, seeded=True)")
@@ -477,6 +618,12 @@ class Engine:
                       "params": np.array([float(getattr(self.P, f)) for f in self._PARAM_FIELDS])}
             if getattr(self, "unroll", 1) == 2:
                 arrays["bsk_unrolled_body"] = self.export_bsk_unrolled_seeded()
+            if self.compression_key_info()[0]:       # the compression key travels with the set: its bodies and (levels, base_log)
+                try:
+                    arrays["compression_key_body"] = self.export_compression_key_seeded()
+                except BmiError:                     # a key loaded by import_compression_key has no seeded form: it travels in full
+                    arrays["compression_key"] = self.export_compression_key()
+                arrays["compression_shape"] = np.array(self.compression_key_info()[:2])
             with open(path, "wb") as f:
                 np.savez(f, **arrays)
             return
@@ -486,6 +633,9 @@ class Engine:
             arrays.update(sk_small=sk_small, sk_big=sk_big)
         if getattr(self, "unroll", 1) == 2:          # the unrolled bootstrap key travels with the set
             arrays["bsk_unrolled"] = self.export_bsk_unrolled()
+        if self.q_bits == TORUS64 and self.compression_key_info()[0]:
+            arrays["compression_key"] = self.export_compression_key()
+            arrays["compression_shape"] = np.array(self.compression_key_info()[:2])
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -509,6 +659,10 @@ class Engine:
                 self.import_keys_seeded(z["pub_key"], z["bsk_body"], z["ksk_body"])
                 if unrolled:
                     self.import_bsk_unrolled_seeded(z["bsk_unrolled_body"])
+                if "compression_key_body" in z.files:
+                    self.import_compression_key_seeded(z["compression_key_body"], *(int(v) for v in z["compression_shape"]))
+                elif "compression_key" in z.files:
+                    self.import_compression_key(z["compression_key"], *(int(v) for v in z["compression_shape"]))
                 return False
             has_secret = "sk_small" in z.files
             self.import_keys(z["sk_small"] if has_secret else None, z["sk_big"] if has_secret else None, z["bsk"], z["ksk"])
@@ -517,6 +671,8 @@ class Engine:
                 self.import_bsk_unrolled(z["bsk_unrolled"])
             elif getattr(self, "unroll", 1) == 2 and has_secret:
                 self.set_bsk_unroll(2)               # no unrolled key in the file: derived from the secret keys just loaded
+            if "compression_key" in z.files:
+                self.import_compression_key(z["compression_key"], *(int(v) for v in z["compression_shape"]))
         return has_secret
 
     def key_bytes(self):

@@ -88,10 +88,10 @@ struct Stream {
         return f.from_i64(e);
     }
 };
-enum : u64 { S_SK_SMALL = 1, S_SK_BIG, S_BSK_MASK, S_BSK_NOISE, S_KSK_MASK, S_KSK_NOISE, S_ENC_MASK, S_ENC_NOISE, S_BSK3_MASK, S_BSK3_NOISE };
+enum : u64 { S_SK_SMALL = 1, S_SK_BIG, S_BSK_MASK, S_BSK_NOISE, S_KSK_MASK, S_KSK_NOISE, S_ENC_MASK, S_ENC_NOISE, S_BSK3_MASK, S_BSK3_NOISE, S_PKSK_MASK, S_PKSK_NOISE };
 // the mask domains are part of the seeded key / ciphertext format (include/bmi_tfhe.h)
 static_assert(S_BSK_MASK == BMI_SEED_DOMAIN_BSK_MASK && S_KSK_MASK == BMI_SEED_DOMAIN_KSK_MASK && S_ENC_MASK == BMI_SEED_DOMAIN_ENC_MASK &&
-                  S_BSK3_MASK == BMI_SEED_DOMAIN_BSK3_MASK,
+                  S_BSK3_MASK == BMI_SEED_DOMAIN_BSK3_MASK && S_PKSK_MASK == BMI_SEED_DOMAIN_PKSK_MASK,
               "the published stream domains are the ones key generation uses");
 
 // --------------------------------------------------------------------------- CSPRNG (production keys and encryptions)
@@ -319,6 +319,15 @@ struct bmi_ctx {
     bool quad() const { return N == 4096; }
     DevBuf<u64> ksk_padded, ks_bias;   // keyswitch key, rows padded to ks_stride words, and its bias vector - keyswitch
     DevBuf<signed char> ks_limbs;      // the keyswitch key as ops->ks_limbs limbs in MFMA operand order - keyswitch_mfma
+    // compression of output ciphertexts (2^64 torus; lwe_pack.hip): the packing keyswitch key [N][pk_levels][2][N] of the key set held
+    // (pk_levels == 0: none; dropped with the key set), its device copy in the same layout, and the product's bias vector [2N]
+    uint32_t pk_levels = 0, pk_base_log = 0;
+    // the (levels, base log) bmi_compression_keygen first used on the key set held (0: not yet): a row's masks and noise are the streams
+    // (key, domain, row number) read from their start, so a second key of ANOTHER shape would reuse them under other messages - refused
+    uint32_t pk_gen_levels = 0, pk_gen_base_log = 0;
+    bool pksk_from_stream = false;     // its masks are words of rng_public's S_PKSK_MASK streams (as bsk3_from_stream)
+    std::vector<u64> pksk;
+    DevBuf<u64> pksk_dev, pk_bias;
     DevBuf<u64> sk_mask;               // the big SECRET key as big_n / 64 words of bits, built on first use (ensure_sk_mask), zeroed and
                                        // dropped with the key set (drop_sk_mask) - lwe_phase
     uint32_t n_luts = 0, lut_cap = 0;
@@ -342,6 +351,10 @@ struct bmi_ctx {
     DevBuf<unsigned __int128> ks_partial;   // partial sums of the sliced scalar keyswitch
     DevBuf<signed char> ks_digits;     // matrix-core keyswitch: digit matrix ...
     DevBuf<int> ks_sums;               // ... and int32 sums
+    DevBuf<uint32_t> pk_digits;        // compression: digit matrix of a slice ...
+    DevBuf<u64> pk_T, pk_acc;          // ... its products [slice][2N], and the block's accumulator [2N]
+    DevBuf<u64> pk_in;                 // host-buffer form: input ciphertexts ...
+    DevBuf<uint32_t> pk_out;           // ... and compressed values
     int variant = 0;
     uint32_t lat_threshold = 512;  // 2 rounds of 256 one-workgroup PBS (11.2 ms) tie with one round of the wave-pair kernel (11.3 ms)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
@@ -403,6 +416,18 @@ void drop_sk_mask(bmi_ctx *c) {
     (void)hipMemset(c->sk_mask.get(), 0, c->sk_mask.bytes());
     (void)hipDeviceSynchronize();
     c->sk_mask.reset();
+}
+// a compression key belongs to the key set it was made for: gone with it (queued kernels may still read it)
+// new_key_set: the streams are new as well (or will never be read again): the shape bmi_compression_keygen is held to is forgotten
+void drop_compression_key(bmi_ctx *c, bool new_key_set) {
+    if (new_key_set) c->pk_gen_levels = c->pk_gen_base_log = 0;
+    if (!c->pksk_dev.empty()) (void)hipDeviceSynchronize();
+    c->pk_levels = c->pk_base_log = 0;
+    c->pksk_from_stream = false;
+    c->pksk.clear();
+    c->pksk.shrink_to_fit();
+    c->pksk_dev.reset();
+    c->pk_bias.reset();
 }
 // keyswitched ciphertexts of a batch (room for 1,024 at least)
 int ensure_small(bmi_ctx *c, size_t count) {
@@ -795,6 +820,7 @@ const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfm
 int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
     HIP_OK(c, hipSetDevice(c->device));
     drop_sk_mask(c);
+    drop_compression_key(c, true);
     const bmi_params &P = c->P;
     const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels, rows = c->rows;
     c->seed = seed;
@@ -1267,6 +1293,7 @@ int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big
         if (!c->f.canonical(ksk[i])) return fail(c, -1, "keyswitch key word not reduced mod q");
     c->have_keys = false;
     drop_sk_mask(c);
+    drop_compression_key(c, true);
     c->have_bsk3 = false;   // an unrolled key belongs to the key set it was generated with: import it again (bmi_import_bsk_unrolled)
     c->mask_src = bmi_ctx::MaskSource::OTHER;
     c->bsk_std.assign(bsk, bsk + bsk_words);
@@ -2024,6 +2051,7 @@ int bmi_import_keys_seeded(bmi_ctx *c, const uint32_t pub_key[8], const uint64_t
     HIP_OK(c, hipSetDevice(c->device));
     c->have_keys = false;
     drop_sk_mask(c);
+    drop_compression_key(c, true);
     c->have_bsk3 = false;
     c->bsk3_from_stream = false;
     c->have_secret = false;   // evaluation-only: the secrets stay with the client
@@ -2096,6 +2124,241 @@ int bmi_expand_seeded_batch_host(bmi_ctx *c, uint64_t first_counter, const uint6
     if (int rc = bmi_expand_seeded_batch(c, first_counter, c->io_b.get(), count, c->io_a.get(), c->stream)) return rc;
     HIP_OK(c, hipMemcpyAsync(out, c->io_a.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+
+// ------------------------------------------------------------------- compression of output ciphertexts (lwe_pack.hip)
+// What every compression entry point needs of a context, and of a (levels, base log) pair.  `what` names the caller.
+static int compression_ok(const bmi_ctx *c, const char *what) {
+    if (!c->t64())
+        return fail(c, -1, std::string(what) + ": compression of output ciphertexts exists on the 2^64 torus only (not on the 49-bit field or "
+                           "Goldilocks)");
+    if (!c->have_keys) return fail(c, -1, std::string(what) + ": no keys: call bmi_keygen first");
+    return 0;
+}
+static int compression_shape_ok(const bmi_ctx *c, const char *what, uint32_t levels, uint32_t base_log) {
+    if (levels < 1 || levels > 4 || base_log < 1 || base_log > 16 || levels * base_log > 63)
+        return fail(c, -1, std::string(what) + ": the compression key's decomposition needs 1 <= levels <= 4, 1 <= base_log <= 16 and "
+                           "levels * base_log <= 63");
+    return 0;
+}
+static int compression_key_held(const bmi_ctx *c, const char *what) {
+    if (int rc = compression_ok(c, what)) return rc;
+    if (!c->pk_levels)
+        return fail(c, -1, std::string(what) + ": no compression key: call bmi_compression_keygen or import one (a new key set drops it)");
+    return 0;
+}
+static int log_modulus_ok(const bmi_ctx *c, const char *what, uint32_t log_modulus) {
+    if (log_modulus < 2 || log_modulus > 32) return fail(c, -1, std::string(what) + ": log_modulus must be in [2, 32]");
+    return 0;
+}
+
+// the compression key (host copy in c->pksk, standard layout) -> device, with the bias vector of the unsigned-digit product:
+// bias[col] = 2^(base_log - 1) * sum over all rows of key[row][col]
+static int upload_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
+    const size_t W = (size_t)2 * c->N, K = (size_t)c->N * levels;
+    std::vector<u64> bias(W, 0);
+    for (size_t r = 0; r < K; r++) {
+        const u64 *row = c->pksk.data() + r * W;
+        for (size_t x = 0; x < W; x++) bias[x] += row[x];
+    }
+    for (u64 &b : bias) b <<= base_log - 1;
+    c->pk_levels = 0;
+    HIP_OK(c, upload(c->pksk_dev, c->pksk.data(), c->pksk.size()));
+    HIP_OK(c, upload(c->pk_bias, bias.data(), bias.size()));
+    c->pk_levels = levels;
+    c->pk_base_log = base_log;
+    return 0;
+}
+
+int bmi_compression_keygen(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
+    if (!c) return -1;
+    if (int rc = compression_ok(c, "bmi_compression_keygen")) return rc;
+    if (!c->have_secret) return fail(c, -1, "bmi_compression_keygen: evaluation-only context: it holds no secret key");
+    if (int rc = compression_shape_ok(c, "bmi_compression_keygen", levels, base_log)) return rc;
+    // One shape per key set.  Row jr takes its masks from the public stream (S_PKSK_MASK, jr) and its noise from the secret stream
+    // (S_PKSK_NOISE, jr), both from their first word: a key of another shape would give row jr the same A and e under another
+    // message, and the difference of the two bodies is an exact combination of secret-key bits.  The same shape again gives the
+    // same key.
+    if (c->pk_gen_levels && (c->pk_gen_levels != levels || c->pk_gen_base_log != base_log))
+        return fail(c, -1, "bmi_compression_keygen: this key set already has a compression key of shape (" + std::to_string(c->pk_gen_levels) +
+                           ", " + std::to_string(c->pk_gen_base_log) + "); a second one of another shape would reuse the rows' mask and noise "
+                           "streams under other messages and reveal the secret key: generate a new key set first");
+    HIP_OK(c, hipSetDevice(c->device));
+    drop_compression_key(c, false);
+    c->pk_gen_levels = levels;
+    c->pk_gen_base_log = base_log;
+    const uint32_t N = c->N;
+    c->pksk.assign((size_t)N * levels * 2 * N, 0);
+    const Stream sm_det(c->seed, S_PKSK_MASK, c->f), se_det(c->seed, S_PKSK_NOISE, c->f);
+    const Stream *smp = &sm_det, *sep = &se_det;
+    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
+    const bool secure = c->secure_rng;
+    const u64 *skb = c->sk_big.data();
+    u64 *key = c->pksk.data();
+    const double sigma = c->P.glwe_noise;
+    // row j * levels + lev = [A | B], B = A S + e + S_j 2^(64 - base_log (lev + 1)) X^0: masks from the public stream (CSPRNG keys:
+    // the first N words of the row's stream), noise from the secret one
+    parallel_for((size_t)N * levels, [=](size_t jr) {
+        RowRng sm(smp, *kpub, S_PKSK_MASK, jr, secure), se(sep, *ksec, S_PKSK_NOISE, jr, secure);
+        const uint32_t j = (uint32_t)(jr / levels), lev = (uint32_t)(jr % levels);
+        u64 *A = key + jr * 2 * N, *B = A + N;
+        for (uint32_t x = 0; x < N; x++) A[x] = sm.uniform((u64)jr * N + x);
+        for (uint32_t x = 0; x < N; x++) B[x] = se.gauss((u64)jr * N + x, sigma);
+        for (uint32_t t = 0; t < N; t++) {
+            if (!skb[t]) continue;
+            for (uint32_t x = 0; x + t < N; x++) B[x + t] += A[x];
+            for (uint32_t x = N - t; x < N; x++) B[x + t - N] -= A[x];
+        }
+        if (skb[j]) B[0] += (u64)1 << (64 - base_log * (lev + 1));
+    });
+    if (int rc = upload_compression_key(c, levels, base_log)) return rc;
+    c->pksk_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
+    return 0;
+}
+
+int bmi_compression_key_info(const bmi_ctx *c, uint32_t *levels, uint32_t *base_log, uint64_t *device_bytes) {
+    if (!c) return -1;
+    if (levels) *levels = c->pk_levels;
+    if (base_log) *base_log = c->pk_base_log;
+    if (device_bytes) *device_bytes = c->pk_levels ? c->pksk_dev.bytes() + c->pk_bias.bytes() : 0;
+    return 0;
+}
+
+int bmi_export_compression_key(const bmi_ctx *c, uint64_t *key) {
+    if (!c || !key) return -1;
+    if (int rc = compression_key_held(c, "bmi_export_compression_key")) return rc;
+    std::memcpy(key, c->pksk.data(), c->pksk.size() * 8);
+    return 0;
+}
+
+int bmi_import_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log, const uint64_t *key) {
+    if (!c || !key) return -1;
+    if (int rc = compression_ok(c, "bmi_import_compression_key")) return rc;
+    if (int rc = compression_shape_ok(c, "bmi_import_compression_key", levels, base_log)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    drop_compression_key(c, false);
+    c->pksk.assign(key, key + (size_t)c->N * levels * 2 * c->N);
+    return upload_compression_key(c, levels, base_log);
+}
+
+int bmi_export_compression_key_seeded(const bmi_ctx *c, uint64_t *bodies) {
+    if (!c || !bodies) return -1;
+    if (int rc = seeded_ok(c, "bmi_export_compression_key_seeded")) return rc;
+    if (int rc = compression_key_held(c, "bmi_export_compression_key_seeded")) return rc;
+    if (!c->pksk_from_stream)
+        return fail(c, -1, "bmi_export_compression_key_seeded: the masks of this compression key did not come from the context's own public "
+                           "stream (a key loaded by bmi_import_compression_key): no seeded form");
+    copy_bodies(c->pksk, (size_t)c->N * c->pk_levels, c->N, c->N, bodies);
+    return 0;
+}
+
+int bmi_import_compression_key_seeded(bmi_ctx *c, uint32_t levels, uint32_t base_log, const uint64_t *bodies) {
+    if (!c || !bodies) return -1;
+    if (int rc = compression_ok(c, "bmi_import_compression_key_seeded")) return rc;
+    if (c->mask_src != bmi_ctx::MaskSource::SEEDED_IMPORT)
+        return fail(c, -1, "bmi_import_compression_key_seeded: the compression key's masks are expanded from the public key of a preceding "
+                           "bmi_import_keys_seeded, and this context has none");
+    if (int rc = compression_shape_ok(c, "bmi_import_compression_key_seeded", levels, base_log)) return rc;
+    HIP_OK(c, hipSetDevice(c->device));
+    drop_compression_key(c, false);
+    if (int rc = expand_seeded_key(c, S_PKSK_MASK, (size_t)c->N * levels, c->N, c->N, bodies, c->pksk)) return rc;
+    if (int rc = upload_compression_key(c, levels, base_log)) return rc;
+    c->pksk_from_stream = true;
+    return 0;
+}
+
+int bmi_compressed_words(const bmi_ctx *c, uint32_t count, uint64_t *words) {
+    if (!c || !words) return -1;
+    if (!c->t64()) return fail(c, -1, "bmi_compressed_words: compression of output ciphertexts exists on the 2^64 torus only");
+    *words = ((u64)count + c->N - 1) / c->N * c->N + count;
+    return 0;
+}
+
+int bmi_compress_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint32_t log_modulus, uint32_t *d_out, void *stream) {
+    if (!c || (count && (!d_in || !d_out))) return -1;
+    if (int rc = compression_key_held(c, "bmi_compress_batch")) return rc;
+    if (int rc = log_modulus_ok(c, "bmi_compress_batch", log_modulus)) return rc;
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    const uint32_t N = c->N, slice = bmit::pack_slice(N), widest = std::min(std::min(count, N), slice);
+    // scratch for the widest slice of this call, at least 64 ciphertexts' worth
+    int rc = grow(c, c->pk_digits, (size_t)widest * N * c->pk_levels * 4, (size_t)64 * N * c->pk_levels * 4);
+    if (!rc) rc = grow(c, c->pk_T, (size_t)widest * 2 * N * 8, (size_t)64 * 2 * N * 8);
+    if (!rc) rc = grow(c, c->pk_acc, (size_t)2 * N * 8, (size_t)2 * N * 8);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    for (uint32_t t0 = 0; t0 < count; t0 += N) {   // blocks of N ciphertexts, each in slices
+        const uint32_t m = std::min(N, count - t0);
+        for (uint32_t s0 = 0; s0 < m; s0 += slice) {
+            const int e = bmit::launch_pack_slice(d_in + (size_t)(t0 + s0) * (N + 1), c->pksk_dev.get(), c->pk_bias.get(), c->pk_digits.get(),
+                                                  c->pk_T.get(), c->pk_acc.get(), std::min(slice, m - s0), s0, N, c->pk_levels,
+                                                  c->pk_base_log, st);
+            if (e) return fail(c, -2, std::string("lwe_pack launch: ") + hipGetErrorString((hipError_t)e));
+        }
+        const int e = bmit::launch_pack_switch(c->pk_acc.get(), d_out + (size_t)(t0 / N) * 2 * N, m, N, log_modulus, st);
+        if (e) return fail(c, -2, std::string("lwe_pack switch launch: ") + hipGetErrorString((hipError_t)e));
+    }
+    return 0;
+}
+
+int bmi_compress_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uint32_t log_modulus, uint32_t *out) {
+    if (!c || (count && (!in || !out))) return -1;
+    if (int rc = compression_key_held(c, "bmi_compress_batch_host")) return rc;
+    if (int rc = log_modulus_ok(c, "bmi_compress_batch_host", log_modulus)) return rc;
+    if (count == 0) return 0;
+    HIP_OK(c, hipSetDevice(c->device));
+    const size_t w = (size_t)(c->N + 1) * 8;
+    u64 words = 0;
+    (void)bmi_compressed_words(c, count, &words);
+    int rc = grow(c, c->pk_in, count * w, 256 * w);
+    if (!rc) rc = grow(c, c->pk_out, words * 4, (size_t)2 * c->N * 4);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->pk_in.get(), in, count * w, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_compress_batch(c, c->pk_in.get(), count, log_modulus, c->pk_out.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(out, c->pk_out.get(), words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bmi_phase_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint64_t *phase) {
+    if (!c || (count && (!data || !phase))) return -1;
+    if (int rc = compression_ok(c, "bmi_phase_compressed")) return rc;
+    if (!c->have_secret) return fail(c, -1, "bmi_phase_compressed: evaluation-only context: it holds no secret key");
+    if (int rc = log_modulus_ok(c, "bmi_phase_compressed", log_modulus)) return rc;
+    const uint32_t N = c->N, up = 64 - log_modulus;
+    const u64 *key = c->sk_big.data();
+    std::vector<u64> A(N), AS(N);
+    for (uint32_t t0 = 0; t0 < count; t0 += N) {
+        const uint32_t m = std::min(N, count - t0);
+        const uint32_t *blk = data + (size_t)(t0 / N) * 2 * N;
+        for (uint32_t x = 0; x < N; x++) {
+            if (log_modulus < 32 && (blk[x] >> log_modulus)) return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
+            A[x] = (u64)blk[x] << up;
+        }
+        std::fill(AS.begin(), AS.end(), 0);
+        for (uint32_t t = 0; t < N; t++)
+            if (key[t]) add_shifted(c->f, AS.data(), A.data(), t, N);
+        for (uint32_t i = 0; i < m; i++) {
+            if (log_modulus < 32 && (blk[N + i] >> log_modulus)) return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
+            phase[t0 + i] = ((u64)blk[N + i] << up) - AS[i];
+        }
+    }
+    return 0;
+}
+
+int bmi_decrypt_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint32_t delta_log, int64_t *msgs) {
+    if (!c || (count && (!data || !msgs))) return -1;
+    if (int rc = compression_ok(c, "bmi_decrypt_compressed")) return rc;
+    if (delta_log == 0 || delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
+    std::vector<u64> ph(count);
+    if (int rc = bmi_phase_compressed(c, data, count, log_modulus, ph.data())) return rc;
+    for (uint32_t i = 0; i < count; i++) {
+        const i64 v = (i64)ph[i];
+        msgs[i] = (v >> delta_log) + ((v >> (delta_log - 1)) & 1);
+    }
     return 0;
 }
 

@@ -315,4 +315,14 @@ int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *id
                    const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
 int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
                      uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
+// lwe_pack.hip: compression of output ciphertexts (LWE-to-GLWE packing keyswitch, then a centred modulus switch).
+// pack_slice = the most ciphertexts one launch_pack_slice takes (its T scratch is then 16 MB).  launch_pack_slice: the m
+// ciphertexts cts [m][N + 1], numbers first .. first + m of their block, are decomposed (digits = m * N * levels uint32 words),
+// multiplied with the compression key (key = [N * levels][2N] words, standard layout; bias[col] = 2^(base_log - 1) * the sum of the
+// key's column col; T = m * 2N words) and their rotations X^i T_i are added to acc = [A: N][B: N] (first == 0 initialises it).
+// launch_pack_switch: acc -> out = N mask values then m body values of log_modulus bits, by the centred switch.
+uint32_t pack_slice(uint32_t N);
+int launch_pack_slice(const u64 *cts, const u64 *key, const u64 *bias, uint32_t *digits, u64 *T, u64 *acc, uint32_t m, uint32_t first,
+                      uint32_t N, uint32_t levels, uint32_t base_log, hipStream_t s);
+int launch_pack_switch(const u64 *acc, uint32_t *out, uint32_t m, uint32_t N, uint32_t log_modulus, hipStream_t s);
 }  // namespace bmit

@@ -426,6 +426,57 @@ int bmi_expand_seeded_batch(bmi_ctx *ctx, uint64_t first_counter, const uint64_t
                             void *stream);
 int bmi_expand_seeded_batch_host(bmi_ctx *ctx, uint64_t first_counter, const uint64_t *bodies, uint32_t count, uint64_t *out);
 
+/* ---- compression of output ciphertexts (2^64 torus, k = 1, every N; csrc/lwe_pack.hip) ------------------------------------------
+ * Every output of a circuit is a big-key LWE ciphertext of (N + 1) * 8 bytes.  Up to N of them are packed into the N coefficients of
+ * ONE GLWE ciphertext by a packing keyswitch, and the 2N GLWE words are modulus-switched to log_modulus bits each (TFHE-rs'
+ * compressed ciphertext list): a full block costs 2N values for N results - 4 bytes per result at 16 bits instead of 8,200.
+ * Integer arithmetic mod 2^64 is the specification (restated in numpy in tests/compress_cases.py).
+ *
+ * Compression key (levels L, base_log b; 1 <= L <= 4, 1 <= b <= 16, L b <= 63): row j L + l, for every big-key coefficient j < N
+ *   and level l < L, is a GLWE encryption [A: N words][B: N words], B = A S + e + S_j 2^(64 - b (l + 1)) X^0, under the context's own
+ *   GLWE key S (whose coefficient vector is sk_big), e Gaussian with glwe_noise.  Layout [N][L][2][N] words, standard domain.  Under
+ *   CSPRNG keys the masks A are the first N words of the public stream (domain PKSK_MASK below, row j L + l), the noise comes from
+ *   the secret stream; the seeded form is the bodies B alone, [N][L][N].  Under the deterministic test keys the key is a
+ *   deterministic function of the seed.  A compression key belongs to its key set: keygen or an import of a key set drops it.
+ *   ONE SHAPE PER KEY SET: row j L + l reads its masks and its noise from the start of the streams (key, domain, j L + l), so two
+ *   keys of different (L, b) made for one key set would share A and e in every common row under different messages, and the
+ *   difference of two such bodies is an exact combination of bits of the secret key.  bmi_compression_keygen therefore remembers
+ *   the first shape it used and refuses any other, with a text, until the next keygen or import of a key set (the same shape
+ *   again gives the same key).  A client never publishes two compression keys of different shape for one key set.
+ * Compression of `count` ciphertexts (a_i, b_i), in blocks of N (ciphertext i of a block lands in coefficient i):
+ *   1. d[i][j][l] = the digits of a_i[j] at (L, b): centred lift, round half up to the top L b bits, balanced digits from the least
+ *      significant one, the top digit absorbs the carry (oracle/tfhe_oracle.c ora_decompose);
+ *   2. T_i = (0, b_i X^0) - sum_{j,l} d[i][j][l] row(j, l);
+ *   3. (A, B) = sum_i X^i T_i (negacyclic);
+ *   4. centred modulus switch to c = log_modulus bits (2 <= c <= 32; the rule of bmi_set_modswitch carried over to a polynomial):
+ *      Sh = 64 - c, e_j = ((A_j + 2^(Sh-1)) mod 2^Sh) - 2^(Sh-1), P_x = sum_{j<=x} e_j (int64), E = P_{N-1},
+ *      B'_x = B_x - ((2 P_x - E) >> 1) (arithmetic shift), out A^_j = ((A_j + 2^(Sh-1)) >> Sh) mod 2^c, B^_x likewise from B'_x.
+ *      (No int64 overflow for c > log2 N; below that the sums wrap.)  The switch error is white, of variance (1 + N/4)/12 4^-c.
+ * Compressed form: uint32 values below 2^c; per block N mask values, then its m body values; blocks concatenated:
+ *   bmi_compressed_words = ceil(count / N) * N + count values.
+ * Decryption (host, secret key): phase_i = B^_i 2^(64-c) - ((A^ 2^(64-c)) S)_i, message = round(phase / 2^delta_log) as bmi_decrypt.
+ * The 49-bit field and Goldilocks refuse every entry point with a bmi_last_error text; so do out-of-range arguments and
+ * bmi_compress_batch without a key.  Noise: error_budget.compression_variance. */
+#define BMI_SEED_DOMAIN_PKSK_MASK 11u
+int bmi_compression_keygen(bmi_ctx *ctx, uint32_t levels, uint32_t base_log);   /* needs the secret keys; one shape per key set */
+/* *levels = 0 where the context holds no compression key; device_bytes = the key's device copy and the product's bias vector */
+int bmi_compression_key_info(const bmi_ctx *ctx, uint32_t *levels, uint32_t *base_log, uint64_t *device_bytes);
+int bmi_export_compression_key(const bmi_ctx *ctx, uint64_t *key);              /* [N][L][2][N] */
+int bmi_import_compression_key(bmi_ctx *ctx, uint32_t levels, uint32_t base_log, const uint64_t *key);   /* evaluation-only contexts too */
+/* bodies [N][L][N]; refused as bmi_export_keys_seeded is, and for a key loaded by bmi_import_compression_key */
+int bmi_export_compression_key_seeded(const bmi_ctx *ctx, uint64_t *bodies);
+/* after bmi_import_keys_seeded, whose public key expands the masks on the device: the device then holds word for word the key of the
+ * full import */
+int bmi_import_compression_key_seeded(bmi_ctx *ctx, uint32_t levels, uint32_t base_log, const uint64_t *bodies);
+int bmi_compressed_words(const bmi_ctx *ctx, uint32_t count, uint64_t *words);
+/* d_in [count][N + 1] device words -> d_out [bmi_compressed_words] device uint32 values, on the caller's stream; count == 0
+ * launches nothing.  The context's scratch grows on demand (a block is processed in slices of at most 16 MB of products). */
+int bmi_compress_batch(bmi_ctx *ctx, const uint64_t *d_in, uint32_t count, uint32_t log_modulus, uint32_t *d_out, void *stream);
+int bmi_compress_batch_host(bmi_ctx *ctx, const uint64_t *in, uint32_t count, uint32_t log_modulus, uint32_t *out);
+int bmi_phase_compressed(const bmi_ctx *ctx, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint64_t *phase);
+int bmi_decrypt_compressed(const bmi_ctx *ctx, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint32_t delta_log,
+                           int64_t *msgs);
+
 /* bytes of device memory held by the keys: every resident transform-domain copy of the bootstrap key (one per selectable kernel
  * family, plus the unrolled key when present), and the keyswitch key in word form */
 int bmi_key_bytes(const bmi_ctx *ctx, uint64_t *bsk_bytes, uint64_t *ksk_bytes);

@@ -14,6 +14,8 @@
 #   wu2ab [args]                 tools/unrolled_wide2_ab.py: the two unrolled N = 2048 kernels alternating -> profiles/unrolled_wide2_ab.txt (BMI_OUT=FILE: elsewhere)
 #   msab [args]                  tools/modswitch_ab.py: the standard and the centred modulus switch alternating in one process
 #                                (BMI_OUT=FILE: its lines also written there)                         -> section 2 of profiles/centred_modswitch_ab.txt
+#   cab [args]                   tools/compress_ab.py: compression of output ciphertexts timed beside a round of bootstraps, and the 3x3
+#                                inverse by run against run_compressed alternating in one process    -> profiles/compress_outputs_ab.txt (BMI_OUT=FILE: elsewhere)
 #   phase  <t64f|t64w> [batches] per-phase cycles of the debug build (make -C csrc prof)
 #   inverse [sizes]              encrypted-inverse wall-clocks on the default engine (bmi_amd/inverse_bench.py)
 #   calibrate [preset:bits:rounds ...]   failure-rate calibration of the error budget + phase-kernel time (tools/gpu_failure_rate.py)
@@ -44,6 +46,7 @@ case "$recipe" in
   preset) timeout -k 10 ${BMI_T:-300} python tools/preset_timing.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/preset_timing.log ;;
   wu2ab) timeout -k 10 ${BMI_T:-420} python tools/unrolled_wide2_ab.py --out "${BMI_OUT:-profiles/unrolled_wide2_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -60 ;;
   msab) timeout -k 10 ${BMI_T:-420} python tools/modswitch_ab.py ${BMI_OUT:+--out "$BMI_OUT"} "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
+  cab) timeout -k 10 ${BMI_T:-420} python tools/compress_ab.py --out "${BMI_OUT:-profiles/compress_outputs_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
   phase)
     k=$1; shift
     timeout -k 10 ${BMI_T:-300} python tools/phase_prof_$k.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/phase_$k.log ;;
@@ -80,5 +83,5 @@ PY
     python3 tools/summarize_prof.py $TAG $B $F/prof $F/summary $F/prof_trace.log > $F/summary/summary.log 2>&1 || { tail -20 $F/summary/summary.log; exit 1; }
     rm -rf $F/prof
     tail -c 1500 $F/bench_default.json; echo; cat $F/summary/summary.log ;;
-  *) sed -n 2,24p "$0"; exit 2 ;;
+  *) sed -n 2,26p "$0"; exit 2 ;;
 esac
