@@ -46,6 +46,15 @@ with `count` others into a GLWE ciphertext and cut to c bits per word carries, o
 
 each term held alone to +-15 % (tests/test_compress_model.py, tests/test_gpu_compress.py).
 
+Decompressed inputs (input_variance=...; csrc/lwe_unpack.hip): decompression back to an LWE ciphertext adds no noise of its own - the
+phase of the decompressed ciphertext is bit for bit the compressed one - but what a circuit then reads is no fresh encryption: it
+carries decompressed_variance = source_variance + compression_variance.  The caller says what was compressed: source_variance =
+glwe_noise^2 for fresh encryptions compressed by the client's side, and for chained results the output variance of the circuit that
+produced them (a bootstrapped leaf: pbs_output_variance times its squared coefficients).  failure_probability(..., input_variance=v)
+then uses v (a scalar, or one value per input) for the input leaves in place of glwe_noise^2.  At the key shape (1, 16) the
+rounding term alone is a standard deviation of 2^-13.3 of the torus whatever log_modulus is; it is not negligible against a look-up's
+margin (2x2 inverse on the default set: 10^-5.77 fresh, 10^-5.26 from (1, 16, 16), useless at 12 bits).
+
 Key weights are random: hw(s) = n / 2, hw(S) = kN / 2 (their expectations) unless given."""
 from __future__ import annotations
 
@@ -129,6 +138,13 @@ def compression_variance(P, levels, base_log, log_modulus, count, hw_big=None):
     return key + rounding + switch
 
 
+def decompressed_variance(P, levels, base_log, log_modulus, count, source_variance, hw_big=None):
+    """variance (torus^2) of a ciphertext decompressed from `count` packed together at the key shape (levels, base_log) and
+    log_modulus bits: what the compressed ciphertext carried (source_variance: glwe_noise^2 for a fresh encryption, the producing
+    circuit's output variance for a chained result) plus compression_variance; the decompression adds nothing (module docstring)"""
+    return float(source_variance) + compression_variance(P, levels, base_log, log_modulus, count, hw_big)
+
+
 def _log_erfc(x):
     """log10 of erfc(x), finite for large x (erfc underflows beyond x ~ 26)"""
     x = np.asarray(x, np.float64)
@@ -151,8 +167,10 @@ def _lookup_margin(P, lut_bits, input_variance, v_ks, hs, variance_scale=1.0, ce
 
 
 def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None, hw_big=None, share_rotations=False,
-                        centred_modswitch=False, compressed_outputs=None):
+                        centred_modswitch=False, compressed_outputs=None, input_variance=None):
     """Error budget of `prog` (a program.Program) under the parameter set `P` (tfhe.Params or anything with its fields).
+    input_variance: None (fresh encryptions: glwe_noise^2), or the variance in torus^2 of the inputs as they arrive - a scalar, or
+    an array of n_inputs values - e.g. decompressed_variance(...) for inputs that arrive compressed (module docstring).
     centred_modswitch: the budget of an engine in modulus-switch mode 1 (only the rounding term of the mod-switch changes).
     compressed_outputs: None, or (levels, base_log, log_modulus) of outputs that come home compressed (Executor.run_compressed):
     compression_variance of the program's outputs packed together is added to every output's own variance.
@@ -167,7 +185,15 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     v_ks = keyswitch_variance(P, hw_big)
     hs = P.n / 2.0 if hw_small is None else float(hw_small)
     leaf_var = np.full(n_in + nn, v_pbs)
-    leaf_var[:n_in] = v_enc
+    if input_variance is None:
+        leaf_var[:n_in] = v_enc
+    else:
+        v_inp = np.asarray(input_variance, np.float64)
+        if v_inp.ndim > 1 or (v_inp.ndim == 1 and v_inp.size != n_in):
+            raise ValueError(f"input_variance: a scalar or {n_in} values, one per input (got shape {v_inp.shape})")
+        if v_inp.size and (not np.all(np.isfinite(v_inp)) or v_inp.min() < 0):
+            raise ValueError("input_variance: variances are finite and not negative")
+        leaf_var[:n_in] = v_inp
     shared = 0
     if share_rotations and nn:
         from .shared_rotation import rotation_groups
@@ -220,14 +246,16 @@ def failure_probability(prog, P, bsk_precision=None, unroll=False, hw_small=None
     return res
 
 
-def engine_failure_probability(prog, eng, hw_small=None, hw_big=None, share_rotations=False, compressed_outputs=None):
+def engine_failure_probability(prog, eng, hw_small=None, hw_big=None, share_rotations=False, compressed_outputs=None,
+                               input_variance=None):
     """failure_probability of `prog` on a live tfhe.Engine as it is configured: its parameters, the precision its bootstrap key is
     stored at, its unrolling and its modulus-switch mode (Engine.modswitch; a stand-in without that attribute counts as mode 0).
     Program.failure_probability(engine) prices the standard switch whatever the engine's mode: program.py is part of the tracer
     fingerprint that names the shipped programs, so the mode is read here instead."""
     return failure_probability(prog, eng.P, eng.bsk_precision if eng.q_bits == TORUS64 else None, getattr(eng, "unroll", 1) == 2,
                                hw_small, hw_big, share_rotations=share_rotations,
-                               centred_modswitch=getattr(eng, "modswitch", 0) == 1, compressed_outputs=compressed_outputs)
+                               centred_modswitch=getattr(eng, "modswitch", 0) == 1, compressed_outputs=compressed_outputs,
+                               input_variance=input_variance)
 
 
 def lookup_failure_probability(P, lut_bits, input_variance=0.0, bsk_precision=None, unroll=False, hw_small=None, hw_big=None,

@@ -248,21 +248,26 @@ class Executor:
     def store_bytes(self):
         return int(self.store.numel() + self.tmp.numel() + self.lvl.numel()) * 8
 
-    def run(self, ct_inputs):
+    def run(self, ct_inputs, input_index=None):
         """ct_inputs: (n_inputs, k*N+1) uint64 ciphertexts (host) -> (n_outputs, k*N+1) uint64 (host); with batch > 1:
-        (batch, n_inputs, k*N+1) -> (batch, n_outputs, k*N+1)"""
-        self._walk(ct_inputs)
+        (batch, n_inputs, k*N+1) -> (batch, n_outputs, k*N+1).
+        Compressed inputs (2^64 torus, one rank): ct_inputs may be a tfhe.CompressedCiphertexts (with batch > 1 a sequence of `batch`
+        of them); only its values and the index go to the device, where Engine.decompress writes the input rows of the store on
+        the walk's stream.  input_index: n_inputs positions of the compressed form, input j = position input_index[j] (any order,
+        repeats allowed; the same for every replica); None = the identity, which needs len(cc) == n_inputs.  Such inputs are not
+        fresh encryptions: error_budget.failure_probability(..., input_variance=decompressed_variance(...)) prices them."""
+        self._walk(ct_inputs, input_index)
         if self.on_gpu:
             self.torch.cuda.synchronize(self.dev)
         res = self.out[: self.n_out].cpu().numpy().view(np.uint64)
         return res if self.batch == 1 else res.reshape(self.batch, -1, self.big)
 
-    def run_decrypted(self, ct_inputs):
+    def run_decrypted(self, ct_inputs, input_index=None):
         """run() with the outputs decrypted where they are (Engine.decrypt_device on the output rows: the context must hold the
         secret key): int64 messages (n_outputs,), with batch > 1 (batch, n_outputs) - 8 bytes per output come home instead of a
-        ciphertext"""
+        ciphertext.  ct_inputs / input_index as in run()."""
         torch = self.torch
-        stream = self._walk(ct_inputs)
+        stream = self._walk(ct_inputs, input_index)
         with torch.cuda.device(self.dev):
             msgs = torch.empty(max(self.n_out, 1), dtype=torch.int64, device=self.dev)
             self.eng.decrypt_device(self.out, self.n_out, self.delta_log, msgs, stream=stream)
@@ -270,16 +275,16 @@ class Executor:
         res = msgs[: self.n_out].cpu().numpy()
         return res if self.batch == 1 else res.reshape(self.batch, -1)
 
-    def run_compressed(self, ct_inputs, log_modulus=16):
+    def run_compressed(self, ct_inputs, log_modulus=16, input_index=None):
         """run() with the outputs compressed where they are (Engine.compress on the output rows, on the walk's stream: the context
         must hold a compression key): a tfhe.CompressedCiphertexts - about 4 bytes per output of a full block at 16 bits come home
         instead of a ciphertext.  With batch > 1 every matrix is compressed separately and a list is returned, so that every client
-        receives its own blocks."""
+        receives its own blocks.  ct_inputs / input_index as in run(): compressed in, compressed out."""
         from .tfhe import CompressedCiphertexts, compressed_words
         torch = self.torch
         if self.world > 1:
             raise NotImplementedError("run_compressed is a one-rank form: under torch.distributed call run()")
-        stream = self._walk(ct_inputs)
+        stream = self._walk(ct_inputs, input_index)
         per, N = self.n_out // self.batch, self.eng.P.N
         words = compressed_words(per, N)
         with torch.cuda.device(self.dev):
@@ -291,15 +296,58 @@ class Executor:
         res = [CompressedCiphertexts(per, N, log_modulus, host[b, :words]) for b in range(self.batch)]
         return res[0] if self.batch == 1 else res
 
-    def _walk(self, ct_inputs):
+    def _compressed_inputs(self, ct_inputs, input_index):
+        """ct_inputs of run() in compressed form -> (list of `batch` CompressedCiphertexts, index as uint32 array or None), or None
+        where ct_inputs is a full array; every mismatch raises with a text"""
+        from .tfhe import CompressedCiphertexts
+        if isinstance(ct_inputs, CompressedCiphertexts):
+            ccs = [ct_inputs]
+        elif isinstance(ct_inputs, (list, tuple)) and ct_inputs and all(isinstance(c, CompressedCiphertexts) for c in ct_inputs):
+            ccs = list(ct_inputs)
+        else:
+            if input_index is not None:
+                raise ValueError("input_index selects positions of compressed inputs: ct_inputs is not a CompressedCiphertexts")
+            return None
+        if self.world > 1:
+            raise NotImplementedError("compressed inputs are a one-rank form: under torch.distributed decompress them first "
+                                      "(Engine.decompress_host) and pass the full ciphertexts")
+        n_in = self.prog.n_inputs
+        if len(ccs) != self.batch:
+            raise ValueError(f"{len(ccs)} compressed input lists for an executor of batch {self.batch}")
+        index = None
+        if input_index is not None:
+            index = np.ascontiguousarray(input_index, dtype=np.int64).reshape(-1)
+            if index.size != n_in:
+                raise ValueError(f"input_index has {index.size} positions, the program has {n_in} inputs")
+        for cc in ccs:
+            self.eng._compressed(cc)
+            if index is None and len(cc) != n_in:
+                raise ValueError(f"{len(cc)} compressed ciphertexts for a program of {n_in} inputs (pass input_index to select)")
+            if index is not None and index.size and (index.min() < 0 or index.max() >= len(cc)):
+                raise ValueError(f"input_index reaches position {int(index.max())} (lowest {int(index.min())}) of {len(cc)} compressed ciphertexts")
+        return ccs, None if index is None else index.astype(np.uint32)
+
+    def _walk(self, ct_inputs, input_index=None):
         """the level walk of run(): leaves the output ciphertexts in self.out, queued on the stream it returns"""
         torch = self.torch
         n_in = self.prog.n_inputs
-        ct = np.ascontiguousarray(ct_inputs, dtype=np.uint64).reshape(self.batch, n_in, self.big)
+        packed = self._compressed_inputs(ct_inputs, input_index)
+        if packed is None:
+            ct = np.ascontiguousarray(ct_inputs, dtype=np.uint64).reshape(self.batch, n_in, self.big)
         import contextlib
         with (torch.cuda.device(self.dev) if self.on_gpu else contextlib.nullcontext()):
             stream = torch.cuda.current_stream().cuda_stream if self.on_gpu else 0
-            self.store.view(self.batch, -1, self.big)[:, :n_in].copy_(torch.from_numpy(ct.view(np.int64)), non_blocking=False)
+            if packed is None:
+                self.store.view(self.batch, -1, self.big)[:, :n_in].copy_(torch.from_numpy(ct.view(np.int64)), non_blocking=False)
+            elif n_in:
+                # the compressed values and the index alone cross to the device; the input rows are written there, before level 1
+                ccs, index = packed
+                d_index = None if index is None else torch.from_numpy(index.view(np.int32)).to(self.dev)
+                self._packed_inputs = [d_index]       # alive until the next walk: the kernels below are only queued
+                for b, cc in enumerate(ccs):
+                    d_words = torch.from_numpy(cc.words.view(np.int32)).to(self.dev)
+                    self._packed_inputs.append(d_words)
+                    self.eng.decompress(d_words, cc.count, cc.log_modulus, self.store[b * self.n_rows1:], index=d_index, stream=stream)
             eng, tmp, lvl = self.eng, self.tmp, self.lvl
             for t, (width, pos, padded) in enumerate(self.levels):
                 if self.glevels is not None:     # one linear combination, keyswitch and rotation per group; every member's row as usual

@@ -170,6 +170,14 @@ class EncryptedMatrixInversion:
             if self.compress_log_modulus:
                 eng.compression_keygen(*self.COMPRESSION_SHAPE)
 
+    def failure_budget(self, input_variance=None):
+        """this instance's error budget (error_budget.engine_failure_probability under its engine, rotation sharing and output
+        compression) for inputs of the given variance in torus^2 - a scalar or one value per input; None: fresh encryptions, the
+        dict `error_budget` holds.  For compressed inputs pass error_budget.decompressed_variance(...)."""
+        from . import error_budget
+        return error_budget.engine_failure_probability(self.program, self._engine(), share_rotations=self.share_rotations,
+                                                       compressed_outputs=self._compressed_outputs(), input_variance=input_variance)
+
     def _executor(self, batch=1):
         """the executor of this circuit for `batch` input matrices per run (one per batch size, built on first use)"""
         if self._exec is None:
@@ -211,7 +219,10 @@ class EncryptedMatrixInversion:
         return self._engine().expand_seeded(enc) if isinstance(enc, SeededCiphertexts) else enc
 
     def evaluate(self, encrypted_quantized_matrix) -> np.ndarray:
-        """the encrypted inverse: (outputs, words) ciphertexts, or with compress_outputs a tfhe.CompressedCiphertexts"""
+        """the encrypted inverse: (outputs, words) ciphertexts, or with compress_outputs a tfhe.CompressedCiphertexts.  The input
+        is what encrypt() returned (full or seeded), or a tfhe.CompressedCiphertexts of the circuit's inputs in order
+        (Engine.compress_host of them, or an earlier circuit's compressed result): its values alone go to the GPU, which
+        decompresses them into the executor's input rows.  Such inputs are no fresh encryptions: failure_budget() prices them."""
         if self.compress_log_modulus:
             return self._executor().run_compressed(self._expanded(encrypted_quantized_matrix), self.compress_log_modulus)
         return self._executor().run(self._expanded(encrypted_quantized_matrix))
@@ -220,7 +231,19 @@ class EncryptedMatrixInversion:
         """B encrypted matrices (a sequence of encrypt() results, or one (B, inputs, words) array) through the circuit in ONE walk of
         its levels: every level is B times wider, so the look-ups run on the throughput kernel instead of B x depth rounds of the
         latency kernel (executor.py, `batch`) - the serving form.  Returns (B, outputs, words); decrypt() each.  With
-        compress_outputs: a list of B tfhe.CompressedCiphertexts, every matrix in blocks of its own."""
+        compress_outputs: a list of B tfhe.CompressedCiphertexts, every matrix in blocks of its own.  B tfhe.CompressedCiphertexts
+        (a list or tuple of them) are decompressed on the GPU as in evaluate(); mixed with other forms they are refused."""
+        from .tfhe import CompressedCiphertexts
+        seq = encrypted_quantized_matrices
+        if isinstance(seq, (list, tuple)) and any(isinstance(e, CompressedCiphertexts) for e in seq):
+            if not all(isinstance(e, CompressedCiphertexts) for e in seq):
+                raise ValueError("evaluate_many: compressed inputs mixed with full or seeded ones: pass one form (Engine.decompress_host "
+                                 "turns a CompressedCiphertexts into full ciphertexts)")
+            ex = self._executor(len(seq))
+            if self.compress_log_modulus:
+                res = ex.run_compressed(list(seq), self.compress_log_modulus)
+                return res if isinstance(res, list) else [res]
+            return ex.run(list(seq)).reshape(len(seq), -1, self._engine().P.big)
         enc = np.ascontiguousarray(np.stack([np.asarray(self._expanded(e)) for e in encrypted_quantized_matrices]), dtype=np.uint64)
         if enc.ndim != 3:
             raise ValueError("expected B encrypted matrices of shape (inputs, words)")

@@ -119,6 +119,8 @@ _SIGS = {
     "bmi_compress_batch_host": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "bmi_phase_compressed": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "bmi_decrypt_compressed": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+    "bmi_decompress_batch": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bmi_decompress_batch_host": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
 }
 
 # domains of the public mask streams (include/bmi_tfhe.h BMI_SEED_DOMAIN_*): part of the seeded key / ciphertext format
@@ -581,6 +583,57 @@ class Engine:
         out = np.zeros(self._compressed(cc).count, np.int64)
         self._ck(self.lib.bmi_decrypt_compressed(self.h, _ptr(cc.words), cc.count, cc.log_modulus, int(delta_log), _ptr(out)),
                  "bmi_decrypt_compressed")
+        return out
+
+    # ---- ... and back (csrc/lwe_unpack.hip): no key of any kind, so a context without keys or an evaluation-only one serves
+    def decompress(self, words, count, log_modulus, d_out, index=None, stream=0):
+        """d_out (device tensor, rows x (N + 1) words) = big-key LWE ciphertexts of the positions index[r] (None: all `count`, in
+        order) of the compressed form `words`, on `stream` (bmi_decompress_batch): the sample extraction of coefficient index[r]
+        mod N of its block, shifted back up to 2^64 - the phase under sk_big is bit for bit phase_compressed's.  words and index
+        are device tensors of 32-bit values (which the caller keeps alive until the stream has run), or numpy arrays, which are
+        uploaded beside d_out and kept alive here until the next call.  The sizes of words and d_out are checked; every
+        index < count is the caller's contract here; decompress_host checks it."""
+        uploads = []
+
+        def dev(a):
+            if a is None or hasattr(a, "data_ptr"):
+                return a
+            import torch
+            uploads.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).reshape(-1).view(np.int32)).to(d_out.device))
+            return uploads[-1]
+        d_words, d_index = dev(words), dev(index)
+        rows = int(count) if index is None else int(d_index.numel())
+        if int(d_words.numel()) != compressed_words(count, self.P.N) or d_words.element_size() != 4:
+            raise BmiError(f"{count} ciphertexts at N = {self.P.N} compress to {compressed_words(count, self.P.N)} 32-bit values, not "
+                           f"{int(d_words.numel())} of {d_words.element_size()} bytes")
+        if d_index is not None and d_index.element_size() != 4:
+            raise BmiError("decompress: the index is a tensor of 32-bit values")
+        if int(d_out.numel()) * d_out.element_size() < rows * self.P.big * 8:
+            raise BmiError(f"decompress: d_out holds {int(d_out.numel()) * d_out.element_size()} bytes, {rows} rows of {self.P.big} words "
+                           f"need {rows * self.P.big * 8}")
+        if index is not None and rows == 0:
+            return d_out          # (an empty index has no address to tell it from an absent one)
+        if uploads:
+            self._decompress_uploads = uploads
+        self._ck(self.lib.bmi_decompress_batch(self.h, _ptr(d_words), int(count), int(log_modulus), _ptr(d_index), rows, _ptr(d_out),
+                                               C.c_void_p(stream)), "bmi_decompress_batch")
+        return d_out
+
+    def decompress_host(self, cc, index=None):
+        """CompressedCiphertexts -> (rows, N + 1) uint64 ciphertexts of its positions index (None: all, in order); refuses an
+        index >= len(cc) and a value that does not fit log_modulus bits (bmi_decompress_batch_host)"""
+        self._compressed(cc)
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            if index.size and (index.min() < 0 or index.max() > 0xFFFFFFFF):
+                raise BmiError("decompress_host: an index is negative or does not fit 32 bits")
+            index = index.astype(np.uint32)
+        rows = cc.count if index is None else index.size
+        out = np.zeros((rows, self.P.big), np.uint64)
+        if index is not None and rows == 0:
+            return out
+        self._ck(self.lib.bmi_decompress_batch_host(self.h, _ptr(cc.words), cc.count, cc.log_modulus, _ptr(index), rows, _ptr(out)),
+                 "bmi_decompress_batch_host")
         return out
 
     def keygen_from_secret(self, sk_small, sk_big, seed=0):

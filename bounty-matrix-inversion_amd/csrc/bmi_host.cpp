@@ -354,7 +354,7 @@ struct bmi_ctx {
     DevBuf<uint32_t> pk_digits;        // compression: digit matrix of a slice ...
     DevBuf<u64> pk_T, pk_acc;          // ... its products [slice][2N], and the block's accumulator [2N]
     DevBuf<u64> pk_in;                 // host-buffer form: input ciphertexts ...
-    DevBuf<uint32_t> pk_out;           // ... and compressed values
+    DevBuf<uint32_t> pk_out;           // ... and compressed values (decompression's host-buffer form: the other way round, index in io_ids)
     int variant = 0;
     uint32_t lat_threshold = 512;  // 2 rounds of 256 one-workgroup PBS (11.2 ms) tie with one round of the wave-pair kernel (11.3 ms)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
@@ -2359,6 +2359,62 @@ int bmi_decrypt_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t coun
         const i64 v = (i64)ph[i];
         msgs[i] = (v >> delta_log) + ((v >> (delta_log - 1)) & 1);
     }
+    return 0;
+}
+
+// Decompression (lwe_unpack.hip) needs no key of any kind: the modulus, the shape and the arguments are all it checks.
+static int decompression_ok(const bmi_ctx *c, const char *what, uint32_t count, uint32_t log_modulus, bool has_index, uint32_t rows) {
+    if (!c->t64())
+        return fail(c, -1, std::string(what) + ": compression of output ciphertexts exists on the 2^64 torus only (not on the 49-bit field or "
+                           "Goldilocks)");
+    if (c->big_n != c->N) return fail(c, -1, std::string(what) + ": compressed ciphertexts exist for k = 1 only");
+    if (int rc = log_modulus_ok(c, what, log_modulus)) return rc;
+    if (!has_index && rows != count)
+        return fail(c, -1, std::string(what) + ": without an index the rows are the positions 0 .. count - 1: rows must equal count (" +
+                           std::to_string(rows) + " rows asked of " + std::to_string(count) + " ciphertexts)");
+    if (rows && !count) return fail(c, -1, std::string(what) + ": rows asked of an empty compressed form");
+    return 0;
+}
+
+int bmi_decompress_batch(bmi_ctx *c, const uint32_t *d_in, uint32_t count, uint32_t log_modulus, const uint32_t *d_index, uint32_t rows,
+                         uint64_t *d_out, void *stream) {
+    if (!c || (rows && (!d_in || !d_out))) return -1;
+    if (int rc = decompression_ok(c, "bmi_decompress_batch", count, log_modulus, d_index != nullptr, rows)) return rc;
+    if (rows == 0) return 0;
+    if ((uintptr_t)d_out & 7) return fail(c, -1, "bmi_decompress_batch: d_out is not aligned to 8 bytes");
+    HIP_OK(c, hipSetDevice(c->device));
+    const int e = bmit::launch_unpack(d_in, d_index, d_out, count, rows, c->N, log_modulus, (hipStream_t)stream);
+    if (e) return fail(c, -2, std::string("lwe_unpack launch: ") + hipGetErrorString((hipError_t)e));
+    return 0;
+}
+
+int bmi_decompress_batch_host(bmi_ctx *c, const uint32_t *in, uint32_t count, uint32_t log_modulus, const uint32_t *index, uint32_t rows,
+                              uint64_t *out) {
+    if (!c || (rows && (!in || !out))) return -1;
+    if (int rc = decompression_ok(c, "bmi_decompress_batch_host", count, log_modulus, index != nullptr, rows)) return rc;
+    if (rows == 0) return 0;
+    if (index)
+        for (uint32_t r = 0; r < rows; r++)
+            if (index[r] >= count)
+                return fail(c, -1, "bmi_decompress_batch_host: index " + std::to_string(index[r]) + " (row " + std::to_string(r) +
+                                   ") is not below the count of " + std::to_string(count) + " ciphertexts");
+    u64 words = 0;
+    (void)bmi_compressed_words(c, count, &words);
+    if (log_modulus < 32)
+        for (u64 x = 0; x < words; x++)
+            if (in[x] >> log_modulus) return fail(c, -1, "bmi_decompress_batch_host: a value does not fit log_modulus bits");
+    HIP_OK(c, hipSetDevice(c->device));
+    const size_t w = (size_t)(c->N + 1) * 8;
+    int rc = grow(c, c->pk_out, words * 4, (size_t)2 * c->N * 4);
+    if (!rc) rc = grow(c, c->pk_in, rows * w, 256 * w);
+    if (!rc && index) rc = grow(c, c->io_ids, (size_t)rows * 4, 256 * sizeof(uint32_t));
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->pk_out.get(), in, words * 4, hipMemcpyHostToDevice, c->stream));
+    if (index) HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), index, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    rc = bmi_decompress_batch(c, c->pk_out.get(), count, log_modulus, index ? c->io_ids.get() : nullptr, rows, c->pk_in.get(), c->stream);
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpyAsync(out, c->pk_in.get(), rows * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -325,4 +325,9 @@ uint32_t pack_slice(uint32_t N);
 int launch_pack_slice(const u64 *cts, const u64 *key, const u64 *bias, uint32_t *digits, u64 *T, u64 *acc, uint32_t m, uint32_t first,
                       uint32_t N, uint32_t levels, uint32_t base_log, hipStream_t s);
 int launch_pack_switch(const u64 *acc, uint32_t *out, uint32_t m, uint32_t N, uint32_t log_modulus, hipStream_t s);
+// lwe_unpack.hip: decompression back to big-key LWE ciphertexts.  in = the compressed form of `count` ciphertexts (per block N mask
+// values, then its body values); out[r] (N + 1 words) = the sample extraction of position index[r] (index == nullptr: position r),
+// shifted up to 2^64; every index[r] < count is the caller's contract; rows == 0 launches nothing
+int launch_unpack(const uint32_t *in, const uint32_t *index, u64 *out, uint32_t count, uint32_t rows, uint32_t N, uint32_t log_modulus,
+                  hipStream_t s);
 }  // namespace bmit

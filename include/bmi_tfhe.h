@@ -456,7 +456,18 @@ int bmi_expand_seeded_batch_host(bmi_ctx *ctx, uint64_t first_counter, const uin
  *   bmi_compressed_words = ceil(count / N) * N + count values.
  * Decryption (host, secret key): phase_i = B^_i 2^(64-c) - ((A^ 2^(64-c)) S)_i, message = round(phase / 2^delta_log) as bmi_decrypt.
  * The 49-bit field and Goldilocks refuse every entry point with a bmi_last_error text; so do out-of-range arguments and
- * bmi_compress_batch without a key.  Noise: error_budget.compression_variance. */
+ * bmi_compress_batch without a key.  Noise: error_budget.compression_variance.
+ * Decompression back to big-key LWE ciphertexts (csrc/lwe_unpack.hip; no key of any kind, so a context that has run no keygen and
+ *   an evaluation-only context serve it): the negacyclic sample extraction of coefficient i of its block, shifted back up to 2^64.
+ *   With i = idx mod N and A^ / B^ the mask and body values of block idx / N, taken mod 2^c, row r of the output is
+ *     out[r][j] = A^[i - j] 2^(64-c)          for j <= i
+ *     out[r][j] = 0 - A^[N + i - j] 2^(64-c)  for i < j < N
+ *     out[r][N] = B^[i] 2^(64-c)
+ *   an ordinary ciphertext of N + 1 words whose phase under sk_big is, bit for bit, the phase_i above of position idx: it goes
+ *   through the keyswitch and the blind rotation as any other.  An optional index list picks positions in any order, with repeats.
+ *   Noise: decompression itself adds none.  A decompressed ciphertext carries the error of the ciphertext that was compressed plus
+ *   the compression's own (error_budget.decompressed_variance = the source's variance + compression_variance); it is NOT a fresh
+ *   encryption, and a circuit that takes such inputs is budgeted with failure_probability(..., input_variance=...). */
 #define BMI_SEED_DOMAIN_PKSK_MASK 11u
 int bmi_compression_keygen(bmi_ctx *ctx, uint32_t levels, uint32_t base_log);   /* needs the secret keys; one shape per key set */
 /* *levels = 0 where the context holds no compression key; device_bytes = the key's device copy and the product's bias vector */
@@ -476,6 +487,15 @@ int bmi_compress_batch_host(bmi_ctx *ctx, const uint64_t *in, uint32_t count, ui
 int bmi_phase_compressed(const bmi_ctx *ctx, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint64_t *phase);
 int bmi_decrypt_compressed(const bmi_ctx *ctx, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint32_t delta_log,
                            int64_t *msgs);
+/* d_in = the compressed form of `count` ciphertexts (device uint32 values) -> d_out [rows][N + 1] device words, on the caller's
+ * stream: row r = position d_index[r] (device uint32 values), or position r where d_index is NULL, which needs rows == count.
+ * rows == 0 launches nothing.  THE INDEX IS THE CALLER'S CONTRACT: every d_index[r] < count; the device form cannot refuse a larger
+ * one, which reads values that are not there.  Values are taken mod 2^log_modulus. */
+int bmi_decompress_batch(bmi_ctx *ctx, const uint32_t *d_in, uint32_t count, uint32_t log_modulus, const uint32_t *d_index,
+                         uint32_t rows, uint64_t *d_out, void *stream);
+/* the same from and to host memory; refuses an index >= count and a value that does not fit log_modulus bits */
+int bmi_decompress_batch_host(bmi_ctx *ctx, const uint32_t *in, uint32_t count, uint32_t log_modulus, const uint32_t *index,
+                              uint32_t rows, uint64_t *out);
 
 /* bytes of device memory held by the keys: every resident transform-domain copy of the bootstrap key (one per selectable kernel
  * family, plus the unrolled key when present), and the keyswitch key in word form */

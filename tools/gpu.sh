@@ -16,6 +16,8 @@
 #                                (BMI_OUT=FILE: its lines also written there)                         -> section 2 of profiles/centred_modswitch_ab.txt
 #   cab [args]                   tools/compress_ab.py: compression of output ciphertexts timed beside a round of bootstraps, and the 3x3
 #                                inverse by run against run_compressed alternating in one process    -> profiles/compress_outputs_ab.txt (BMI_OUT=FILE: elsewhere)
+#   dab [args]                   tools/decompress_ab.py: decompression back to LWE ciphertexts by events beside a device-to-device copy of
+#                                the same output bytes, alternating in one process                     -> profiles/decompress_ab.txt (BMI_OUT=FILE: elsewhere)
 #   phase  <t64f|t64w> [batches] per-phase cycles of the debug build (make -C csrc prof)
 #   inverse [sizes]              encrypted-inverse wall-clocks on the default engine (bmi_amd/inverse_bench.py)
 #   calibrate [preset:bits:rounds ...]   failure-rate calibration of the error budget + phase-kernel time (tools/gpu_failure_rate.py)
@@ -47,6 +49,7 @@ case "$recipe" in
   wu2ab) timeout -k 10 ${BMI_T:-420} python tools/unrolled_wide2_ab.py --out "${BMI_OUT:-profiles/unrolled_wide2_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -60 ;;
   msab) timeout -k 10 ${BMI_T:-420} python tools/modswitch_ab.py ${BMI_OUT:+--out "$BMI_OUT"} "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
   cab) timeout -k 10 ${BMI_T:-420} python tools/compress_ab.py --out "${BMI_OUT:-profiles/compress_outputs_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
+  dab) timeout -k 10 ${BMI_T:-300} python tools/decompress_ab.py --out "${BMI_OUT:-profiles/decompress_ab.txt}" "$@" 2>&1 | grep -v amdgpu.ids | tail -40 ;;
   phase)
     k=$1; shift
     timeout -k 10 ${BMI_T:-300} python tools/phase_prof_$k.py "$@" 2>&1 | grep -v amdgpu.ids | tee gpurun_out/phase_$k.log ;;
