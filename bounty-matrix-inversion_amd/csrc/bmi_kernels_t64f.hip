@@ -10,8 +10,13 @@
 // multiply-accumulate is 4 fused multiply-adds per complex point (2 coefficients) instead of 6 instructions per coefficient.
 //
 // Structure = k_blind_rotate_t64: a pair of wavefronts per ciphertext, four ciphertexts per workgroup; wavefront c owns input
-// polynomial c (decomposes it, transforms its L digit polynomials once, multiplies them with both key columns per limb),
-// publishes the partner's partial sum through its LDS tile, adds the partner's, and runs the inverse transform of output c.
+// polynomial c (decomposes it, transforms its L digit polynomials once, multiplies them with both key columns of both limbs),
+// publishes the partner's partial sums through its LDS tile, adds the partner's, and runs the inverse transforms of output c.
+// Order of a CMUX (EXPERIMENTS A31, profiles/limb_order_ab.txt): ALL 4 L product rows first - column, then limb, then level:
+// (limb 0, partner's column) -> tile, (limb 0, own column), (limb 1, partner's column) -> tile, (limb 1, own column) - then both
+// inverse transforms, then ONE recombination.  After the last row the digit transforms X (96 registers) are dead: limb 0's rounded
+// result waits in registers across the second inverse transform instead of going through the accumulator in LDS, and both inverse
+// transforms use one set of table twiddles.  The key stream has no gap: every row but the CMUX's first is requested one row ahead.
 //
 // Roles of the eight wavefronts of a workgroup: ciphertext slot ctl = wave >> 1, polynomial c = wave & 1, partner = wave ^ 1.
 // Wavefronts w and w + 4 share a SIMD, so the two wavefronts of a ciphertext sit on different SIMDs and each SIMD holds one
@@ -20,37 +25,50 @@
 // L1 - in part.  With all eight wavefronts in phase (before the offset below) the trailing wavefronts asked for a row two to
 // five rows after the leaders and a workgroup fetched 2.1 x one copy of the key from L2 per CMUX (4,207 M 128-byte read requests
 // per launch of 8,192 against 1,982 M).  With the offset a row's four readers are two of each group, a forward phase apart by
-// design, and it is 2.4 x (4,778 M, same call) - in the faster kernel.  That traffic is not what holds the kernel: making the two wavefronts of a ciphertext SIMD-mates (ctl = wave % 4, c = wave / 4), which keeps the
+// design, and it is 2.4 x (4,778 M, same call) - in the faster kernel; with all product rows in front of the inverse transforms
+// it is 2.8 x (5,546 M against 4,779 M in one call, EXPERIMENTS A31) - again in the faster kernel.  That traffic is not what holds the kernel: making the two wavefronts of a ciphertext SIMD-mates (ctl = wave % 4, c = wave / 4), which keeps the
 // four readers of a row together, brought it down to 1.3 x and was 1.2 - 1.7 ms per 8,192 SLOWER; a workgroup barrier at each limb's
 // first row was 8 ms slower (profiles/key_row_sharing_ab.txt, EXPERIMENTS A19).  These roles stay.
 // What a CMUX keeps in registers instead of re-reading from LDS: the forward transforms' table twiddles (ForwardTwiddles: loaded
-// once, used by the L transforms) and the lane's own 16 accumulator words across the back edge (`keep`).
+// once, used by the L transforms), the inverse transforms' (InverseTwiddles: loaded after the last hand-off, used by both), limb 0's
+// rounded result (x0) and the lane's own 16 accumulator words across the back edge (`keep`).
 //
-// Who may touch a tile when (pair_sync.hpp; `hand` counts the hand-offs of the pair: 2 per CMUX, one per limb, strictly increasing;
-// pub[w] / ack[w] are written by wavefront w only).  Tile T_w of wavefront w is WRITTEN by w alone - the exchanges of its forward
-// transforms, the partial it publishes, the exchanges of its inverse transform - and READ by the partner w' = w ^ 1 only between w'
-// seeing pub[w] = h and w' storing ack[w'] = h:
-//   w:  stores partial h into T_w; pub[w] = h (release: the stores are visible before the flag)
-//   w': sees pub[w] = h; reads T_w (8 reads per lane); waits until they have returned (lgkmcnt(0)); ack[w'] = h
-//   w:  first two butterfly stages of the first DFT8 of inverse transform h (registers only); sees ack[w'] = h; only then the
-//       first store of the transform into T_w
-// Where the stores of an exchange sit: the forward transforms and the partial issue their eight ds_write_b128 back to back after
-// the arithmetic; the two exchanges of the inverse transform issue them from inside the last butterfly stage of the DFT8 in front
-// (fftw::dft8_emit: two stores, then the next pair's four f64 instructions), so the VGPR-to-LDS transfer of a pair runs under
-// arithmetic of the same wavefront (-0.9 ms per 8,192; the same arrangement of the forward transforms' twiddle multiplications
-// and of the partial's last product row measured nothing and +0.3 ms: profiles/exchange_bubbles_ab.txt, EXPERIMENTS A20).  The
-// protocol does not see the difference: the wait for ack[w'] = h and the wavefront fence still precede the first store in program
-// order, every store of an exchange still precedes the fence in front of its reads, and an earlier read of T_w by w itself has
-// been consumed by the arithmetic the stores depend on.
-// Every later write of T_w follows that store in w's program order: the rest of inverse transform h; then partial h + 1 (second
-// limb: stored after inverse transform h has returned), guarded in turn by ack[w'] = h + 1; then, in the next CMUX, the forward
-// transforms (after inverse transform h + 1) and partial h + 2.  So no write of T_w can overtake a read of it by w', for both limbs
-// and across consecutive CMUXes.  Reads by w' never see a stale partial: it reads only after pub[w] = h, which w stores after the
-// partial.  The flags need no reset: each is compared for equality with a value its only writer stores exactly once.
-// No deadlock: w waits for pub[w'] = h and for ack[w'] = h; w' stores pub[w'] = h before any of its waits of hand-off h (its last
-// wait before that is for ack[w] = h - 1, stored by w before w reached hand-off h), and stores ack[w'] = h after waiting for
-// pub[w] = h only, which w has stored before either of its waits.  Dead pairs (beyond `count`) run the whole protocol on a copy of
-// the last ciphertext.  The per-CMUX workgroup barrier is reached by every wavefront outside any hand-off, at either site.
+// Who may touch a tile when (pair_sync.hpp; a CMUX has two hand-offs, h0 = 2 i + 1 for limb 0 and h1 = 2 i + 2 for limb 1, strictly
+// increasing; pub[w] / ack[w] are written by wavefront w only).  Tile T_w of wavefront w is WRITTEN by w alone - the exchanges of its
+// forward transforms, the two partials it publishes, the exchanges of its inverse transforms - and READ by the partner w' = w ^ 1 only
+// between w' seeing pub[w] = h and w' storing ack[w'] = h.  One CMUX of w, in program order:
+//   L rows (limb 0, column c^1); stores partial h0 into T_w; pub[w] = h0 (release: the stores are visible before the flag)
+//   L rows (limb 0, column c); sees pub[w'] = h0; reads T_w' (8 reads per lane) and adds; waits until they have returned; ack[w] = h0
+//   L rows (limb 1, column c^1); sees ack[w'] = h0 (w' has read partial h0); stores partial h1 into T_w; pub[w] = h1
+//   L rows (limb 1, column c); sees pub[w'] = h1; reads T_w' and adds; ack[w] = h1
+//   first two butterfly stages of the first DFT8 of the first inverse transform (registers only); sees ack[w'] = h1; only then the
+//   first store of that transform into T_w; the second inverse transform; the recombination
+// Every wait but the last looks at a flag the partner stored L rows before it reached the same point of ITS program; the last one
+// sits under the first DFT8.  Where the stores of an exchange sit: the forward transforms and the partials issue their eight
+// ds_write_b128 back to back after the arithmetic; the two exchanges of an inverse transform issue them from inside the last
+// butterfly stage of the DFT8 in front (fftw::dft8_emit: two stores, then the next pair's four f64 instructions), so the VGPR-to-LDS
+// transfer of a pair runs under arithmetic of the same wavefront (profiles/exchange_bubbles_ab.txt, EXPERIMENTS A20).  The protocol
+// does not see the difference: the wait for ack[w'] = h1 and the wavefront fence still precede the first store in program order,
+// every store of an exchange still precedes the fence in front of its reads, and an earlier read of T_w by w itself has been
+// consumed by the arithmetic the stores depend on.
+// No write of T_w can overtake a read of it by w': partial h1 is stored after ack[w'] = h0 is seen; the first inverse transform's
+// stores after ack[w'] = h1; everything later - the second inverse transform, the next CMUX's forward transforms and its partial
+// h0 + 2 - follows that store in w's program order, and w' reads T_w again only after pub[w] = h0 + 2.  Reads by w' never see a stale
+// partial: it reads only after pub[w] = h, which w stores after the partial.  The flags need no reset: each is compared for equality
+// with a value its only writer stores exactly once - which is also why pub[w] = h1 must follow ack[w'] = h0: a partner that had not
+// yet looked for pub[w] = h0 would never see it.
+// No deadlock: the waits of w, in order, are for pub[w'] = h0, ack[w'] = h0, pub[w'] = h1, ack[w'] = h1.  w' stores pub[w'] = h0
+// before any of its waits of this CMUX (its last wait before is for ack[w] = h0 - 1, stored by w before w began this CMUX); it stores
+// ack[w'] = h0 after waiting for pub[w] = h0 only, which w stored before its first wait; pub[w'] = h1 after waiting for ack[w] = h0,
+// which w stored before waiting for ack[w'] = h0; ack[w'] = h1 after waiting for pub[w] = h1, which w stored before waiting for
+// pub[w'] = h1.  Each store a wait depends on precedes, in its writer's program, every wait of the writer that could depend on the
+// waiting wavefront's later stores: the waits cannot form a cycle (tests/test_pair_handoff_order_model.py explores every interleaving
+// of three CMUXes).  Dead pairs (beyond `count`) run the whole protocol on a copy of the last ciphertext.  The per-CMUX workgroup
+// barrier is reached by every wavefront outside any hand-off, at either site.
+// Registers: with X, two limb sums and two key rows live (224 of 256) the product phase has no room for the loop's invariant
+// addresses, and hoisted they were spilled (212 B of scratch, 41 reloads per CMUX).  So the wavefront's number is a scalar, and the
+// lane and wavefront numbers are taken from opaque per-CMUX copies (lane_a, lane_i, wave_i): the addresses are recomputed, about 80
+// 32-bit vector and 40 scalar instructions per CMUX, and <3, 10> compiles to no scratch at all (the order before: 12 B).
 //
 // Who is in which phase when (EXPERIMENTS A22, profiles/phase_offset_ab.txt).  Wavefronts 0 .. CTS-1 are group A, CTS .. 2 CTS-1
 // group B; each SIMD holds one wavefront of each group and both wavefronts of a pair are in the same group, so the pair protocol
@@ -137,19 +155,17 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     double *accs = tiles + 2 * CTS * SCRATCH_WORDS;          // accumulators: exact integers word / 2^PRE, centred mod 2^AB
     double *at_base = accs + 2 * CTS * N;
     uint32_t *flags = reinterpret_cast<uint32_t *>(at_base + CTS * BMI_AT_WORDS);  // [2 CTS] published, [2 CTS] consumed
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the wavefront's number as a scalar: its roles, tiles, flags and key rows are then addressed from scalar registers (as vector
+    // values they were loop invariants that the product phase - 224 registers of operands - had no room for)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int ctl = wave >> 1, c = wave & 1;
     if (threadIdx.x < 4 * CTS) flags[threadIdx.x] = 0;
     for (int i = threadIdx.x; i < TW_WORDS; i += blockDim.x) lds[i] = g_tw[i];
     const uint32_t ct_raw = blockIdx.x * CTS + ctl;
     const bool live = ct_raw < count;
     const uint32_t ct = live ? ct_raw : count - 1;
-    double *tile = tiles + wave * SCRATCH_WORDS;
-    const double *ptile = tiles + (wave ^ 1) * SCRATCH_WORDS;
     double *accf = accs + wave * N;
     uint16_t *at = reinterpret_cast<uint16_t *>(at_base + ctl * BMI_AT_WORDS);
-    uint32_t *f_pub = flags + wave, *f_pub_partner = flags + (wave ^ 1);
-    uint32_t *f_ack = flags + 2 * CTS + wave, *f_ack_partner = flags + 2 * CTS + (wave ^ 1);
     const u64 *lwe = small_cts + (size_t)ct * (n + 1);
     t64::stage_lwe<LOG_N + 1>(at, lwe, n, lane + 64 * c, 128);   // by the pair of wavefronts
     __syncthreads();
@@ -164,7 +180,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         });
     }
 
-    uint32_t hand = 0;   // handshake counter of the pair (one per inverse transform)
+    uint32_t hand = 0;   // hand-off counter of the pair (two per CMUX: one per limb)
     double dev = 0.0;    // STATS: largest |value - nearest integer| this lane has rounded away
     PH_DECL();
     // this lane's own 16 accumulator words, carried across the back edge: the recombination below stores them and the next CMUX
@@ -172,10 +188,21 @@ __global__ void __launch_bounds__(128 * TF_CTS)
     double keep[16];
     static_for<0, 16>([&](auto J) { keep[J] = accf[lane + 64 * J]; });
     for (uint32_t i = 0; i < n; i++) {
+        // the wavefront's group, its tile, its partner's and the four flags come from an opaque per-CMUX copy of the wavefront's number:
+        // a few scalar instructions per CMUX instead of loop invariants in vector registers (the flag addresses and the barrier's
+        // condition are vector operands: hoisted, they were spilled and reloaded inside the loop)
+        int wave_i = wave;
+        asm volatile("" : "+s"(wave_i));
         PH_MARK(7);
-        barrier_if(threadIdx.x >= 64 * CTS);   // barrier i of group B (the group flag is recomputed at each site, not carried)
+        barrier_if(wave_i >= CTS);   // barrier i of group B (the group flag is recomputed at each site, not carried)
         PH_MARK(0);   // resync barrier
         const uint32_t a_t = at[i];
+        double *tile = tiles + wave_i * SCRATCH_WORDS;
+        const double *ptile = tiles + (wave_i ^ 1) * SCRATCH_WORDS;
+        uint32_t *f_pub = flags + wave_i, *f_pub_partner = flags + (wave_i ^ 1);
+        uint32_t *f_ack = flags + 2 * CTS + wave_i, *f_ack_partner = flags + 2 * CTS + (wave_i ^ 1);
+        int lane_a = lane;   // (opaque per-CMUX copy for the phases in front of the product rows: see lane_i below)
+        asm volatile("" : "+v"(lane_a));
         // this wavefront's L GGSW rows: [row = L c + lev][column][limb][N]
         const double *bsk_c = bsk + ((size_t)i * 4 * L + c * 2 * L) * LIMBS * N;
         __builtin_amdgcn_s_setprio(0);   // issue priority: 0 through the forward transforms, 1 in the limb loop (header: SIMD-mates are in different phases)
@@ -184,24 +211,25 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         {
             double vr[16], vs[16];  // all 16 reads in flight before the first use
             static_for<0, 16>([&](auto J) {
-                vr[J] = accf[((lane + 2 * N - a_t) + 64 * J) & (N - 1)];   // (= lane + 64 J + 2 N - a_t; in this association <3, 10> compiles to 28 B of scratch per lane, in the other to 36)
+                vr[J] = accf[((lane_a + 2 * N - a_t) + 64 * J) & (N - 1)];   // (= lane + 64 J + 2 N - a_t)
                 vs[J] = keep[J];
             });
             sched_fence();
             static_for<0, 16>([&](auto J) {
-                const uint32_t e = ((lane + 2 * N - a_t) + 64 * J) & (2 * N - 1);
+                const uint32_t e = ((lane_a + 2 * N - a_t) + 64 * J) & (2 * N - 1);
                 const double d = mod_ab<AB>(((e & N) ? -vr[J] : vr[J]) - vs[J]);            // the centred lift of the u64 difference, / 2^PRE
                 r[J] = t64::rounded_top_f64<L, BG, AB>(d);
             });
         }
         PH_MARK(1);   // accumulator reads, difference, rounding
         double X[L][16];   // the L digit polynomials, evaluation layout, live across the limb loop
-        // key rows in the order they are multiplied: t = limb * 2 L + q; q < L: (level q, partner's column c^1) - its partial sum is
-        // published while the own column (q >= L: level q - L, column c) is still being multiplied.  A row is 8 complex words per
-        // lane; the NEXT row is requested before the current one is multiplied (two register sets), the first one before the last
-        // forward transform: a row's 32 multiply-adds are far shorter than the latency of its loads.
+        // key rows in the order they are multiplied: t = seg * L + lev, seg = 0 .. 3 = (limb 0, partner's column c^1), (limb 0, own
+        // column c), (limb 1, c^1), (limb 1, c) - every product row of the CMUX before either inverse transform.  A partner's-column
+        // sum is published while the own column of the same limb is still being multiplied.  A row is 8 complex words per lane; the
+        // NEXT row is requested before the current one is multiplied (two register sets), across the column and limb boundaries too,
+        // the first one before the last forward transform: a row's 32 multiply-adds are far shorter than the latency of its loads.
         auto row_ptr = [&](int t) {
-            const int j = t / (2 * L), q = t % (2 * L), lev = q % L, col = q < L ? (c ^ 1) : c;
+            const int seg = t / L, lev = t % L, j = seg >> 1, col = (seg & 1) ? c : (c ^ 1);
             return reinterpret_cast<const double2 *>(bsk_c + ((size_t)(lev * 2 + col) * LIMBS + j) * N);
         };
         double2 kb[2][8];
@@ -209,7 +237,7 @@ __global__ void __launch_bounds__(128 * TF_CTS)
         // the forward transforms' 15 table twiddles per lane, read from LDS once per CMUX instead of once per transform (the
         // wavefront fences inside a transform keep the compiler from doing this itself): 30 ds_read_b128 fewer per CMUX
         ForwardTwiddles ftw;
-        load_forward_twiddles(ftw, lane, lds);
+        load_forward_twiddles(ftw, lane_a, lds);
         sched_fence();
         static_for<0, L>([&](auto LEV) {
             constexpr int lev = L - 1 - LEV;  // least significant digit first
@@ -227,81 +255,110 @@ __global__ void __launch_bounds__(128 * TF_CTS)
                 fetch(kb[0], 0);
                 pin();
             }
-            forward(X[lev], lane, ftw, tile);
+            forward(X[lev], lane_a, ftw, tile);
         });
         __builtin_amdgcn_s_setprio(1);
         PH_MARK(2);   // digits + L forward transforms
-        barrier_if(threadIdx.x < 64 * CTS);   // barrier i of group A
+        barrier_if(wave_i < CTS);   // barrier i of group A
         PH_MARK(0);
-        double acc[16];
-        static_for<0, LIMBS * 2 * L>([&](auto T) {
-            constexpr int t = T, j = t / (2 * L), q = t % (2 * L), lev = q % L, cur = t & 1;
-            if constexpr (q == 0) hand++;
-            // (the first row of the next limb is requested after the inverse transform: requested before the hand-off instead it
-            // compiles without more scratch but measured 1.2 ms per 8,192 slower - profiles/pair_handoff_ab.txt)
-            if constexpr (t + 1 < LIMBS * 2 * L && q != 2 * L - 1) fetch(kb[cur ^ 1], t + 1);
+        const uint32_t h0 = hand + 1, h1 = hand + 2;   // the CMUX's two hand-offs: limb 0's partial sums, limb 1's
+        hand = h1;
+        double acc[16], acc0[16];   // acc: segments 0, 2, 3 in turn (limb 1's sum at the end); acc0: segment 1, limb 0's sum
+        // publishes the partner's-column sum of a limb through this wavefront's tile (free since the last transform, or since the
+        // partner acknowledged the partial before)
+        auto publish = [&](uint32_t h) {
+            wave_sync();
+            static_for<0, 8>([&](auto P) {
+                reinterpret_cast<double2 *>(tile)[P * 64 + lane] = double2{acc[P], acc[P + 8]};
+            });
+            pair_post(f_pub, h);
+        };
+        // adds the partner's partial h to the own column's sum and acknowledges it: the partner posted it L rows ago
+        auto take = [&](double (&a)[16], uint32_t h) {
+            PH_MARK(3);   // 4L rows of products (+ publishing the partner's partials)
+            pair_wait(f_pub_partner, h);
+            PH_MARK(4);   // waiting for the partner's partials (and for its acknowledgement of limb 0's)
+            static_for<0, 8>([&](auto P) {
+                const double2 p = reinterpret_cast<const double2 *>(ptile)[P * 64 + lane];
+                a[P] += p.x;
+                a[P + 8] += p.y;
+            });
+            pin();
+            pair_ack(f_ack, h);           // the eight reads above have landed: the partner may overwrite its tile
+            pin();
+            PH_MARK(5);   // adding the partner's partials, posting the acknowledgements
+        };
+        // The lane number as the inverse transforms and the recombination see it: an opaque copy made per CMUX.  The LDS addresses
+        // derived from it (rotated exchange slots, the 16 accumulator words) are then computed after the last product row instead
+        // of being hoisted out of the loop, where with X, two sums and two key rows live (224 registers) they were spilled: 212 B
+        // of scratch and 41 reloads per CMUX at three levels without these copies (lane_a, lane_i, wave_i), none with them.
+        int lane_i = lane;
+        asm volatile("" : "+v"(lane_i));
+        InverseTwiddles itw;
+        static_for<0, 4 * L>([&](auto T) {
+            constexpr int t = T, seg = t / L, lev = t % L, cur = t & 1;
+            if constexpr (t + 1 < 4 * L) fetch(kb[cur ^ 1], t + 1);
             sched_fence();
+            double (&a)[16] = seg == 1 ? acc0 : acc;
             static_for<0, 8>([&](auto P) {
                 const double xr = X[lev][P], xi = X[lev][P + 8];
                 if constexpr (lev == 0) {
-                    acc[P] = __builtin_fma(xr, kb[cur][P].x, -(xi * kb[cur][P].y));
-                    acc[P + 8] = __builtin_fma(xr, kb[cur][P].y, xi * kb[cur][P].x);
+                    a[P] = __builtin_fma(xr, kb[cur][P].x, -(xi * kb[cur][P].y));
+                    a[P + 8] = __builtin_fma(xr, kb[cur][P].y, xi * kb[cur][P].x);
                 } else {
-                    acc[P] = __builtin_fma(xr, kb[cur][P].x, __builtin_fma(-xi, kb[cur][P].y, acc[P]));
-                    acc[P + 8] = __builtin_fma(xr, kb[cur][P].y, __builtin_fma(xi, kb[cur][P].x, acc[P + 8]));
+                    a[P] = __builtin_fma(xr, kb[cur][P].x, __builtin_fma(-xi, kb[cur][P].y, a[P]));
+                    a[P + 8] = __builtin_fma(xr, kb[cur][P].y, __builtin_fma(xi, kb[cur][P].x, a[P + 8]));
                 }
             });
-            if constexpr (q == L - 1) {
-                // the partner's partial goes through this wavefront's tile (free since the last transform)
-                wave_sync();
-                static_for<0, 8>([&](auto P) {
-                    reinterpret_cast<double2 *>(tile)[P * 64 + lane] = double2{acc[P], acc[P + 8]};
-                });
-                pair_post(f_pub, hand);
+            if constexpr (lev == L - 1 && seg == 0) publish(h0);
+            if constexpr (lev == L - 1 && seg == 2) {
+                // limb 1's partial overwrites limb 0's: the partner has read that one once its acknowledgement - posted when it
+                // finished ITS segment 1, L rows ago - is seen
+                pin();
+                PH_MARK(3);
+                pair_wait(f_ack_partner, h0);
+                PH_MARK(4);
+                pin();
+                publish(h1);
             }
             pin();
-            if constexpr (q == 2 * L - 1) {
-                PH_MARK(3);   // 2L rows of products (+ publishing the partner's partial)
-                pair_wait(f_pub_partner, hand);
-                PH_MARK(4);   // waiting for the partner's partial
-                static_for<0, 8>([&](auto P) {
-                    const double2 p = reinterpret_cast<const double2 *>(ptile)[P * 64 + lane];
-                    acc[P] += p.x;
-                    acc[P + 8] += p.y;
-                });
-                pin();
-                pair_ack(f_ack, hand);           // the eight reads above have landed: the partner may overwrite its tile
-                pin();
-                PH_MARK(5);   // adding the partner's partial, posting the acknowledgement (the WAIT for the partner's is in phase 6)
-                // the partner has read this tile once its acknowledgement is seen: the inverse transform waits for it just before its
-                // first store to the tile, between the second and the last butterfly stage of its first DFT8 (registers only)
-                inverse(acc, lane, lds, tile, [&]() {
-                    pin();
-                    pair_wait(f_ack_partner, hand);
-                    pin();
-                });
-                PH_MARK(6);   // inverse transform, including the wait for the partner's acknowledgement after its first DFT8
-                if constexpr (t + 1 < LIMBS * 2 * L) {
-                    fetch(kb[cur ^ 1], t + 1);
-                    pin();
-                }
-                // the limb's exact integer result (|.| < 2^45: nearest integer of the transform's output), shifted into place
-                static_for<0, 16>([&](auto J) {
-                    double x = __builtin_rint(acc[J]);
-                    if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(acc[J] - x));
-                    if constexpr (j > 0) {
-                        // x 2^(LB j) mod 2^AB: only the low AB - LB j bits of the limb's integer survive the shift
-                        constexpr double W = (double)(1ull << (AB - LB * j));
-                        x = __builtin_fma(-W, __builtin_rint(x * (1.0 / W)), x);
-                        keep[J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << (LB * j)), accf[lane + 64 * J]));
-                        accf[lane + 64 * J] = keep[J];
-                    } else {
-                        accf[lane + 64 * J] += x;   // (reduced mod 2^AB with the last limb: 2^47 + 2^45 + 2^47 stays exact)
-                    }
-                });
+            if constexpr (lev == L - 1 && seg == 1) take(acc0, h0);
+            if constexpr (lev == L - 1 && seg == 3) {
+                take(acc, h1);
+                // X is dead from here: the inverse transforms' 15 table twiddles per lane are read from LDS once for both transforms
+                // (requested after the hand-off; requested in front of its wait the kernel measured 3.7 ms per 8,192 SLOWER)
+                load_inverse_twiddles(itw, lane_i, lds);
                 pin();
             }
         });
+        // the partner has read this tile (limb 1's partial) once its acknowledgement is seen: the first inverse transform waits for
+        // it just before its first store to the tile, between the second and the last butterfly stage of its first DFT8 (registers only)
+        auto ack_hook = [&]() {
+            pin();
+            pair_wait(f_ack_partner, h1);
+            pin();
+        };
+        inverse(acc0, lane_i, itw, tile, ack_hook);
+        // limb 0's exact integer result (|.| < 2^45: nearest integer of the transform's output), held across the second transform
+        double x0[16];
+        static_for<0, 16>([&](auto J) {
+            x0[J] = __builtin_rint(acc0[J]);
+            if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(acc0[J] - x0[J]));
+        });
+        pin();
+        inverse(acc, lane_i, itw, tile);
+        PH_MARK(6);   // both inverse transforms, including the wait for the partner's acknowledgement after the first DFT8
+        // limb 1's result shifted into place, x 2^LB mod 2^AB: only the low AB - LB bits of the limb's integer survive the shift;
+        // one pass over the lane's own accumulator words: old + limb 0 (2^47 + 2^45 stays exact), then the shifted limb 1, reduced
+        static_for<0, 16>([&](auto J) {
+            double x = __builtin_rint(acc[J]);
+            if constexpr (STATS) dev = __builtin_fmax(dev, __builtin_fabs(acc[J] - x));
+            constexpr double W = (double)(1ull << (AB - LB));
+            x = __builtin_fma(-W, __builtin_rint(x * (1.0 / W)), x);
+            keep[J] = mod_ab<AB>(__builtin_fma(x, (double)(1ull << LB), accf[lane_i + 64 * J] + x0[J]));
+            accf[lane_i + 64 * J] = keep[J];
+        });
+        pin();
     }
 
     PH_MARK(7);

@@ -293,6 +293,55 @@ __device__ __forceinline__ void inverse(double (&x)[16], int lane, const double 
     });
 }
 
+// The inverse transform's table twiddles of one lane, held in registers by a caller that runs several transforms in a row
+// (60 VGPRs): the 7 words of TW_T2 (t2[0] = 1 is never multiplied and never loaded) and the 8 of TW_T1 - the same words as
+// ForwardTwiddles, which the inverse multiplies by conjugated.
+struct InverseTwiddles {
+    double2 t2[8], t1[8];
+};
+__device__ __forceinline__ void load_inverse_twiddles(InverseTwiddles &f, int lane, const double *tw) {
+    const double2 *tw2 = reinterpret_cast<const double2 *>(tw);
+    static_for<1, 8>([&](auto D) { f.t2[D] = tw2[TW_T2 / 2 + D * 8 + (lane & 7)]; });
+    static_for<0, 8>([&](auto K) { f.t1[K] = tw2[TW_T1 / 2 + K * 64 + lane]; });
+}
+// The same transform with the twiddles preloaded: every value and every operation is inverse()'s, only the 15 LDS reads are gone.
+template <class Pre = NoHook>
+__device__ __forceinline__ void inverse(double (&x)[16], int lane, const InverseTwiddles &f, double *scratch, Pre pre = Pre()) {
+    double2 *sc = reinterpret_cast<double2 *>(scratch);
+    const int r1 = ex1_row(lane), a = lane & 7, base = ex2_base(lane);
+    C v[8];
+    static_for<0, 8>([&](auto Cc) { v[Cc] = C{x[Cc], x[Cc + 8]}; });
+    dft8_emit<true>(   // over c -> a
+        v,
+        [&]() {
+            pre();
+            wave_sync();
+        },
+        [&](auto A) { sc[base + a * 8 + ((A + a) & 7)] = double2{v[A].r, v[A].i}; });
+    wave_sync();
+    static_for<0, 8>([&](auto D) {
+        const double2 t = sc[base + D * 8 + ((a + D) & 7)];
+        v[D] = C{t.x, t.y};
+    });
+    static_for<1, 8>([&](auto D) { v[D] = cmul<true>(v[D], f.t2[D].x, f.t2[D].y); });
+    sched_fence();
+    dft8_emit<true>(v, [&]() { wave_sync(); }, [&](auto B) { sc[r1 + 8 * B] = double2{v[B].r, v[B].i}; });   // over d -> b
+    wave_sync();
+    static_for<0, 8>([&](auto K) {
+        const double2 t = sc[K * ROWC + lane];
+        v[K] = C{t.x, t.y};
+    });
+    static_for<0, 8>([&](auto K) { v[K] = cmul<true>(v[K], f.t1[K].x, f.t1[K].y); });
+    dft8<true>(v);   // over k2 -> r
+    x[0] = v[0].r * (1.0 / 512);
+    x[8] = v[0].i * (1.0 / 512);
+    static_for<1, 8>([&](auto R) {
+        const C t = cmul<true>(v[R], TWIST_C[R] * (1.0 / 512), TWIST_S[R] * (1.0 / 512));
+        x[R] = t.r;
+        x[R + 8] = t.i;
+    });
+}
+
 // word offset (in doubles) of evaluation value (lane, register c) inside a transform-domain key polynomial: complex words in
 // [c][lane] order, so that a wavefront requests one 16-byte word per lane and register
 __host__ __device__ __forceinline__ int eval_offset(int lane, int c) { return (c * 64 + lane) * 2; }

@@ -8,12 +8,21 @@
 //                                                       pair_wait(pub_P, h)
 //                                                       reads P's tile (eight ds_read_b128 per lane)
 //                                                       pair_ack(ack_Q, h)   ordered after those reads only
-//   first two butterfly stages of the first register DFT8 of P's inverse transform
-//   pair_wait(ack_Q, h)      (the hook of fftw::inverse)
-//   first store of the inverse transform into P's tile
-// Both wavefronts of a pair play both roles in every hand-off.  No wait of hand-off h depends on anything the partner does after
-// one of ITS waits of hand-off h or later: pub(h) is posted after the wait for ack(h - 1), which the partner posted before it
-// reached its wait for pub(h) - so the waits cannot form a cycle.
+//   pair_wait(ack_Q, h)
+//   next write of P's tile
+// Both wavefronts of a pair play both roles in every hand-off.  In bmi_kernels_t64f.hip a CMUX has two hand-offs through the one
+// tile, h0 (limb 0) and h1 (limb 1), with L key rows between any two waits but the last:
+//   rows (limb 0, partner's column); store partial; pair_post(pub, h0)
+//   rows (limb 0, own column);       pair_wait(pub_partner, h0); add the partner's partial; pair_ack(ack, h0)
+//   rows (limb 1, partner's column); pair_wait(ack_partner, h0); store partial; pair_post(pub, h1)
+//   rows (limb 1, own column);       pair_wait(pub_partner, h1); add the partner's partial; pair_ack(ack, h1)
+//   first two butterfly stages of the first register DFT8 of the first inverse transform;
+//   pair_wait(ack_partner, h1)       (the hook of fftw::inverse); first store of the transform into the tile; second inverse transform
+// (the other two kernels have one hand-off per inverse transform: post, wait + read + ack, the hook's wait.)
+// No wait depends on anything the partner does after one of ITS waits for the same or a later flag value: pub(h) is posted after the
+// wait for ack(h - 1), which the partner posted before it reached its wait for pub(h), and ack(h) is posted after the wait for pub(h)
+// only - so the waits cannot form a cycle.  The flags are compared for EQUALITY: pub(h + 1) must not be posted before the partner's
+// ack(h) is seen, or a partner that has not yet looked for pub(h) never finds it (tests/test_pair_handoff_order_model.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
