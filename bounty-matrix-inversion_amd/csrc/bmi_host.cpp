@@ -1644,7 +1644,9 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
         return rc ? fail(c, -2, std::string("keyswitch (matrix cores) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
     }
     if (c->P.n + 1 > 3 * 256)   // ks_lincomb.hpp: KS_COLS x KS_THREADS output columns per workgroup
-        return fail(c, -1, "the scalar keyswitch kernel takes n <= 767; this parameter set needs the matrix-core form");
+        return fail(c, -1, c->ks_mfma_ok ? "the scalar keyswitch kernel takes n <= 767; this parameter set needs the matrix-core form"
+                                         : "no keyswitch kernel takes this parameter set: the scalar kernel takes n <= 767, and the matrix-core "
+                                           "form takes at most 16 levels with int32 column sums (k N levels 2^(base_log + 6) < 2^31)");
     // Scalar form.  The row walk (k*N*levels rows) of one workgroup is the latency of a small batch, so it is split over
     // `slices` workgroups per tile of 8 ciphertexts (partial 128-bit sums + a reduce kernel) until the launch
     // has ~1024 workgroups; large batches fill the chip with one slice.
@@ -1652,6 +1654,12 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
     uint32_t slices = 1;
     if (c->variant == 0 || c->variant == 2)
         while (slices < 64 && tiles * slices * 2 <= 1024) slices *= 2;
+    // A workgroup stages the digits of its slice in dynamic LDS (ks_scalar_lds_bytes): whatever the batch size and the
+    // pinned rotation variant, the coefficients are split until that fits the kernel's limit (64 KiB: 1024 x 8 levels unsplit).
+    while (slices < 64 && ks_scalar_lds_bytes(c->big_n, c->P.ks_levels, slices) > BMI_KS_LDS_MAX) slices *= 2;
+    if (ks_scalar_lds_bytes(c->big_n, c->P.ks_levels, slices) > BMI_KS_LDS_MAX)
+        return fail(c, -1, "the scalar keyswitch kernel cannot stage this parameter set's digits: 8 x ceil(k N / 64) x levels bytes exceed "
+                           "its 64 KiB of LDS");
     if (slices > 1)
         if (int rc = grow(c, c->ks_partial, (size_t)slices * count * c->ks_stride * 16, KS_PARTIAL_BYTES)) return rc;
     int rc = c->ops->keyswitch(d_in, c->ksk_padded.get(), c->ks_bias.get(), d_small, slices > 1 ? c->ks_partial.get() : nullptr, slices,

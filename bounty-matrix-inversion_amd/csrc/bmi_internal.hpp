@@ -31,6 +31,16 @@ constexpr int BMI_LDS_WORDS_MAX = 160 * 1024 / 8;   // 160 KB of LDS per workgro
 #define BMI_KS_MFMA_MIN 1  // smallest batch that takes the matrix-core keyswitch (0.05 ms against 0.14 ms scalar even at one ciphertext)
 #endif
 
+// Scalar keyswitch (ks_lincomb.hpp): a workgroup stages one byte per (ciphertext of its tile of 8, coefficient of its slice, level)
+// in dynamic LDS.  The kernel is launched without raising its dynamic-LDS limit, so a request stays within the 64 KiB every kernel
+// has by default: bmi_keyswitch_batch picks `slices` accordingly and the launcher refuses anything larger before launching.
+constexpr int BMI_KS_TILE = 8;
+constexpr size_t BMI_KS_LDS_MAX = 64 * 1024;
+inline size_t ks_scalar_lds_bytes(uint32_t big_n, uint32_t levels, uint32_t slices) {
+    const uint32_t per = slices > 1 ? (big_n + slices - 1) / slices : big_n;
+    return (size_t)BMI_KS_TILE * per * levels;
+}
+
 #ifndef BMI_TP_CTS
 #define BMI_TP_CTS 2  // ciphertexts (= wavefront pairs) per workgroup in the throughput blind rotation
 #endif

@@ -19,7 +19,7 @@ typedef int64_t i64;
 // LDS as d + B/2 (unsigned), so the inner multiply-accumulate is unsigned: acc(96 bit) += d' * K is two
 // v_mad_u64_u32 and one add; the bias sum_rows (B/2) * K is a per-key constant (ks_bias, computed at keygen)
 // and is added back at the end:  -sum d K = bias - sum d' K.
-constexpr int KS_TILE = 8;
+constexpr int KS_TILE = BMI_KS_TILE;
 constexpr int KS_THREADS = 256;
 constexpr int KS_COLS = 3;  // ceil(631 / 256)
 
@@ -182,7 +182,10 @@ int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out
                      hipStream_t s) {
     if (count == 0) return 0;
     const dim3 tiles((count + KS_TILE - 1) / KS_TILE);
-    if (slices <= 1 || partial == nullptr) {
+    if (partial == nullptr) slices = 1;
+    // the staged digits must fit the dynamic LDS the kernels have (the caller chooses `slices` for that): refused, not launched
+    if (ks_scalar_lds_bytes(big_n, levels, slices) > BMI_KS_LDS_MAX) return (int)hipErrorInvalidValue;
+    if (slices <= 1) {
         const size_t lds = (size_t)KS_TILE * big_n * levels;
         hipLaunchKernelGGL((k_keyswitch<false, F>), tiles, dim3(KS_THREADS), lds, s, in, ksk, ks_bias, out,
                            (unsigned __int128 *)nullptr, count, n, big_n, levels, base_log, ks_stride, big_n);

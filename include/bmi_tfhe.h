@@ -358,7 +358,9 @@ int bmi_import_bsk_unrolled(bmi_ctx *ctx, const uint64_t *bsk3);
 int bmi_export_bsk_unrolled(const bmi_ctx *ctx, uint64_t *bsk3);
 
 /* Selects the keyswitch kernel: 0 = auto (int8 matrix-core product when the parameter set allows it),
- * 1 = scalar 96-bit multiply-accumulate kernel. */
+ * 1 = scalar 96-bit multiply-accumulate kernel.  The matrix-core form takes at most 16 levels, the scalar kernel n <= 767
+ * (it splits the coefficients over workgroups until a workgroup's digits fit its 64 KiB of LDS); bmi_keyswitch_batch refuses,
+ * before any launch, a parameter set that the selected kernel - or, with more than 16 levels and n > 767, either - cannot take. */
 int bmi_set_keyswitch_variant(bmi_ctx *ctx, int variant);
 
 /* ---- compiler passes on a traced circuit in flat (CSR) form; context-free, CPU only -----------------------------

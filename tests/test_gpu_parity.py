@@ -119,8 +119,8 @@ def test_keyswitch_bit_exact(eng, ora):
 
 
 def test_keyswitch_matrix_core_path_bit_exact(eng, ora):
-    """Batches >= 64 take the int8 matrix-core keyswitch (ks_mfma.hpp): ragged tile counts, extreme words, and the
-    scalar kernel on the same inputs must all agree with the oracle bit for bit."""
+    """Every batch from one ciphertext up takes the int8 matrix-core keyswitch (ks_mfma.hpp; BMI_KS_MFMA_MIN = 1): ragged tile
+    counts, extreme words, and the scalar kernel on the same inputs must all agree with the oracle bit for bit."""
     to, ctx, sk_small = ora.to, ora.ctx, ora.sk_small
     rng = np.random.default_rng(14)
     Q = eng.modulus
