@@ -227,15 +227,14 @@ class DevBuf {
     size_t bytes_ = 0;
 };
 
-// The launchers that differ by modulus only: bmi_ctx_create picks one table per context.  The two NTT operations exist on the
-// prime fields only (null on the torus) and take the context: each field has its own twiddle table and key copy.
+// The launchers that differ by modulus only: bmi_ctx_create picks one table per context.  The NTT test hook exists on the
+// prime fields only (null on the torus) and takes the context: each field has its own twiddle table.
 struct FieldOps {
     decltype(&bmi::launch_keyswitch) keyswitch;
     decltype(&bmi::launch_keyswitch_mfma) keyswitch_mfma;
     decltype(&bmi::launch_ksk_to_limbs) ksk_to_limbs;
     decltype(&bmi::launch_lincomb) lincomb;
     decltype(&bmi::launch_lwe_phase) lwe_phase;
-    int (*bsk_to_ntt)(bmi_ctx *c, const u64 *std_polys);   // builds the NTT-domain key copy
     int (*negacyclic_mul)(const bmi_ctx *c, const u64 *a, const u64 *b, u64 *out, uint32_t count);
     uint32_t ks_limbs;   // limbs per keyswitch-key word of the matrix-core keyswitch
 };
@@ -281,7 +280,7 @@ struct bmi_ctx {
     DevBuf<u64> luts;           // BMI_LUT_CAP test polynomials of N words (49-bit field: centred doubles) - every blind rotation
     // The bootstrap key on the device, one field per layout (with its conversion and the kernel that reads it).  A copy exists where
     // its kernel is selectable on the context (upload_eval_keys; the torus exact-transform pair when first chosen:
-    // build_exact_torus_copies).  A field that is not empty holds a whole copy (build_copy).  Replaced with the key set.
+    // rotplan::on_demand_copies).  A field that is not empty holds a whole copy (build_copy).  Replaced with the key set.
     struct BskCopies {
         DevBuf<u64> ntt_gl;        // Goldilocks, NTT domain (bsk_to_ntt): blind_rotate_lat / _tp
         DevBuf<double> ntt49;      // 49-bit N = 1024, NTT domain (bsk_to_ntt): blind_rotate_tpx
@@ -356,7 +355,7 @@ struct bmi_ctx {
     DevBuf<u64> pk_in;                 // host-buffer form: input ciphertexts ...
     DevBuf<uint32_t> pk_out;           // ... and compressed values (decompression's host-buffer form: the other way round, index in io_ids)
     int variant = 0;
-    uint32_t lat_threshold = 512;  // 2 rounds of 256 one-workgroup PBS (11.2 ms) tie with one round of the wave-pair kernel (11.3 ms)
+    uint32_t lat_threshold = 0;    // auto dispatch: the latency kernels up to this batch size (rotplan::initial_settings)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
     uint32_t modswitch = 0;   // 0 = the rotation kernels' own rounding, 1 = centred (bmi_set_modswitch): bmi_pbs_batch / _shared_batch run
                               // k_modswitch_centre on the scratch small ciphertexts between the keyswitch and the rotation
@@ -372,6 +371,33 @@ int fail(const bmi_ctx *c, int code, const std::string &msg) {
     if (c) c->err = msg;
     else g_create_error = msg;
     return code;
+}
+
+using rotplan::Copy;
+using rotplan::Rot;
+
+// A context as rotation_plan.hpp takes it: its shape, its settings and what it holds.  Which kernel runs, which key copies get
+// built and what the setters accept is decided there, from these three; the entry points below act on the answers.
+rotplan::Shape shape_of(const bmi_params &P) {
+    return {P.q_bits == BMI_Q_TORUS64 ? rotplan::Modulus::torus64 : P.q_bits == 49 ? rotplan::Modulus::field49 : rotplan::Modulus::goldilocks,
+            P.log_N, P.bs_levels, P.bs_base_log};
+}
+rotplan::Settings settings_of(const bmi_ctx *c) { return {c->bsk_prec, c->bsk_prec_explicit, c->unroll, c->variant, c->lat_threshold}; }
+// (the one place where a buffer's presence is read as a fact about the context)
+rotplan::Held held_of(const bmi_ctx *c) {
+    const bmi_ctx::BskCopies &K = c->bsk;
+    const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
+    const std::pair<Copy, bool> present[] = {
+        {Copy::ntt_gl, !K.ntt_gl.empty()}, {Copy::ntt49, !K.ntt49.empty()}, {Copy::lat49, !K.lat49.empty()}, {Copy::wide49, !K.wide49.empty()},
+        {Copy::quad49, !K.quad49.empty()}, {Copy::exact, !K.exact.empty()}, {Copy::exact_lat, !K.exact_lat.empty()}, {Copy::fft, !K.fft.empty()},
+        {Copy::fft_lat, !K.fft_lat.empty()}, {Copy::wide, !K.wide.empty()}, {Copy::wide2, !K.wide2.empty()}, {Copy::quad, !K.quad.empty()},
+        {Copy::u_lat49, !K3.lat49.empty()}, {Copy::u_wide49, !K3.wide49.empty()}, {Copy::u_exact_lat, !K3.exact_lat.empty()},
+        {Copy::u_fft_lat, !K3.fft_lat.empty()}, {Copy::u_wide, !K3.wide.empty()}};
+    static_assert(sizeof(present) / sizeof(present[0]) == (size_t)Copy::COUNT, "one entry per key copy");
+    rotplan::Held h{0, c->have_keys, c->have_bsk3};
+    for (const auto &p : present)
+        if (p.second) h.copies |= rotplan::bit(p.first);
+    return h;
 }
 #define HIP_OK(ctx, call)                                                                              \
     do {                                                                                               \
@@ -529,30 +555,12 @@ std::vector<u64> build_twiddles_quad(const Fq &f) {
     return tw;
 }
 
-// precision a torus context stores its bootstrap key at unless bmi_set_bsk_precision says otherwise: 48 bits (two 24-bit limbs)
-// where the decomposition base leaves room for it (Bg <= 2^10: the default torus set), else the exact key (three 22-bit limbs)
-// (N = 2048: 46 bits, two 23-bit limbs; N = 4096: 44 bits, two 22-bit limbs - the lengths at which the floating-point transform's error
-// bound still certifies the rounding)
-int default_bsk_precision(const bmi_params &P) { return P.log_N == 12 ? 44 : P.log_N == 11 ? 46 : (P.bs_base_log <= 10 ? 48 : 64); }
-
+// (ring size and bootstrap decomposition: the plan's lists; a q_bits not refused yet counts as Goldilocks there, as before)
 bool params_supported(const bmi_params &P, std::string &why) {
-    if (P.log_N < 10 || P.log_N > 12 || (P.log_N != 10 && P.q_bits != 49 && P.q_bits != BMI_Q_TORUS64)) {
-        why = "log_N must be 10 (N = 1024), 11 (N = 2048: 49-bit field or 2^64 torus) or 12 (N = 4096: 49-bit field or 2^64 torus)";
-        return false;
-    }
+    const rotplan::Shape shape = shape_of(P);
+    if (!(why = rotplan::ring_refusal(shape)).empty()) return false;
     if (P.k != 1) { why = "only k = 1 has a HIP kernel in this build"; return false; }
-    const bool lb_default = P.bs_levels == 3 && P.bs_base_log == 15;
-    const bool lb_f64 = lb_default || (P.bs_levels == 2 && P.bs_base_log == 15) || (P.bs_levels == 1 && P.bs_base_log == 23);
-    // (2, 2^15) and (1, 2^23): the templated 49-bit kernels (N = 1024 wave-pair / latency kernels, N = 2048), and (2, 2^15) on the torus
-    const bool ok_lb = (lb_default && P.q_bits != BMI_Q_TORUS64) || (P.q_bits == 49 && P.log_N <= 11 && lb_f64) ||
-                       (P.q_bits == BMI_Q_TORUS64 && P.log_N == 10 && bmit::shape_supported(default_bsk_precision(P), P.bs_levels, P.bs_base_log)) ||
-                       (P.q_bits == BMI_Q_TORUS64 && P.log_N == 11 && bmit::shape_supported_wide(default_bsk_precision(P), P.bs_levels, P.bs_base_log)) ||
-                       (P.q_bits == BMI_Q_TORUS64 && P.log_N == 12 && bmit::shape_supported_quad(default_bsk_precision(P), P.bs_levels, P.bs_base_log));
-    if (!ok_lb) {
-        why = "(l, Bg) must be (3, 2^15); the 49-bit field at N <= 2048 also takes (2, 2^15) and (1, 2^23), the 2^64 torus (3 or 2, 2^10) "
-              "and, at N = 1024, (3 or 2, 2^15)";
-        return false;
-    }
+    if (!(why = rotplan::decomposition_refusal(shape)).empty()) return false;
     if (P.n == 0 || P.n > BMI_MAX_LWE_N) { why = "n must be in [1, 1024]"; return false; }
     if (P.q_bits != 0 && P.q_bits != 64 && P.q_bits != 49 && P.q_bits != BMI_Q_TORUS64) {
         why = "q_bits must be 64 (2^64-2^32+1), 49 (2^49-720895) or BMI_Q_TORUS64 (2^64)";
@@ -651,75 +659,55 @@ int build_copy(bmi_ctx *c, DevBuf<T> &dst, size_t bytes, const char *what, Launc
     return 0;
 }
 
-// 2^64 torus at N = 1024: the key copies of the exact-transform kernels (bsk.exact, bsk.exact_lat).  d_std = the standard-domain
-// key on the device, or null to upload it from the host copy.  Contexts whose key has floating-point-transform copies build these
-// on demand only (kernel variants 1 / 3 / 4).
-int build_exact_torus_copies(bmi_ctx *c, const u64 *d_std) {
-    if (!c->bsk.exact.empty() && !c->bsk.exact_lat.empty()) return 0;
-    DevBuf<u64> own;
-    if (!d_std) {
-        HIP_OK(c, upload(own, c->bsk_std.data(), c->bsk_std.size()));
-        d_std = own.get();
-    }
-    const size_t bytes = c->bsk_std.size() * 8 * c->bsk_limbs();
-    const uint32_t polys = (uint32_t)(c->bsk_std.size() / c->N);
-    int rc = 0;
-    if (c->bsk.exact.empty())
-        rc = build_copy(c, c->bsk.exact, bytes, "bsk_to_limbs",
-                        [&](double *d) { return bmit::launch_bsk_to_limbs(d_std, d, c->tw_wave.get(), polys, c->bsk_prec, c->stream); });
-    if (!rc && c->bsk.exact_lat.empty())
-        rc = build_copy(c, c->bsk.exact_lat, bytes, "bsk_to_lat (torus)",
-                        [&](double *d) { return bmit::launch_bsk_to_lat(d_std, d, c->tw_half.get(), polys, c->bsk_prec, c->stream); });
-    return rc;
-}
-
-// The bootstrap key (host copy in c->bsk_std) -> device, in the layout of every kernel selectable on this context
-int upload_bsk(bmi_ctx *c) {
-    DevBuf<u64> d_std;
-    HIP_OK(c, upload(d_std, c->bsk_std.data(), c->bsk_std.size()));
-    const u64 *std_polys = d_std.get();
-    const uint32_t polys = (uint32_t)(c->bsk_std.size() / c->N);
-    const size_t bytes = d_std.bytes() * (c->t64() ? c->bsk_limbs() : 1);
+// How each kind of key copy is built: its field, its conversion launcher and the table that launcher reads.  std_polys = the
+// `polys` standard-domain polynomials of the plain (Copy::ntt_gl .. quad) or the unrolled key (Copy::u_*) on the device.
+int build_key_copy(bmi_ctx *c, Copy kind, const u64 *std_polys, uint32_t polys, size_t bytes) {
     const int prec = c->bsk_prec;
     const hipStream_t st = c->stream;
-    auto &K = c->bsk;
-    if (c->t64() && c->wide()) {   // N = 2048: one ciphertext per workgroup, and two (batches beyond 256)
-        // (40 bits, the precision of the unrolled kernel only: no plain key copy)
-        if (!bmit::shape_supported_wide(prec, c->P.bs_levels, c->P.bs_base_log)) return 0;
-        const int rc = build_copy(c, K.wide, bytes, "bsk_to_wide (torus)",
-                                  [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
-        return rc ? rc : build_copy(c, K.wide2, bytes, "bsk_to_wide2 (torus)",
-                                    [&](double *d) { return bmit::launch_bsk_to_wide2(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    bmi_ctx::BskCopies &K = c->bsk;
+    bmi_ctx::Bsk3Copies &K3 = c->bsk3;
+    const char *u_lat = "bsk_to_lat (unrolled key)";
+    switch (kind) {
+    case Copy::ntt_gl: return build_copy(c, K.ntt_gl, bytes, "bsk_to_ntt", [&](u64 *d) { return bmi::launch_bsk_to_ntt(std_polys, d, c->tw_gl.get(), polys, st); });
+    case Copy::ntt49: return build_copy(c, K.ntt49, bytes, "bsk_to_ntt", [&](double *d) { return bmi49::launch_bsk_to_ntt(std_polys, d, c->tw_wave.get(), polys, st); });
+    case Copy::lat49: return build_copy(c, K.lat49, bytes, "bsk_to_lat", [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, false, st); });
+    case Copy::wide49: return build_copy(c, K.wide49, bytes, "bsk_to_wide", [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
+    case Copy::quad49: return build_copy(c, K.quad49, bytes, "bsk_to_quad", [&](double *d) { return bmi49::launch_bsk_to_quad(std_polys, d, c->tw_wave.get(), c->tw_quad49.get(), polys, st); });
+    case Copy::exact: return build_copy(c, K.exact, bytes, "bsk_to_limbs", [&](double *d) { return bmit::launch_bsk_to_limbs(std_polys, d, c->tw_wave.get(), polys, prec, st); });
+    case Copy::exact_lat: return build_copy(c, K.exact_lat, bytes, "bsk_to_lat (torus)", [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
+    case Copy::fft: return build_copy(c, K.fft, bytes, "bsk_to_fft (torus)", [&](double *d) { return bmit::launch_bsk_to_fft(std_polys, d, c->tw_fft.get(), polys, prec, st); });
+    case Copy::fft_lat: return build_copy(c, K.fft_lat, bytes, "bsk_to_latf (torus)", [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
+    case Copy::wide: return build_copy(c, K.wide, bytes, "bsk_to_wide (torus)", [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    case Copy::wide2: return build_copy(c, K.wide2, bytes, "bsk_to_wide2 (torus)", [&](double *d) { return bmit::launch_bsk_to_wide2(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    case Copy::quad: return build_copy(c, K.quad, bytes, "bsk_to_quad (torus)", [&](double *d) { return bmit::launch_bsk_to_quad(std_polys, d, c->tw_eighth.get(), polys, prec, st); });
+    case Copy::u_lat49: return build_copy(c, K3.lat49, bytes, u_lat, [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, true, st); });
+    case Copy::u_wide49: return build_copy(c, K3.wide49, bytes, u_lat, [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
+    case Copy::u_exact_lat: return build_copy(c, K3.exact_lat, bytes, u_lat, [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
+    case Copy::u_fft_lat: return build_copy(c, K3.fft_lat, bytes, u_lat, [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
+    case Copy::u_wide: return build_copy(c, K3.wide, bytes, "bsk_to_wide (unrolled key)", [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
+    case Copy::COUNT: break;
     }
-    if (c->t64() && c->quad())
-        return build_copy(c, K.quad, bytes, "bsk_to_quad (torus)",
-                          [&](double *d) { return bmit::launch_bsk_to_quad(std_polys, d, c->tw_eighth.get(), polys, prec, st); });
-    if (c->t64() && !c->tw_fft.empty() && bmit::shape_supported_fft(prec, c->P.bs_levels, c->P.bs_base_log)) {
-        // the kernels auto dispatch runs on this key (48 bits, base 2^10): the wave-pair and the latency form of
-        // bmi_kernels_t64f.hip, exact limb products through the floating-point transform.  The two copies of the
-        // exact-transform kernels (variants 1 / 3 / 4: A/B only) are built when such a variant is first pinned.
-        const int rc = build_copy(c, K.fft, bytes, "bsk_to_fft (torus)",
-                                  [&](double *d) { return bmit::launch_bsk_to_fft(std_polys, d, c->tw_fft.get(), polys, prec, st); });
-        return rc ? rc : build_copy(c, K.fft_lat, bytes, "bsk_to_latf (torus)",
-                                    [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
-    }
-    if (c->t64())   // (a precision that only the unrolled kernel takes - 42 bits at base 2^10: no plain key copy)
-        return bmit::shape_supported(prec, c->P.bs_levels, c->P.bs_base_log) ? build_exact_torus_copies(c, std_polys) : 0;
-    if (c->wide())
-        return build_copy(c, K.wide49, bytes, "bsk_to_wide",
-                          [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
-    if (c->quad())
-        return build_copy(c, K.quad49, bytes, "bsk_to_quad",
-                          [&](double *d) { return bmi49::launch_bsk_to_quad(std_polys, d, c->tw_wave.get(), c->tw_quad49.get(), polys, st); });
-    const int rc = c->ops->bsk_to_ntt(c, std_polys);
-    if (rc || !c->f64()) return rc;
-    // second copy of the key, in the slot order of the split-transform latency kernel
-    return build_copy(c, K.lat49, bytes, "bsk_to_lat",
-                      [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, false, st); });
+    return fail(c, -2, "unknown key copy");
 }
 
-// Evaluation keys (host copies in c->bsk_std / c->ksk) -> device: bootstrap key (upload_bsk), keyswitch key in word form
-// (+ bias vector) and in limb form.
+// Builds those of the copies `kinds` (bits of rotplan::Copy) of the standard-domain key `std_key` (host words) that the context
+// does not hold yet, in the order of the enumeration.  The plan names the copies: rotplan::plain_copies for a new key set,
+// on_demand_copies for a kernel that auto dispatch never runs, unrolled_copies for the unrolled key.
+int build_copies(bmi_ctx *c, uint32_t kinds, const std::vector<u64> &std_key) {
+    kinds &= ~held_of(c).copies;
+    if (!kinds) return 0;
+    DevBuf<u64> d_std;
+    HIP_OK(c, upload(d_std, std_key.data(), std_key.size()));
+    const uint32_t polys = (uint32_t)(std_key.size() / c->N);
+    const size_t bytes = d_std.bytes() * (c->t64() ? c->bsk_limbs() : 1);
+    for (int k = 0; k < (int)Copy::COUNT; k++)
+        if (kinds & rotplan::bit((Copy)k))
+            if (int rc = build_key_copy(c, (Copy)k, d_std.get(), polys, bytes)) return rc;
+    return 0;
+}
+
+// Evaluation keys (host copies in c->bsk_std / c->ksk) -> device: bootstrap key (in the layout of every kernel selectable on the
+// context: rotplan::plain_copies), keyswitch key in word form (+ bias vector) and in limb form.
 int upload_eval_keys(bmi_ctx *c) {
     const bmi_params &P = c->P;
     const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels;
@@ -731,7 +719,7 @@ int upload_eval_keys(bmi_ctx *c) {
     c->have_keys = false;
     c->bsk = {};    // the copies of the previous key set
     c->bsk3 = {};
-    if (int rc = upload_bsk(c)) return rc;
+    if (int rc = build_copies(c, rotplan::plain_copies(shape_of(P), c->bsk_prec), c->bsk_std)) return rc;
     const size_t ksk_rows = (size_t)k * N * lk;
     HIP_OK(c, c->ksk_padded.alloc(ksk_rows * c->ks_stride * sizeof(u64)));
     HIP_OK(c, hipMemset(c->ksk_padded.get(), 0, c->ksk_padded.bytes()));
@@ -774,47 +762,19 @@ int upload_bsk3(bmi_ctx *c) {
         for (u64 &w : c->bsk3_std) w = t64::round_key_word(w, c->bsk_prec);
     c->have_bsk3 = false;
     c->bsk3 = {};
-    DevBuf<u64> d_std;
-    HIP_OK(c, upload(d_std, c->bsk3_std.data(), words));
-    const u64 *std_polys = d_std.get();
-    const uint32_t polys = (uint32_t)(words / c->N);
-    const size_t bytes = words * 8 * (c->t64() ? c->bsk_limbs() : 1);
-    const int prec = c->bsk_prec;
-    const hipStream_t st = c->stream;
-    const char *what = "bsk_to_lat (unrolled key)";
-    int rc;
-    if (c->t64() && c->wide())   // N = 2048: the per-polynomial layout of the plain kernel, over [pairs][3][2 l rows][2] polynomials
-        rc = build_copy(c, c->bsk3.wide, bytes, "bsk_to_wide (unrolled key)",
-                        [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
-    else if (c->t64() && bmit::shape_supported_unrolled_fft(prec, c->P.bs_levels, c->P.bs_base_log))   // slot-pair order of the half FFT
-        rc = build_copy(c, c->bsk3.fft_lat, bytes, what,
-                        [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
-    else if (c->t64())
-        rc = build_copy(c, c->bsk3.exact_lat, bytes, what,
-                        [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
-    else if (c->wide())
-        rc = build_copy(c, c->bsk3.wide49, bytes, what,
-                        [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
-    else
-        rc = build_copy(c, c->bsk3.lat49, bytes, what,
-                        [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, true, st); });
-    if (rc) return rc;
+    if (int rc = build_copies(c, rotplan::unrolled_copies(shape_of(c->P), c->bsk_prec), c->bsk3_std)) return rc;
     c->have_bsk3 = true;
     return 0;
 }
 
 const FieldOps GOLDILOCKS_OPS = {bmi::launch_keyswitch, bmi::launch_keyswitch_mfma, bmi::launch_ksk_to_limbs, bmi::launch_lincomb, bmi::launch_lwe_phase,
-    [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt_gl, c->bsk_std.size() * 8, "bsk_to_ntt", [&](u64 *d) {
-        return bmi::launch_bsk_to_ntt(std_polys, d, c->tw_gl.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
     [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi::launch_negacyclic_mul(a, b, o, c->tw_gl.get(), m, c->stream); },
     bmi::KS_LIMBS};
 const FieldOps FIELD49_OPS = {bmi49::launch_keyswitch, bmi49::launch_keyswitch_mfma, bmi49::launch_ksk_to_limbs, bmi49::launch_lincomb, bmi49::launch_lwe_phase,
-    [](bmi_ctx *c, const u64 *std_polys) { return build_copy(c, c->bsk.ntt49, c->bsk_std.size() * 8, "bsk_to_ntt", [&](double *d) {
-        return bmi49::launch_bsk_to_ntt(std_polys, d, c->tw_wave.get(), (uint32_t)(c->bsk_std.size() / c->N), c->stream); }); },
     [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi49::launch_negacyclic_mul(a, b, o, c->tw_wave.get(), m, c->stream); },
     bmi49::KS_LIMBS};
 const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfma, bmit::launch_ksk_to_limbs, bmit::launch_lincomb, bmit::launch_lwe_phase,
-                              nullptr, nullptr, bmit::KS_LIMBS};
+                              nullptr, bmit::KS_LIMBS};
 
 // evaluation keys for the secret keys held in c->sk_small / c->sk_big, deterministic in `seed`
 int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
@@ -882,107 +842,19 @@ int ensure_ks_mfma(bmi_ctx *c, uint32_t count) {
     return rc ? rc : grow(c, c->ks_sums, sums, (size_t)32 << 20);
 }
 
-// The blind-rotation launchers (bmi_internal.hpp), one member each: choose_rotation picks one, launch_rotation runs it.
-enum class Rot {
-    t64_wide_u, t64_wide_u2, t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
-    f49_wide_u, f49_wide, f49_quad, f49_lat2u, f49_lat2, f49_tpx,                                                   // 49-bit field
-    gl_lat, gl_tp,                                                                                                  // Goldilocks
-};
-
-// The kernel of bmi_blind_rotate_batch for a batch of `count` on this context: 0 and *rot, or a refusal.
+// The kernel of bmi_blind_rotate_batch for a batch of `count` on this context (rotplan::choose_rotation): 0 and *rot, or a refusal.
 int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
-    // unrolled key (49-bit field and 2^64 torus at N = 1024 / 2048: bmi_set_bsk_unroll refuses the rest): kernels that give the same
-    // words, so that a ciphertext's bits never depend on the batch it travelled in
-    if (c->unroll == 2 && !c->have_bsk3)
-        return fail(c, -1, "unrolling selected but the context holds no unrolled key: generate keys after bmi_set_bsk_unroll, or bmi_import_bsk_unrolled");
-    const int v = c->variant;
-    // variant 0 = auto: the latency kernel (one workgroup per ciphertext) while the batch cannot fill the chip
-    // with wave-pair work, the throughput kernel beyond that (49-bit field: the exchange-once form).
-    const bool latency = v == 2 || (v == 0 && count <= c->lat_threshold);
-    // torus, batches beyond one round of 256: two ciphertexts per workgroup sharing the key words (variants 1 / 3 pin it, 2 pins
-    // the one-ciphertext form); the same words either way.  The unrolled N = 2048 pair (wu / wu2) follows the plain pair's rule:
-    // one round of wu2 (up to 512 ciphertexts on 256 compute units) measures 11.35 ms against 7.6 ms for one round of wu (up to
-    // 256) and 15.25 ms for two (257 .. 512), so wu2 wins from 257 on and wu up to 256; at 1,024 / 2,048 / 8,192 wu2 takes 0.74 of
-    // wu's time (profiles/unrolled_wide2_ab.txt; 512 is the smallest batch measured - between 257 and 512 both kernels run the
-    // round counts they run at 512).
-    const bool two_per_wg = v == 1 || v == 3 || (v == 0 && count > 256);
-    const int prec = c->bsk_prec;
-    const uint32_t lv = c->P.bs_levels, bl = c->P.bs_base_log;
-    if (c->t64()) {
-        if (c->wide() && c->unroll == 2) *rot = two_per_wg ? Rot::t64_wide_u2 : Rot::t64_wide_u;   // one key copy serves both
-        else if (c->wide() && c->bsk.wide.empty())
-            return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
-        else if (c->wide() && !c->bsk.wide2.empty() && two_per_wg) *rot = Rot::t64_wide2;
-        else if (c->wide()) *rot = Rot::t64_wide;   // N = 2048 / 4096: one workgroup per ciphertext
-        else if (c->quad()) *rot = Rot::t64_quad;
-        else if (c->unroll == 2)   // the floating-point-transform route where the key is at 42 bits, else the exact transform
-            *rot = !bmit::shape_supported_unrolled_fft(prec, lv, bl) ? Rot::t64_lat2u : two_per_wg ? Rot::t64_tp2u_fft : Rot::t64_lat2u_fft;
-        else {   // N = 1024: latency kernel (one workgroup per ciphertext) for small batches, wave pairs beyond
-            if (c->bsk.fft.empty() && !bmit::shape_supported(prec, lv, bl))
-                return fail(c, -1, "this bootstrap-key precision exists for the unrolled kernel only: bmi_set_bsk_unroll(ctx, 2) before keygen");
-            if ((v == 5 || v == 6) && c->bsk.fft.empty())
-                return fail(c, -1, "kernel variant " + std::to_string(v) + " needs the bootstrap key at 48 bits of precision in base 2^10 (the torus default)");
-            // (floating-point-transform kernels: two rounds of 256 one-workgroup bootstraps, 7.7 ms, still beat the wave-pair kernel's
-            // 8.4 ms up to 1,024 ciphertexts; three rounds do not)
-            const bool lat_t = v == 2 || v == 4 || v == 6 || (v == 0 && count <= c->lat_threshold);
-            // through the floating-point transform where its key copy exists (48-bit key, base 2^10): variants 4 (latency) and
-            // 1 / 3 (wave pairs) pin the exact transform mod 2^49 - 720895, 5 and 6 the floating-point one
-            const bool fft = !c->bsk.fft.empty() && (lat_t ? v != 4 : v == 0 || v == 5);
-            *rot = lat_t ? (fft ? Rot::t64_lat_fft : Rot::t64_lat) : (fft ? Rot::t64_fft : Rot::t64_exact);
-        }
-    } else if (c->f64()) {
-        if (c->wide()) *rot = c->unroll == 2 ? Rot::f49_wide_u : Rot::f49_wide;   // N = 2048 / 4096: one kernel for every batch size
-        else if (c->quad()) *rot = Rot::f49_quad;
-        else *rot = c->unroll == 2 ? Rot::f49_lat2u : latency ? Rot::f49_lat2 : Rot::f49_tpx;
-    } else {
-        *rot = latency ? Rot::gl_lat : Rot::gl_tp;
-    }
+    const rotplan::Choice ch = rotplan::choose_rotation(shape_of(c->P), settings_of(c), held_of(c), count);
+    if (!ch.refusal.empty()) return fail(c, -1, ch.refusal);
+    *rot = ch.rot;
     return 0;
-}
-
-// The __global__ function a member launches: bmi_rotation_kernel answers with it
-const char *rotation_name(Rot rot) {
-    switch (rot) {
-    case Rot::t64_wide_u: return "k_blind_rotate_wu_t64f";
-    case Rot::t64_wide_u2: return "k_blind_rotate_wu2_t64f";
-    case Rot::t64_wide2: return "k_blind_rotate_w2_t64f";
-    case Rot::t64_wide: return "k_blind_rotate_w_t64f";
-    case Rot::t64_quad: return "k_blind_rotate_q_t64f";
-    case Rot::t64_tp2u_fft: return "k_blind_rotate_tp2u_t64f";
-    case Rot::t64_lat2u_fft: return "k_blind_rotate_lat2u_t64f";
-    case Rot::t64_lat2u: return "k_blind_rotate_lat2u_t64";
-    case Rot::t64_lat_fft: return "k_blind_rotate_lat_t64f";
-    case Rot::t64_lat: return "k_blind_rotate_lat_t64";
-    case Rot::t64_fft: return "k_blind_rotate_t64f";
-    case Rot::t64_exact: return "k_blind_rotate_t64";
-    case Rot::f49_wide_u: return "k_blind_rotate_wide49u";
-    case Rot::f49_wide: return "k_blind_rotate_wide49";
-    case Rot::f49_quad: return "k_blind_rotate_quad49";
-    case Rot::f49_lat2u: return "k_blind_rotate_lat2u_49";
-    case Rot::f49_lat2: return "k_blind_rotate_lat2_49";
-    case Rot::f49_tpx: return "k_blind_rotate_tpx49";
-    case Rot::gl_lat: return "k_blind_rotate_lat";
-    case Rot::gl_tp: return "k_blind_rotate_tp";
-    }
-    return "";
-}
-
-// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the nine floating-point-transform kernels of the torus.
-// Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not the prime fields.
-bool has_accumulator_form(Rot rot) {
-    switch (rot) {
-    case Rot::t64_wide_u: case Rot::t64_wide_u2: case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft:
-    case Rot::t64_lat_fft: case Rot::t64_fft:
-        return true;
-    default: return false;
-    }
 }
 
 // Launches `rot` on the context's key copies and tables.  stat: as in bmit::launch_blind_rotate_fft, for the kernels that take it.
 // glwe (has_accumulator_form(rot) only): out receives the accumulators [count][2N] instead of the extracted samples [count][N + 1].
 int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *out, unsigned long long *stat,
                     bool glwe, hipStream_t st) {
-    if (glwe && !has_accumulator_form(rot)) return (int)hipErrorInvalidValue;
+    if (glwe && !rotplan::has_accumulator_form(rot)) return (int)hipErrorInvalidValue;
     const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
     const int p = c->bsk_prec;
     const u64 *luts = c->luts.get();
@@ -1130,8 +1002,10 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
     if (c->P.q_bits == 49) c->f = Fq{f49::Q, 49};
     if (c->P.q_bits == BMI_Q_TORUS64) {
         c->f = Fq{0, 64, true};
-        c->bsk_prec = default_bsk_precision(c->P);
     }
+    const rotplan::Settings initial = rotplan::initial_settings(shape_of(c->P));
+    c->bsk_prec = initial.bsk_prec;
+    c->lat_threshold = initial.lat_threshold;
     c->ops = c->f64() ? &FIELD49_OPS : c->t64() ? &TORUS64_OPS : &GOLDILOCKS_OPS;
     c->device = device;
     c->N = 1u << params->log_N;
@@ -1493,32 +1367,8 @@ int bmi_lut_get(const bmi_ctx *c, uint32_t lut_id, uint64_t *test_vector) {
 
 int bmi_set_bsk_precision(bmi_ctx *c, uint32_t bits) {
     if (!c) return -1;
-    if (!c->t64()) return fail(c, -1, "the bootstrap-key precision option exists on the 2^64 torus only");
-    if (!t64::precision_ok((int)bits)) return fail(c, -1, "bootstrap-key precision must be 64 (exact), 48, 46, 44, 42 or 40 bits");
-    if (c->have_keys) return fail(c, -1, "set the bootstrap-key precision before generating or importing keys");
-    if (c->wide() || c->quad()) {
-        // N = 2048 in unrolled mode (bmi_set_bsk_unroll first - which selects it by itself when no precision was set): 40 bits only
-        if (c->wide() && c->unroll == 2) {
-            if (!bmit::shape_supported_wide_unrolled((int)bits, c->P.bs_levels, c->P.bs_base_log))
-                return fail(c, -1, "at N = 2048 the unrolled torus kernel takes the key at 40 bits of precision (two 20-bit limbs) only: the six-times "
-                                   "larger limb sums of the unrolled step must stay inside the transform's certified range (bmi_kernels_t64wu.hip)");
-        } else if (!(c->quad() ? bmit::shape_supported_quad : bmit::shape_supported_wide)((int)bits, c->P.bs_levels, c->P.bs_base_log))
-            return fail(c, -1, "at N = 2048 the torus kernel takes the key at 46 bits of precision (two 23-bit limbs) only - and at 40 bits (two 20-bit "
-                               "limbs) for the unrolled kernel (bmi_set_bsk_unroll) -, at N = 4096 at 44 bits (two "
-                               "22-bit limbs): the lengths at which the floating-point transform's error bound certifies the rounding "
-                               "(fft_quarter_f64.hpp, fft_eighth_f64.hpp)");
-        c->bsk_prec = (int)bits;
-        c->bsk_prec_explicit = true;
-        return 0;
-    }
-    // 42 bits at base 2^10: in unrolled mode only (bmi_set_bsk_unroll first - which selects it by itself when no precision was set)
-    const bool unrolled_fft = c->unroll == 2 && bmit::shape_supported_unrolled_fft((int)bits, c->P.bs_levels, c->P.bs_base_log);
-    if (!bmit::shape_supported((int)bits, c->P.bs_levels, c->P.bs_base_log) && !unrolled_fft)
-        return fail(c, -1, "no kernel for this precision at this decomposition: base 2^10 takes 48 (default) or 64 bits - and 42 bits for the "
-                           "unrolled floating-point-transform kernel (bmi_set_bsk_unroll) -, base 2^15 takes 64 (default) or 42 bits (a limb sum "
-                           "must stay below p/2: t64_common.hpp)");
-    if (c->unroll == 2 && !unrolled_fft && !bmit::shape_supported_unrolled((int)bits, c->P.bs_levels, c->P.bs_base_log))
-        return fail(c, -1, "the unrolled torus kernels take the key at 48 bits (exact transform) or 42 bits (floating-point transform) at base 2^10");
+    const std::string refusal = rotplan::set_precision_refusal(shape_of(c->P), settings_of(c), held_of(c), bits);
+    if (!refusal.empty()) return fail(c, -1, refusal);
     c->bsk_prec = (int)bits;
     c->bsk_prec_explicit = true;
     return 0;
@@ -1532,32 +1382,9 @@ int bmi_get_bsk_precision(const bmi_ctx *c, uint32_t *bits) {
 
 int bmi_set_bsk_unroll(bmi_ctx *c, uint32_t factor) {
     if (!c) return -1;
-    if (factor != 1 && factor != 2) return fail(c, -1, "the unrolling factor is 1 or 2");
-    if (factor == 2 && !((c->f64() && !c->quad()) || c->t64()))
-        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field and the 2^64 torus at N = 1024 and N = 2048 only");
-    if (factor == 2 && c->t64() && c->quad())
-        return fail(c, -1, "bootstrap-key unrolling has no HIP kernel on the 2^64 torus at N = 4096");
-    if (factor == 2 && c->t64() && c->wide() && !bmit::shape_supported_wide_unrolled(40, c->P.bs_levels, c->P.bs_base_log))
-        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled kernel exists for l = 2 or 3 levels in base 2^10");
-    if (c->t64() && !c->bsk_prec_explicit && !c->have_keys) {
-        // the precision nobody chose follows the mode: the unrolled step runs through the floating-point transform on a key stored
-        // at 42 bits (k_blind_rotate_lat2u_t64f: 2.9 ms per bootstrap against 3.3 of the exact-transform kernel on the 48-bit key,
-        // which bmi_set_bsk_precision(ctx, 48) still selects); back to the set's default when unrolling is switched off
-        // (N = 2048: 40 bits, the only precision of k_blind_rotate_wu_t64f)
-        if (factor == 2 && c->wide()) c->bsk_prec = 40;
-        else if (factor == 2 && bmit::shape_supported_unrolled_fft(42, c->P.bs_levels, c->P.bs_base_log)) c->bsk_prec = 42;
-        if (factor == 1) c->bsk_prec = default_bsk_precision(c->P);
-    }
-    if (factor == 2 && c->t64() && c->wide() && c->bsk_prec != 40)
-        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled kernel takes the key at 40 bits of precision only (chosen by itself when no "
-                           "precision was set, before keygen): the limb sums of its three scaled products must stay inside the transform's "
-                           "certified range");
-    if (factor == 2 && c->t64() && !c->wide() && !bmit::shape_supported_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log) &&
-        !bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
-        return fail(c, -1, "on the 2^64 torus the unrolled kernels take the key at 48 or 42 bits at base 2^10 (the default torus set): the limb sums of "
-                           "its three scaled products must stay below p/2");
-    if (factor == 2 && c->wide() && !c->t64() && c->P.bs_levels > 2)
-        return fail(c, -1, "at N = 2048 the unrolled kernel exists for l <= 2 (at l = 3 it would not fit the registers: the plain kernel is faster)");
+    const rotplan::UnrollChoice ch = rotplan::set_unroll(shape_of(c->P), settings_of(c), held_of(c), factor);
+    if (!ch.refusal.empty()) return fail(c, -1, ch.refusal);
+    c->bsk_prec = ch.bsk_prec;   // (the precision nobody chose follows the mode)
     c->unroll = factor;
     if (factor == 2 && c->have_keys && !c->have_bsk3) {
         if (!c->have_secret) return 0;   // evaluation-only context: the key arrives through bmi_import_bsk_unrolled
@@ -1570,11 +1397,8 @@ int bmi_set_bsk_unroll(bmi_ctx *c, uint32_t factor) {
 
 int bmi_import_bsk_unrolled(bmi_ctx *c, const uint64_t *bsk3) {
     if (!c || !bsk3) return -1;
-    if (!((c->f64() || c->t64()) && !c->quad()))
-        return fail(c, -1, "bootstrap-key unrolling has HIP kernels for the 49-bit field and the 2^64 torus at N = 1024 and N = 2048 only");
-    if (c->t64() && c->wide() && !bmit::shape_supported_wide_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
-        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled key is stored at 40 bits of precision: bmi_set_bsk_unroll(ctx, 2) before the key set");
-    if (!c->have_keys) return fail(c, -1, "no keys: import or generate the key set first");
+    const std::string refusal = rotplan::import_unrolled_refusal(shape_of(c->P), settings_of(c), held_of(c));
+    if (!refusal.empty()) return fail(c, -1, refusal);
     const size_t words = c->bsk3_words();
     for (size_t i = 0; i < words; i++)
         if (!c->f.canonical(bsk3[i])) return fail(c, -1, "unrolled bootstrap key word not reduced mod q");
@@ -1617,16 +1441,14 @@ int bmi_rotation_kernel(const bmi_ctx *c, uint32_t count, const char **name) {
     if (!c || !name) return -1;
     Rot rot;
     if (int rc = choose_rotation(c, count, &rot)) return rc;
-    *name = rotation_name(rot);
+    *name = rotplan::rotation_name(rot);
     return 0;
 }
 
 int bmi_set_kernel_variant(bmi_ctx *c, int variant) {
     if (!c) return -1;
-    if (variant < 0 || variant > 6) return fail(c, -1, "variant must be 0..6");
-    if (variant >= 5 && !c->t64()) return fail(c, -1, "kernel variants 5 and 6 (floating-point transform) exist on the 2^64 torus only");
-    if (c->f64() && !c->wide() && !c->quad() && (variant == 1 || variant == 4))
-        return fail(c, -1, "kernel variants 1 and 4 are refused on the 49-bit field at N = 1024: 3 and 2 replaced their kernels there");
+    const std::string refusal = rotplan::set_variant_refusal(shape_of(c->P), variant);
+    if (!refusal.empty()) return fail(c, -1, refusal);
     c->variant = variant;
     return 0;
 }
@@ -1677,11 +1499,10 @@ static int blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_
     HIP_OK(c, hipSetDevice(c->device));
     Rot rot;
     if (int rc = choose_rotation(c, count, &rot)) return rc;
-    if (glwe && !has_accumulator_form(rot))
+    if (glwe && !rotplan::has_accumulator_form(rot))
         return fail(c, -1, "the accumulator form exists for the floating-point-transform kernels only: not for a pinned exact-transform variant "
                            "(1 / 3 / 4), nor for the unrolled key pinned at 48 bits of precision (the exact-transform unrolled kernel)");
-    if (rot == Rot::t64_lat || rot == Rot::t64_exact)
-        if (int rc = build_exact_torus_copies(c, nullptr)) return rc;   // (a no-op once built)
+    if (int rc = build_copies(c, rotplan::on_demand_copies(rot), c->bsk_std)) return rc;   // (a no-op once built)
     const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, glwe, (hipStream_t)stream);
     if (rc) return fail(c, -2, std::string(glwe ? "blind_rotate (accumulator form) launch: " : "blind_rotate launch: ") + hipGetErrorString((hipError_t)rc));
     return 0;
@@ -1944,20 +1765,9 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
                         double *max_distance) {
     if (!c || !small_in || !lut_ids || !out || !max_distance) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    // its own kernel rule (batch size plays a part for the unrolled 40-bit key at N = 2048 only, where choose_rotation decides: the
-    // kernel that would run that batch): the unrolled kernel where the unrolled 42-bit key is in use, else at N = 1024
-    // the latency form when kernel variant 6 / 2 is selected, else the N = 2048 / 4096 kernel, else the wave-pair kernel
-    const bool ufft = c->t64() && c->unroll == 2 && c->have_bsk3 && bmit::shape_supported_unrolled_fft(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log);
-    const bool uwide = c->t64() && c->unroll == 2 && c->have_bsk3 && !c->bsk3.wide.empty();   // N = 2048, the unrolled 40-bit key
-    const bool wide_key = !c->bsk.wide.empty() || !c->bsk.quad.empty();
-    if (c->bsk.fft.empty() && !wide_key && !ufft && !uwide)
-        return fail(c, -1, "the floating-point-transform kernels exist on the 2^64 torus with the bootstrap key at 48 bits (N = 1024), 46 bits "
-                           "(N = 2048) or 44 bits (N = 4096) in base 2^10");
-    Rot rot_uwide = Rot::t64_wide_u;
-    if (uwide)
-        if (int rc = choose_rotation(c, count, &rot_uwide)) return rc;
-    const Rot rot = uwide ? rot_uwide : ufft ? Rot::t64_lat2u_fft : !wide_key && (c->variant == 6 || c->variant == 2) ? Rot::t64_lat_fft
-                    : wide_key ? (c->quad() ? Rot::t64_quad : Rot::t64_wide) : Rot::t64_fft;
+    const rotplan::Choice ch = rotplan::margin_rotation(shape_of(c->P), settings_of(c), held_of(c), count);
+    if (!ch.refusal.empty()) return fail(c, -1, ch.refusal);
+    const Rot rot = ch.rot;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
     HIP_OK(c, hipSetDevice(c->device));
     int rc = ensure_io(c, count);
@@ -2092,9 +1902,8 @@ int bmi_import_bsk_unrolled_seeded(bmi_ctx *c, const uint64_t *bsk3_bodies) {
     if (!c->have_keys || c->mask_src != bmi_ctx::MaskSource::SEEDED_IMPORT)
         return fail(c, -1, "bmi_import_bsk_unrolled_seeded: the unrolled key's masks are expanded from the public key of a preceding "
                            "bmi_import_keys_seeded, and this context has none");
-    if (c->quad()) return fail(c, -1, "bootstrap-key unrolling has no HIP kernel on the 2^64 torus at N = 4096");
-    if (c->wide() && !bmit::shape_supported_wide_unrolled(c->bsk_prec, c->P.bs_levels, c->P.bs_base_log))
-        return fail(c, -1, "on the 2^64 torus at N = 2048 the unrolled key is stored at 40 bits of precision: bmi_set_bsk_unroll(ctx, 2) before the key set");
+    const std::string refusal = rotplan::import_unrolled_seeded_refusal(shape_of(c->P), settings_of(c));
+    if (!refusal.empty()) return fail(c, -1, refusal);
     HIP_OK(c, hipSetDevice(c->device));
     if (int rc = expand_seeded_key(c, S_BSK3_MASK, (size_t)c->pairs() * 3 * c->rows, c->big_n, c->N, bsk3_bodies, c->bsk3_std)) return rc;
     if (int rc = upload_bsk3(c)) return rc;

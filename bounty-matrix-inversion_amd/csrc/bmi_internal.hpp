@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "goldilocks.hpp"
+#include "rotation_plan.hpp"
 
 #ifndef BMI_DEFAULT_Q_BITS
 #define BMI_DEFAULT_Q_BITS 65  // modulus of bmi_default_params(): 65 = BMI_Q_TORUS64 (q = 2^64, Concrete's own: the default since round 4), 49 (f64 kernels mod 2^49 - 720895) or 64 (Goldilocks)
@@ -226,9 +227,7 @@ namespace bmit {
 using gl::i64;
 using gl::u64;
 constexpr uint32_t KS_LIMBS = 9;    // balanced base-256 limbs of a keyswitch-key word
-// (precision, levels, base log) combinations with instantiated kernels
-bool shape_supported(int prec, uint32_t levels, uint32_t base_log);
-bool shape_supported_unrolled(int prec, uint32_t levels, uint32_t base_log);
+// (the (precision, levels, base log) combinations with instantiated kernels: bmit::shape_supported*, rotation_plan.hpp)
 int launch_bsk_to_limbs(const u64 *std_polys, double *limb_polys, const double *g_tw, uint32_t n_polys, int prec,
                         hipStream_t s);
 int launch_blind_rotate(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_limbs,
@@ -247,7 +246,6 @@ int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, con
                               uint32_t levels, uint32_t base_log, hipStream_t s);
 // wave pairs with the exact limb products carried by the folded complex FFT (bmi_kernels_t64f.hip, fft_wave_f64.hpp): key copy
 // [poly][limb][8 registers][64 lanes] complex words; tables fftw::TW_WORDS doubles; same results as launch_blind_rotate
-bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s);
 // stat (may be null): receives, as the bit pattern of a double, the largest distance of a limb sum from the integer it was rounded to
 // glwe (every launcher below that takes it): out receives the
@@ -264,7 +262,6 @@ int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, c
 // the unrolled step (two LWE coefficients) through the floating-point transform (bmi_kernels_t64fu.hip): key at 42 bits of precision
 // (two 21-bit limbs: the six-times larger limb sums stay inside the transform's certified range); bsk3_latf = launch_bsk_to_latf of
 // the unrolled key, g_zeta_pow = exp(i pi x / 1024) for x in [0, 1024) as (re, im); stat as in launch_blind_rotate_fft
-bool shape_supported_unrolled_fft(int prec, uint32_t levels, uint32_t base_log);
 int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                   const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
                                   uint32_t levels, uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
@@ -275,7 +272,6 @@ int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, 
 // N = 4096 (bmi_kernels_t64q.hip, fft_eighth_f64.hpp): key at 44 bits of precision (two 22-bit limbs), one workgroup per ciphertext,
 // one decomposition level of tiles in LDS at a time; key copy per (polynomial, limb) [t 8][256 slots] complex words A_k / 4; tables
 // ffte::ET_WORDS doubles
-bool shape_supported_quad(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw_e, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
@@ -288,7 +284,6 @@ int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, con
 // N = 2048 (bmi_kernels_t64w.hip, fft_quarter_f64.hpp): key at 46 bits of precision (two 23-bit limbs), one workgroup of 16
 // wavefronts per ciphertext (auto dispatch: up to 256 ciphertexts; launch_blind_rotate_wide2 beyond); key copy per (polynomial, limb) 1,024 complex words A_k / 2 in the order of the
 // multiplying threads; tables fftq::QT_WORDS doubles; stat as in launch_blind_rotate_fft
-bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log);
 int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);
 int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
@@ -297,7 +292,6 @@ int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, cons
 // stay inside the transform's certified range), one workgroup per ciphertext (auto dispatch: up to 256 ciphertexts;
 // launch_blind_rotate_wide_u2 beyond); bsk3_w = launch_bsk_to_wide of the
 // unrolled key [ceil(n/2)][3 keys][2 l rows][2] polynomials at prec = 40, g_zeta_oct = exp(i pi x / 2048) for x in [0, 512] as (re, im)
-bool shape_supported_wide_unrolled(int prec, uint32_t levels, uint32_t base_log);
 int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
                                unsigned long long *stat, bool glwe, hipStream_t s);

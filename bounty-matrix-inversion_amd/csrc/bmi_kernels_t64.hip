@@ -439,17 +439,8 @@ int launch_bsk_to_limbs(const u64 *std_polys, double *limb_polys, const double *
     return 0;
 }
 
-// the instantiated (precision, levels, base log) combinations; bmi_host.cpp params_supported / bmi_set_bsk_precision admit
-// exactly these
-#define BMIT_FOR_EACH_SHAPE(X) X(64, 3, 15) X(64, 2, 15) X(42, 3, 15) X(42, 2, 15) X(48, 3, 10) X(48, 2, 10) X(64, 3, 10)
-
-bool shape_supported(int prec, uint32_t levels, uint32_t base_log) {
-#define BMIT_SHAPE_OK(P, L, B) if (prec == P && levels == L && base_log == B) return true;
-    BMIT_FOR_EACH_SHAPE(BMIT_SHAPE_OK)
-#undef BMIT_SHAPE_OK
-    return false;
-}
-
+// (the instantiated (precision, levels, base log) combinations: BMIT_FOR_EACH_SHAPE, rotation_plan.hpp, where shape_supported reads
+// the same list)
 int launch_blind_rotate(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_limbs,
                         const double *g_tw, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
                         uint32_t base_log, hipStream_t s) {

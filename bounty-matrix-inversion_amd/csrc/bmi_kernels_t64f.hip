@@ -552,11 +552,6 @@ PH_EXPORT(bmi_debug_phase_prof_t64f, g_phase_f)
 
 namespace bmit {
 
-// (precision, levels, base log) combinations the transform's error bound was established for
-bool shape_supported_fft(int prec, uint32_t levels, uint32_t base_log) {
-    return prec == 48 && base_log == 10 && (levels == 3 || levels == 2);
-}
-
 int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s) {
     if (prec != 48) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);

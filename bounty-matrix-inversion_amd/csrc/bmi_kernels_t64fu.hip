@@ -313,11 +313,6 @@ __global__ void __launch_bounds__(H_THREADS)
 
 namespace bmit {
 
-// (precision, levels, base log) of the unrolled floating-point-transform kernel: the 42-bit key (two 21-bit limbs) in base 2^10
-bool shape_supported_unrolled_fft(int prec, uint32_t levels, uint32_t base_log) {
-    return prec == 42 && base_log == 10 && (levels == 3 || levels == 2);
-}
-
 // two ciphertexts per workgroup (key words shared in registers): the throughput form, same words as launch_blind_rotate_lat2u_fft
 int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,

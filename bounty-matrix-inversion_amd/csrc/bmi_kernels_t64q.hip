@@ -236,11 +236,6 @@ __global__ void __launch_bounds__(QF_THREADS)
 
 namespace bmit {
 
-// (precision, levels, base log) combinations the N = 4096 transform's error bound was established for
-bool shape_supported_quad(int prec, uint32_t levels, uint32_t base_log) {
-    return prec == 44 && base_log == 10 && (levels == 3 || levels == 2);
-}
-
 int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw_e, uint32_t n_polys, int prec, hipStream_t s) {
     if (prec != 44) return (int)hipErrorInvalidValue;
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);

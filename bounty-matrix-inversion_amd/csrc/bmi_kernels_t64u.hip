@@ -173,15 +173,7 @@ PH_EXPORT(bmi_debug_phase_prof_unrolled_t64, g_phase_tu)
 
 namespace bmit {
 
-#define BMIT_FOR_EACH_SHAPE_U(X) X(48, 3, 10) X(48, 2, 10)
-
-bool shape_supported_unrolled(int prec, uint32_t levels, uint32_t base_log) {
-#define BMIT_SHAPE_OK(P, L, B) if (prec == P && levels == L && base_log == B) return true;
-    BMIT_FOR_EACH_SHAPE_U(BMIT_SHAPE_OK)
-#undef BMIT_SHAPE_OK
-    return false;
-}
-
+// (the instantiated combinations: BMIT_FOR_EACH_SHAPE_U, rotation_plan.hpp)
 int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_lat,
                               const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, int prec,
                               uint32_t levels, uint32_t base_log, hipStream_t s) {

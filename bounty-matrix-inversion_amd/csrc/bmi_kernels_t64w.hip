@@ -223,11 +223,6 @@ PH_EXPORT(bmi_debug_phase_prof_t64w, g_phase_w)
 
 namespace bmit {
 
-// (precision, levels, base log) combinations the N = 2048 transform's error bound was established for
-bool shape_supported_wide(int prec, uint32_t levels, uint32_t base_log) {
-    return prec == 46 && base_log == 10 && (levels == 3 || levels == 2);
-}
-
 int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s) {
     if (prec != 46 && prec != 40) return (int)hipErrorInvalidValue;   // 40: the unrolled key (bmi_kernels_t64wu.hip)
     const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);

@@ -211,11 +211,6 @@ __global__ void __launch_bounds__(W_THREADS)
 
 namespace bmit {
 
-// (precision, levels, base log) of the N = 2048 unrolled kernel: the 40-bit key (two 20-bit limbs) in base 2^10
-bool shape_supported_wide_unrolled(int prec, uint32_t levels, uint32_t base_log) {
-    return prec == 40 && base_log == 10 && (levels == 3 || levels == 2);
-}
-
 int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
                                unsigned long long *stat, bool glwe, hipStream_t s) {
