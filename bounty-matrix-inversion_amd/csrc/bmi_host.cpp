@@ -4,18 +4,15 @@
 // batch call needs a HIP device and fails loudly without one.
 #include <hip/hip_runtime.h>
 
-#include <errno.h>
-#include <sys/random.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/bmi_tfhe.h"
+#include "host_crypto.hpp"
 #include "bmi_internal.hpp"
 #include "field49.hpp"
 #include "ntt_wave.hpp"
@@ -29,169 +26,14 @@
 
 using gl::i64;
 using gl::u64;
+// The library's cryptography - generators, key rows, encryption, phase, decoding - is host_crypto.hpp; this file holds the context,
+// checks arguments and state, and does the device work.
+using namespace hc;
+static_assert(GOLDILOCKS_P == gl::P && FIELD49_Q == f49::Q, "host_crypto.hpp states the moduli of goldilocks.hpp and field49.hpp");
 
 namespace {
 
-// --------------------------------------------------------------------------- deterministic RNG
-// Counter-based splitmix64 (same specification as the oracle so that key generation can be
-// cross-checked bit for bit): value(stream, idx) = mix(stream_key + (idx + 1) * GOLDEN).
-inline u64 mix64(u64 z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-// Arithmetic mod the context's ciphertext modulus on the host (keygen, encryption, LUT construction): plain
-// 128-bit remainders - none of this is on the hot path.
-struct Fq {
-    u64 q = gl::P;
-    uint32_t bits = 64;
-    bool torus = false;   // q = 2^64 exactly (q field unused): plain wrap-around arithmetic
-    u64 add(u64 a, u64 b) const { return torus ? a + b : (u64)(((unsigned __int128)a + b) % q); }
-    u64 sub(u64 a, u64 b) const { return torus ? a - b : (a >= b ? a - b : (u64)((unsigned __int128)a + q - b)); }
-    u64 neg(u64 a) const { return torus ? (u64)0 - a : (a ? q - a : 0); }
-    u64 mul(u64 a, u64 b) const { return torus ? a * b : (u64)(((unsigned __int128)a * b) % q); }
-    u64 from_i64(long long v) const {  // as f49::from_i64: |v| in unsigned arithmetic, canonical for -(multiple of q)
-        if (torus) return (u64)v;
-        if (v >= 0) return (u64)v % q;
-        const u64 m = ((u64)0 - (u64)v) % q;
-        return m ? q - m : 0;
-    }
-    long long centered(u64 a) const { return torus ? (long long)a : (a > (q >> 1) ? (long long)(a - q) : (long long)a); }
-    bool canonical(u64 a) const { return torus || a < q; }
-    u64 pow(u64 b, u64 e) const {
-        u64 r = 1;
-        while (e) {
-            if (e & 1) r = mul(r, b);
-            b = mul(b, b);
-            e >>= 1;
-        }
-        return r;
-    }
-};
-
-struct Stream {
-    u64 key;
-    Fq f;
-    Stream(u64 seed, u64 id, const Fq &fq) : key(mix64(seed ^ (id * 0xD6E8FEB86659FD93ULL))), f(fq) {}
-    u64 raw(u64 idx) const { return mix64(key + (idx + 1) * 0x9E3779B97F4A7C15ULL); }
-    u64 bit(u64 idx) const { return raw(idx) & 1; }
-    u64 uniform(u64 idx) const {
-        u64 u = raw(idx);
-        if (f.torus) return u;
-        return f.bits == 64 ? (u >= f.q ? u - f.q : u) : u % f.q;
-    }
-    u64 gauss(u64 idx, double sigma) const {  // Box-Muller, rounded to an element of Z_q
-        const double u1 = (double)((raw(2 * idx) >> 11) + 1) * (1.0 / 9007199254740992.0);
-        const double u2 = (double)(raw(2 * idx + 1) >> 11) * (1.0 / 9007199254740992.0);
-        const double g = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925286766559 * u2);
-        const long long e = std::llround(g * sigma * (f.bits == 64 ? 18446744073709551616.0 : (double)f.q));
-        return f.from_i64(e);
-    }
-};
-enum : u64 { S_SK_SMALL = 1, S_SK_BIG, S_BSK_MASK, S_BSK_NOISE, S_KSK_MASK, S_KSK_NOISE, S_ENC_MASK, S_ENC_NOISE, S_BSK3_MASK, S_BSK3_NOISE, S_PKSK_MASK, S_PKSK_NOISE };
-// the mask domains are part of the seeded key / ciphertext format (include/bmi_tfhe.h)
-static_assert(S_BSK_MASK == BMI_SEED_DOMAIN_BSK_MASK && S_KSK_MASK == BMI_SEED_DOMAIN_KSK_MASK && S_ENC_MASK == BMI_SEED_DOMAIN_ENC_MASK &&
-                  S_BSK3_MASK == BMI_SEED_DOMAIN_BSK3_MASK && S_PKSK_MASK == BMI_SEED_DOMAIN_PKSK_MASK,
-              "the published stream domains are the ones key generation uses");
-
-// --------------------------------------------------------------------------- CSPRNG (production keys and encryptions)
-// ChaCha20 (D. J. Bernstein's original variant: 256-bit key, 64-bit nonce, 64-bit block counter) keyed from the
-// operating system (getrandom).  Secret material (key bits, noise) and public material (masks) use two independent keys,
-// so that the public evaluation-key words say nothing about the stream the secrets came from.  Every (domain, row) pair
-// is its own nonce: rows are sampled in parallel and sequentially within a row.
-struct ChaKey {
-    uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool fill_from_os() {
-        size_t got = 0;
-        unsigned char *p = reinterpret_cast<unsigned char *>(k);
-        while (got < sizeof(k)) {
-            const ssize_t r = getrandom(p + got, sizeof(k) - got, 0);
-            if (r < 0) {
-                if (errno == EINTR) continue;
-                return false;
-            }
-            got += (size_t)r;
-        }
-        return true;
-    }
-};
-inline uint32_t rotl32(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
-inline void chacha_block(const ChaKey &key, u64 nonce, u64 counter, uint32_t out[16]) {
-    uint32_t in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3],
-                       key.k[4], key.k[5], key.k[6], key.k[7], (uint32_t)counter, (uint32_t)(counter >> 32),
-                       (uint32_t)nonce, (uint32_t)(nonce >> 32)};
-    uint32_t x[16];
-    for (int i = 0; i < 16; i++) x[i] = in[i];
-#define BMI_QR(a, b, c, d)                  \
-    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 16); \
-    x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 12); \
-    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 8);  \
-    x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 7)
-    for (int r = 0; r < 10; r++) {
-        BMI_QR(0, 4, 8, 12); BMI_QR(1, 5, 9, 13); BMI_QR(2, 6, 10, 14); BMI_QR(3, 7, 11, 15);
-        BMI_QR(0, 5, 10, 15); BMI_QR(1, 6, 11, 12); BMI_QR(2, 7, 8, 13); BMI_QR(3, 4, 9, 14);
-    }
-#undef BMI_QR
-    for (int i = 0; i < 16; i++) out[i] = x[i] + in[i];
-}
-struct ChaStream {
-    const ChaKey *key;
-    u64 nonce, counter = 0;
-    uint32_t buf[16];
-    int pos = 16;
-    ChaStream(const ChaKey &k, u64 domain, u64 row) : key(&k), nonce((domain << 56) | (row & ((1ULL << 56) - 1))) {}
-    // the stream of a whole nonce, positioned at its 64-bit word `first_word` (bmi_seeded_mask_words)
-    ChaStream(const ChaKey &k, u64 whole_nonce, u64 first_word, int) : key(&k), nonce(whole_nonce), counter(first_word / 8) {
-        for (u64 skip = first_word % 8; skip; skip--) (void)next64();
-    }
-    u64 next64() {
-        if (pos > 14) {
-            chacha_block(*key, nonce, counter++, buf);
-            pos = 0;
-        }
-        const u64 v = (u64)buf[pos] | ((u64)buf[pos + 1] << 32);
-        pos += 2;
-        return v;
-    }
-    u64 bit() { return next64() & 1; }
-    u64 uniform(const Fq &f) {   // rejection sampling: exactly uniform on [0, q)
-        for (;;) {
-            const u64 u = f.bits == 64 ? next64() : next64() >> (64 - f.bits);
-            if (f.torus || u < f.q) return u;
-        }
-    }
-    u64 gauss(const Fq &f, double sigma) {
-        const double u1 = (double)((next64() >> 11) + 1) * (1.0 / 9007199254740992.0);
-        const double u2 = (double)(next64() >> 11) * (1.0 / 9007199254740992.0);
-        const double g = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925286766559 * u2);
-        return f.from_i64(std::llround(g * sigma * (f.bits == 64 ? 18446744073709551616.0 : (double)f.q)));
-    }
-};
-// One row's source of masks / noise: the CSPRNG (sequential within the row) or, for the test-only deterministic key
-// generation, the counter-indexed splitmix streams the oracle reproduces bit for bit.
-struct RowRng {
-    const Stream *det;
-    ChaStream cha;
-    bool secure;
-    RowRng(const Stream *d, const ChaKey &k, u64 domain, u64 row, bool sec) : det(d), cha(k, domain, row), secure(sec) {}
-    u64 uniform(u64 idx) { return secure ? cha.uniform(det->f) : det->uniform(idx); }
-    u64 gauss(u64 idx, double sigma) { return secure ? cha.gauss(det->f, sigma) : det->gauss(idx, sigma); }
-    u64 bit(u64 idx) { return secure ? cha.bit() : det->bit(idx); }
-};
-
 thread_local std::string g_create_error;
-
-template <class F>
-void parallel_for(size_t n, F f) {
-    unsigned nt = std::max(1u, std::min(std::thread::hardware_concurrency(), 32u));
-    if (n < 4 * nt) nt = 1;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++)
-        th.emplace_back([=]() {
-            for (size_t i = t; i < n; i += nt) f(i);
-        });
-    for (auto &x : th) x.join();
-}
 
 // One device allocation, owned: freed when the buffer is destroyed, reset or assigned over.  Move-only.
 template <class T>
@@ -256,6 +98,7 @@ struct bmi_ctx {
     int bsk_limbs() const { return t64::limbs_of(bsk_prec); }
     bool secure_rng = false;       // true: keys / encryptions drawn from the CSPRNG below; false: test-only seeded streams
     ChaKey rng_secret, rng_public; // independent ChaCha20 keys from getrandom(): secrets + noise / public masks
+    Sampler sampler(u64 of_seed) const { return {of_seed, f, secure_rng, rng_secret, rng_public}; }   // what the generators draw from
     // Where the mask words of the evaluation keys held came from (beside have_keys; the seeded forms of chacha_expand.hip):
     // OWN_STREAM = drawn by this context from rng_public (CSPRNG key generation), SEEDED_IMPORT = expanded from the public key of
     // bmi_import_keys_seeded, which rng_public then holds; OTHER = anything else (bmi_import_keys, the deterministic test streams):
@@ -470,12 +313,6 @@ int ensure_io(bmi_ctx *c, size_t count) {
 }
 constexpr size_t KS_PARTIAL_BYTES = (size_t)96 << 20;  // covers every split configuration (<= 1024 workgroups x 8 ciphertexts)
 
-// out += X^t * a  (negacyclic), coefficient-wise in Z_q
-void add_shifted(const Fq &f, u64 *out, const u64 *a, uint32_t t, uint32_t N) {
-    for (uint32_t j = 0; j + t < N; j++) out[j + t] = f.add(out[j + t], a[j]);
-    for (uint32_t j = N - t; j < N; j++) out[j + t - N] = f.sub(out[j + t - N], a[j]);
-}
-
 // Twiddle tables of the wave NTT as canonical integers mod q: W1[k1][l] = psi^(l (2 k1 + 1)),
 // W1I = psi^-(..) / N, W2[v][t] = (psi^32)^(t v), W2I its inverse (layout shared by both fields).
 std::vector<u64> build_twiddles(const Fq &f, u64 psi, u64 psi_inv, u64 n_inv) {
@@ -580,70 +417,24 @@ int rekey_csprng(bmi_ctx *c) {
     return 0;
 }
 int gen_secret_keys(bmi_ctx *c, uint64_t seed) {
-    const uint32_t n = c->P.n, kN = c->P.k * c->N;
-    c->sk_small.assign(n, 0);
-    c->sk_big.assign(kN, 0);
-    Stream s1(seed, S_SK_SMALL, c->f), s2(seed, S_SK_BIG, c->f);
-    RowRng r1(&s1, c->rng_secret, S_SK_SMALL, 0, c->secure_rng), r2(&s2, c->rng_secret, S_SK_BIG, 0, c->secure_rng);
-    for (uint32_t i = 0; i < n; i++) c->sk_small[i] = r1.bit(i);
-    for (uint32_t i = 0; i < kN; i++) c->sk_big[i] = r2.bit(i);
+    c->sk_small.assign(c->P.n, 0);
+    c->sk_big.assign(c->big_n, 0);
+    secret_key_bits(c->sampler(seed), S_SK_SMALL, c->P.n, c->sk_small.data());
+    secret_key_bits(c->sampler(seed), S_SK_BIG, c->big_n, c->sk_big.data());
     return 0;
 }
 
-// GGSW encryptions (standard domain) of the bits msg[0..) under the GLWE key, rows numbered g * rows + comp * l + lev:
-// B = sum_j A_j * S_j + E by shifted adds (S binary); mask / noise streams as in oracle/tfhe_oracle.c ggsw_rows.
+// GGSW encryptions of the bits msg under the context's GLWE key, drawn from the streams (mask_stream, noise_stream) of `seed`
 void gen_ggsw_rows(bmi_ctx *c, uint64_t seed, u64 mask_stream, u64 noise_stream, const std::vector<u64> &msg, u64 *out) {
     const bmi_params &P = c->P;
-    const uint32_t N = c->N, k = P.k, l = P.bs_levels, rows = c->rows;
-    const Stream sm_det(seed, mask_stream, c->f), se_det(seed, noise_stream, c->f);
-    const Stream *smp = &sm_det, *sep = &se_det;
-    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-    const bool secure = c->secure_rng;
-    const Fq f = c->f;
-    const u64 *skb = c->sk_big.data();
-    const u64 *bits = msg.data();
-    const double sigma = P.glwe_noise;
-    const uint32_t bl = P.bs_base_log;
-    parallel_for(msg.size() * rows, [=](size_t ir) {
-        RowRng sm(smp, *kpub, mask_stream, ir, secure), se(sep, *ksec, noise_stream, ir, secure);
-        const uint32_t i = (uint32_t)(ir / rows), r = (uint32_t)(ir % rows), comp = r / l, lev = r % l;
-        u64 *row = out + ir * (k + 1) * N;
-        u64 *B = row + (size_t)k * N;
-        for (uint32_t x = 0; x < N; x++) B[x] = se.gauss((u64)ir * N + x, sigma);
-        for (uint32_t j = 0; j < k; j++) {
-            u64 *A = row + (size_t)j * N;
-            for (uint32_t x = 0; x < N; x++) A[x] = sm.uniform(((u64)ir * (k + 1) + j) * N + x);
-            for (uint32_t t = 0; t < N; t++)
-                if (skb[(size_t)j * N + t]) add_shifted(f, B, A, t, N);
-        }
-        if (!bits[i]) return;
-        const u64 g = (u64)1 << (f.bits - bl * (lev + 1));
-        if (secure && comp < k) {
-            // CSPRNG keys: a row of component comp < k encrypts -g S_comp in its BODY (the form of TFHE-rs and Concrete; the same
-            // phase, the same noise), so that every mask word stays a word of the public stream - what the seeded form of the key
-            // rests on.  Adding g to the mask polynomial instead, as below, would make that word tell the key bit to whoever
-            // knows the stream.
-            for (uint32_t x = 0; x < N; x++)
-                if (skb[(size_t)comp * N + x]) B[x] = f.sub(B[x], g);
-        } else {
-            row[(size_t)comp * N] = f.add(row[(size_t)comp * N], g);   // deterministic test keys: as oracle/tfhe_oracle.c ggsw_rows
-        }
-    });
+    ggsw_rows(c->sampler(seed), mask_stream, noise_stream, c->sk_big.data(), c->N, P.k, P.bs_levels, P.bs_base_log, P.glwe_noise, msg.data(),
+              msg.size(), out);
 }
 
-// the unrolled bootstrap key of the secret keys held: per pair (s, s') = (s_2i, s_2i+1) the GGSW encryptions of s s', s (1 - s'),
-// (1 - s) s'; an odd n is completed by s_n = 0 (host copy only; upload_bsk3 sends it to the device)
+// the unrolled bootstrap key of the secret keys held (host copy only; upload_bsk3 sends it to the device)
 void gen_bsk3(bmi_ctx *c, uint64_t seed) {
-    const uint32_t n = c->P.n;
-    std::vector<u64> msg((size_t)c->pairs() * 3);
-    for (uint32_t i = 0; i < c->pairs(); i++) {
-        const u64 s1 = c->sk_small[2 * i], s2 = 2 * i + 1 < n ? c->sk_small[2 * i + 1] : 0;
-        msg[3 * i] = s1 & s2;
-        msg[3 * i + 1] = s1 & (s2 ^ 1);
-        msg[3 * i + 2] = (s1 ^ 1) & s2;
-    }
     c->bsk3_std.assign(c->bsk3_words(), 0);
-    gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, msg, c->bsk3_std.data());
+    gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, unrolled_messages(c->sk_small.data(), c->P.n), c->bsk3_std.data());
     c->bsk3_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
 }
 
@@ -728,12 +519,7 @@ int upload_eval_keys(bmi_ctx *c) {
     // bias vector of the unsigned-digit keyswitch: (B/2) * sum_rows ksk[row][col]
     {
         std::vector<u64> bias(c->ks_stride, 0);
-        const u64 half = (u64)1 << (P.ks_base_log - 1);
-        for (size_t r = 0; r < ksk_rows; r++) {
-            const u64 *row = c->ksk.data() + r * (n + 1);
-            for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.add(bias[x], row[x]);
-        }
-        for (uint32_t x = 0; x <= n; x++) bias[x] = c->f.mul(bias[x], half);
+        column_bias(c->f, c->ksk.data(), ksk_rows, n + 1, P.ks_base_log, bias.data());
         HIP_OK(c, upload(c->ks_bias, bias.data(), bias.size()));
     }
     // limb-wise copy of the keyswitch key for the matrix-core keyswitch (int8 operands, int32 sums: the digits must
@@ -796,30 +582,7 @@ int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
     if (c->unroll == 2) gen_bsk3(c, seed);
     // --- keyswitch key
     c->ksk.assign((size_t)k * N * lk * (n + 1), 0);
-    {
-        const Stream sm_det(seed, S_KSK_MASK, c->f), se_det(seed, S_KSK_NOISE, c->f);
-        const Stream *smp = &sm_det, *sep = &se_det;
-        const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-        const bool secure = c->secure_rng;
-        const Fq f = c->f;
-        const u64 *skb = c->sk_big.data();
-        const u64 *sks = c->sk_small.data();
-        u64 *ksk = c->ksk.data();
-        const double sigma = P.lwe_noise;
-        const uint32_t bl = P.ks_base_log;
-        parallel_for((size_t)k * N * lk, [=](size_t jr) {
-            RowRng sm(smp, *kpub, S_KSK_MASK, jr, secure), se(sep, *ksec, S_KSK_NOISE, jr, secure);
-            const uint32_t j = (uint32_t)(jr / lk), lev = (uint32_t)(jr % lk);
-            u64 *row = ksk + jr * (n + 1);
-            u64 b = se.gauss(jr, sigma);
-            for (uint32_t x = 0; x < n; x++) {
-                row[x] = sm.uniform((u64)jr * (n + 1) + x);
-                if (sks[x]) b = f.add(b, row[x]);
-            }
-            if (skb[j]) b = f.add(b, (u64)1 << (f.bits - bl * (lev + 1)));
-            row[n] = b;
-        });
-    }
+    ksk_rows(c->sampler(seed), c->sk_small.data(), n, c->sk_big.data(), c->big_n, lk, P.ks_base_log, P.lwe_noise, c->ksk.data());
     c->have_secret = true;
     if (int rc = upload_eval_keys(c)) return rc;
     return c->unroll == 2 ? upload_bsk3(c) : 0;
@@ -1118,10 +881,7 @@ int bmi_keygen_insecure_deterministic(bmi_ctx *c, uint64_t seed) {
 int bmi_keygen_from_secret(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big, uint64_t seed) {
     if (!c || !sk_small || !sk_big) return -1;
     const uint32_t n = c->P.n, kN = c->P.k * c->N;
-    for (uint32_t i = 0; i < n; i++)
-        if (sk_small[i] > 1) return fail(c, -1, "secret keys are binary");
-    for (uint32_t i = 0; i < kN; i++)
-        if (sk_big[i] > 1) return fail(c, -1, "secret keys are binary");
+    if (!is_binary(sk_small, n) || !is_binary(sk_big, kN)) return fail(c, -1, "secret keys are binary");
     c->sk_small.assign(sk_small, sk_small + n);
     c->sk_big.assign(sk_big, sk_big + kN);
     if (seed == 0) {            // production: masks and noise from the CSPRNG
@@ -1135,24 +895,13 @@ int bmi_keygen_from_secret(bmi_ctx *c, const uint64_t *sk_small, const uint64_t 
 // ct words on the 2^64 torus <-> words mod q: the modulus switch round(x * q / 2^64) and back.  Context-free (host).
 int bmi_torus64_to_field(uint32_t q_bits, const uint64_t *in, uint64_t words, uint64_t *out) {
     if (!in || !out || (q_bits != 64 && q_bits != 49)) return -1;
-    const u64 q = q_bits == 49 ? f49::Q : gl::P;
-    for (u64 i = 0; i < words; i++) {
-        const unsigned __int128 t = (unsigned __int128)in[i] * q + ((unsigned __int128)1 << 63);
-        const u64 r = (u64)(t >> 64);
-        out[i] = r >= q ? r - q : r;
-    }
+    torus64_to_field(q_bits == 49 ? f49::Q : gl::P, in, words, out);
     return 0;
 }
 
 int bmi_field_to_torus64(uint32_t q_bits, const uint64_t *in, uint64_t words, uint64_t *out) {
     if (!in || !out || (q_bits != 64 && q_bits != 49)) return -1;
-    const u64 q = q_bits == 49 ? f49::Q : gl::P;
-    for (u64 i = 0; i < words; i++) {
-        if (in[i] >= q) return -1;
-        const unsigned __int128 t = ((unsigned __int128)in[i] << 64) + (q >> 1);   // round(in * 2^64 / q) mod 2^64
-        out[i] = (u64)(t / q);
-    }
-    return 0;
+    return field_to_torus64(q_bits == 49 ? f49::Q : gl::P, in, words, out) ? 0 : -1;
 }
 
 int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big, const uint64_t *bsk, const uint64_t *ksk) {
@@ -1174,10 +923,7 @@ int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big
     c->ksk.assign(ksk, ksk + ksk_words);
     c->have_secret = sk_small != nullptr;
     if (c->have_secret) {
-        for (uint32_t i = 0; i < P.n; i++)
-            if (sk_small[i] > 1) return fail(c, -1, "secret keys are binary");
-        for (uint32_t i = 0; i < c->big_n; i++)
-            if (sk_big[i] > 1) return fail(c, -1, "secret keys are binary");
+        if (!is_binary(sk_small, P.n) || !is_binary(sk_big, c->big_n)) return fail(c, -1, "secret keys are binary");
         c->sk_small.assign(sk_small, sk_small + P.n);
         c->sk_big.assign(sk_big, sk_big + c->big_n);
     } else {
@@ -1213,28 +959,8 @@ static int encrypt_rows(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
     if (delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
-    const Stream sm_det(c->seed, S_ENC_MASK, c->f), se_det(c->seed, S_ENC_NOISE, c->f);
-    const Stream *smp = &sm_det, *sep = &se_det;
-    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-    const bool secure = c->secure_rng;
-    const Fq f = c->f;
-    const uint32_t dim = c->big_n;
-    const u64 first = c->enc_counter;   // secure contexts: never reset while the CSPRNG keys live (one nonce per ciphertext)
-    const u64 *key = c->sk_big.data();
-    const double sigma = c->P.glwe_noise;
-    parallel_for(count, [=](size_t i) {
-        RowRng sm(smp, *kpub, S_ENC_MASK, first + i, secure), se(sep, *ksec, S_ENC_NOISE, first + i, secure);
-        u64 *ct = ct_out ? ct_out + i * (dim + 1) : nullptr;
-        const u64 torus = f.mul(f.from_i64(msgs[i]), (u64)1 << delta_log);
-        u64 b = f.add(torus, se.gauss(first + i, sigma));
-        for (uint32_t x = 0; x < dim; x++) {
-            const u64 a = sm.uniform((first + i) * (u64)(dim + 1) + x);
-            if (ct) ct[x] = a;
-            if (key[x]) b = f.add(b, a);
-        }
-        if (ct) ct[dim] = b;
-        else bodies_out[i] = b;
-    });
+    // (secure contexts: the counter is never reset while the CSPRNG keys live - one nonce per ciphertext)
+    lwe_encrypt(c->sampler(c->seed), c->sk_big.data(), c->big_n, c->P.glwe_noise, c->enc_counter, msgs, count, delta_log, ct_out, bodies_out);
     c->enc_counter += count;
     return 0;
 }
@@ -1248,15 +974,7 @@ int bmi_phase(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint64_t 
     if (!c || !ct_in || !phase) return -1;
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
-    const uint32_t dim = c->big_n;
-    const u64 *key = c->sk_big.data();
-    for (uint32_t i = 0; i < count; i++) {
-        const u64 *ct = ct_in + (size_t)i * (dim + 1);
-        u64 p = ct[dim];
-        for (uint32_t x = 0; x < dim; x++)
-            if (key[x]) p = c->f.sub(p, ct[x]);
-        phase[i] = p;
-    }
+    lwe_phase(c->f, c->sk_big.data(), c->big_n, ct_in, count, phase);
     return 0;
 }
 
@@ -1266,10 +984,7 @@ int bmi_decrypt(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint32_
     std::vector<u64> ph(count);
     int rc = bmi_phase(c, ct_in, count, ph.data());
     if (rc) return rc;
-    for (uint32_t i = 0; i < count; i++) {
-        const i64 v = c->f.centered(ph[i]);
-        msgs[i] = (v >> delta_log) + ((v >> (delta_log - 1)) & 1);
-    }
+    for (uint32_t i = 0; i < count; i++) msgs[i] = decode(c->f, ph[i], delta_log);
     return 0;
 }
 
@@ -1804,14 +1519,10 @@ int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, ui
 }
 
 // ------------------------------------------------------------------- seeded keys and ciphertexts (chacha_expand.hip)
-// The specification of the seeded forms: words first_word .. first_word + count of the ChaCha20 stream (pub_key, nonce), drawn the
-// way key generation draws a row's masks on the 2^64 torus (ChaStream::next64).  Context-free, host only.
+// The specification of the seeded forms (hc::seeded_mask_words).  Context-free, host only.
 int bmi_seeded_mask_words(const uint32_t pub_key[8], uint64_t nonce, uint64_t first_word, uint64_t count, uint64_t *out) {
     if (!pub_key || (count && !out)) return -1;
-    ChaKey key;
-    std::memcpy(key.k, pub_key, sizeof(key.k));
-    ChaStream s(key, nonce, first_word, 0);
-    for (u64 i = 0; i < count; i++) out[i] = s.next64();
+    seeded_mask_words(pub_key, nonce, first_word, count, out);
     return 0;
 }
 
@@ -1844,12 +1555,6 @@ static int expand_seeded_key(bmi_ctx *c, u64 domain, size_t rows, uint32_t mask_
     HIP_OK(c, hipMemcpyAsync(full.data(), d_full.get(), rows * pitch * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
     return 0;
-}
-
-// the body words ([rows][body_w]) of a standard-domain array [rows][mask_w + body_w]
-static void copy_bodies(const std::vector<u64> &full, size_t rows, uint32_t mask_w, uint32_t body_w, u64 *bodies) {
-    const size_t pitch = (size_t)mask_w + body_w;
-    for (size_t r = 0; r < rows; r++) std::memcpy(bodies + r * body_w, full.data() + r * pitch + mask_w, (size_t)body_w * 8);
 }
 
 int bmi_export_keys_seeded(const bmi_ctx *c, uint32_t pub_key[8], uint64_t *bsk_bodies, uint64_t *ksk_bodies) {
@@ -1974,13 +1679,8 @@ static int log_modulus_ok(const bmi_ctx *c, const char *what, uint32_t log_modul
 // the compression key (host copy in c->pksk, standard layout) -> device, with the bias vector of the unsigned-digit product:
 // bias[col] = 2^(base_log - 1) * sum over all rows of key[row][col]
 static int upload_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
-    const size_t W = (size_t)2 * c->N, K = (size_t)c->N * levels;
-    std::vector<u64> bias(W, 0);
-    for (size_t r = 0; r < K; r++) {
-        const u64 *row = c->pksk.data() + r * W;
-        for (size_t x = 0; x < W; x++) bias[x] += row[x];
-    }
-    for (u64 &b : bias) b <<= base_log - 1;
+    std::vector<u64> bias((size_t)2 * c->N);
+    column_bias(c->f, c->pksk.data(), (size_t)c->N * levels, bias.size(), base_log, bias.data());
     c->pk_levels = 0;
     HIP_OK(c, upload(c->pksk_dev, c->pksk.data(), c->pksk.size()));
     HIP_OK(c, upload(c->pk_bias, bias.data(), bias.size()));
@@ -2006,30 +1706,8 @@ int bmi_compression_keygen(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
     drop_compression_key(c, false);
     c->pk_gen_levels = levels;
     c->pk_gen_base_log = base_log;
-    const uint32_t N = c->N;
-    c->pksk.assign((size_t)N * levels * 2 * N, 0);
-    const Stream sm_det(c->seed, S_PKSK_MASK, c->f), se_det(c->seed, S_PKSK_NOISE, c->f);
-    const Stream *smp = &sm_det, *sep = &se_det;
-    const ChaKey *ksec = &c->rng_secret, *kpub = &c->rng_public;
-    const bool secure = c->secure_rng;
-    const u64 *skb = c->sk_big.data();
-    u64 *key = c->pksk.data();
-    const double sigma = c->P.glwe_noise;
-    // row j * levels + lev = [A | B], B = A S + e + S_j 2^(64 - base_log (lev + 1)) X^0: masks from the public stream (CSPRNG keys:
-    // the first N words of the row's stream), noise from the secret one
-    parallel_for((size_t)N * levels, [=](size_t jr) {
-        RowRng sm(smp, *kpub, S_PKSK_MASK, jr, secure), se(sep, *ksec, S_PKSK_NOISE, jr, secure);
-        const uint32_t j = (uint32_t)(jr / levels), lev = (uint32_t)(jr % levels);
-        u64 *A = key + jr * 2 * N, *B = A + N;
-        for (uint32_t x = 0; x < N; x++) A[x] = sm.uniform((u64)jr * N + x);
-        for (uint32_t x = 0; x < N; x++) B[x] = se.gauss((u64)jr * N + x, sigma);
-        for (uint32_t t = 0; t < N; t++) {
-            if (!skb[t]) continue;
-            for (uint32_t x = 0; x + t < N; x++) B[x + t] += A[x];
-            for (uint32_t x = N - t; x < N; x++) B[x + t - N] -= A[x];
-        }
-        if (skb[j]) B[0] += (u64)1 << (64 - base_log * (lev + 1));
-    });
+    c->pksk.assign((size_t)c->N * levels * 2 * c->N, 0);
+    compression_key_rows(c->sampler(c->seed), c->sk_big.data(), c->N, levels, base_log, c->P.glwe_noise, c->pksk.data());
     if (int rc = upload_compression_key(c, levels, base_log)) return rc;
     c->pksk_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
     return 0;
@@ -2145,24 +1823,8 @@ int bmi_phase_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count,
     if (int rc = compression_ok(c, "bmi_phase_compressed")) return rc;
     if (!c->have_secret) return fail(c, -1, "bmi_phase_compressed: evaluation-only context: it holds no secret key");
     if (int rc = log_modulus_ok(c, "bmi_phase_compressed", log_modulus)) return rc;
-    const uint32_t N = c->N, up = 64 - log_modulus;
-    const u64 *key = c->sk_big.data();
-    std::vector<u64> A(N), AS(N);
-    for (uint32_t t0 = 0; t0 < count; t0 += N) {
-        const uint32_t m = std::min(N, count - t0);
-        const uint32_t *blk = data + (size_t)(t0 / N) * 2 * N;
-        for (uint32_t x = 0; x < N; x++) {
-            if (log_modulus < 32 && (blk[x] >> log_modulus)) return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
-            A[x] = (u64)blk[x] << up;
-        }
-        std::fill(AS.begin(), AS.end(), 0);
-        for (uint32_t t = 0; t < N; t++)
-            if (key[t]) add_shifted(c->f, AS.data(), A.data(), t, N);
-        for (uint32_t i = 0; i < m; i++) {
-            if (log_modulus < 32 && (blk[N + i] >> log_modulus)) return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
-            phase[t0 + i] = ((u64)blk[N + i] << up) - AS[i];
-        }
-    }
+    if (!compressed_phase(c->f, c->sk_big.data(), c->N, data, count, log_modulus, phase))
+        return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
     return 0;
 }
 
@@ -2172,10 +1834,7 @@ int bmi_decrypt_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t coun
     if (delta_log == 0 || delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
     std::vector<u64> ph(count);
     if (int rc = bmi_phase_compressed(c, data, count, log_modulus, ph.data())) return rc;
-    for (uint32_t i = 0; i < count; i++) {
-        const i64 v = (i64)ph[i];
-        msgs[i] = (v >> delta_log) + ((v >> (delta_log - 1)) & 1);
-    }
+    for (uint32_t i = 0; i < count; i++) msgs[i] = decode(c->f, ph[i], delta_log);
     return 0;
 }
 
