@@ -69,17 +69,9 @@ class DevBuf {
     size_t bytes_ = 0;
 };
 
-// The launchers that differ by modulus only: bmi_ctx_create picks one table per context.  The NTT test hook exists on the
-// prime fields only (null on the torus) and takes the context: each field has its own twiddle table.
-struct FieldOps {
-    decltype(&bmi::launch_keyswitch) keyswitch;
-    decltype(&bmi::launch_keyswitch_mfma) keyswitch_mfma;
-    decltype(&bmi::launch_ksk_to_limbs) ksk_to_limbs;
-    decltype(&bmi::launch_lincomb) lincomb;
-    decltype(&bmi::launch_lwe_phase) lwe_phase;
-    int (*negacyclic_mul)(const bmi_ctx *c, const u64 *a, const u64 *b, u64 *out, uint32_t count);
-    uint32_t ks_limbs;   // limbs per keyswitch-key word of the matrix-core keyswitch
-};
+using rotplan::Copy;
+using rotplan::Rot;
+using rotplan::Table;
 
 }  // namespace
 
@@ -106,54 +98,23 @@ struct bmi_ctx {
     enum class MaskSource { OTHER, OWN_STREAM, SEEDED_IMPORT } mask_src = MaskSource::OTHER;
     bool bsk3_from_stream = false; // ... and the same for the unrolled key held: its masks are words of rng_public's S_BSK3_MASK streams
     std::vector<u64> sk_small, sk_big, bsk_std, ksk;
-    // Tables (bmi_ctx_create), with the kernels that read them; empty where the context's modulus and N have no such kernel.
-    DevBuf<u64> tw_gl;          // Goldilocks: wave-NTT twiddles (ntt_wave.hpp) - bsk_to_ntt, negacyclic_mul, blind_rotate_lat / _tp
-    DevBuf<double> tw_wave;     // 49-bit field and torus: the same mod 2^49 - 720895, centred doubles - 49-bit bsk_to_ntt, blind_rotate_tpx
-                                // and their N = 2048 / 4096 forms, negacyclic_mul; torus bsk_to_limbs, blind_rotate
-    DevBuf<double> tw_half;     // 49-bit field and torus: half transform (ntt_half_f64.hpp) - bsk_to_lat, blind_rotate_lat2 / _lat / _lat2u
-    DevBuf<double> root_pow;    // 49-bit N <= 2048 and torus: psi^x, x < 2048 (psi_2048; N = 2048: psi_4096) - blind_rotate_lat2u, 49-bit _wide_u
-    DevBuf<double> tw_wide49;   // 49-bit N = 2048: T / T^-1 of the even/odd combination - bsk_to_wide, blind_rotate_wide / _wide_u
-    DevBuf<double> tw_quad49;   // 49-bit N = 4096: T_1..T_3, then their inverses - bsk_to_quad, blind_rotate_quad
-    DevBuf<double> tw_fft;      // torus N = 1024: folded complex FFT (fft_wave_f64.hpp) - bsk_to_fft, blind_rotate_fft
-    DevBuf<double> tw_fft_half; // torus N = 1024: half FFT (fft_half_f64.hpp) - bsk_to_latf, blind_rotate_lat_fft / _lat2u_fft / _tp2u_fft
-    DevBuf<double> zeta_pow;    // torus N = 1024: exp(i pi x / 1024), x in [0, 1024) as (re, im) - blind_rotate_lat2u_fft / _tp2u_fft
-    DevBuf<double> zeta_oct;    // torus N = 2048: exp(i pi x / 2048), x in [0, 512] as (re, im), one octant - blind_rotate_wide_u
-    DevBuf<double> tw_quarter;  // torus N = 2048: quarter transforms (fft_quarter_f64.hpp) - bsk_to_wide / _wide2, blind_rotate_wide / _wide2
-    DevBuf<double> tw_eighth;   // torus N = 4096: eighth transforms (fft_eighth_f64.hpp) - bsk_to_quad, blind_rotate_quad
+    // Tables (bmi_ctx_create), one per rotplan::Table, where the kernels that read each are listed; empty where the context's
+    // modulus and N have no such kernel (rotplan::context_tables).
+    DevBuf<void> tables[(int)Table::COUNT];
+    DevWords table(Table t) const { return {t == Table::none ? nullptr : tables[(int)t].get()}; }
     DevBuf<u64> luts;           // BMI_LUT_CAP test polynomials of N words (49-bit field: centred doubles) - every blind rotation
-    // The bootstrap key on the device, one field per layout (with its conversion and the kernel that reads it).  A copy exists where
-    // its kernel is selectable on the context (upload_eval_keys; the torus exact-transform pair when first chosen:
-    // rotplan::on_demand_copies).  A field that is not empty holds a whole copy (build_copy).  Replaced with the key set.
-    struct BskCopies {
-        DevBuf<u64> ntt_gl;        // Goldilocks, NTT domain (bsk_to_ntt): blind_rotate_lat / _tp
-        DevBuf<double> ntt49;      // 49-bit N = 1024, NTT domain (bsk_to_ntt): blind_rotate_tpx
-        DevBuf<double> lat49;      // 49-bit N = 1024, split-transform slot order (bsk_to_lat): blind_rotate_lat2
-        DevBuf<double> wide49;     // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide
-        DevBuf<double> quad49;     // 49-bit N = 4096 (bsk_to_quad): blind_rotate_quad
-        DevBuf<double> exact;      // torus N = 1024, limb polynomials of the exact transform (bsk_to_limbs): blind_rotate
-        DevBuf<double> exact_lat;  // ... in the slot order of its latency form (bsk_to_lat): blind_rotate_lat
-        DevBuf<double> fft;        // torus N = 1024, floating-point transform (bsk_to_fft): blind_rotate_fft
-        DevBuf<double> fft_lat;    // ... in half-transform slot pairs (bsk_to_latf): blind_rotate_lat_fft
-        DevBuf<double> wide;       // torus N = 2048 (bsk_to_wide): blind_rotate_wide
-        DevBuf<double> wide2;      // torus N = 2048, two ciphertexts per workgroup (bsk_to_wide2): blind_rotate_wide2
-        DevBuf<double> quad;       // torus N = 4096 (bsk_to_quad): blind_rotate_quad
-        size_t bytes() const {
-            return ntt_gl.bytes() + ntt49.bytes() + lat49.bytes() + wide49.bytes() + quad49.bytes() + exact.bytes() + exact_lat.bytes() +
-                   fft.bytes() + fft_lat.bytes() + wide.bytes() + wide2.bytes() + quad.bytes();
-        }
-    } bsk;
+    // The bootstrap key on the device, one buffer per layout (rotplan::Copy, with its conversion and the kernel that reads it).  A
+    // copy exists where its kernel is selectable on the context (upload_eval_keys; the torus exact-transform pair when first chosen:
+    // rotplan::on_demand_copies).  A buffer that is not empty holds a whole copy (build_key_copy).  Replaced with the key set.
+    DevBuf<void> copies[(int)Copy::COUNT];
+    void drop_copies(bool unrolled) {   // the copies of the plain key, or those of the unrolled key
+        for (int k = 0; k < (int)Copy::COUNT; k++)
+            if (rotplan::row((Copy)k).unrolled == unrolled) copies[k].reset();
+    }
     // bootstrap-key unrolling (49-bit field at N = 1024 / 2048, 2^64 torus; bmi_set_bsk_unroll): per pair of LWE coefficients the GGSW encryptions of
     // s s', s (1 - s'), (1 - s) s'; host copy in the standard domain, device copy in the layout of the context's unrolled kernel (upload_bsk3)
     uint32_t unroll = 1;
     std::vector<u64> bsk3_std;
-    struct Bsk3Copies {
-        DevBuf<double> lat49;      // 49-bit N = 1024, paired slot order (bsk_to_lat): blind_rotate_lat2u
-        DevBuf<double> wide49;     // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide_u
-        DevBuf<double> exact_lat;  // torus, exact transform (bsk_to_lat): blind_rotate_lat2u
-        DevBuf<double> fft_lat;    // torus, key at 42 bits: floating-point transform (bsk_to_latf): blind_rotate_lat2u_fft / _tp2u_fft
-        DevBuf<double> wide;       // torus N = 2048, key at 40 bits (bsk_to_wide): blind_rotate_wide_u
-        size_t bytes() const { return lat49.bytes() + wide49.bytes() + exact_lat.bytes() + fft_lat.bytes() + wide.bytes(); }
-    } bsk3;
     bool have_bsk3 = false;
     uint32_t pairs() const { return (P.n + 1) / 2; }
     size_t bsk3_words() const { return (size_t)pairs() * 3 * rows * (P.k + 1) * N; }
@@ -216,9 +177,6 @@ int fail(const bmi_ctx *c, int code, const std::string &msg) {
     return code;
 }
 
-using rotplan::Copy;
-using rotplan::Rot;
-
 // A context as rotation_plan.hpp takes it: its shape, its settings and what it holds.  Which kernel runs, which key copies get
 // built and what the setters accept is decided there, from these three; the entry points below act on the answers.
 rotplan::Shape shape_of(const bmi_params &P) {
@@ -228,18 +186,9 @@ rotplan::Shape shape_of(const bmi_params &P) {
 rotplan::Settings settings_of(const bmi_ctx *c) { return {c->bsk_prec, c->bsk_prec_explicit, c->unroll, c->variant, c->lat_threshold}; }
 // (the one place where a buffer's presence is read as a fact about the context)
 rotplan::Held held_of(const bmi_ctx *c) {
-    const bmi_ctx::BskCopies &K = c->bsk;
-    const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
-    const std::pair<Copy, bool> present[] = {
-        {Copy::ntt_gl, !K.ntt_gl.empty()}, {Copy::ntt49, !K.ntt49.empty()}, {Copy::lat49, !K.lat49.empty()}, {Copy::wide49, !K.wide49.empty()},
-        {Copy::quad49, !K.quad49.empty()}, {Copy::exact, !K.exact.empty()}, {Copy::exact_lat, !K.exact_lat.empty()}, {Copy::fft, !K.fft.empty()},
-        {Copy::fft_lat, !K.fft_lat.empty()}, {Copy::wide, !K.wide.empty()}, {Copy::wide2, !K.wide2.empty()}, {Copy::quad, !K.quad.empty()},
-        {Copy::u_lat49, !K3.lat49.empty()}, {Copy::u_wide49, !K3.wide49.empty()}, {Copy::u_exact_lat, !K3.exact_lat.empty()},
-        {Copy::u_fft_lat, !K3.fft_lat.empty()}, {Copy::u_wide, !K3.wide.empty()}};
-    static_assert(sizeof(present) / sizeof(present[0]) == (size_t)Copy::COUNT, "one entry per key copy");
     rotplan::Held h{0, c->have_keys, c->have_bsk3};
-    for (const auto &p : present)
-        if (p.second) h.copies |= rotplan::bit(p.first);
+    for (int k = 0; k < (int)Copy::COUNT; k++)
+        if (!c->copies[k].empty()) h.copies |= rotplan::bit((Copy)k);
     return h;
 }
 #define HIP_OK(ctx, call)                                                                              \
@@ -438,8 +387,8 @@ void gen_bsk3(bmi_ctx *c, uint64_t seed) {
     c->bsk3_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
 }
 
-// Builds one key copy of `bytes` bytes into a fresh buffer (launch(buffer) converts into it on the context's stream) and moves
-// it into dst only once the launch and the stream synchronisation have succeeded: a field that is not empty holds a whole copy.
+// Builds a device buffer of `bytes` bytes: fresh (launch(buffer) fills it on the context's stream), and moved into dst only once
+// the launch and the stream synchronisation have succeeded, so that a buffer that is not empty is whole.
 template <class T, class Launch>
 int build_copy(bmi_ctx *c, DevBuf<T> &dst, size_t bytes, const char *what, Launch launch) {
     DevBuf<T> fresh;
@@ -450,35 +399,42 @@ int build_copy(bmi_ctx *c, DevBuf<T> &dst, size_t bytes, const char *what, Launc
     return 0;
 }
 
-// How each kind of key copy is built: its field, its conversion launcher and the table that launcher reads.  std_polys = the
-// `polys` standard-domain polynomials of the plain (Copy::ntt_gl .. quad) or the unrolled key (Copy::u_*) on the device.
+// How each kind of key copy is built, in the order of rotplan::Copy: its conversion launcher and what a failure is reported as
+// (the tables the launcher reads are in the copy's row).  paired: the slot order of the 49-bit unrolled kernel.
+struct Converter {
+    int (*launch)(const KeyConv &);
+    const char *what;
+    bool paired;
+};
+const char *const U_LAT = "bsk_to_lat (unrolled key)";
+const Converter CONVERTERS[] = {
+    {bmi::launch_bsk_to_ntt, "bsk_to_ntt", false},              // ntt_gl
+    {bmi49::launch_bsk_to_ntt, "bsk_to_ntt", false},            // ntt49
+    {bmi49::launch_bsk_to_lat, "bsk_to_lat", false},            // lat49
+    {bmi49::launch_bsk_to_wide, "bsk_to_wide", false},          // wide49
+    {bmi49::launch_bsk_to_quad, "bsk_to_quad", false},          // quad49
+    {bmit::launch_bsk_to_limbs, "bsk_to_limbs", false},         // exact
+    {bmit::launch_bsk_to_lat, "bsk_to_lat (torus)", false},     // exact_lat
+    {bmit::launch_bsk_to_fft, "bsk_to_fft (torus)", false},     // fft
+    {bmit::launch_bsk_to_latf, "bsk_to_latf (torus)", false},   // fft_lat
+    {bmit::launch_bsk_to_wide, "bsk_to_wide (torus)", false},   // wide
+    {bmit::launch_bsk_to_wide2, "bsk_to_wide2 (torus)", false}, // wide2
+    {bmit::launch_bsk_to_quad, "bsk_to_quad (torus)", false},   // quad
+    {bmi49::launch_bsk_to_lat, U_LAT, true},                    // u_lat49
+    {bmi49::launch_bsk_to_wide, U_LAT, false},                  // u_wide49
+    {bmit::launch_bsk_to_lat, U_LAT, false},                    // u_exact_lat
+    {bmit::launch_bsk_to_latf, U_LAT, false},                   // u_fft_lat
+    {bmit::launch_bsk_to_wide, "bsk_to_wide (unrolled key)", false},   // u_wide
+};
+static_assert(sizeof(CONVERTERS) / sizeof(CONVERTERS[0]) == (size_t)Copy::COUNT, "one converter per key copy");
+
+// std_polys = the `polys` standard-domain polynomials of the plain (Copy::ntt_gl .. quad) or the unrolled key (Copy::u_*) on the device
 int build_key_copy(bmi_ctx *c, Copy kind, const u64 *std_polys, uint32_t polys, size_t bytes) {
-    const int prec = c->bsk_prec;
-    const hipStream_t st = c->stream;
-    bmi_ctx::BskCopies &K = c->bsk;
-    bmi_ctx::Bsk3Copies &K3 = c->bsk3;
-    const char *u_lat = "bsk_to_lat (unrolled key)";
-    switch (kind) {
-    case Copy::ntt_gl: return build_copy(c, K.ntt_gl, bytes, "bsk_to_ntt", [&](u64 *d) { return bmi::launch_bsk_to_ntt(std_polys, d, c->tw_gl.get(), polys, st); });
-    case Copy::ntt49: return build_copy(c, K.ntt49, bytes, "bsk_to_ntt", [&](double *d) { return bmi49::launch_bsk_to_ntt(std_polys, d, c->tw_wave.get(), polys, st); });
-    case Copy::lat49: return build_copy(c, K.lat49, bytes, "bsk_to_lat", [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, false, st); });
-    case Copy::wide49: return build_copy(c, K.wide49, bytes, "bsk_to_wide", [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
-    case Copy::quad49: return build_copy(c, K.quad49, bytes, "bsk_to_quad", [&](double *d) { return bmi49::launch_bsk_to_quad(std_polys, d, c->tw_wave.get(), c->tw_quad49.get(), polys, st); });
-    case Copy::exact: return build_copy(c, K.exact, bytes, "bsk_to_limbs", [&](double *d) { return bmit::launch_bsk_to_limbs(std_polys, d, c->tw_wave.get(), polys, prec, st); });
-    case Copy::exact_lat: return build_copy(c, K.exact_lat, bytes, "bsk_to_lat (torus)", [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
-    case Copy::fft: return build_copy(c, K.fft, bytes, "bsk_to_fft (torus)", [&](double *d) { return bmit::launch_bsk_to_fft(std_polys, d, c->tw_fft.get(), polys, prec, st); });
-    case Copy::fft_lat: return build_copy(c, K.fft_lat, bytes, "bsk_to_latf (torus)", [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
-    case Copy::wide: return build_copy(c, K.wide, bytes, "bsk_to_wide (torus)", [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
-    case Copy::wide2: return build_copy(c, K.wide2, bytes, "bsk_to_wide2 (torus)", [&](double *d) { return bmit::launch_bsk_to_wide2(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
-    case Copy::quad: return build_copy(c, K.quad, bytes, "bsk_to_quad (torus)", [&](double *d) { return bmit::launch_bsk_to_quad(std_polys, d, c->tw_eighth.get(), polys, prec, st); });
-    case Copy::u_lat49: return build_copy(c, K3.lat49, bytes, u_lat, [&](double *d) { return bmi49::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, true, st); });
-    case Copy::u_wide49: return build_copy(c, K3.wide49, bytes, u_lat, [&](double *d) { return bmi49::launch_bsk_to_wide(std_polys, d, c->tw_wave.get(), c->tw_wide49.get(), polys, st); });
-    case Copy::u_exact_lat: return build_copy(c, K3.exact_lat, bytes, u_lat, [&](double *d) { return bmit::launch_bsk_to_lat(std_polys, d, c->tw_half.get(), polys, prec, st); });
-    case Copy::u_fft_lat: return build_copy(c, K3.fft_lat, bytes, u_lat, [&](double *d) { return bmit::launch_bsk_to_latf(std_polys, d, c->tw_fft_half.get(), polys, prec, st); });
-    case Copy::u_wide: return build_copy(c, K3.wide, bytes, "bsk_to_wide (unrolled key)", [&](double *d) { return bmit::launch_bsk_to_wide(std_polys, d, c->tw_quarter.get(), polys, prec, st); });
-    case Copy::COUNT: break;
-    }
-    return fail(c, -2, "unknown key copy");
+    const Converter &cv = CONVERTERS[(int)kind];
+    const rotplan::CopyRow &row = rotplan::row(kind);
+    return build_copy(c, c->copies[(int)kind], bytes, cv.what, [&](void *d) {
+        return cv.launch(KeyConv{std_polys, d, {c->table(row.tab[0]), c->table(row.tab[1])}, polys, c->bsk_prec, cv.paired, c->stream});
+    });
 }
 
 // Builds those of the copies `kinds` (bits of rotplan::Copy) of the standard-domain key `std_key` (host words) that the context
@@ -508,8 +464,8 @@ int upload_eval_keys(bmi_ctx *c) {
         for (u64 &w : c->bsk_std) w = t64::round_key_word(w, c->bsk_prec);
     }
     c->have_keys = false;
-    c->bsk = {};    // the copies of the previous key set
-    c->bsk3 = {};
+    c->drop_copies(false);   // the copies of the previous key set
+    c->drop_copies(true);
     if (int rc = build_copies(c, rotplan::plain_copies(shape_of(P), c->bsk_prec), c->bsk_std)) return rc;
     const size_t ksk_rows = (size_t)k * N * lk;
     HIP_OK(c, c->ksk_padded.alloc(ksk_rows * c->ks_stride * sizeof(u64)));
@@ -530,7 +486,7 @@ int upload_eval_keys(bmi_ctx *c) {
         const uint32_t cbs = (n + 1 + 31) / 32;
         const size_t bytes = (size_t)cbs * (ksk_rows / 32) * c->ops->ks_limbs * 1024;
         if (int rc = build_copy(c, c->ks_limbs, bytes, "ksk_to_limbs", [&](signed char *d) {
-                return c->ops->ksk_to_limbs(c->ksk_padded.get(), d, (uint32_t)ksk_rows, n, c->ks_stride, c->stream);
+                return c->ops->ksk_to_limbs(c->ksk_padded.get(), d, (uint32_t)ksk_rows, n, c->ks_stride, c->ops->ks_limbs, c->stream);
             }))
             return rc;
     }
@@ -538,7 +494,7 @@ int upload_eval_keys(bmi_ctx *c) {
     return 0;
 }
 
-// unrolled bootstrap key (host copy in c->bsk3_std) -> device, in the layout of the context's unrolled kernel (bmi_ctx::Bsk3Copies)
+// unrolled bootstrap key (host copy in c->bsk3_std) -> device, in the layout of the context's unrolled kernel (rotplan::unrolled_copies)
 int upload_bsk3(bmi_ctx *c) {
     HIP_OK(c, hipSetDevice(c->device));
     const size_t words = c->bsk3_words();
@@ -547,20 +503,11 @@ int upload_bsk3(bmi_ctx *c) {
     if (c->t64() && c->bsk_prec != 64)
         for (u64 &w : c->bsk3_std) w = t64::round_key_word(w, c->bsk_prec);
     c->have_bsk3 = false;
-    c->bsk3 = {};
+    c->drop_copies(true);
     if (int rc = build_copies(c, rotplan::unrolled_copies(shape_of(c->P), c->bsk_prec), c->bsk3_std)) return rc;
     c->have_bsk3 = true;
     return 0;
 }
-
-const FieldOps GOLDILOCKS_OPS = {bmi::launch_keyswitch, bmi::launch_keyswitch_mfma, bmi::launch_ksk_to_limbs, bmi::launch_lincomb, bmi::launch_lwe_phase,
-    [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi::launch_negacyclic_mul(a, b, o, c->tw_gl.get(), m, c->stream); },
-    bmi::KS_LIMBS};
-const FieldOps FIELD49_OPS = {bmi49::launch_keyswitch, bmi49::launch_keyswitch_mfma, bmi49::launch_ksk_to_limbs, bmi49::launch_lincomb, bmi49::launch_lwe_phase,
-    [](const bmi_ctx *c, const u64 *a, const u64 *b, u64 *o, uint32_t m) { return bmi49::launch_negacyclic_mul(a, b, o, c->tw_wave.get(), m, c->stream); },
-    bmi49::KS_LIMBS};
-const FieldOps TORUS64_OPS = {bmit::launch_keyswitch, bmit::launch_keyswitch_mfma, bmit::launch_ksk_to_limbs, bmit::launch_lincomb, bmit::launch_lwe_phase,
-                              nullptr, bmit::KS_LIMBS};
 
 // evaluation keys for the secret keys held in c->sk_small / c->sk_big, deterministic in `seed`
 int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
@@ -613,46 +560,32 @@ int choose_rotation(const bmi_ctx *c, uint32_t count, Rot *rot) {
     return 0;
 }
 
-// Launches `rot` on the context's key copies and tables.  stat: as in bmit::launch_blind_rotate_fft, for the kernels that take it.
+// The launcher of each kernel, in the order of rotplan::Rot
+int (*const LAUNCHERS[])(const RotBatch &) = {
+    bmit::launch_blind_rotate_wide_u, bmit::launch_blind_rotate_wide_u2, bmit::launch_blind_rotate_wide2, bmit::launch_blind_rotate_wide,
+    bmit::launch_blind_rotate_quad, bmit::launch_blind_rotate_tp2u_fft, bmit::launch_blind_rotate_lat2u_fft, bmit::launch_blind_rotate_lat2u,
+    bmit::launch_blind_rotate_lat_fft, bmit::launch_blind_rotate_lat, bmit::launch_blind_rotate_fft, bmit::launch_blind_rotate,
+    bmi49::launch_blind_rotate_wide_u, bmi49::launch_blind_rotate_wide, bmi49::launch_blind_rotate_quad, bmi49::launch_blind_rotate_lat2u,
+    bmi49::launch_blind_rotate_lat2, bmi49::launch_blind_rotate_tpx,
+    bmi::launch_blind_rotate_lat, bmi::launch_blind_rotate_tp,
+};
+static_assert(sizeof(LAUNCHERS) / sizeof(LAUNCHERS[0]) == (size_t)Rot::COUNT, "one launcher per kernel");
+
+// Launches `rot` on the key copy and the tables its row names; hipErrorInvalidValue where the context does not hold one of them (the
+// plan never answers with such a kernel: tests/c_abi/rotation_plan_table.cpp).  stat: as RotBatch::stat, for the kernels that take it.
 // glwe (has_accumulator_form(rot) only): out receives the accumulators [count][2N] instead of the extracted samples [count][N + 1].
 int launch_rotation(const bmi_ctx *c, Rot rot, const u64 *cts, const uint32_t *ids, uint32_t count, u64 *out, unsigned long long *stat,
                     bool glwe, hipStream_t st) {
-    if (glwe && !rotplan::has_accumulator_form(rot)) return (int)hipErrorInvalidValue;
-    const uint32_t n = c->P.n, lv = c->P.bs_levels, bl = c->P.bs_base_log;
-    const int p = c->bsk_prec;
-    const u64 *luts = c->luts.get();
-    const double *luts49 = reinterpret_cast<const double *>(luts);   // the 49-bit field's test polynomials are centred doubles
-    const bmi_ctx::BskCopies &K = c->bsk;
-    const bmi_ctx::Bsk3Copies &K3 = c->bsk3;
-    switch (rot) {
-    case Rot::t64_wide_u: return bmit::launch_blind_rotate_wide_u(cts, ids, luts, K3.wide.get(), c->tw_quarter.get(), c->zeta_oct.get(), out, count, n,
-                                                                   p, lv, bl, stat, glwe, st);
-    case Rot::t64_wide_u2: return bmit::launch_blind_rotate_wide_u2(cts, ids, luts, K3.wide.get(), c->tw_quarter.get(), c->zeta_oct.get(), out, count, n,
-                                                                     p, lv, bl, stat, glwe, st);
-    case Rot::t64_wide2: return bmit::launch_blind_rotate_wide2(cts, ids, luts, K.wide2.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, glwe, st);
-    case Rot::t64_wide: return bmit::launch_blind_rotate_wide(cts, ids, luts, K.wide.get(), c->tw_quarter.get(), out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_quad: return bmit::launch_blind_rotate_quad(cts, ids, luts, K.quad.get(), c->tw_eighth.get(), out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_tp2u_fft: return bmit::launch_blind_rotate_tp2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(), out,
-                                                                      count, n, p, lv, bl, glwe, st);
-    case Rot::t64_lat2u_fft: return bmit::launch_blind_rotate_lat2u_fft(cts, ids, luts, K3.fft_lat.get(), c->tw_fft_half.get(), c->zeta_pow.get(),
-                                                                        out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_lat2u: return bmit::launch_blind_rotate_lat2u(cts, ids, luts, K3.exact_lat.get(), c->tw_half.get(), c->root_pow.get(), out, count,
-                                                                n, p, lv, bl, st);
-    case Rot::t64_lat_fft: return bmit::launch_blind_rotate_lat_fft(cts, ids, luts, K.fft_lat.get(), c->tw_fft_half.get(), out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_lat: return bmit::launch_blind_rotate_lat(cts, ids, luts, K.exact_lat.get(), c->tw_half.get(), out, count, n, p, lv, bl, st);
-    case Rot::t64_fft: return bmit::launch_blind_rotate_fft(cts, ids, luts, K.fft.get(), c->tw_fft.get(), out, count, n, p, lv, bl, stat, glwe, st);
-    case Rot::t64_exact: return bmit::launch_blind_rotate(cts, ids, luts, K.exact.get(), c->tw_wave.get(), out, count, n, p, lv, bl, st);
-    case Rot::f49_wide_u: return bmi49::launch_blind_rotate_wide_u(cts, ids, luts49, K3.wide49.get(), c->tw_wave.get(), c->tw_wide49.get(),
-                                                                   c->root_pow.get(), out, count, n, lv, bl, st);
-    case Rot::f49_wide: return bmi49::launch_blind_rotate_wide(cts, ids, luts49, K.wide49.get(), c->tw_wave.get(), c->tw_wide49.get(), out, count, n, lv, bl, st);
-    case Rot::f49_quad: return bmi49::launch_blind_rotate_quad(cts, ids, luts49, K.quad49.get(), c->tw_wave.get(), c->tw_quad49.get(), out, count, n, st);
-    case Rot::f49_lat2u: return bmi49::launch_blind_rotate_lat2u(cts, ids, luts49, K3.lat49.get(), c->tw_half.get(), c->root_pow.get(), out, count, n, lv, bl, st);
-    case Rot::f49_lat2: return bmi49::launch_blind_rotate_lat2(cts, ids, luts49, K.lat49.get(), c->tw_half.get(), out, count, n, lv, bl, st);
-    case Rot::f49_tpx: return bmi49::launch_blind_rotate_tpx(cts, ids, luts49, K.ntt49.get(), c->tw_wave.get(), out, count, n, lv, bl, st);
-    case Rot::gl_lat: return bmi::launch_blind_rotate_lat(cts, ids, luts, K.ntt_gl.get(), c->tw_gl.get(), out, count, n, st);
-    case Rot::gl_tp: return bmi::launch_blind_rotate_tp(cts, ids, luts, K.ntt_gl.get(), c->tw_gl.get(), out, count, n, st);
+    const rotplan::RotRow &row = rotplan::row(rot);
+    if (glwe && !row.accumulator) return (int)hipErrorInvalidValue;
+    RotBatch b{cts, ids, {c->luts.get()}, {c->copies[(int)row.key].get()}, {}, out, count, c->P.n, c->bsk_prec, c->P.bs_levels, c->P.bs_base_log,
+               row.stat ? stat : nullptr, glwe, st};
+    if (!b.key.p) return (int)hipErrorInvalidValue;
+    for (int t = 0; t < 3; t++) {
+        b.tab[t] = c->table(row.tab[t]);
+        if (row.tab[t] != Table::none && !b.tab[t].p) return (int)hipErrorInvalidValue;
     }
-    return (int)hipErrorInvalidValue;
+    return LAUNCHERS[(int)rot](b);
 }
 
 // accumulators of a batch (room for 256 at least)
@@ -769,7 +702,7 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
     const rotplan::Settings initial = rotplan::initial_settings(shape_of(c->P));
     c->bsk_prec = initial.bsk_prec;
     c->lat_threshold = initial.lat_threshold;
-    c->ops = c->f64() ? &FIELD49_OPS : c->t64() ? &TORUS64_OPS : &GOLDILOCKS_OPS;
+    c->ops = c->f64() ? &bmi49::OPS : c->t64() ? &bmit::OPS : &bmi::OPS;
     c->device = device;
     c->N = 1u << params->log_N;
     c->big_n = params->k * c->N;
@@ -782,61 +715,70 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
     if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
     hipError_t up = hipSuccess;   // the first failure of the table uploads below
-    auto put = [&](auto &dst, const auto &host) {
-        if (up == hipSuccess) up = upload(dst, host.data(), host.size());
+    const uint32_t tabs = rotplan::context_tables(shape_of(c->P));   // the tables this modulus and N have kernels for
+    auto want = [&](Table t) { return (tabs & rotplan::bit(t)) != 0; };
+    auto put = [&](Table t, const auto &host) {
+        const size_t bytes = host.size() * sizeof(host[0]);
+        if (up == hipSuccess) up = c->tables[(int)t].alloc(bytes);
+        if (up == hipSuccess) up = hipMemcpy(c->tables[(int)t].get(), host.data(), bytes, hipMemcpyHostToDevice);
     };
     const Fq f49q{f49::Q, 49};   // the torus kernels transform mod the 49-bit prime as well
-    if (c->f64() || c->t64()) {
-        put(c->tw_wave, to_centred_doubles(build_twiddles(f49q, nttf::PSI_U, nttf::PSI_INV_U, nttf::N_INV_U)));
-        put(c->tw_half, to_centred_doubles(build_twiddles_half(f49q, nttf::PSI_U, nttf::PSI_INV_U)));
-    } else {
-        put(c->tw_gl, build_twiddles(c->f, nttw::PSI, nttw::PSI_INV, nttw::N_INV));
-    }
-    if (c->t64() && c->N == 1024) {   // tables of the folded 512-point complex transform (fft_wave_f64.hpp): powers of zeta = exp(i pi / 1024)
+    if (want(Table::tw_wave)) put(Table::tw_wave, to_centred_doubles(build_twiddles(f49q, nttf::PSI_U, nttf::PSI_INV_U, nttf::N_INV_U)));
+    if (want(Table::tw_half)) put(Table::tw_half, to_centred_doubles(build_twiddles_half(f49q, nttf::PSI_U, nttf::PSI_INV_U)));
+    if (want(Table::tw_gl)) put(Table::tw_gl, build_twiddles(c->f, nttw::PSI, nttw::PSI_INV, nttw::N_INV));
+    auto zeta_pow = [](uint32_t e, double *dst) {   // zeta = exp(i pi / 1024)
+        const long double ang = 3.14159265358979323846264338327950288L * (long double)(e % 2048) / 1024.0L;
+        dst[0] = (double)cosl(ang);
+        dst[1] = (double)sinl(ang);
+    };
+    if (want(Table::tw_fft)) {   // tables of the folded 512-point complex transform (fft_wave_f64.hpp): powers of zeta
         std::vector<double> tf(fftw::TW_WORDS);
-        auto zeta_pow = [](uint32_t e, double *dst) {
-            const long double ang = 3.14159265358979323846264338327950288L * (long double)(e % 2048) / 1024.0L;
-            dst[0] = (double)cosl(ang);
-            dst[1] = (double)sinl(ang);
-        };
         for (uint32_t k2 = 0; k2 < 8; k2++)
             for (uint32_t lane = 0; lane < 64; lane++) zeta_pow(lane * (4 * k2 + 1), &tf[fftw::TW_T1 + (k2 * 64 + lane) * 2]);
         for (uint32_t d = 0; d < 8; d++)
             for (uint32_t a = 0; a < 8; a++) zeta_pow(32 * a * d, &tf[fftw::TW_T2 + (d * 8 + a) * 2]);
-        put(c->tw_fft, tf);
+        put(Table::tw_fft, tf);
+    }
+    if (want(Table::tw_fft_half)) {
         std::vector<double> th(ffth::HT_WORDS);
         ffth::build_tables(th.data());
-        put(c->tw_fft_half, th);
+        put(Table::tw_fft_half, th);
+    }
+    if (want(Table::zeta_pow)) {
         std::vector<double> zp(2048);
         for (uint32_t x = 0; x < 1024; x++) zeta_pow(x, &zp[2 * x]);
-        put(c->zeta_pow, zp);
+        put(Table::zeta_pow, zp);
     }
-    if ((c->f64() && !c->quad()) || c->t64()) {   // psi^x for the unrolled blind rotation (X^c at the root psi^e is psi^(e c))
+    if (want(Table::root_pow)) {   // psi^x for the unrolled blind rotation (X^c at the root psi^e is psi^(e c))
         // N = 1024: psi = psi_2048, x in [0, 2048).  N = 2048: psi = psi_4096, x in [0, 2048) (the upper half is the negative)
         std::vector<u64> rp(2048);
         const u64 psi = c->wide() ? f49q.pow(f49::GEN, (f49q.q - 1) / 4096) : (u64)nttf::PSI_U;
         rp[0] = 1;
         for (uint32_t x = 1; x < 2048; x++) rp[x] = f49q.mul(rp[x - 1], psi);
-        put(c->root_pow, to_centred_doubles(rp));
+        put(Table::root_pow, to_centred_doubles(rp));
     }
-    if (c->t64() && (c->wide() || c->quad())) {   // tables of the quarter / eighth transforms: powers of zeta = exp(i pi / N)
-        static_assert(ffte::ET_WORDS == fftq::QT_WORDS, "the two table sets share a size");
-        std::vector<double> tq(fftq::QT_WORDS);
-        if (c->quad()) ffte::build_tables(tq.data());
-        else fftq::build_tables(tq.data());
-        put(c->quad() ? c->tw_eighth : c->tw_quarter, tq);
+    // tables of the quarter / eighth transforms: powers of zeta = exp(i pi / N)
+    static_assert(ffte::ET_WORDS == fftq::QT_WORDS, "the two table sets share a size");
+    std::vector<double> tq(fftq::QT_WORDS);
+    if (want(Table::tw_quarter)) {
+        fftq::build_tables(tq.data());
+        put(Table::tw_quarter, tq);
     }
-    if (c->t64() && c->wide()) {   // one octant of the powers of zeta = exp(i pi / 2048): the unrolled kernel folds the rest onto it
+    if (want(Table::tw_eighth)) {
+        ffte::build_tables(tq.data());
+        put(Table::tw_eighth, tq);
+    }
+    if (want(Table::zeta_oct)) {   // one octant of the powers of zeta = exp(i pi / 2048): the unrolled kernel folds the rest onto it
         std::vector<double> zo(2 * 513);
         for (uint32_t x = 0; x <= 512; x++) {
             const long double ang = 3.14159265358979323846264338327950288L * (long double)x / 2048.0L;
             zo[2 * x] = (double)cosl(ang);
             zo[2 * x + 1] = (double)sinl(ang);
         }
-        put(c->zeta_oct, zo);
+        put(Table::zeta_oct, zo);
     }
-    if (c->wide() && !c->t64()) put(c->tw_wide49, to_centred_doubles(build_twiddles_wide(c->f)));
-    if (c->quad() && !c->t64()) put(c->tw_quad49, to_centred_doubles(build_twiddles_quad(c->f)));
+    if (want(Table::tw_wide49)) put(Table::tw_wide49, to_centred_doubles(build_twiddles_wide(c->f)));
+    if (want(Table::tw_quad49)) put(Table::tw_quad49, to_centred_doubles(build_twiddles_quad(c->f)));
     c->lut_cap = BMI_LUT_CAP;
     if (up == hipSuccess) up = c->luts.alloc((size_t)c->lut_cap * c->N * 8);
     if (c->t64()) {   // the tables' sparse factors (shared rotations): no entries until a table is registered
@@ -948,7 +890,11 @@ int bmi_export_keys(const bmi_ctx *c, uint64_t *sk_small, uint64_t *sk_big, uint
 int bmi_key_bytes(const bmi_ctx *c, uint64_t *bsk_bytes, uint64_t *ksk_bytes) {
     if (!c) return -1;
     // every resident device copy (one per kernel family that is selectable on this context), plus the unrolled key
-    if (bsk_bytes) *bsk_bytes = c->bsk.bytes() + (c->have_bsk3 ? c->bsk3.bytes() : 0);
+    if (bsk_bytes) {
+        *bsk_bytes = 0;
+        for (int k = 0; k < (int)Copy::COUNT; k++)
+            if (!rotplan::row((Copy)k).unrolled || c->have_bsk3) *bsk_bytes += c->copies[k].bytes();
+    }
     if (ksk_bytes) *ksk_bytes = (u64)c->big_n * c->P.ks_levels * (c->P.n + 1) * 8;
     return 0;
 }
@@ -1512,7 +1458,8 @@ int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, ui
     HIP_OK(c, upload(da, a, words));
     HIP_OK(c, upload(db, b, words));
     HIP_OK(c, dc.alloc(words * 8));
-    if (c->ops->negacyclic_mul(c, da.get(), db.get(), dc.get(), count)) return fail(c, -2, "negacyclic_mul launch failed");
+    const DevWords g_tw = c->table(c->f64() ? Table::tw_wave : Table::tw_gl);   // each field has its own twiddle table
+    if (c->ops->negacyclic_mul(da.get(), db.get(), dc.get(), g_tw, count, c->stream)) return fail(c, -2, "negacyclic_mul launch failed");
     HIP_OK(c, hipStreamSynchronize(c->stream));
     HIP_OK(c, hipMemcpy(out, dc.get(), words * 8, hipMemcpyDeviceToHost));
     return 0;

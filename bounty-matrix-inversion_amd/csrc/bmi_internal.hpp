@@ -125,36 +125,82 @@ inline int with_levels_stats_glwe(uint32_t levels, bool stats, bool glwe, F f) {
     return with_levels(levels, [&](auto L) { return f(L, std::false_type{}, std::true_type{}); });
 }
 
+// ------------------------------------------------------------------------------------------ what the host hands the launchers
+// Device words are u64 on Goldilocks (and the test polynomials of the torus) and doubles elsewhere, 8 bytes either way.  The host
+// carries test polynomials, key copies and tables untyped, as DevWords; a launcher names the type its kernel declares, .u() or
+// .d().  This is the one place where the two element types meet.
+struct DevWords {
+    const void *p = nullptr;
+    const gl::u64 *u() const { return static_cast<const gl::u64 *>(p); }
+    const double *d() const { return static_cast<const double *>(p); }
+};
+
+// A batch to rotate: the one argument of every launch_blind_rotate_*.  launch_rotation (bmi_host.cpp) fills key and tab from the
+// kernel's row (rotplan::row(rot): its key copy, its tables in the order the kernel takes them).
+struct RotBatch {
+    const gl::u64 *cts;         // [count][n + 1] small ciphertexts
+    const uint32_t *ids;        // [count] ids of the test polynomials
+    DevWords luts;              // BMI_LUT_CAP test polynomials of N words (49-bit field: centred doubles)
+    DevWords key, tab[3];
+    gl::u64 *out;               // [count][N + 1] extracted samples
+    uint32_t count, n;
+    int prec;                   // torus: the precision the key is stored at
+    uint32_t levels, base_log;  // of the bootstrap decomposition
+    // stat (may be null; the kernels of a row with the stat flag): receives, as the bit pattern of a double, the largest distance of
+    // a limb sum from the integer it was rounded to
+    unsigned long long *stat;
+    // glwe (the kernels of a row with the accumulator flag): out receives the ACCUMULATOR, [count][mask N][body N] words in natural
+    // order, instead of the extracted samples [count][N + 1]; stat must be null
+    bool glwe;
+    hipStream_t s;
+};
+
+// A key to convert: the one argument of every launch_bsk_to_*.  dst = one key copy (rotplan::Copy) of the n_polys standard-domain
+// polynomials std_polys; tab = the tables of the copy's row; prec: the torus; paired: the 49-bit launch_bsk_to_lat.
+struct KeyConv {
+    const gl::u64 *std_polys;
+    void *dst;
+    DevWords tab[2];
+    uint32_t n_polys;
+    int prec;
+    bool paired;
+    hipStream_t s;
+};
+
+// The launchers that differ by modulus only, instantiated once per field policy (field_ops.hpp): each of bmi_kernels.hip,
+// bmi_kernels_f64.hip and bmi_kernels_t64.hip exports one table, bmi_ctx_create picks one per context.
+struct FieldOps {
+    // slices > 1 (with a partial buffer of slices * count * ks_stride 16-byte words): latency form for small batches
+    // ks_bias[col] = (B/2) * sum over all rows of ksk[row][col] mod q (the digits are staged unsigned, d + B/2)
+    int (*keyswitch)(const gl::u64 *in, const gl::u64 *ksk, const gl::u64 *ks_bias, gl::u64 *out, void *partial, uint32_t slices,
+                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride, hipStream_t s);
+    // Keyswitch on the matrix cores (ks_mfma.hpp): the key as ks_limbs balanced base-256 limbs in MFMA operand order,
+    // digits = count * big_n * levels bytes, sums = slices * count * ks_limbs * ceil((n+1)/32)*32 int32 words.
+    int (*ksk_to_limbs)(const gl::u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, uint32_t ks_limbs, hipStream_t s);
+    int (*keyswitch_mfma)(const gl::u64 *in, const signed char *limbs, signed char *digits, int *sums, gl::u64 *out, uint32_t slices,
+                          uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, hipStream_t s);
+    int (*lincomb)(const gl::u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const gl::i64 *coef, const gl::u64 *const_body,
+                   gl::u64 *out, uint32_t count, uint32_t width, hipStream_t s);
+    // lwe_phase.hpp: phase (and, with msgs, the decoded message and the signed error) of big-key ciphertexts; key_mask = the big
+    // secret key as big_n / 64 words of bits
+    int (*lwe_phase)(const gl::u64 *ct, const gl::u64 *key_mask, gl::u64 *phase, const gl::i64 *expected, gl::i64 *msgs, gl::i64 *err,
+                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
+    // the NTT test hook: on the prime fields only (null on the torus); g_tw = the field's own twiddle table (tw_gl / tw_wave)
+    int (*negacyclic_mul)(const gl::u64 *a, const gl::u64 *b, gl::u64 *c, DevWords g_tw, uint32_t count, hipStream_t s);
+    uint32_t ks_limbs;   // limbs per keyswitch-key word of the matrix-core keyswitch (9; the 49-bit field: 7)
+};
+
+// Goldilocks (bmi_kernels.hip): key copy, twiddles and test polynomials are u64
 namespace bmi {
 using gl::i64;
 using gl::u64;
 
-int launch_bsk_to_ntt(const u64 *std_polys, u64 *ntt_polys, const u64 *g_tw, uint32_t n_polys, hipStream_t s);
-int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const u64 *g_tw, uint32_t count, hipStream_t s);
-int launch_blind_rotate_tp(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const u64 *bsk,
-                           const u64 *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s);
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const u64 *bsk,
-                            const u64 *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s);
-// slices > 1 (with a partial buffer of slices * count * ks_stride 16-byte words): latency form for small batches
-// ks_bias[col] = (B/2) * sum over all rows of ksk[row][col] mod q (the digits are staged unsigned, d + B/2)
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s);
-// Keyswitch on the matrix cores (ks_mfma.hpp): the key as KS_LIMBS balanced base-256 limbs in MFMA operand order,
-// digits = count * big_n * levels bytes, sums = slices * count * KS_LIMBS * ceil((n+1)/32)*32 int32 words.
-constexpr uint32_t KS_LIMBS = 9;
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s);
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s);
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
+extern const FieldOps OPS;
+int launch_bsk_to_ntt(const KeyConv &k);
+int launch_blind_rotate_tp(const RotBatch &b);
+int launch_blind_rotate_lat(const RotBatch &b);
 // store[rows[i]] = src[i] (rows of `width` words); field independent
 int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32_t count, uint32_t width, hipStream_t s);
-// lwe_phase.hpp: phase (and, with msgs, the decoded message and the signed error) of big-key ciphertexts; key_mask = the big
-// secret key as big_n / 64 words of bits
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
 // modswitch_centre.hip: out = the `count` small ciphertexts in ([count][n + 1], may be the same buffer) with the body minus half the
 // sum of the mask words' rounding errors to the 2N positions; torus: q = 2^64, else the 49-bit field (Goldilocks has no such kernel)
 int launch_modswitch_centre(const u64 *in, u64 *out, uint32_t count, uint32_t n, uint32_t log_N, bool torus, hipStream_t s);
@@ -171,53 +217,26 @@ int launch_place_bodies(const u64 *bodies, u64 *base, u64 pitch, uint32_t w, u64
 namespace bmi49 {
 using gl::i64;
 using gl::u64;
-int launch_bsk_to_ntt(const u64 *std_polys, double *ntt_polys, const double *g_tw, uint32_t n_polys, hipStream_t s);
-int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw, uint32_t count, hipStream_t s);
-// third parameter set N = 4096: key copy in slot order (scaled by 1/4); g_t = T_1, T_2, T_3, then their inverses ([6][1024])
-int launch_bsk_to_quad(const u64 *std_polys, double *quad_polys, const double *g_tw, const double *g_t, uint32_t n_polys,
-                       hipStream_t s);
-int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_quad,
-                             const double *g_tw, const double *g_t, u64 *out, uint32_t count, uint32_t n, hipStream_t s);
-// second parameter set N = 2048: key copy in slot order (scaled by 1/2), table T / T^-1 of the even/odd combination
-int launch_bsk_to_wide(const u64 *std_polys, double *wide_polys, const double *g_tw, const double *g_tw_wide,
-                       uint32_t n_polys, hipStream_t s);
-int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_wide,
-                             const double *g_tw, const double *g_tw_wide, u64 *out, uint32_t count, uint32_t n,
-                             uint32_t levels, uint32_t base_log, hipStream_t s);
-// N = 2048 with the unrolled key: bsk3_wide = launch_bsk_to_wide of the unrolled key, g_root_pow = psi_4096^x for x in [0, 2048)
-int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_wide,
-                               const double *g_tw, const double *g_tw_wide, const double *g_root_pow, u64 *out, uint32_t count,
-                               uint32_t n, uint32_t levels, uint32_t base_log, hipStream_t s);
-// latency kernel, two wavefronts per transform (ntt_half_f64.hpp): own key copy in slot order, own twiddle tables
+extern const FieldOps OPS;
+// (levels, base log) of the bootstrap decomposition: (3, 15), (2, 15) and (1, 23) are instantiated in the kernels of N <= 2048;
+// the 49-bit N = 4096 kernel and the Goldilocks ones take (3, 15) only
+int launch_bsk_to_ntt(const KeyConv &k);          // tab = tw_wave
+int launch_blind_rotate_tpx(const RotBatch &b);   // key ntt49; tab = tw_wave
+// third parameter set N = 4096: key copy in slot order (scaled by 1/4); tab = tw_wave, then T_1, T_2, T_3 and their inverses ([6][1024])
+int launch_bsk_to_quad(const KeyConv &k);
+int launch_blind_rotate_quad(const RotBatch &b);
+// second parameter set N = 2048: key copy in slot order (scaled by 1/2); tab = tw_wave, then T / T^-1 of the even/odd combination
+int launch_bsk_to_wide(const KeyConv &k);
+int launch_blind_rotate_wide(const RotBatch &b);
+// N = 2048 with the unrolled key: key = launch_bsk_to_wide of the unrolled key, tab[2] = psi_4096^x for x in [0, 2048)
+int launch_blind_rotate_wide_u(const RotBatch &b);
+// latency kernel, two wavefronts per transform (ntt_half_f64.hpp): own key copy in slot order, own twiddle tables (tab = tw_half)
 // paired: A_lo[p], A_hi[p] side by side (one 16-byte request per slot; the unrolled kernel's layout), else [A_lo 512][A_hi 512]
-int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, bool paired, hipStream_t s);
-// (levels, base log) of the bootstrap decomposition: (3, 15), (2, 15) and (1, 23) are instantiated in the three kernels
-// below; the 49-bit N = 4096 kernel and the Goldilocks ones take (3, 15) only
-int launch_blind_rotate_lat2(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat,
-                             const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
-                             hipStream_t s);
-// the same with the unrolled key (two LWE coefficients per step): bsk3_lat = [ceil(n/2)][3 keys] GGSW copies in the PAIRED slot
-// order of launch_bsk_to_lat, g_root_pow = psi^x for x in [0, 2N) as centred doubles
-int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat,
-                              const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n,
-                              uint32_t levels, uint32_t base_log, hipStream_t s);
-int launch_blind_rotate_tpx(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                            const double *g_tw, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
-                            hipStream_t s);
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s);
-// Keyswitch on the matrix cores (ks_mfma.hpp): the key as KS_LIMBS balanced base-256 limbs in MFMA operand order,
-// digits = count * big_n * levels bytes, sums = slices * count * KS_LIMBS * ceil((n+1)/32)*32 int32 words.
-constexpr uint32_t KS_LIMBS = 7;
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s);
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s);
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
+int launch_bsk_to_lat(const KeyConv &k);
+int launch_blind_rotate_lat2(const RotBatch &b);
+// the same with the unrolled key (two LWE coefficients per step): key = [ceil(n/2)][3 keys] GGSW copies in the PAIRED slot
+// order of launch_bsk_to_lat, tab[1] = psi^x for x in [0, 2N) as centred doubles
+int launch_blind_rotate_lat2u(const RotBatch &b);
 }  // namespace bmi49
 
 // The 2^64 torus (bmi_kernels_t64*.hip): ciphertexts, test polynomials and keyswitch key are plain u64
@@ -226,80 +245,54 @@ int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *
 namespace bmit {
 using gl::i64;
 using gl::u64;
-constexpr uint32_t KS_LIMBS = 9;    // balanced base-256 limbs of a keyswitch-key word
+extern const FieldOps OPS;
 // (the (precision, levels, base log) combinations with instantiated kernels: bmit::shape_supported*, rotation_plan.hpp)
-int launch_bsk_to_limbs(const u64 *std_polys, double *limb_polys, const double *g_tw, uint32_t n_polys, int prec,
-                        hipStream_t s);
-int launch_blind_rotate(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_limbs,
-                        const double *g_tw, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                        uint32_t base_log, hipStream_t s);
+// exact transform mod 2^49 - 720895, wave pairs (bmi_kernels_t64.hip): tab = tw_wave
+int launch_bsk_to_limbs(const KeyConv &k);
+int launch_blind_rotate(const RotBatch &b);
 // latency form (one workgroup of 16 wavefronts per ciphertext): own key copy, per limb in the slot order of the two-wave
 // half transform ([poly][limb][512 slots][A_lo, A_hi]); tables of ntt_half_f64.hpp
-int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, int prec, hipStream_t s);
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_lat,
-                            const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, hipStream_t s);
-// the same with the unrolled key (two LWE coefficients per step; bmi_kernels_t64u.hip): bsk3_lat = launch_bsk_to_lat of the
-// unrolled key [ceil(n/2)][3 keys] GGSW copies, g_root_pow = psi^x (mod 2^49 - 720895) for x in [0, 2N) as centred doubles
-int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_lat,
-                              const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                              uint32_t levels, uint32_t base_log, hipStream_t s);
+int launch_bsk_to_lat(const KeyConv &k);
+int launch_blind_rotate_lat(const RotBatch &b);
+// the same with the unrolled key (two LWE coefficients per step; bmi_kernels_t64u.hip): key = launch_bsk_to_lat of the
+// unrolled key [ceil(n/2)][3 keys] GGSW copies, tab[1] = psi^x (mod 2^49 - 720895) for x in [0, 2N) as centred doubles
+int launch_blind_rotate_lat2u(const RotBatch &b);
 // wave pairs with the exact limb products carried by the folded complex FFT (bmi_kernels_t64f.hip, fft_wave_f64.hpp): key copy
 // [poly][limb][8 registers][64 lanes] complex words; tables fftw::TW_WORDS doubles; same results as launch_blind_rotate
-int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s);
-// stat (may be null): receives, as the bit pattern of a double, the largest distance of a limb sum from the integer it was rounded to
-// glwe (every launcher below that takes it): out receives the
-// ACCUMULATOR, [count][mask N][body N] words in natural order, instead of the extracted samples [count][N + 1]; stat must be null
-int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                            const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
+int launch_bsk_to_fft(const KeyConv &k);
+int launch_blind_rotate_fft(const RotBatch &b);
 // latency form (one workgroup of 16 wavefronts per ciphertext, half transforms: fft_half_f64.hpp): own key copy, per (polynomial,
 // limb) 256 slots of [F_k, F_{k+256}]; tables ffth::HT_WORDS doubles
-int launch_bsk_to_latf(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, int prec, hipStream_t s);
-int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                                const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
+int launch_bsk_to_latf(const KeyConv &k);
+int launch_blind_rotate_lat_fft(const RotBatch &b);
 // the unrolled step (two LWE coefficients) through the floating-point transform (bmi_kernels_t64fu.hip): key at 42 bits of precision
-// (two 21-bit limbs: the six-times larger limb sums stay inside the transform's certified range); bsk3_latf = launch_bsk_to_latf of
-// the unrolled key, g_zeta_pow = exp(i pi x / 1024) for x in [0, 1024) as (re, im); stat as in launch_blind_rotate_fft
-int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
-                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s);
+// (two 21-bit limbs: the six-times larger limb sums stay inside the transform's certified range); key = launch_bsk_to_latf of
+// the unrolled key, tab[1] = exp(i pi x / 1024) for x in [0, 1024) as (re, im)
+int launch_blind_rotate_lat2u_fft(const RotBatch &b);
 // ... and its throughput form: two ciphertexts per workgroup, every key word a thread loads multiplied with both (same words)
-int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
-                                 const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                 uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s);
+int launch_blind_rotate_tp2u_fft(const RotBatch &b);
 // N = 4096 (bmi_kernels_t64q.hip, fft_eighth_f64.hpp): key at 44 bits of precision (two 22-bit limbs), one workgroup per ciphertext,
 // one decomposition level of tiles in LDS at a time; key copy per (polynomial, limb) [t 8][256 slots] complex words A_k / 4; tables
 // ffte::ET_WORDS doubles
-int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw_e, uint32_t n_polys, int prec, hipStream_t s);
-int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e,
-                             u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             bool glwe, hipStream_t s);
+int launch_bsk_to_quad(const KeyConv &k);
+int launch_blind_rotate_quad(const RotBatch &b);
 // N = 2048, throughput form (bmi_kernels_t64w2.hip): two ciphertexts per workgroup, every key word multiplied with both; its own key copy,
 // per (polynomial, limb) [t 4][256 slots] complex words A_k / 2; tables and results as launch_blind_rotate_wide
-int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);
-int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
-                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s);
+int launch_bsk_to_wide2(const KeyConv &k);
+int launch_blind_rotate_wide2(const RotBatch &b);
 // N = 2048 (bmi_kernels_t64w.hip, fft_quarter_f64.hpp): key at 46 bits of precision (two 23-bit limbs), one workgroup of 16
-// wavefronts per ciphertext (auto dispatch: up to 256 ciphertexts; launch_blind_rotate_wide2 beyond); key copy per (polynomial, limb) 1,024 complex words A_k / 2 in the order of the
-// multiplying threads; tables fftq::QT_WORDS doubles; stat as in launch_blind_rotate_fft
-int launch_bsk_to_wide(const u64 *std_polys, double *w_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s);
-int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w, const double *g_tw_q,
-                             u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             bool glwe, hipStream_t s);
+// wavefronts per ciphertext (auto dispatch: up to 256 ciphertexts; launch_blind_rotate_wide2 beyond); key copy per (polynomial, limb)
+// 1,024 complex words A_k / 2 in the order of the multiplying threads; tables fftq::QT_WORDS doubles
+int launch_bsk_to_wide(const KeyConv &k);
+int launch_blind_rotate_wide(const RotBatch &b);
 // N = 2048 with the unrolled key (bmi_kernels_t64wu.hip): key at 40 bits of precision (two 20-bit limbs: the six-times larger limb sums
 // stay inside the transform's certified range), one workgroup per ciphertext (auto dispatch: up to 256 ciphertexts;
-// launch_blind_rotate_wide_u2 beyond); bsk3_w = launch_bsk_to_wide of the
-// unrolled key [ceil(n/2)][3 keys][2 l rows][2] polynomials at prec = 40, g_zeta_oct = exp(i pi x / 2048) for x in [0, 512] as (re, im)
-int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
-                               const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
-                               unsigned long long *stat, bool glwe, hipStream_t s);
+// launch_blind_rotate_wide_u2 beyond); key = launch_bsk_to_wide of the unrolled key [ceil(n/2)][3 keys][2 l rows][2] polynomials at
+// prec = 40, tab[1] = exp(i pi x / 2048) for x in [0, 512] as (re, im)
+int launch_blind_rotate_wide_u(const RotBatch &b);
 // ... and its throughput form (bmi_kernels_t64wu2.hip): two ciphertexts per workgroup, every key word a thread loads multiplied with
 // both, one decomposition level of tiles in LDS at a time; the SAME key copy and tables, the same words
-int launch_blind_rotate_wide_u2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
-                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
-                                unsigned long long *stat, bool glwe, hipStream_t s);
+int launch_blind_rotate_wide_u2(const RotBatch &b);
 // glwe_lookup.hip: the look-ups of groups that share one rotation.  glwe = [groups][2N] accumulators of a rotation of the groups'
 // base polynomials; group g serves the tables lut_ids[group_ptr[g] .. group_ptr[g+1]) and writes their LWE rows out[t] (N + 1
 // words) = SampleExtract_0(ACC_g * P_t), P_t the table's sparse factor scaled by 2^(its scale - the scale of base_ids[g]).
@@ -308,17 +301,6 @@ constexpr uint32_t BMI_SPARSE_CAP = 64;   // entries of a table's sparse factor:
 int launch_glwe_lookup(const u64 *glwe, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids,
                        const uint2 *sparse_head, const int2 *sparse, u64 *out, uint32_t groups, uint32_t total, uint32_t N,
                        hipStream_t s);
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s);
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s);
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s);
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s);
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s);
 // lwe_pack.hip: compression of output ciphertexts (LWE-to-GLWE packing keyswitch, then a centred modulus switch).
 // pack_slice = the most ciphertexts one launch_pack_slice takes (its T scratch is then 16 MB).  launch_pack_slice: the m
 // ciphertexts cts [m][N + 1], numbers first .. first + m of their block, are decomposed (digits = m * N * levels uint32 words),

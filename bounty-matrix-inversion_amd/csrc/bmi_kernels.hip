@@ -21,6 +21,7 @@
 #include "ks_lincomb.hpp"
 #include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
+#include "field_ops.hpp"
 #include "ntt_wave.hpp"
 
 using gl::u64;
@@ -330,56 +331,34 @@ struct FieldG {
 // ------------------------------------------------------------------------------------- launchers
 namespace bmi {
 
-int launch_bsk_to_ntt(const u64 *std_polys, u64 *ntt_polys, const u64 *g_tw, uint32_t n_polys, hipStream_t s) {
-    hipLaunchKernelGGL(k_bsk_to_ntt, dim3((n_polys + 3) / 4), dim3(256), 0, s, std_polys, ntt_polys, g_tw, n_polys);
+int launch_bsk_to_ntt(const KeyConv &k) {
+    hipLaunchKernelGGL(k_bsk_to_ntt, dim3((k.n_polys + 3) / 4), dim3(256), 0, k.s, k.std_polys, (u64 *)k.dst, k.tab[0].u(), k.n_polys);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const u64 *g_tw, uint32_t count, hipStream_t s) {
-    hipLaunchKernelGGL(k_negacyclic_mul, dim3((count + 3) / 4), dim3(256), 0, s, a, b, c, g_tw, count);
+static int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, DevWords g_tw, uint32_t count, hipStream_t s) {
+    hipLaunchKernelGGL(k_negacyclic_mul, dim3((count + 3) / 4), dim3(256), 0, s, a, b, c, g_tw.u(), count);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_tp(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const u64 *bsk,
-                           const u64 *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    if (count == 0) return 0;
+int launch_blind_rotate_tp(const RotBatch &b) {
+    if (b.count == 0) return 0;
     constexpr int CTS = BMI_TP_CTS;
-    hipLaunchKernelGGL((k_blind_rotate_tp<CTS>), dim3((count + CTS - 1) / CTS), dim3(128 * CTS), 0, s, small_cts,
-                       lut_ids, luts, bsk, g_tw, out, count, n);
+    hipLaunchKernelGGL((k_blind_rotate_tp<CTS>), dim3((b.count + CTS - 1) / CTS), dim3(128 * CTS), 0, b.s, b.cts,
+                       b.ids, b.luts.u(), b.key.u(), b.tab[0].u(), b.out, b.count, b.n);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const u64 *bsk,
-                            const u64 *g_tw, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    if (count == 0) return 0;
-    return launch_with_lds<k_blind_rotate_lat>(dim3(count), dim3(LAT_THREADS), (size_t)LAT_LDS_WORDS * sizeof(u64), s, small_cts, lut_ids, luts,
-                                               bsk, g_tw, out, count, n);
+int launch_blind_rotate_lat(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return launch_with_lds<k_blind_rotate_lat>(dim3(b.count), dim3(LAT_THREADS), (size_t)LAT_LDS_WORDS * sizeof(u64), b.s, b.cts, b.ids, b.luts.u(),
+                                               b.key.u(), b.tab[0].u(), b.out, b.count, b.n);
 }
 
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s) {
-    return ksl::launch_keyswitch<FieldG>(in, ksk, ks_bias, out, partial, slices, count, n, big_n, levels, base_log,
-                                         ks_stride, s);
-}
-
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s) {
-    return ksm::launch_ksk_to_limbs<FieldG>(ksk, limbs, rows, n, ks_stride, KS_LIMBS, s);
-}
-
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s) {
-    return ksm::launch_keyswitch<FieldG, KS_LIMBS>(in, limbs, digits, sums, out, slices, count, n, big_n, levels, base_log, s);
-}
-
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s) {
-    return ksl::launch_lincomb<FieldG>(store, row_ptr, idx, coef, const_body, out, count, width, s);
-}
+const FieldOps OPS = field_ops<FieldG, 9>(launch_negacyclic_mul);
 
 // store[rows[i]] = src[i] for i < count (rows of `width` words): the executor's level buffer -> recycled store rows
 __global__ void __launch_bounds__(256) k_scatter_rows(const u64 *__restrict__ src, u64 *__restrict__ store,
@@ -394,11 +373,6 @@ int launch_scatter_rows(const u64 *src, u64 *store, const uint32_t *rows, uint32
     hipLaunchKernelGGL(k_scatter_rows, dim3(count), dim3(256), 0, s, src, store, rows, width);
     BMI_LAUNCH_CHECK();
     return 0;
-}
-
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s) {
-    return lwp::launch_lwe_phase<FieldG>(ct, key_mask, phase, expected, msgs, err, count, big_n, delta_log, s);
 }
 
 }  // namespace bmi

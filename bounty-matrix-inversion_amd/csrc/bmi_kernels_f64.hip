@@ -17,6 +17,7 @@
 #include "ks_lincomb.hpp"
 #include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
+#include "field_ops.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
 #include "pair_sync.hpp"
@@ -1021,115 +1022,79 @@ PH_EXPORT(bmi_debug_phase_prof, g_phase)
 
 namespace bmi49 {
 
-int launch_bsk_to_ntt(const u64 *std_polys, double *ntt_polys, const double *g_tw, uint32_t n_polys, hipStream_t s) {
-    hipLaunchKernelGGL(k_bsk_to_ntt49, dim3((n_polys + 3) / 4), dim3(256), 0, s, std_polys, ntt_polys, g_tw, n_polys);
+int launch_bsk_to_ntt(const KeyConv &k) {
+    hipLaunchKernelGGL(k_bsk_to_ntt49, dim3((k.n_polys + 3) / 4), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, const double *g_tw, uint32_t count, hipStream_t s) {
-    hipLaunchKernelGGL(k_negacyclic_mul49, dim3((count + 3) / 4), dim3(256), 0, s, a, b, c, g_tw, count);
+static int launch_negacyclic_mul(const u64 *a, const u64 *b, u64 *c, DevWords g_tw, uint32_t count, hipStream_t s) {
+    hipLaunchKernelGGL(k_negacyclic_mul49, dim3((count + 3) / 4), dim3(256), 0, s, a, b, c, g_tw.d(), count);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_tpx(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk,
-                            const double *g_tw, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
-                            hipStream_t s) {
-    if (count == 0) return 0;
-    return with_shape49(levels, base_log, [&](auto L, auto BG) {
-        return launch_with_lds<k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>>(dim3((count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS),
-                                                                           (size_t)TPX_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
-                                                                           luts, bsk, g_tw, out, count, n);
+int launch_blind_rotate_tpx(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return with_shape49(b.levels, b.base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_tpx49<BMI_TPX49_PF, L, BG>>(dim3((b.count + TPX_CTS - 1) / TPX_CTS), dim3(128 * TPX_CTS),
+                                                                           (size_t)TPX_LDS_WORDS * sizeof(double), b.s, b.cts, b.ids,
+                                                                           b.luts.d(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n);
     });
 }
 
-int launch_bsk_to_quad(const u64 *std_polys, double *quad_polys, const double *g_tw, const double *g_t, uint32_t n_polys,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_bsk_to_quad49, dim3(n_polys), dim3(256), 0, s, std_polys, quad_polys, g_tw, g_t, n_polys);
+int launch_bsk_to_quad(const KeyConv &k) {
+    hipLaunchKernelGGL(k_bsk_to_quad49, dim3(k.n_polys), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.tab[1].d(), k.n_polys);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_quad,
-                             const double *g_tw, const double *g_t, u64 *out, uint32_t count, uint32_t n, hipStream_t s) {
-    if (count == 0) return 0;
-    return launch_with_lds<k_blind_rotate_quad49>(dim3(count), dim3(Q_THREADS), (size_t)Q_LDS_WORDS * sizeof(double), s, small_cts, lut_ids,
-                                                  luts, bsk_quad, g_tw, g_t, out, count, n);
+int launch_blind_rotate_quad(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return launch_with_lds<k_blind_rotate_quad49>(dim3(b.count), dim3(Q_THREADS), (size_t)Q_LDS_WORDS * sizeof(double), b.s, b.cts, b.ids,
+                                                  b.luts.d(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n);
 }
 
-int launch_bsk_to_wide(const u64 *std_polys, double *wide_polys, const double *g_tw, const double *g_tw_wide,
-                       uint32_t n_polys, hipStream_t s) {
-    hipLaunchKernelGGL(k_bsk_to_wide49, dim3(n_polys), dim3(128), 0, s, std_polys, wide_polys, g_tw, g_tw_wide, n_polys);
+int launch_bsk_to_wide(const KeyConv &k) {
+    hipLaunchKernelGGL(k_bsk_to_wide49, dim3(k.n_polys), dim3(128), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.tab[1].d(), k.n_polys);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_wide(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_wide,
-                             const double *g_tw, const double *g_tw_wide, u64 *out, uint32_t count, uint32_t n,
-                             uint32_t levels, uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
-    return with_shape49(levels, base_log, [&](auto L, auto BG) {
-        return launch_with_lds<k_blind_rotate_wide49<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)W_LDS_WORDS * sizeof(double), s, small_cts,
-                                                              lut_ids, luts, bsk_wide, g_tw, g_tw_wide, out, count, n);
+int launch_blind_rotate_wide(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return with_shape49(b.levels, b.base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_wide49<L, BG>>(dim3(b.count), dim3(W_THREADS), (size_t)W_LDS_WORDS * sizeof(double), b.s, b.cts,
+                                                              b.ids, b.luts.d(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n);
     });
 }
 
-int launch_blind_rotate_wide_u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_wide,
-                               const double *g_tw, const double *g_tw_wide, const double *g_root_pow, u64 *out, uint32_t count,
-                               uint32_t n, uint32_t levels, uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
-    if (levels == 3) return (int)hipErrorInvalidValue;   // 2 l <= four GGSW rows: the kernel has one round
-    return with_shape49(levels, base_log, [&](auto L, auto BG) {
+int launch_blind_rotate_wide_u(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (b.levels == 3) return (int)hipErrorInvalidValue;   // 2 l <= four GGSW rows: the kernel has one round
+    return with_shape49(b.levels, b.base_log, [&](auto L, auto BG) {
         if constexpr (L < 3)
-            return launch_with_lds<k_blind_rotate_wide49u<L, BG>>(dim3(count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), s, small_cts,
-                                                                   lut_ids, luts, bsk3_wide, g_tw, g_tw_wide, g_root_pow, out, count, n);
+            return launch_with_lds<k_blind_rotate_wide49u<L, BG>>(dim3(b.count), dim3(W_THREADS), (size_t)WU_LDS_WORDS * sizeof(double), b.s, b.cts,
+                                                                   b.ids, b.luts.d(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.tab[2].d(), b.out, b.count, b.n);
         else return (int)hipErrorInvalidValue;
     });
 }
 
-int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, bool paired, hipStream_t s) {
-    if (paired) hipLaunchKernelGGL(k_bsk_to_lat49<true>, dim3((n_polys + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys);
-    else hipLaunchKernelGGL(k_bsk_to_lat49<false>, dim3((n_polys + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys);
+int launch_bsk_to_lat(const KeyConv &k) {
+    if (k.paired) hipLaunchKernelGGL(k_bsk_to_lat49<true>, dim3((k.n_polys + 1) / 2), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys);
+    else hipLaunchKernelGGL(k_bsk_to_lat49<false>, dim3((k.n_polys + 1) / 2), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_lat2(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk_lat,
-                             const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, uint32_t levels, uint32_t base_log,
-                             hipStream_t s) {
-    if (count == 0) return 0;
-    return with_shape49(levels, base_log, [&](auto L, auto BG) {
-        return launch_with_lds<k_blind_rotate_lat2_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2_LDS_WORDS * sizeof(double), s, small_cts,
-                                                               lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
+int launch_blind_rotate_lat2(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return with_shape49(b.levels, b.base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_lat2_49<L, BG>>(dim3(b.count), dim3(L2_THREADS), (size_t)L2_LDS_WORDS * sizeof(double), b.s, b.cts,
+                                                               b.ids, b.luts.d(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n);
     });
 }
 
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s) {
-    return ksl::launch_keyswitch<Field49>(in, ksk, ks_bias, out, partial, slices, count, n, big_n, levels, base_log,
-                                          ks_stride, s);
-}
-
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s) {
-    return ksm::launch_ksk_to_limbs<Field49>(ksk, limbs, rows, n, ks_stride, KS_LIMBS, s);
-}
-
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s) {
-    return ksm::launch_keyswitch<Field49, KS_LIMBS>(in, limbs, digits, sums, out, slices, count, n, big_n, levels, base_log, s);
-}
-
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s) {
-    return ksl::launch_lincomb<Field49>(store, row_ptr, idx, coef, const_body, out, count, width, s);
-}
-
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s) {
-    return lwp::launch_lwe_phase<Field49>(ct, key_mask, phase, expected, msgs, err, count, big_n, delta_log, s);
-}
+const FieldOps OPS = field_ops<Field49, 7>(launch_negacyclic_mul);
 
 }  // namespace bmi49

@@ -172,13 +172,11 @@ extern "C" int bmi_debug_wg_times_unrolled(unsigned long long *out2048) {
 
 namespace bmi49 {
 
-int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const double *luts, const double *bsk3_lat,
-                              const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n,
-                              uint32_t levels, uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
-    return with_shape49(levels, base_log, [&](auto L, auto BG) {
-        return launch_with_lds<k_blind_rotate_lat2u_49<L, BG>>(dim3(count), dim3(L2_THREADS), (size_t)L2U_LDS_WORDS * sizeof(double), s, small_cts,
-                                                                lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
+int launch_blind_rotate_lat2u(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    return with_shape49(b.levels, b.base_log, [&](auto L, auto BG) {
+        return launch_with_lds<k_blind_rotate_lat2u_49<L, BG>>(dim3(b.count), dim3(L2_THREADS), (size_t)L2U_LDS_WORDS * sizeof(double), b.s, b.cts,
+                                                                b.ids, b.luts.d(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n);
     });
 }
 

@@ -25,6 +25,7 @@
 #include "ks_lincomb.hpp"
 #include "lwe_phase.hpp"
 #include "ks_mfma.hpp"
+#include "field_ops.hpp"
 #include "ntt_half_f64.hpp"
 #include "ntt_wave_f64.hpp"
 #include "pair_sync.hpp"
@@ -430,77 +431,47 @@ struct FieldT {
 
 namespace bmit {
 
-int launch_bsk_to_limbs(const u64 *std_polys, double *limb_polys, const double *g_tw, uint32_t n_polys, int prec,
-                        hipStream_t s) {
-    if (!t64::precision_ok(prec)) return (int)hipErrorInvalidValue;
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_limbs_t64, dim3((items + 3) / 4), dim3(256), 0, s, std_polys, limb_polys, g_tw, n_polys, prec);
+int launch_bsk_to_limbs(const KeyConv &k) {
+    if (!t64::precision_ok(k.prec)) return (int)hipErrorInvalidValue;
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_limbs_t64, dim3((items + 3) / 4), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
 // (the instantiated (precision, levels, base log) combinations: BMIT_FOR_EACH_SHAPE, rotation_plan.hpp, where shape_supported reads
 // the same list)
-int launch_blind_rotate(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_limbs,
-                        const double *g_tw, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                        uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
+int launch_blind_rotate(const RotBatch &b) {
+    if (b.count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B)                                                                                          \
-        return launch_with_lds<k_blind_rotate_t64<P, L, B>>(dim3((count + T64_CTS - 1) / T64_CTS), dim3(128 * T64_CTS),                      \
-                                                             (size_t)T64_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_limbs, \
-                                                             g_tw, out, count, n);
+    if (b.prec == P && b.levels == L && b.base_log == B)                                                                                      \
+        return launch_with_lds<k_blind_rotate_t64<P, L, B>>(dim3((b.count + T64_CTS - 1) / T64_CTS), dim3(128 * T64_CTS),                      \
+                                                             (size_t)T64_LDS_WORDS * sizeof(double), b.s, b.cts, b.ids, b.luts.u(), b.key.d(), \
+                                                             b.tab[0].d(), b.out, b.count, b.n);
     BMIT_FOR_EACH_SHAPE(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;
 }
 
-int launch_bsk_to_lat(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, int prec, hipStream_t s) {
-    if (!t64::precision_ok(prec)) return (int)hipErrorInvalidValue;
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_lat_t64, dim3((items + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys, prec);
+int launch_bsk_to_lat(const KeyConv &k) {
+    if (!t64::precision_ok(k.prec)) return (int)hipErrorInvalidValue;
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_lat_t64, dim3((items + 1) / 2), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_lat(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_lat,
-                            const double *g_tw_h, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
+int launch_blind_rotate_lat(const RotBatch &b) {
+    if (b.count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B)                                                                                             \
-        return launch_with_lds<k_blind_rotate_lat_t64<L, P, B>>(dim3(count), dim3(LT_THREADS), (size_t)LT_LDS_WORDS * sizeof(double), s, small_cts, \
-                                                                 lut_ids, luts, bsk_lat, g_tw_h, out, count, n);
+    if (b.prec == P && b.levels == L && b.base_log == B)                                                                                       \
+        return launch_with_lds<k_blind_rotate_lat_t64<L, P, B>>(dim3(b.count), dim3(LT_THREADS), (size_t)LT_LDS_WORDS * sizeof(double), b.s, b.cts, \
+                                                                 b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n);
     BMIT_FOR_EACH_SHAPE(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;
 }
 
-int launch_keyswitch(const u64 *in, const u64 *ksk, const u64 *ks_bias, u64 *out, void *partial, uint32_t slices,
-                     uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels, uint32_t base_log, uint32_t ks_stride,
-                     hipStream_t s) {
-    return ksl::launch_keyswitch<FieldT>(in, ksk, ks_bias, out, partial, slices, count, n, big_n, levels, base_log,
-                                         ks_stride, s);
-}
-
-int launch_ksk_to_limbs(const u64 *ksk, signed char *limbs, uint32_t rows, uint32_t n, uint32_t ks_stride, hipStream_t s) {
-    return ksm::launch_ksk_to_limbs<FieldT>(ksk, limbs, rows, n, ks_stride, KS_LIMBS, s);
-}
-
-int launch_keyswitch_mfma(const u64 *in, const signed char *limbs, signed char *digits, int *sums, u64 *out,
-                          uint32_t slices, uint32_t count, uint32_t n, uint32_t big_n, uint32_t levels,
-                          uint32_t base_log, hipStream_t s) {
-    return ksm::launch_keyswitch<FieldT, KS_LIMBS>(in, limbs, digits, sums, out, slices, count, n, big_n, levels, base_log, s);
-}
-
-int launch_lincomb(const u64 *store, const uint32_t *row_ptr, const uint32_t *idx, const i64 *coef,
-                   const u64 *const_body, u64 *out, uint32_t count, uint32_t width, hipStream_t s) {
-    return ksl::launch_lincomb<FieldT>(store, row_ptr, idx, coef, const_body, out, count, width, s);
-}
-
-int launch_lwe_phase(const u64 *ct, const u64 *key_mask, u64 *phase, const i64 *expected, i64 *msgs, i64 *err,
-                     uint32_t count, uint32_t big_n, uint32_t delta_log, hipStream_t s) {
-    return lwp::launch_lwe_phase<FieldT>(ct, key_mask, phase, expected, msgs, err, count, big_n, delta_log, s);
-}
+const FieldOps OPS = field_ops<FieldT, 9>(nullptr);
 
 }  // namespace bmit

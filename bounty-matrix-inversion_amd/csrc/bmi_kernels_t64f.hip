@@ -552,42 +552,38 @@ PH_EXPORT(bmi_debug_phase_prof_t64f, g_phase_f)
 
 namespace bmit {
 
-int launch_bsk_to_fft(const u64 *std_polys, double *limb_polys, const double *g_tw_fft, uint32_t n_polys, int prec, hipStream_t s) {
-    if (prec != 48) return (int)hipErrorInvalidValue;
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_fft_t64, dim3((items + 3) / 4), dim3(256), 0, s, std_polys, limb_polys, g_tw_fft, n_polys, prec);
+int launch_bsk_to_fft(const KeyConv &k) {
+    if (k.prec != 48) return (int)hipErrorInvalidValue;
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_fft_t64, dim3((items + 3) / 4), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_bsk_to_latf(const u64 *std_polys, double *lat_polys, const double *g_tw_h, uint32_t n_polys, int prec, hipStream_t s) {
-    if (prec != 48 && prec != 42) return (int)hipErrorInvalidValue;   // (42: the unrolled key of bmi_kernels_t64fu.hip)
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_latf_t64, dim3((items + 1) / 2), dim3(256), 0, s, std_polys, lat_polys, g_tw_h, n_polys, prec);
+int launch_bsk_to_latf(const KeyConv &k) {
+    if (k.prec != 48 && k.prec != 42) return (int)hipErrorInvalidValue;   // (42: the unrolled key of bmi_kernels_t64fu.hip)
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_latf_t64, dim3((items + 1) / 2), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_lat_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                                const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                                uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS, GLWE>>(dim3(count), dim3(H_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), s,
-                                                                             small_cts, lut_ids, luts, bsk_fft, g_tw_fft, out, count, n, stat);
+int launch_blind_rotate_lat_fft(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_fft(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(b.levels, b.stat != nullptr, b.glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_lat_t64f<L, 10, STATS, GLWE>>(dim3(b.count), dim3(H_THREADS), (size_t)LF_LDS_WORDS * sizeof(double), b.s,
+                                                                             b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n, b.stat);
     });
 }
 
-int launch_blind_rotate_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_fft,
-                            const double *g_tw_fft, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels,
-                            uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_t64f<L, 10, STATS, GLWE>>(dim3((count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS),
-                                                                         (size_t)TF_LDS_WORDS * sizeof(double), s, small_cts, lut_ids, luts, bsk_fft,
-                                                                         g_tw_fft, out, count, n, stat);
+int launch_blind_rotate_fft(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_fft(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(b.levels, b.stat != nullptr, b.glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_t64f<L, 10, STATS, GLWE>>(dim3((b.count + TF_CTS - 1) / TF_CTS), dim3(128 * TF_CTS),
+                                                                         (size_t)TF_LDS_WORDS * sizeof(double), b.s, b.cts, b.ids, b.luts.u(), b.key.d(),
+                                                                         b.tab[0].d(), b.out, b.count, b.n, b.stat);
     });
 }
 

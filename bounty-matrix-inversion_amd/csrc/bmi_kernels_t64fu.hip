@@ -314,25 +314,21 @@ __global__ void __launch_bounds__(H_THREADS)
 namespace bmit {
 
 // two ciphertexts per workgroup (key words shared in registers): the throughput form, same words as launch_blind_rotate_lat2u_fft
-int launch_blind_rotate_tp2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
-                                 const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                 uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_glwe(levels, glwe, [&](auto L, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42, GLWE>>(dim3((count + 1) / 2), dim3(H_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), s,
-                                                                           small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n);
+int launch_blind_rotate_tp2u_fft(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_unrolled_fft(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_glwe(b.levels, b.glwe, [&](auto L, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_tp2u_t64f<L, 10, 42, GLWE>>(dim3((b.count + 1) / 2), dim3(H_THREADS), (size_t)U2_LDS_WORDS * sizeof(double), b.s,
+                                                                           b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n);
     });
 }
 
-int launch_blind_rotate_lat2u_fft(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_latf,
-                                  const double *g_tw_h, const double *g_zeta_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                                  uint32_t levels, uint32_t base_log, unsigned long long *stat, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_unrolled_fft(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS, GLWE>>(dim3(count), dim3(H_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), s,
-                                                                                   small_cts, lut_ids, luts, bsk3_latf, g_tw_h, g_zeta_pow, out, count, n, stat);
+int launch_blind_rotate_lat2u_fft(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_unrolled_fft(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(b.levels, b.stat != nullptr, b.glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_lat2u_t64f<L, 10, 42, STATS, GLWE>>(dim3(b.count), dim3(H_THREADS), (size_t)UF_LDS_WORDS * sizeof(double), b.s,
+                                                                                   b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n, b.stat);
     });
 }
 

@@ -236,22 +236,20 @@ __global__ void __launch_bounds__(QF_THREADS)
 
 namespace bmit {
 
-int launch_bsk_to_quad(const u64 *std_polys, double *q_polys, const double *g_tw_e, uint32_t n_polys, int prec, hipStream_t s) {
-    if (prec != 44) return (int)hipErrorInvalidValue;
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_q_t64, dim3(items), dim3(512), 0, s, std_polys, q_polys, g_tw_e, n_polys, prec);
+int launch_bsk_to_quad(const KeyConv &k) {
+    if (k.prec != 44) return (int)hipErrorInvalidValue;
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_q_t64, dim3(items), dim3(512), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_quad(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_q, const double *g_tw_e,
-                             u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, unsigned long long *stat,
-                             bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_quad(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_q_t64f<L, 10, 44, STATS, GLWE>>(dim3(count), dim3(QF_THREADS), (size_t)QF_LDS_WORDS * sizeof(double), s,
-                                                                               small_cts, lut_ids, luts, bsk_q, g_tw_e, out, count, n, stat);
+int launch_blind_rotate_quad(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_quad(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(b.levels, b.stat != nullptr, b.glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_q_t64f<L, 10, 44, STATS, GLWE>>(dim3(b.count), dim3(QF_THREADS), (size_t)QF_LDS_WORDS * sizeof(double), b.s,
+                                                                              b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n, b.stat);
     });
 }
 

@@ -174,15 +174,13 @@ PH_EXPORT(bmi_debug_phase_prof_unrolled_t64, g_phase_tu)
 namespace bmit {
 
 // (the instantiated combinations: BMIT_FOR_EACH_SHAPE_U, rotation_plan.hpp)
-int launch_blind_rotate_lat2u(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_lat,
-                              const double *g_tw_h, const double *g_root_pow, u64 *out, uint32_t count, uint32_t n, int prec,
-                              uint32_t levels, uint32_t base_log, hipStream_t s) {
-    if (count == 0) return 0;
+int launch_blind_rotate_lat2u(const RotBatch &b) {
+    if (b.count == 0) return 0;
 #define BMIT_GO(P, L, B) \
-    if (prec == P && levels == L && base_log == B)                                                                                            \
-        return launch_with_lds<k_blind_rotate_lat2u_t64<L, B, P>>(dim3(count), dim3(LU_THREADS),                                               \
-                                                                   (size_t)lu_lds_words<Scheme<P>::LIMBS>() * sizeof(double), s, small_cts,    \
-                                                                   lut_ids, luts, bsk3_lat, g_tw_h, g_root_pow, out, count, n);
+    if (b.prec == P && b.levels == L && b.base_log == B)                                                                                      \
+        return launch_with_lds<k_blind_rotate_lat2u_t64<L, B, P>>(dim3(b.count), dim3(LU_THREADS),                                             \
+                                                                   (size_t)lu_lds_words<Scheme<P>::LIMBS>() * sizeof(double), b.s, b.cts,      \
+                                                                   b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n);
     BMIT_FOR_EACH_SHAPE_U(BMIT_GO)
 #undef BMIT_GO
     return (int)hipErrorInvalidValue;

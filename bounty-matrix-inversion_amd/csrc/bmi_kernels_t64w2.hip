@@ -213,21 +213,20 @@ __global__ void __launch_bounds__(W_THREADS)
 
 namespace bmit {
 
-int launch_bsk_to_wide2(const u64 *std_polys, double *w2_polys, const double *g_tw_q, uint32_t n_polys, int prec, hipStream_t s) {
-    if (prec != 46) return (int)hipErrorInvalidValue;
-    const uint32_t items = n_polys * (uint32_t)t64::limbs_of(prec);
-    hipLaunchKernelGGL(k_bsk_to_w2_t64, dim3(items), dim3(256), 0, s, std_polys, w2_polys, g_tw_q, n_polys, prec);
+int launch_bsk_to_wide2(const KeyConv &k) {
+    if (k.prec != 46) return (int)hipErrorInvalidValue;
+    const uint32_t items = k.n_polys * (uint32_t)t64::limbs_of(k.prec);
+    hipLaunchKernelGGL(k_bsk_to_w2_t64, dim3(items), dim3(256), 0, k.s, k.std_polys, (double *)k.dst, k.tab[0].d(), k.n_polys, k.prec);
     BMI_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_blind_rotate_wide2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk_w2, const double *g_tw_q,
-                              u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_wide(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_glwe(levels, glwe, [&](auto L, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((count + 1) / 2), dim3(W_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), s,
-                                                                        small_cts, lut_ids, luts, bsk_w2, g_tw_q, out, count, n);
+int launch_blind_rotate_wide2(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_wide(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_glwe(b.levels, b.glwe, [&](auto L, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_w2_t64f<L, 10, 46, GLWE>>(dim3((b.count + 1) / 2), dim3(W_THREADS), (size_t)W2_LDS_WORDS * sizeof(double), b.s,
+                                                                        b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.out, b.count, b.n);
     });
 }
 

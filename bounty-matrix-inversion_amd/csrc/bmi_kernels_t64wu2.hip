@@ -249,14 +249,12 @@ __global__ void __launch_bounds__(W_THREADS)
 
 namespace bmit {
 
-int launch_blind_rotate_wide_u2(const u64 *small_cts, const uint32_t *lut_ids, const u64 *luts, const double *bsk3_w, const double *g_tw_q,
-                                const double *g_zeta_oct, u64 *out, uint32_t count, uint32_t n, int prec, uint32_t levels, uint32_t base_log,
-                                unsigned long long *stat, bool glwe, hipStream_t s) {
-    if (count == 0) return 0;
-    if (!shape_supported_wide_unrolled(prec, levels, base_log)) return (int)hipErrorInvalidValue;
-    return with_levels_stats_glwe(levels, stat != nullptr, glwe, [&](auto L, auto STATS, auto GLWE) {
-        return launch_with_lds<k_blind_rotate_wu2_t64f<L, 10, 40, STATS, GLWE>>(dim3((count + 1) / 2), dim3(W_THREADS), (size_t)WU2_LDS_WORDS * sizeof(double),
-                                                                                s, small_cts, lut_ids, luts, bsk3_w, g_tw_q, g_zeta_oct, out, count, n, stat);
+int launch_blind_rotate_wide_u2(const RotBatch &b) {
+    if (b.count == 0) return 0;
+    if (!shape_supported_wide_unrolled(b.prec, b.levels, b.base_log)) return (int)hipErrorInvalidValue;
+    return with_levels_stats_glwe(b.levels, b.stat != nullptr, b.glwe, [&](auto L, auto STATS, auto GLWE) {
+        return launch_with_lds<k_blind_rotate_wu2_t64f<L, 10, 40, STATS, GLWE>>(dim3((b.count + 1) / 2), dim3(W_THREADS), (size_t)WU2_LDS_WORDS * sizeof(double), b.s,
+                                                                                b.cts, b.ids, b.luts.u(), b.key.d(), b.tab[0].d(), b.tab[1].d(), b.out, b.count, b.n, b.stat);
     });
 }
 

@@ -3,8 +3,9 @@
 // setters accept.  Plain structs and inline host functions - no context, no HIP, no device pointer - so that bmi_host.cpp, the
 // launchers' own guards (bmi_kernels_t64*.hip) and a program without a GPU (tests/c_abi/rotation_plan_table.cpp) read the same
 // text.  bmi_host.cpp describes a context to these functions (shape, settings, what it holds) and acts on the answer: a refusal is
-// the text of bmi_last_error.  A new kernel family is added HERE (its predicate, its key copy, its place in choose_rotation) and in
-// launch_rotation / build_key_copy of bmi_host.cpp, which know the device pointers.
+// the text of bmi_last_error.  A new kernel family is added in two places: HERE (its predicate, its row in ROT_ROWS - and in
+// COPY_ROWS / Table where it brings a key layout or a table of its own -, its place in choose_rotation) and as one launcher in the
+// tables LAUNCHERS / CONVERTERS of bmi_host.cpp, in the order of the enumerations.
 #pragma once
 #include <stdint.h>
 
@@ -75,19 +76,88 @@ struct Settings {
     uint32_t lat_threshold;   // auto: the latency kernels up to this batch size
 };
 
-// The device copies of a bootstrap key, one per layout (bmi_ctx::BskCopies, then bmi_ctx::Bsk3Copies: the unrolled key's), in the
-// order they are built
+// The tables a context uploads at creation (bmi_ctx::tables, built by bmi_ctx_create), with the kernels that read them.  A context
+// holds those its modulus and N have a kernel for: context_tables.
+enum class Table {
+    tw_gl,         // Goldilocks: wave-NTT twiddles (ntt_wave.hpp) - bsk_to_ntt, negacyclic_mul, blind_rotate_lat / _tp
+    tw_wave,       // 49-bit field and torus: the same mod 2^49 - 720895, centred doubles - 49-bit bsk_to_ntt, blind_rotate_tpx
+                   // and their N = 2048 / 4096 forms, negacyclic_mul; torus bsk_to_limbs, blind_rotate
+    tw_half,       // 49-bit field and torus: half transform (ntt_half_f64.hpp) - bsk_to_lat, blind_rotate_lat2 / _lat / _lat2u
+    root_pow,      // 49-bit N <= 2048 and torus: psi^x, x < 2048 (psi_2048; N = 2048: psi_4096) - blind_rotate_lat2u, 49-bit _wide_u
+    tw_wide49,     // 49-bit N = 2048: T / T^-1 of the even/odd combination - bsk_to_wide, blind_rotate_wide / _wide_u
+    tw_quad49,     // 49-bit N = 4096: T_1..T_3, then their inverses - bsk_to_quad, blind_rotate_quad
+    tw_fft,        // torus N = 1024: folded complex FFT (fft_wave_f64.hpp) - bsk_to_fft, blind_rotate_fft
+    tw_fft_half,   // torus N = 1024: half FFT (fft_half_f64.hpp) - bsk_to_latf, blind_rotate_lat_fft / _lat2u_fft / _tp2u_fft
+    zeta_pow,      // torus N = 1024: exp(i pi x / 1024), x in [0, 1024) as (re, im) - blind_rotate_lat2u_fft / _tp2u_fft
+    zeta_oct,      // torus N = 2048: exp(i pi x / 2048), x in [0, 512] as (re, im), one octant - blind_rotate_wide_u
+    tw_quarter,    // torus N = 2048: quarter transforms (fft_quarter_f64.hpp) - bsk_to_wide / _wide2, blind_rotate_wide / _wide2
+    tw_eighth,     // torus N = 4096: eighth transforms (fft_eighth_f64.hpp) - bsk_to_quad, blind_rotate_quad
+    COUNT,
+    none = COUNT   // an unused table slot of a row
+};
+constexpr uint32_t bit(Table t) { return t == Table::none ? 0 : 1u << (int)t; }
+inline uint32_t context_tables(const Shape &s) {
+    if (!s.f64() && !s.t64()) return bit(Table::tw_gl);
+    uint32_t t = bit(Table::tw_wave) | bit(Table::tw_half);   // (the torus kernels transform mod the 49-bit prime as well)
+    if (s.t64() || !s.quad()) t |= bit(Table::root_pow);
+    if (s.t64()) return t | (s.wide() ? bit(Table::tw_quarter) | bit(Table::zeta_oct) : s.quad() ? bit(Table::tw_eighth)
+                                      : bit(Table::tw_fft) | bit(Table::tw_fft_half) | bit(Table::zeta_pow));
+    return t | (s.wide() ? bit(Table::tw_wide49) : s.quad() ? bit(Table::tw_quad49) : 0);
+}
+
+// The device copies of a bootstrap key, one per layout (bmi_ctx::copies), in the order they are built: the layout, the conversion
+// that makes it and the kernels that read it
 enum class Copy {
-    ntt_gl, ntt49, lat49, wide49, quad49, exact, exact_lat, fft, fft_lat, wide, wide2, quad,   // the plain key
-    u_lat49, u_wide49, u_exact_lat, u_fft_lat, u_wide,                                          // the unrolled key
+    // the plain key
+    ntt_gl,        // Goldilocks, NTT domain (bsk_to_ntt): blind_rotate_lat / _tp
+    ntt49,         // 49-bit N = 1024, NTT domain (bsk_to_ntt): blind_rotate_tpx
+    lat49,         // 49-bit N = 1024, split-transform slot order (bsk_to_lat): blind_rotate_lat2
+    wide49,        // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide
+    quad49,        // 49-bit N = 4096 (bsk_to_quad): blind_rotate_quad
+    exact,         // torus N = 1024, limb polynomials of the exact transform (bsk_to_limbs): blind_rotate
+    exact_lat,     // ... in the slot order of its latency form (bsk_to_lat): blind_rotate_lat
+    fft,           // torus N = 1024, floating-point transform (bsk_to_fft): blind_rotate_fft
+    fft_lat,       // ... in half-transform slot pairs (bsk_to_latf): blind_rotate_lat_fft
+    wide,          // torus N = 2048 (bsk_to_wide): blind_rotate_wide
+    wide2,         // torus N = 2048, two ciphertexts per workgroup (bsk_to_wide2): blind_rotate_wide2
+    quad,          // torus N = 4096 (bsk_to_quad): blind_rotate_quad
+    // the unrolled key
+    u_lat49,       // 49-bit N = 1024, paired slot order (bsk_to_lat): blind_rotate_lat2u
+    u_wide49,      // 49-bit N = 2048 (bsk_to_wide): blind_rotate_wide_u
+    u_exact_lat,   // torus, exact transform (bsk_to_lat): blind_rotate_lat2u
+    u_fft_lat,     // torus, key at 42 bits: floating-point transform (bsk_to_latf): blind_rotate_lat2u_fft / _tp2u_fft
+    u_wide,        // torus N = 2048, key at 40 bits (bsk_to_wide): blind_rotate_wide_u / _wide_u2
     COUNT
 };
 constexpr uint32_t bit(Copy k) { return 1u << (int)k; }
-inline const char *copy_name(Copy k) {
-    static const char *const names[] = {"ntt_gl", "ntt49", "lat49", "wide49", "quad49", "exact", "exact_lat", "fft", "fft_lat",
-                                        "wide", "wide2", "quad", "u_lat49", "u_wide49", "u_exact_lat", "u_fft_lat", "u_wide"};
-    return names[(int)k];
-}
+struct CopyRow {
+    const char *name;
+    bool unrolled;    // a copy of the unrolled key
+    Table tab[2];     // what its converter reads, in the order it takes them
+};
+constexpr Table NO_TABLE = Table::none;
+constexpr CopyRow COPY_ROWS[] = {
+    {"ntt_gl", false, {Table::tw_gl, NO_TABLE}},
+    {"ntt49", false, {Table::tw_wave, NO_TABLE}},
+    {"lat49", false, {Table::tw_half, NO_TABLE}},
+    {"wide49", false, {Table::tw_wave, Table::tw_wide49}},
+    {"quad49", false, {Table::tw_wave, Table::tw_quad49}},
+    {"exact", false, {Table::tw_wave, NO_TABLE}},
+    {"exact_lat", false, {Table::tw_half, NO_TABLE}},
+    {"fft", false, {Table::tw_fft, NO_TABLE}},
+    {"fft_lat", false, {Table::tw_fft_half, NO_TABLE}},
+    {"wide", false, {Table::tw_quarter, NO_TABLE}},
+    {"wide2", false, {Table::tw_quarter, NO_TABLE}},
+    {"quad", false, {Table::tw_eighth, NO_TABLE}},
+    {"u_lat49", true, {Table::tw_half, NO_TABLE}},
+    {"u_wide49", true, {Table::tw_wave, Table::tw_wide49}},
+    {"u_exact_lat", true, {Table::tw_half, NO_TABLE}},
+    {"u_fft_lat", true, {Table::tw_fft_half, NO_TABLE}},
+    {"u_wide", true, {Table::tw_quarter, NO_TABLE}},
+};
+static_assert(sizeof(COPY_ROWS) / sizeof(COPY_ROWS[0]) == (size_t)Copy::COUNT, "one row per key copy");
+constexpr const CopyRow &row(Copy k) { return COPY_ROWS[(int)k]; }
+inline const char *copy_name(Copy k) { return row(k).name; }
 
 struct Held {
     uint32_t copies;   // bit(Copy) of every copy on the device
@@ -134,45 +204,49 @@ enum class Rot {
     t64_wide_u, t64_wide_u2, t64_wide2, t64_wide, t64_quad, t64_tp2u_fft, t64_lat2u_fft, t64_lat2u, t64_lat_fft, t64_lat, t64_fft, t64_exact,   // 2^64 torus
     f49_wide_u, f49_wide, f49_quad, f49_lat2u, f49_lat2, f49_tpx,                                                   // 49-bit field
     gl_lat, gl_tp,                                                                                                  // Goldilocks
+    COUNT
 };
 
-// The __global__ function a member launches: bmi_rotation_kernel answers with it
-inline const char *rotation_name(Rot rot) {
-    switch (rot) {
-    case Rot::t64_wide_u: return "k_blind_rotate_wu_t64f";
-    case Rot::t64_wide_u2: return "k_blind_rotate_wu2_t64f";
-    case Rot::t64_wide2: return "k_blind_rotate_w2_t64f";
-    case Rot::t64_wide: return "k_blind_rotate_w_t64f";
-    case Rot::t64_quad: return "k_blind_rotate_q_t64f";
-    case Rot::t64_tp2u_fft: return "k_blind_rotate_tp2u_t64f";
-    case Rot::t64_lat2u_fft: return "k_blind_rotate_lat2u_t64f";
-    case Rot::t64_lat2u: return "k_blind_rotate_lat2u_t64";
-    case Rot::t64_lat_fft: return "k_blind_rotate_lat_t64f";
-    case Rot::t64_lat: return "k_blind_rotate_lat_t64";
-    case Rot::t64_fft: return "k_blind_rotate_t64f";
-    case Rot::t64_exact: return "k_blind_rotate_t64";
-    case Rot::f49_wide_u: return "k_blind_rotate_wide49u";
-    case Rot::f49_wide: return "k_blind_rotate_wide49";
-    case Rot::f49_quad: return "k_blind_rotate_quad49";
-    case Rot::f49_lat2u: return "k_blind_rotate_lat2u_49";
-    case Rot::f49_lat2: return "k_blind_rotate_lat2_49";
-    case Rot::f49_tpx: return "k_blind_rotate_tpx49";
-    case Rot::gl_lat: return "k_blind_rotate_lat";
-    case Rot::gl_tp: return "k_blind_rotate_tp";
-    }
-    return "";
-}
-
-// The kernels with an accumulator form (bmi_blind_rotate_glwe_batch): the nine floating-point-transform kernels of the torus.
-// Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not the prime fields.
-inline bool has_accumulator_form(Rot rot) {
-    switch (rot) {
-    case Rot::t64_wide_u: case Rot::t64_wide_u2: case Rot::t64_wide2: case Rot::t64_wide: case Rot::t64_quad: case Rot::t64_tp2u_fft: case Rot::t64_lat2u_fft:
-    case Rot::t64_lat_fft: case Rot::t64_fft:
-        return true;
-    default: return false;
-    }
-}
+// What launch_rotation needs to know of a member, one row each in the order of the enumeration:
+//   name         the __global__ function it launches: bmi_rotation_kernel answers with it
+//   key          the key copy it reads
+//   tab          the tables it reads, in the order the kernel takes them
+//   accumulator  it has an accumulator form (bmi_blind_rotate_glwe_batch): the nine floating-point-transform kernels of the torus.
+//                Not the exact-transform ones (the pair a pinned variant 1 / 3 / 4 selects, the unrolled key pinned at 48 bits), not
+//                the prime fields.
+//   stat         it takes the statistics pointer of bmi_fft_margin_host (the two-ciphertext forms w2 and tp2u have none)
+struct RotRow {
+    const char *name;
+    Copy key;
+    Table tab[3];
+    bool accumulator, stat;
+};
+constexpr RotRow ROT_ROWS[] = {
+    {"k_blind_rotate_wu_t64f", Copy::u_wide, {Table::tw_quarter, Table::zeta_oct, NO_TABLE}, true, true},
+    {"k_blind_rotate_wu2_t64f", Copy::u_wide, {Table::tw_quarter, Table::zeta_oct, NO_TABLE}, true, true},   // one key copy serves both
+    {"k_blind_rotate_w2_t64f", Copy::wide2, {Table::tw_quarter, NO_TABLE, NO_TABLE}, true, false},
+    {"k_blind_rotate_w_t64f", Copy::wide, {Table::tw_quarter, NO_TABLE, NO_TABLE}, true, true},
+    {"k_blind_rotate_q_t64f", Copy::quad, {Table::tw_eighth, NO_TABLE, NO_TABLE}, true, true},
+    {"k_blind_rotate_tp2u_t64f", Copy::u_fft_lat, {Table::tw_fft_half, Table::zeta_pow, NO_TABLE}, true, false},
+    {"k_blind_rotate_lat2u_t64f", Copy::u_fft_lat, {Table::tw_fft_half, Table::zeta_pow, NO_TABLE}, true, true},
+    {"k_blind_rotate_lat2u_t64", Copy::u_exact_lat, {Table::tw_half, Table::root_pow, NO_TABLE}, false, false},
+    {"k_blind_rotate_lat_t64f", Copy::fft_lat, {Table::tw_fft_half, NO_TABLE, NO_TABLE}, true, true},
+    {"k_blind_rotate_lat_t64", Copy::exact_lat, {Table::tw_half, NO_TABLE, NO_TABLE}, false, false},
+    {"k_blind_rotate_t64f", Copy::fft, {Table::tw_fft, NO_TABLE, NO_TABLE}, true, true},
+    {"k_blind_rotate_t64", Copy::exact, {Table::tw_wave, NO_TABLE, NO_TABLE}, false, false},
+    {"k_blind_rotate_wide49u", Copy::u_wide49, {Table::tw_wave, Table::tw_wide49, Table::root_pow}, false, false},
+    {"k_blind_rotate_wide49", Copy::wide49, {Table::tw_wave, Table::tw_wide49, NO_TABLE}, false, false},
+    {"k_blind_rotate_quad49", Copy::quad49, {Table::tw_wave, Table::tw_quad49, NO_TABLE}, false, false},
+    {"k_blind_rotate_lat2u_49", Copy::u_lat49, {Table::tw_half, Table::root_pow, NO_TABLE}, false, false},
+    {"k_blind_rotate_lat2_49", Copy::lat49, {Table::tw_half, NO_TABLE, NO_TABLE}, false, false},
+    {"k_blind_rotate_tpx49", Copy::ntt49, {Table::tw_wave, NO_TABLE, NO_TABLE}, false, false},
+    {"k_blind_rotate_lat", Copy::ntt_gl, {Table::tw_gl, NO_TABLE, NO_TABLE}, false, false},
+    {"k_blind_rotate_tp", Copy::ntt_gl, {Table::tw_gl, NO_TABLE, NO_TABLE}, false, false},
+};
+static_assert(sizeof(ROT_ROWS) / sizeof(ROT_ROWS[0]) == (size_t)Rot::COUNT, "one row per kernel");
+constexpr const RotRow &row(Rot rot) { return ROT_ROWS[(int)rot]; }
+inline const char *rotation_name(Rot rot) { return row(rot).name; }
+inline bool has_accumulator_form(Rot rot) { return row(rot).accumulator; }
 
 // ------------------------------------------------------------------------------------------------ which copies a key set gets
 // The plain key, in the layout of every kernel selectable on the context.

@@ -15,6 +15,11 @@
 //   import_unrolled_seeded    the shape and precision checks of bmi_import_bsk_unrolled_seeded (after a seeded key set)
 //   same as <seq> #i          the context is in the state that sequence was in at its i-th block of variant .. import_unrolled
 //                             lines: that block applies here
+//
+// Beside the printing, the rows of the plan (ROT_ROWS, COPY_ROWS) are held to the plan itself: at every `variant` and `margin`
+// answer the kernel's key copy must be held (or built on demand) and its tables among those a context of that shape uploads; so
+// must the tables of every copy's converter; and the accumulator and statistics flags must be the lists below.  A miss is
+// reported on stderr, and the program then ends with status 1 and the number of misses.
 #include <cstdio>
 #include <map>
 #include <string>
@@ -36,6 +41,62 @@ struct Ctx {
     Held held;
 };
 
+static int misses = 0;
+static void expect(bool ok, const Ctx &c, const char *who, const char *what) {
+    if (ok) return;
+    misses++;
+    fprintf(stderr, "MISS %s logN=%u l=%u Bg=%u prec=%d unroll=%u: %s %s\n", modulus_name(c.shape.modulus), c.shape.log_N, c.shape.bs_levels,
+            c.shape.bs_base_log, c.set.bsk_prec, c.set.unroll, who, what);
+}
+// a kernel the plan answered with: launch_rotation must find its key copy and its tables on the device (a context without keys
+// names its kernel too, to bmi_rotation_kernel, but every entry point that launches refuses it before: no copy to ask for)
+static void check_answer(const Ctx &c, Rot rot) {
+    const RotRow &r = row(rot);
+    expect(!c.held.have_keys || c.held.has(r.key) || (on_demand_copies(rot) & bit(r.key)) != 0, c, r.name,
+           "reads a key copy that is neither held nor built on demand");
+    for (Table t : r.tab) expect((bit(t) & ~context_tables(c.shape)) == 0, c, r.name, "names a table that the context does not upload");
+}
+// the copies held: their converters ran on tables of the context
+static void check_copies(const Ctx &c) {
+    for (int k = 0; k < (int)Copy::COUNT; k++)
+        for (Table t : row((Copy)k).tab)
+            expect(!c.held.has((Copy)k) || (bit(t) & ~context_tables(c.shape)) == 0, c, copy_name((Copy)k), "is converted with a table that the context does not upload");
+}
+// the flags, against the lists the switches of launch_rotation and has_accumulator_form spelled out before the rows existed
+static void check_flags() {
+    const Rot accumulator[] = {Rot::t64_wide_u, Rot::t64_wide_u2, Rot::t64_wide2, Rot::t64_wide, Rot::t64_quad, Rot::t64_tp2u_fft, Rot::t64_lat2u_fft,
+                               Rot::t64_lat_fft, Rot::t64_fft};
+    const Rot stat[] = {Rot::t64_wide_u, Rot::t64_wide_u2, Rot::t64_wide, Rot::t64_quad, Rot::t64_lat2u_fft, Rot::t64_lat_fft, Rot::t64_fft};
+    const Ctx none{Shape{Modulus::goldilocks, 0, 0, 0}, Settings{0, false, 0, 0, 0}, Held{0, false, false}};
+    // ... and the key copy and tables each case of that switch handed its launcher.  (Holding a copy is not enough to tell two
+    // copies apart that are always built together, such as fft and fft_lat: a row naming the wrong one of them passes check_answer.)
+    const Table no = Table::none;
+    const struct { Rot rot; Copy key; Table tab[3]; } wiring[] = {
+        {Rot::t64_wide_u, Copy::u_wide, {Table::tw_quarter, Table::zeta_oct, no}}, {Rot::t64_wide_u2, Copy::u_wide, {Table::tw_quarter, Table::zeta_oct, no}},
+        {Rot::t64_wide2, Copy::wide2, {Table::tw_quarter, no, no}}, {Rot::t64_wide, Copy::wide, {Table::tw_quarter, no, no}},
+        {Rot::t64_quad, Copy::quad, {Table::tw_eighth, no, no}}, {Rot::t64_tp2u_fft, Copy::u_fft_lat, {Table::tw_fft_half, Table::zeta_pow, no}},
+        {Rot::t64_lat2u_fft, Copy::u_fft_lat, {Table::tw_fft_half, Table::zeta_pow, no}}, {Rot::t64_lat2u, Copy::u_exact_lat, {Table::tw_half, Table::root_pow, no}},
+        {Rot::t64_lat_fft, Copy::fft_lat, {Table::tw_fft_half, no, no}}, {Rot::t64_lat, Copy::exact_lat, {Table::tw_half, no, no}},
+        {Rot::t64_fft, Copy::fft, {Table::tw_fft, no, no}}, {Rot::t64_exact, Copy::exact, {Table::tw_wave, no, no}},
+        {Rot::f49_wide_u, Copy::u_wide49, {Table::tw_wave, Table::tw_wide49, Table::root_pow}}, {Rot::f49_wide, Copy::wide49, {Table::tw_wave, Table::tw_wide49, no}},
+        {Rot::f49_quad, Copy::quad49, {Table::tw_wave, Table::tw_quad49, no}}, {Rot::f49_lat2u, Copy::u_lat49, {Table::tw_half, Table::root_pow, no}},
+        {Rot::f49_lat2, Copy::lat49, {Table::tw_half, no, no}}, {Rot::f49_tpx, Copy::ntt49, {Table::tw_wave, no, no}},
+        {Rot::gl_lat, Copy::ntt_gl, {Table::tw_gl, no, no}}, {Rot::gl_tp, Copy::ntt_gl, {Table::tw_gl, no, no}}};
+    static_assert(sizeof(wiring) / sizeof(wiring[0]) == (size_t)Rot::COUNT, "one case per kernel");
+    for (const auto &w : wiring) {
+        const RotRow &r = row(w.rot);
+        expect(r.key == w.key, none, r.name, "reads another key copy than its launcher was handed");
+        expect(r.tab[0] == w.tab[0] && r.tab[1] == w.tab[1] && r.tab[2] == w.tab[2], none, r.name, "reads other tables than its launcher was handed");
+    }
+    for (int k = 0; k < (int)Rot::COUNT; k++) {
+        bool acc = false, st = false;
+        for (Rot r : accumulator) acc = acc || r == (Rot)k;
+        for (Rot r : stat) st = st || r == (Rot)k;
+        expect(has_accumulator_form((Rot)k) == acc, none, rotation_name((Rot)k), "has the wrong accumulator flag");
+        expect(row((Rot)k).stat == st, none, rotation_name((Rot)k), "has the wrong statistics flag");
+    }
+}
+
 static std::string verdict(const std::string &refusal, const std::string &ok) { return refusal.empty() ? ok : "REFUSED: " + refusal; }
 
 static uint64_t copies_bytes(const Ctx &c) {
@@ -43,7 +104,7 @@ static uint64_t copies_bytes(const Ctx &c) {
     const uint64_t poly_words = (uint64_t)2 * c.shape.bs_levels * 2 << c.shape.log_N;   // one GGSW: (k + 1) l rows of k + 1 polynomials
     uint64_t bytes = 0;
     for (int k = 0; k < (int)Copy::COUNT; k++)
-        if (c.held.has((Copy)k)) bytes += (k < (int)Copy::u_lat49 ? N_LWE : (N_LWE + 1) / 2 * 3) * poly_words * 8 * limbs;
+        if (c.held.has((Copy)k)) bytes += (row((Copy)k).unrolled ? (N_LWE + 1) / 2 * 3 : N_LWE) * poly_words * 8 * limbs;
     return bytes;
 }
 
@@ -51,6 +112,7 @@ static void print_keys(const char *step, const Ctx &c) {
     std::string names;
     for (int k = 0; k < (int)Copy::COUNT; k++)
         if (c.held.has((Copy)k)) names += (names.empty() ? "" : ",") + std::string(copy_name((Copy)k));
+    check_copies(c);
     printf("  %s -> copies=%s bytes=%llu\n", step, names.empty() ? "none" : names.c_str(), (unsigned long long)copies_bytes(c));
 }
 
@@ -90,6 +152,7 @@ static std::string per_count(const Ctx &c, Rule rule) {
     std::vector<std::string> ans;
     for (uint32_t n : COUNTS) {
         const Choice ch = rule(c.shape, c.set, c.held, n);
+        if (ch.refusal.empty()) check_answer(c, ch.rot);
         ans.push_back(verdict(ch.refusal, rotation_name(ch.rot)));
     }
     bool same = true;
@@ -211,5 +274,7 @@ int main() {
     context(T, 10, 4, 10);
     context(T, 11, 3, 15);    // N = 2048 / 4096 on the torus: base 2^10 only
     context(T, 12, 3, 15);
-    return 0;
+    check_flags();
+    if (misses) fprintf(stderr, "%d checks of the rows missed\n", misses);
+    return misses ? 1 : 0;
 }

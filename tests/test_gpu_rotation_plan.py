@@ -3,8 +3,11 @@ csrc/rotation_plan.hpp alone; its format is described in tests/c_abi/rotation_pl
 every sequence on a fresh Engine - set_bsk_unroll / set_bsk_precision with the precision they leave, keygen with the bytes of the
 key copies built (key_bytes), set_kernel_variant and rotation_kernel for every variant and batch size, the refusal of
 fft_margin_host, import_bsk_unrolled - with every BmiError text.  All parameter sets have n = 8: dispatch does not look at n, and a
-key set is then small.  No blind rotation is launched: the accepted lines of the margin hook (it would launch its kernel) and the
-import_unrolled_seeded lines (they need a seeded key set first) are checked by the host-only test alone."""
+key set is then small.  These two tests launch no blind rotation: the accepted lines of the margin hook (it would launch its
+kernel) and the import_unrolled_seeded lines (they need a seeded key set first) are checked by the host-only test alone.
+
+test_every_kernel_rotates_on_the_key_copy_and_tables_of_its_row then launches each of the 20 kernels once on such a context: a row
+of the plan that named the wrong key copy or table would produce wrong words, not an error."""
 import os
 import re
 
@@ -123,3 +126,75 @@ def test_refused_contexts_say_what_the_table_says():
     for modulus, log_N, l, bg, want, _ in refused:
         P = tfhe.default_params(q_bits=Q_BITS[modulus], n=N_LWE, log_N=log_N, bs_levels=l, bs_base_log=bg)
         assert answer(lambda: tfhe.Engine(P)) == want, (modulus, log_N, l, bg)
+
+
+# One line per kernel (rotplan::Rot): a context on which the dispatch answers with it for batches of 1 and 3 -
+# (kernel, modulus, log_N, l, Bg, key precision to set or None, unrolling factor, kernel variant to pin, accumulator form, variant
+# under which fft_margin_host runs it or None)
+KERNELS = [
+    ("k_blind_rotate_wu_t64f", "torus64", 11, 3, 10, None, 2, 0, True, 0),
+    ("k_blind_rotate_wu2_t64f", "torus64", 11, 3, 10, None, 2, 1, True, 1),
+    ("k_blind_rotate_w2_t64f", "torus64", 11, 3, 10, None, 1, 1, True, None),
+    ("k_blind_rotate_w_t64f", "torus64", 11, 3, 10, None, 1, 0, True, 0),
+    ("k_blind_rotate_q_t64f", "torus64", 12, 3, 10, None, 1, 0, True, 0),
+    ("k_blind_rotate_tp2u_t64f", "torus64", 10, 3, 10, None, 2, 1, True, None),
+    ("k_blind_rotate_lat2u_t64f", "torus64", 10, 3, 10, None, 2, 0, True, 0),
+    ("k_blind_rotate_lat2u_t64", "torus64", 10, 3, 10, 48, 2, 0, False, None),
+    ("k_blind_rotate_lat_t64f", "torus64", 10, 3, 10, None, 1, 0, True, 6),
+    ("k_blind_rotate_lat_t64", "torus64", 10, 3, 10, None, 1, 4, False, None),
+    ("k_blind_rotate_t64f", "torus64", 10, 3, 10, None, 1, 5, True, 0),
+    ("k_blind_rotate_t64", "torus64", 10, 3, 10, None, 1, 1, False, None),
+    ("k_blind_rotate_wide49u", "field49", 11, 2, 15, None, 2, 0, False, None),
+    ("k_blind_rotate_wide49", "field49", 11, 3, 15, None, 1, 0, False, None),
+    ("k_blind_rotate_quad49", "field49", 12, 3, 15, None, 1, 0, False, None),
+    ("k_blind_rotate_lat2u_49", "field49", 10, 3, 15, None, 2, 0, False, None),
+    ("k_blind_rotate_lat2_49", "field49", 10, 3, 15, None, 1, 2, False, None),
+    ("k_blind_rotate_tpx49", "field49", 10, 3, 15, None, 1, 3, False, None),
+    ("k_blind_rotate_lat", "goldilocks", 10, 3, 15, None, 1, 2, False, None),
+    ("k_blind_rotate_tp", "goldilocks", 10, 3, 15, None, 1, 1, False, None),
+]
+
+
+def extract(glwe, N):
+    """SampleExtract_0 of accumulators [rows][2N]: o[0] = A[0], o[x] = -A[N - x], o[N] = B[0]"""
+    out = np.zeros((glwe.shape[0], N + 1), np.uint64)
+    out[:, 0] = glwe[:, 0]
+    out[:, 1:N] = np.uint64(0) - glwe[:, N - 1:0:-1]
+    out[:, N] = glwe[:, N]
+    return out
+
+
+@pytest.mark.parametrize("kernel,modulus,log_N,l,bg,precision,unroll,variant,accumulator,margin_variant", KERNELS, ids=[k[0] for k in KERNELS])
+def test_every_kernel_rotates_on_the_key_copy_and_tables_of_its_row(kernel, modulus, log_N, l, bg, precision, unroll, variant, accumulator,
+                                                                    margin_variant):
+    """Batches of 1 and 3 (odd: the two-ciphertexts-per-workgroup kernels run their padding slot) through the kernel, confirmed by
+    rotation_kernel: every output decrypts to the registered 4-bit table's value.  The nine kernels with an accumulator form: its
+    sample extraction is the plain rotation, word for word; the seven that fft_margin_host can run: the same words again, and a
+    largest rounding distance below 1/2."""
+    from bmi_amd import tfhe
+    e = tfhe.Engine(tfhe.default_params(q_bits=Q_BITS[modulus], n=N_LWE, log_N=log_N, bs_levels=l, bs_base_log=bg))
+    try:
+        if precision:
+            e.set_bsk_precision(precision)
+        if unroll == 2:
+            e.set_bsk_unroll(2)
+        e.keygen(0x5EED)
+        dl = e.delta_log()
+        table = np.array([(5 * m + 3) % 16 - 8 for m in range(-8, 8)])
+        lid = e.lut_register(table, 4, dl)
+        for count in (1, 3):
+            msgs = np.array([-8, 7, 2])[:count]
+            ids = np.full(count, lid, np.uint32)
+            small = e.keyswitch_host(e.encrypt(msgs, dl))
+            e.set_kernel_variant(variant)
+            assert e.rotation_kernel(count) == kernel
+            out = e.blind_rotate_host(small, ids)
+            assert list(e.decrypt(out, dl)) == [int(table[m + 8]) for m in msgs], count
+            if accumulator:
+                assert np.array_equal(extract(e.blind_rotate_glwe_host(small, ids), e.P.N), out), count
+            if margin_variant is not None:
+                e.set_kernel_variant(margin_variant)
+                words, distance = e.fft_margin_host(small, ids)
+                assert np.array_equal(words, out) and 0 <= distance < 0.5, (count, distance)
+    finally:
+        e.close()

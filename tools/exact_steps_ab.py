@@ -21,6 +21,8 @@ CONFIGS = {
     "lat2u_t64": (lambda: tfhe.default_params(q_bits=tfhe.TORUS64), 48, 2, 0, "k_blind_rotate_lat2u_t64"),
     "wide49": (lambda: tfhe.preset_params("secure128"), None, 1, 0, "k_blind_rotate_wide49"),
     "wide49u": (lambda: tfhe.preset_params("secure128"), None, 2, 0, "k_blind_rotate_wide49u"),
+    # the default torus set under auto dispatch: what a change to the host's launch path costs per call (profiles/launch_rows_ab.txt)
+    "default_t64": (lambda: tfhe.default_params(q_bits=tfhe.TORUS64), None, 1, 0, "k_blind_rotate_lat_t64f"),
 }
 BATCHES = (1, 256)
 
