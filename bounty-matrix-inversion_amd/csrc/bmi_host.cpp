@@ -146,18 +146,14 @@ struct bmi_ctx {
     std::vector<uint2> sparse_head_host;
     uint32_t base_id_of_unit[64] = {};   // id + 1 of the base polynomial registered for a unit, 0 = none yet
     // growable device scratch (grow)
-    DevBuf<u64> glwe;                  // accumulators of bmi_pbs_shared_batch and of the host-buffer forms ([groups][2 k N])
-    DevBuf<uint32_t> io_groups;        // host-buffer forms of the shared look-ups: group_ptr [groups + 1], then base ids [groups]
-    DevBuf<u64> small;                 // keyswitched ciphertexts of bmi_pbs_batch and of the host-buffer forms
-    DevBuf<u64> io_a, io_b;            // host-buffer forms: input and output ciphertexts, and look-up ids
-    DevBuf<uint32_t> io_ids;
+    DevBuf<u64> glwe;                  // accumulators of bmi_pbs_shared_batch ([groups][2 k N])
+    DevBuf<u64> small;                 // keyswitched ciphertexts of bmi_pbs_batch / bmi_pbs_shared_batch
+    DevBuf<unsigned char> arena;       // every region of a host-buffer form's call (Stage)
     DevBuf<unsigned __int128> ks_partial;   // partial sums of the sliced scalar keyswitch
     DevBuf<signed char> ks_digits;     // matrix-core keyswitch: digit matrix ...
     DevBuf<int> ks_sums;               // ... and int32 sums
     DevBuf<uint32_t> pk_digits;        // compression: digit matrix of a slice ...
     DevBuf<u64> pk_T, pk_acc;          // ... its products [slice][2N], and the block's accumulator [2N]
-    DevBuf<u64> pk_in;                 // host-buffer form: input ciphertexts ...
-    DevBuf<uint32_t> pk_out;           // ... and compressed values (decompression's host-buffer form: the other way round, index in io_ids)
     int variant = 0;
     uint32_t lat_threshold = 0;    // auto dispatch: the latency kernels up to this batch size (rotplan::initial_settings)
     int ks_variant = 0;  // 0 = auto (matrix cores when the shape allows), 1 = scalar kernel
@@ -214,6 +210,72 @@ int grow(bmi_ctx *c, DevBuf<T> &b, size_t need, size_t floor_bytes) {
     HIP_OK(c, b.alloc(std::max(need, floor_bytes)));
     return 0;
 }
+// What a launcher returned (a hipError_t as an int) -> the entry point's result: 0, or -2 and "<what><the error's name>"
+int launched(const bmi_ctx *c, const char *what, int rc) {
+    return rc ? fail(c, -2, std::string(what) + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+// The device side of one host-buffer form's call.  The entry point checks its arguments and the context's state, names its regions
+// - each a count of elements of one type that is uploaded from a host pointer, filled with zeros, downloaded to a host pointer at the
+// end, or several of these - and passes the device-pointer form to run().  All regions lie in the context's one arena, each from a
+// 256-byte boundary; the arena grows before anything is queued (at most one device synchronisation per call, none once it holds
+// the largest call so far).  Everything is queued on the context's stream, and run() returns only after that stream has drained,
+// whatever refused or failed in between: no caller's array and no local variable is still in reach of a queued copy.
+struct Stage {
+    template <class T>
+    struct Ref { int i; };   // a region, and through operator[] its device pointer (inside run())
+    struct Region {
+        size_t at, bytes;
+        const void *up;
+        void *down;
+        bool zero;
+    };
+    Region regions[6];   // (the shared look-ups name five)
+    int n = 0;
+    size_t total = 0;
+    unsigned char *base = nullptr;
+    static size_t aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+    template <class T>
+    Ref<T> region(size_t count, const T *up, T *down, bool zero = false) {
+        regions[n] = Region{total, count * sizeof(T), up, down, zero};
+        total += aligned(count * sizeof(T));
+        return {n++};
+    }
+    template <class T>
+    Ref<T> upload(const T *from, size_t count) { return region<T>(count, from, nullptr); }
+    template <class T>
+    Ref<T> download(T *to, size_t count) { return region<T>(count, nullptr, to); }
+    template <class T>
+    T *operator[](Ref<T> r) const { return (T *)(base + regions[r.i].at); }
+
+    template <class Form>
+    int queue(bmi_ctx *c, Form device_form) const {
+        for (int i = 0; i < n; i++) {
+            const Region &r = regions[i];
+            if (r.zero && r.bytes) HIP_OK(c, hipMemsetAsync(base + r.at, 0, r.bytes, c->stream));
+            if (r.up && r.bytes) HIP_OK(c, hipMemcpyAsync(base + r.at, r.up, r.bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        if (int rc = device_form()) return rc;
+        for (int i = 0; i < n; i++)
+            if (regions[i].down && regions[i].bytes)
+                HIP_OK(c, hipMemcpyAsync(regions[i].down, base + regions[i].at, regions[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+    template <class Form>
+    int run(bmi_ctx *c, Form device_form) {
+        HIP_OK(c, hipSetDevice(c->device));
+        // the floor, held from the first call on (an empty call has pointers too): bmi_pbs_batch_host of 256 ciphertexts
+        const size_t floor_bytes = 2 * aligned((size_t)256 * (c->big_n + 1) * sizeof(u64)) + aligned(256 * sizeof(uint32_t));
+        if (int rc = grow(c, c->arena, std::max(total, floor_bytes), 0)) return rc;
+        base = c->arena.get();
+        const int rc = queue(c, device_form);
+        const hipError_t drained = hipStreamSynchronize(c->stream);   // the one way out once a copy may be queued
+        if (rc || drained == hipSuccess) return rc;   // (the first error stands)
+        return fail(c, -2, std::string("hipStreamSynchronize(c->stream): ") + hipGetErrorString(drained));
+    }
+};
+
 // The device copy of the big secret key (bmi_phase_batch / bmi_decrypt_batch): bit x % 64 of word x / 64 is key bit x.
 int ensure_sk_mask(bmi_ctx *c) {
     if (!c->sk_mask.empty()) return 0;
@@ -251,14 +313,6 @@ void drop_compression_key(bmi_ctx *c, bool new_key_set) {
 int ensure_small(bmi_ctx *c, size_t count) {
     const size_t w = (size_t)(c->P.n + 1) * sizeof(u64);
     return grow(c, c->small, count * w, 1024 * w);
-}
-// ... and the host-buffer forms' input / output ciphertexts and look-up ids (room for 256 at least)
-int ensure_io(bmi_ctx *c, size_t count) {
-    const size_t w = (size_t)(c->big_n + 1) * sizeof(u64);
-    int rc = ensure_small(c, count);
-    if (!rc) rc = grow(c, c->io_a, count * w, 256 * w);
-    if (!rc) rc = grow(c, c->io_b, count * w, 256 * w);
-    return rc ? rc : grow(c, c->io_ids, count * sizeof(uint32_t), 256 * sizeof(uint32_t));
 }
 constexpr size_t KS_PARTIAL_BYTES = (size_t)96 << 20;  // covers every split configuration (<= 1024 workgroups x 8 ciphertexts)
 
@@ -1124,7 +1178,7 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
         if (int rc = ensure_ks_mfma(c, count)) return rc;
         const int rc = c->ops->keyswitch_mfma(d_in, c->ks_limbs.get(), c->ks_digits.get(), c->ks_sums.get(), d_small, ks_mfma_slices(c, count),
                                               count, c->P.n, c->big_n, c->P.ks_levels, c->P.ks_base_log, (hipStream_t)stream);
-        return rc ? fail(c, -2, std::string("keyswitch (matrix cores) launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+        return launched(c, "keyswitch (matrix cores) launch: ", rc);
     }
     if (c->P.n + 1 > 3 * 256)   // ks_lincomb.hpp: KS_COLS x KS_THREADS output columns per workgroup
         return fail(c, -1, c->ks_mfma_ok ? "the scalar keyswitch kernel takes n <= 767; this parameter set needs the matrix-core form"
@@ -1147,7 +1201,7 @@ int bmi_keyswitch_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint64
         if (int rc = grow(c, c->ks_partial, (size_t)slices * count * c->ks_stride * 16, KS_PARTIAL_BYTES)) return rc;
     int rc = c->ops->keyswitch(d_in, c->ksk_padded.get(), c->ks_bias.get(), d_small, slices > 1 ? c->ks_partial.get() : nullptr, slices,
                                count, c->P.n, c->big_n, c->P.ks_levels, c->P.ks_base_log, c->ks_stride, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("keyswitch launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "keyswitch launch: ", rc);
 }
 
 // bmi_blind_rotate_batch (d_out = [count][N + 1] samples) and, with glwe, bmi_blind_rotate_glwe_batch (d_out = [count][2N] accumulators)
@@ -1164,9 +1218,8 @@ static int blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_
         return fail(c, -1, "the accumulator form exists for the floating-point-transform kernels only: not for a pinned exact-transform variant "
                            "(1 / 3 / 4), nor for the unrolled key pinned at 48 bits of precision (the exact-transform unrolled kernel)");
     if (int rc = build_copies(c, rotplan::on_demand_copies(rot), c->bsk_std)) return rc;   // (a no-op once built)
-    const int rc = launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, glwe, (hipStream_t)stream);
-    if (rc) return fail(c, -2, std::string(glwe ? "blind_rotate (accumulator form) launch: " : "blind_rotate launch: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    return launched(c, glwe ? "blind_rotate (accumulator form) launch: " : "blind_rotate launch: ",
+                    launch_rotation(c, rot, d_small, d_lut_ids, count, d_out, nullptr, glwe, (hipStream_t)stream));
 }
 
 int bmi_blind_rotate_batch(bmi_ctx *c, const uint64_t *d_small, const uint32_t *d_lut_ids, uint32_t count,
@@ -1184,7 +1237,7 @@ int bmi_modswitch_centre_batch(bmi_ctx *c, const uint64_t *d_small_in, uint32_t 
     if (count == 0) return 0;
     HIP_OK(c, hipSetDevice(c->device));
     const int rc = bmi::launch_modswitch_centre(d_small_in, d_small_out, count, c->P.n, c->P.log_N, c->t64(), (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("modswitch_centre launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "modswitch_centre launch: ", rc);
 }
 
 int bmi_pbs_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_lut_ids, uint32_t count, uint64_t *d_out,
@@ -1211,7 +1264,7 @@ int bmi_glwe_lookup_batch(bmi_ctx *c, const uint64_t *d_glwe, const uint32_t *d_
     HIP_OK(c, hipSetDevice(c->device));
     const int rc = bmit::launch_glwe_lookup(d_glwe, d_group_ptr, d_base_ids, d_lut_ids, c->sparse_head.get(), c->sparse.get(), d_out, groups,
                                             total, c->N, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("glwe_lookup launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "glwe_lookup launch: ", rc);
 }
 
 int bmi_pbs_shared_batch(bmi_ctx *c, const uint64_t *d_in, const uint32_t *d_group_ptr, const uint32_t *d_base_ids,
@@ -1233,7 +1286,7 @@ int bmi_lincomb_batch(bmi_ctx *c, const uint64_t *d_store, const uint32_t *d_row
     if (!c || (count && (!d_store || !d_row_ptr || !d_const_body || !d_out))) return -1;
     HIP_OK(c, hipSetDevice(c->device));
     int rc = c->ops->lincomb(d_store, d_row_ptr, d_idx, (const i64 *)d_coef, d_const_body, d_out, count, c->big_n + 1, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("lincomb launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "lincomb launch: ", rc);
 }
 
 // phase (d_msgs null) or decryption of device-resident ciphertexts: the checks of bmi_phase, then one launch of k_lwe_phase
@@ -1246,7 +1299,7 @@ static int phase_decrypt_batch(bmi_ctx *c, const uint64_t *d_ct, uint32_t count,
     if (int rc = ensure_sk_mask(c)) return rc;
     const int rc = c->ops->lwe_phase(d_ct, c->sk_mask.get(), d_phase, (const i64 *)d_expected, (i64 *)d_msgs, (i64 *)d_err, count, c->big_n,
                                      delta_log, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("lwe_phase launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "lwe_phase launch: ", rc);
 }
 
 int bmi_phase_batch(bmi_ctx *c, const uint64_t *d_ct, uint32_t count, uint64_t *d_phase, void *stream) {
@@ -1266,7 +1319,7 @@ int bmi_scatter_rows(bmi_ctx *c, const uint64_t *d_src, uint32_t count, uint64_t
     if (!c || (count && (!d_src || !d_store || !d_rows))) return -1;
     HIP_OK(c, hipSetDevice(c->device));
     int rc = bmi::launch_scatter_rows(d_src, d_store, d_rows, count, c->big_n + 1, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("scatter_rows launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "scatter_rows launch: ", rc);
 }
 
 int bmi_reserve(bmi_ctx *c, uint32_t max_count) {
@@ -1301,70 +1354,45 @@ int bmi_sync(bmi_ctx *c, void *stream) {
 }
 
 // ------------------------------------------------------------------- host-buffer convenience forms
+// Each checks what can be checked on the host, names its regions and hands the device-pointer form to Stage::run.
 int bmi_pbs_batch_host(bmi_ctx *c, const uint64_t *in, const uint32_t *lut_ids, uint32_t count, uint64_t *out) {
     if (!c || !in || !lut_ids || !out) return -1;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_io(c, count);
-    if (rc) return rc;
-    const size_t w = (size_t)(c->big_n + 1) * 8;
-    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, count * w, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_pbs_batch(c, c->io_a.get(), c->io_ids.get(), count, c->io_b.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), count * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t w = (size_t)c->big_n + 1;
+    Stage s;
+    const auto d_in = s.upload(in, count * w);
+    const auto d_ids = s.upload(lut_ids, count);
+    const auto d_out = s.download(out, count * w);
+    return s.run(c, [&] { return bmi_pbs_batch(c, s[d_in], s[d_ids], count, s[d_out], c->stream); });
 }
 
 int bmi_keyswitch_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uint64_t *small_out) {
     if (!c || !in || !small_out) return -1;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_io(c, count);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, (size_t)count * (c->big_n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_keyswitch_batch(c, c->io_a.get(), count, c->small.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(small_out, c->small.get(), (size_t)count * (c->P.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_in = s.upload(in, (size_t)count * (c->big_n + 1));
+    const auto d_small = s.download(small_out, (size_t)count * (c->P.n + 1));
+    return s.run(c, [&] { return bmi_keyswitch_batch(c, s[d_in], count, s[d_small], c->stream); });
 }
 
 int bmi_modswitch_centre_batch_host(bmi_ctx *c, const uint64_t *small_in, uint32_t count, uint64_t *small_out) {
     if (!c) return -1;
     if (!small_in || !small_out) return fail(c, -1, "bmi_modswitch_centre_batch_host: null ciphertext pointer");
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_small(c, count);
-    if (rc) return rc;
-    const size_t bytes = (size_t)count * (c->P.n + 1) * 8;
-    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, bytes, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_modswitch_centre_batch(c, c->small.get(), count, c->small.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(small_out, c->small.get(), bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_small = s.region((size_t)count * (c->P.n + 1), small_in, small_out);   // switched in place
+    return s.run(c, [&] { return bmi_modswitch_centre_batch(c, s[d_small], count, s[d_small], c->stream); });
 }
 
-// bmi_blind_rotate_batch_host (rows of N + 1 words through io_b) and, with glwe, bmi_blind_rotate_glwe_batch_host (rows of 2N words
-// through the accumulator buffer)
+// bmi_blind_rotate_batch_host (rows of N + 1 words) and, with glwe, bmi_blind_rotate_glwe_batch_host (rows of 2N words)
 static int blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *out, bool glwe) {
     if (!c || !small_in || !lut_ids || !out) return -1;
     if (glwe)
         if (int rc = shared_rotation_ok(c)) return rc;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_io(c, count);
-    if (!rc && glwe) rc = ensure_glwe(c, count);
-    if (rc) return rc;
-    u64 *d_out = glwe ? c->glwe.get() : c->io_b.get();
-    const size_t width = glwe ? (size_t)2 * c->big_n : (size_t)c->big_n + 1;
-    HIP_OK(c, hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream));
-    rc = blind_rotate_batch(c, c->small.get(), c->io_ids.get(), count, d_out, glwe, c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, d_out, count * width * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_small = s.upload(small_in, (size_t)count * (c->P.n + 1));
+    const auto d_ids = s.upload(lut_ids, count);
+    const auto d_out = s.download(out, count * (glwe ? (size_t)2 * c->big_n : (size_t)c->big_n + 1));
+    return s.run(c, [&] { return blind_rotate_batch(c, s[d_small], s[d_ids], count, s[d_out], glwe, c->stream); });
 }
 
 int bmi_blind_rotate_batch_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,
@@ -1377,49 +1405,36 @@ int bmi_blind_rotate_glwe_batch_host(bmi_ctx *c, const uint64_t *small_in, const
     return blind_rotate_batch_host(c, small_in, lut_ids, count, glwe_out, true);
 }
 
-// uploads the group description of a host-buffer form: io_groups = group_ptr [groups + 1], base ids [groups]; io_ids = lut_ids [total]
-static int upload_groups(bmi_ctx *c, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids, uint32_t groups, uint32_t total) {
-    if (int bad = check_groups(c, group_ptr, base_ids, lut_ids, groups, total)) return bad;
-    int rc = ensure_io(c, std::max(groups, total));
-    if (!rc) rc = ensure_glwe(c, groups);
-    if (!rc) rc = grow(c, c->io_groups, ((size_t)2 * groups + 1) * 4, 4096);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->io_groups.get(), group_ptr, ((size_t)groups + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->io_groups.get() + groups + 1, base_ids, (size_t)groups * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), lut_ids, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-    return 0;
+// the group description of a host-buffer form: group_ptr [groups + 1], base ids [groups], lut_ids [total]
+struct GroupRefs {
+    Stage::Ref<uint32_t> ptr, base, ids;
+};
+static GroupRefs stage_groups(Stage &s, const uint32_t *group_ptr, const uint32_t *base_ids, const uint32_t *lut_ids, uint32_t groups, uint32_t total) {
+    return {s.upload(group_ptr, (size_t)groups + 1), s.upload(base_ids, groups), s.upload(lut_ids, total)};
 }
 
 int bmi_glwe_lookup_batch_host(bmi_ctx *c, const uint64_t *glwe_in, const uint32_t *group_ptr, const uint32_t *base_ids,
                                const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out) {
     if (!c || !glwe_in || !group_ptr || !base_ids || !lut_ids || !out) return -1;
     if (int rc = shared_rotation_ok(c)) return rc;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = upload_groups(c, group_ptr, base_ids, lut_ids, groups, total);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->glwe.get(), glwe_in, (size_t)groups * 2 * c->big_n * 8, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_glwe_lookup_batch(c, c->glwe.get(), c->io_groups.get(), c->io_groups.get() + groups + 1, c->io_ids.get(), groups, total,
-                               c->io_b.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)total * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    if (int bad = check_groups(c, group_ptr, base_ids, lut_ids, groups, total)) return bad;
+    Stage s;
+    const auto d_glwe = s.upload(glwe_in, (size_t)groups * 2 * c->big_n);
+    const GroupRefs g = stage_groups(s, group_ptr, base_ids, lut_ids, groups, total);
+    const auto d_out = s.download(out, (size_t)total * (c->big_n + 1));
+    return s.run(c, [&] { return bmi_glwe_lookup_batch(c, s[d_glwe], s[g.ptr], s[g.base], s[g.ids], groups, total, s[d_out], c->stream); });
 }
 
 int bmi_pbs_shared_batch_host(bmi_ctx *c, const uint64_t *in, const uint32_t *group_ptr, const uint32_t *base_ids,
                               const uint32_t *lut_ids, uint32_t groups, uint32_t total, uint64_t *out) {
     if (!c || !in || !group_ptr || !base_ids || !lut_ids || !out) return -1;
     if (int rc = shared_rotation_ok(c)) return rc;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = upload_groups(c, group_ptr, base_ids, lut_ids, groups, total);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->io_a.get(), in, (size_t)groups * (c->big_n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_pbs_shared_batch(c, c->io_a.get(), c->io_groups.get(), c->io_groups.get() + groups + 1, c->io_ids.get(), groups, total,
-                              c->io_b.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->io_b.get(), (size_t)total * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    if (int bad = check_groups(c, group_ptr, base_ids, lut_ids, groups, total)) return bad;
+    Stage s;
+    const auto d_in = s.upload(in, (size_t)groups * (c->big_n + 1));
+    const GroupRefs g = stage_groups(s, group_ptr, base_ids, lut_ids, groups, total);
+    const auto d_out = s.download(out, (size_t)total * (c->big_n + 1));
+    return s.run(c, [&] { return bmi_pbs_shared_batch(c, s[d_in], s[g.ptr], s[g.base], s[g.ids], groups, total, s[d_out], c->stream); });
 }
 
 int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count, uint64_t *out,
@@ -1428,41 +1443,32 @@ int bmi_fft_margin_host(bmi_ctx *c, const uint64_t *small_in, const uint32_t *lu
     if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
     const rotplan::Choice ch = rotplan::margin_rotation(shape_of(c->P), settings_of(c), held_of(c), count);
     if (!ch.refusal.empty()) return fail(c, -1, ch.refusal);
-    const Rot rot = ch.rot;
     if (int bad = check_lut_ids(c, lut_ids, count)) return bad;
-    HIP_OK(c, hipSetDevice(c->device));
-    int rc = ensure_io(c, count);
-    if (rc) return rc;
-    DevBuf<unsigned long long> d_stat;
-    HIP_OK(c, d_stat.alloc(8));
-    hipError_t e = hipMemsetAsync(d_stat.get(), 0, 8, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->small.get(), small_in, (size_t)count * (c->P.n + 1) * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->io_ids.get(), lut_ids, count * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)launch_rotation(c, rot, c->small.get(), c->io_ids.get(), count, c->io_b.get(), d_stat.get(), false, c->stream);
-    unsigned long long bits = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(out, c->io_b.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bits, d_stat.get(), 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, -2, std::string("bmi_fft_margin_host: ") + hipGetErrorString(e));
-    std::memcpy(max_distance, &bits, 8);
-    return 0;
+    unsigned long long bits = 0;   // the statistic word: zero on the device before the kernel, here after it
+    Stage s;
+    const auto d_small = s.upload(small_in, (size_t)count * (c->P.n + 1));
+    const auto d_ids = s.upload(lut_ids, count);
+    const auto d_out = s.download(out, (size_t)count * (c->big_n + 1));
+    const auto d_stat = s.region<unsigned long long>(1, nullptr, &bits, true);
+    const int rc = s.run(c, [&] {
+        return launched(c, "bmi_fft_margin_host: ", launch_rotation(c, ch.rot, s[d_small], s[d_ids], count, s[d_out], s[d_stat], false, c->stream));
+    });
+    if (!rc) std::memcpy(max_distance, &bits, 8);
+    return rc;
 }
 
 int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, uint32_t count, uint64_t *out) {
     if (!c || !a || !b || !out) return -1;
     if (c->wide() || c->quad()) return fail(c, -1, "the transform test hook exists for N = 1024 only");
     if (c->t64()) return fail(c, -1, "no transform exists mod 2^64: the test hook covers the two prime fields");
-    HIP_OK(c, hipSetDevice(c->device));
     const size_t words = (size_t)count * c->N;
-    DevBuf<u64> da, db, dc;
-    HIP_OK(c, upload(da, a, words));
-    HIP_OK(c, upload(db, b, words));
-    HIP_OK(c, dc.alloc(words * 8));
+    Stage s;
+    const auto da = s.upload(a, words), db = s.upload(b, words);
+    const auto dc = s.download(out, words);
     const DevWords g_tw = c->table(c->f64() ? Table::tw_wave : Table::tw_gl);   // each field has its own twiddle table
-    if (c->ops->negacyclic_mul(da.get(), db.get(), dc.get(), g_tw, count, c->stream)) return fail(c, -2, "negacyclic_mul launch failed");
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(out, dc.get(), words * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return s.run(c, [&] {
+        return c->ops->negacyclic_mul(s[da], s[db], s[dc], g_tw, count, c->stream) ? fail(c, -2, "negacyclic_mul launch failed") : 0;
+    });
 }
 
 // ------------------------------------------------------------------- seeded keys and ciphertexts (chacha_expand.hip)
@@ -1497,7 +1503,7 @@ static int expand_seeded_key(bmi_ctx *c, u64 domain, size_t rows, uint32_t mask_
     HIP_OK(c, hipMemcpyAsync(d_bodies.get(), bodies, rows * body_w * 8, hipMemcpyHostToDevice, c->stream));
     int rc = bmi::launch_place_bodies(d_bodies.get(), d_full.get() + mask_w, pitch, body_w, rows, c->stream);
     if (!rc) rc = bmi::launch_chacha_expand(d_full.get(), pitch, mask_w, rows, c->rng_public.k, domain, 0, c->stream);
-    if (rc) return fail(c, -2, std::string("chacha_expand launch: ") + hipGetErrorString((hipError_t)rc));
+    if (rc) return launched(c, "chacha_expand launch: ", rc);
     full.resize(rows * pitch);
     HIP_OK(c, hipMemcpyAsync(full.data(), d_full.get(), rows * pitch * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -1580,22 +1586,18 @@ int bmi_expand_seeded_batch(bmi_ctx *c, uint64_t first_counter, const uint64_t *
     const size_t pitch = (size_t)c->big_n + 1;
     int rc = bmi::launch_place_bodies(d_bodies, d_out + c->big_n, pitch, 1, count, (hipStream_t)stream);
     if (!rc) rc = bmi::launch_chacha_expand(d_out, pitch, c->big_n, count, c->rng_public.k, S_ENC_MASK, first_counter, (hipStream_t)stream);
-    return rc ? fail(c, -2, std::string("chacha_expand launch: ") + hipGetErrorString((hipError_t)rc)) : 0;
+    return launched(c, "chacha_expand launch: ", rc);
 }
 
 int bmi_expand_seeded_batch_host(bmi_ctx *c, uint64_t first_counter, const uint64_t *bodies, uint32_t count, uint64_t *out) {
     if (!c || (count && (!bodies || !out))) return -1;
     if (int rc = seeded_ok(c, "bmi_expand_seeded_batch_host")) return rc;
     if (count == 0) return 0;
-    HIP_OK(c, hipSetDevice(c->device));
-    if (int rc = ensure_io(c, count)) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->io_b.get(), bodies, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-    if (int rc = bmi_expand_seeded_batch(c, first_counter, c->io_b.get(), count, c->io_a.get(), c->stream)) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->io_a.get(), (size_t)count * (c->big_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_bodies = s.upload(bodies, count);
+    const auto d_out = s.download(out, (size_t)count * (c->big_n + 1));
+    return s.run(c, [&] { return bmi_expand_seeded_batch(c, first_counter, s[d_bodies], count, s[d_out], c->stream); });
 }
-
 
 // ------------------------------------------------------------------- compression of output ciphertexts (lwe_pack.hip)
 // What every compression entry point needs of a context, and of a (levels, base log) pair.  `what` names the caller.
@@ -1737,10 +1739,10 @@ int bmi_compress_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint32_
             const int e = bmit::launch_pack_slice(d_in + (size_t)(t0 + s0) * (N + 1), c->pksk_dev.get(), c->pk_bias.get(), c->pk_digits.get(),
                                                   c->pk_T.get(), c->pk_acc.get(), std::min(slice, m - s0), s0, N, c->pk_levels,
                                                   c->pk_base_log, st);
-            if (e) return fail(c, -2, std::string("lwe_pack launch: ") + hipGetErrorString((hipError_t)e));
+            if (e) return launched(c, "lwe_pack launch: ", e);
         }
         const int e = bmit::launch_pack_switch(c->pk_acc.get(), d_out + (size_t)(t0 / N) * 2 * N, m, N, log_modulus, st);
-        if (e) return fail(c, -2, std::string("lwe_pack switch launch: ") + hipGetErrorString((hipError_t)e));
+        if (e) return launched(c, "lwe_pack switch launch: ", e);
     }
     return 0;
 }
@@ -1750,19 +1752,12 @@ int bmi_compress_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uint
     if (int rc = compression_key_held(c, "bmi_compress_batch_host")) return rc;
     if (int rc = log_modulus_ok(c, "bmi_compress_batch_host", log_modulus)) return rc;
     if (count == 0) return 0;
-    HIP_OK(c, hipSetDevice(c->device));
-    const size_t w = (size_t)(c->N + 1) * 8;
     u64 words = 0;
     (void)bmi_compressed_words(c, count, &words);
-    int rc = grow(c, c->pk_in, count * w, 256 * w);
-    if (!rc) rc = grow(c, c->pk_out, words * 4, (size_t)2 * c->N * 4);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->pk_in.get(), in, count * w, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_compress_batch(c, c->pk_in.get(), count, log_modulus, c->pk_out.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->pk_out.get(), words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_in = s.upload(in, (size_t)count * (c->N + 1));
+    const auto d_out = s.download(out, words);
+    return s.run(c, [&] { return bmi_compress_batch(c, s[d_in], count, log_modulus, s[d_out], c->stream); });
 }
 
 int bmi_phase_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint64_t *phase) {
@@ -1806,9 +1801,7 @@ int bmi_decompress_batch(bmi_ctx *c, const uint32_t *d_in, uint32_t count, uint3
     if (rows == 0) return 0;
     if ((uintptr_t)d_out & 7) return fail(c, -1, "bmi_decompress_batch: d_out is not aligned to 8 bytes");
     HIP_OK(c, hipSetDevice(c->device));
-    const int e = bmit::launch_unpack(d_in, d_index, d_out, count, rows, c->N, log_modulus, (hipStream_t)stream);
-    if (e) return fail(c, -2, std::string("lwe_unpack launch: ") + hipGetErrorString((hipError_t)e));
-    return 0;
+    return launched(c, "lwe_unpack launch: ", bmit::launch_unpack(d_in, d_index, d_out, count, rows, c->N, log_modulus, (hipStream_t)stream));
 }
 
 int bmi_decompress_batch_host(bmi_ctx *c, const uint32_t *in, uint32_t count, uint32_t log_modulus, const uint32_t *index, uint32_t rows,
@@ -1826,19 +1819,13 @@ int bmi_decompress_batch_host(bmi_ctx *c, const uint32_t *in, uint32_t count, ui
     if (log_modulus < 32)
         for (u64 x = 0; x < words; x++)
             if (in[x] >> log_modulus) return fail(c, -1, "bmi_decompress_batch_host: a value does not fit log_modulus bits");
-    HIP_OK(c, hipSetDevice(c->device));
-    const size_t w = (size_t)(c->N + 1) * 8;
-    int rc = grow(c, c->pk_out, words * 4, (size_t)2 * c->N * 4);
-    if (!rc) rc = grow(c, c->pk_in, rows * w, 256 * w);
-    if (!rc && index) rc = grow(c, c->io_ids, (size_t)rows * 4, 256 * sizeof(uint32_t));
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->pk_out.get(), in, words * 4, hipMemcpyHostToDevice, c->stream));
-    if (index) HIP_OK(c, hipMemcpyAsync(c->io_ids.get(), index, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
-    rc = bmi_decompress_batch(c, c->pk_out.get(), count, log_modulus, index ? c->io_ids.get() : nullptr, rows, c->pk_in.get(), c->stream);
-    if (rc) return rc;
-    HIP_OK(c, hipMemcpyAsync(out, c->pk_in.get(), rows * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    Stage s;
+    const auto d_in = s.upload(in, words);
+    const auto d_index = s.upload(index, index ? rows : 0);
+    const auto d_out = s.download(out, (size_t)rows * (c->N + 1));
+    return s.run(c, [&] {
+        return bmi_decompress_batch(c, s[d_in], count, log_modulus, index ? s[d_index] : nullptr, rows, s[d_out], c->stream);
+    });
 }
 
 }  // extern "C"

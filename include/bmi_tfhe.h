@@ -245,8 +245,11 @@ int bmi_scatter_rows(bmi_ctx *ctx, const uint64_t *d_src, uint32_t count, uint64
 int bmi_phase_batch(bmi_ctx *ctx, const uint64_t *d_ct, uint32_t count, uint64_t *d_phase, void *stream);
 int bmi_decrypt_batch(bmi_ctx *ctx, const uint64_t *d_ct, uint32_t count, uint32_t delta_log, const int64_t *d_expected,
                       int64_t *d_msgs, int64_t *d_err, void *stream);
-/* Host-buffer convenience forms (what a ctypes/cgo binding over numpy buffers would call):
- * copy in, run on the context's own stream, copy out, synchronise. */
+/* Host-buffer convenience forms (what a ctypes/cgo binding over numpy buffers would call; every entry point named *_host, here
+ * and below): copy in, run the device-pointer form on the context's own stream, copy out, synchronise.  They share ONE SCRATCH
+ * ARENA OWNED BY THE CONTEXT, which grows to the largest call made so far and is never shrunk.  Argument and state refusals are
+ * made before anything is queued; a call that is refused or fails later RETURNS ONLY AFTER THE CONTEXT'S STREAM HAS DRAINED, like a
+ * call that succeeds: the caller's arrays may be freed or reused as soon as a host form has returned, whatever it returned. */
 int bmi_pbs_batch_host(bmi_ctx *ctx, const uint64_t *in, const uint32_t *lut_ids, uint32_t count, uint64_t *out);
 int bmi_keyswitch_batch_host(bmi_ctx *ctx, const uint64_t *in, uint32_t count, uint64_t *small_out);
 int bmi_blind_rotate_batch_host(bmi_ctx *ctx, const uint64_t *small_in, const uint32_t *lut_ids, uint32_t count,

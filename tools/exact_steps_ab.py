@@ -6,8 +6,11 @@ serve) `rounds` rounds in which the three rotate through the positions of a roun
 one warm call, then the mean of five blind rotations between two events.  Per kernel and batch the margin is
 |median(P1) - median(P2)| - what the procedure cannot resolve, measured in the same call - and the branch passes if
 median(B) <= max(median(P1), median(P2)) + margin.  The three engines' outputs are compared word for word as well.
-usage: exact_steps_ab.py <parent .so> <copy of the parent .so> <branch .so> [rounds = 3] [kernel labels, comma separated]"""
-import os, statistics, sys
+With the label host_forms the rule times the host-buffer forms instead (record: profiles/host_forms_ab.txt): on the default torus
+set pbs_host at 5 and 600 ciphertexts, keyswitch_host at 600, compress_host and decompress_host at 1,024; a sample is one warm call,
+then the mean of five calls on the host's clock (each form ends in a stream synchronise).
+usage: exact_steps_ab.py <parent .so> <copy of the parent .so> <branch .so> [rounds = 3] [kernel labels, comma separated | host_forms]"""
+import os, statistics, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "bounty-matrix-inversion_amd"))
 import numpy as np, torch
@@ -39,10 +42,58 @@ def engine_on(lib_path, params, precision, unroll, variant):
     return eng
 
 
+def verdict(ms, unit):
+    """(the medians, margin and verdict of one case as text, whether the branch passes)"""
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    margin = abs(med["P1"] - med["P2"])
+    passes = med["B"] <= max(med["P1"], med["P2"]) + margin
+    return (f"medians {med['P1']:.4f} {med['P2']:.4f} {med['B']:.4f} {unit}  margin {margin:.4f}  {'passes' if passes else 'MISSES'}", passes)
+
+
+def host_forms(libs, rounds):
+    """the host-buffer forms on the default torus set; returns the number of cases outside the margin"""
+    engs = {k: engine_on(p, lambda: tfhe.default_params(q_bits=tfhe.TORUS64), None, 1, 0) for k, p in libs.items()}
+    e0 = engs["P1"]
+    DL = e0.delta_log()
+    table = np.random.default_rng(9).integers(-8, 8, 16)
+    lids = {k: e.lut_register(table, 4, DL) for k, e in engs.items()}
+    for e in engs.values():
+        e.compression_keygen()
+    ct = {B: e0.encrypt(np.random.default_rng(B).integers(-8, 8, B), DL) for B in (5, 600, 1024)}
+    cc = e0.compress_host(ct[1024])
+    words = lambda r: r.words if hasattr(r, "words") else r
+    cases = [("pbs_host", 5, lambda k: engs[k].pbs_host(ct[5], np.full(5, lids[k], np.uint32))),
+             ("pbs_host", 600, lambda k: engs[k].pbs_host(ct[600], np.full(600, lids[k], np.uint32))),
+             ("keyswitch_host", 600, lambda k: engs[k].keyswitch_host(ct[600])),
+             ("compress_host", 1024, lambda k: engs[k].compress_host(ct[1024])),
+             ("decompress_host", 1024, lambda k: engs[k].decompress_host(cc))]
+    misses = 0
+    for name, B, call in cases:
+        ms, outs = {k: [] for k in engs}, {}
+        for r in range(rounds):
+            order = list(engs)[r % 3:] + list(engs)[:r % 3]
+            for k in order:
+                outs[k] = words(call(k))
+                t0 = time.perf_counter()
+                for _ in range(5): call(k)
+                ms[k].append((time.perf_counter() - t0) * 1e3 / 5)
+        same = np.array_equal(outs["P1"], outs["B"]) and np.array_equal(outs["P1"], outs["P2"])
+        text, passes = verdict(ms, "ms")
+        misses += not passes
+        print(f"{name:15} B = {B:4d}  " + "  ".join(f"{k} " + " ".join(f"{x:.3f}" for x in ms[k]) for k in ms) +
+              f"  | {text}  same words {same}", flush=True)
+    for e in engs.values():
+        e.close()
+    return misses
+
+
 def main():
     libs = dict(zip(("P1", "P2", "B"), (os.path.abspath(p) for p in sys.argv[1:4])))
     rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 3
     labels = sys.argv[5].split(",") if len(sys.argv) > 5 else list(CONFIGS)
+    if labels == ["host_forms"]:
+        print(f"{host_forms(libs, rounds)} (form, batch) outside the margin")
+        return
     dev = torch.device("cuda:0")
     s = torch.cuda.current_stream().cuda_stream
     misses = 0
@@ -75,13 +126,10 @@ def main():
                     ms[k].append(t0.elapsed_time(t1) / 5)
             same = np.array_equal(outs["P1"], outs["B"]) and np.array_equal(outs["P1"], outs["P2"])
             ok = list(e0.decrypt(outs["B"], DL)) == [int(table[m + 8]) for m in msgs]
-            med = {k: statistics.median(v) for k, v in ms.items()}
-            margin = abs(med["P1"] - med["P2"])
-            passes = med["B"] <= max(med["P1"], med["P2"]) + margin
+            text, passes = verdict(ms, "ms")
             misses += not passes
             print(f"{label:10} B = {B:3d}  " + "  ".join(f"{k} " + " ".join(f"{x:.3f}" for x in ms[k]) for k in ms) +
-                  f"  | medians {med['P1']:.4f} {med['P2']:.4f} {med['B']:.4f}  margin {margin:.4f}  {'passes' if passes else 'MISSES'}"
-                  f"  same words {same}  decrypts_to_lut {ok}", flush=True)
+                  f"  | {text}  same words {same}  decrypts_to_lut {ok}", flush=True)
         for e in engs.values():
             e.close()
     print(f"{misses} (kernel, batch) outside the margin")
