@@ -26,7 +26,7 @@ class EncryptedMatrixInversion:
 
     def __init__(self, n, sampler=None, qfloat_base=2, qfloat_len=32, qfloat_ints=16, true_division=False,
                  tensorize=False, engine=None, device=0, shard_threshold=None, cache=True, unroll=False, q_bits=None,
-                 params=None, p_error=None, share_rotations=False, centred_modswitch=False, compress_outputs=False):
+                 params=None, p_error=None, share_rotations=False, centred_modswitch=False, compress_outputs=False, client=False):
         """The reference's seven arguments (main.py:17-36), then: engine / device (the GPU context to use) and
         shard_threshold (with torch.distributed initialised on several ranks, levels at least this wide are split
         across the ranks' GPUs; None = every level wider than one kernel round, levels re-packed for the rank count,
@@ -53,7 +53,12 @@ class EncryptedMatrixInversion:
         log_modulus in [2, 32]): keygen also makes the compression key (levels 1, base 2^16), evaluate / evaluate_many return
         tfhe.CompressedCiphertexts - the outputs packed into GLWE ciphertexts and cut to log_modulus bits per word, about 4 bytes
         per output instead of (N + 1) * 8 - and decrypt takes either form; the error budget and the p_error selection add
-        error_budget.compression_variance to every output.  Under torch.distributed: NotImplementedError."""
+        error_budget.compression_variance to every output.  Under torch.distributed: NotImplementedError; client=True: the
+        client's role on a machine without a GPU - this object creates a client.ClientEngine (libbmi_client.so) with the parameter
+        choice above (params, q_bits, p_error, unroll, centred_modswitch - recorded for the error budget, the server switches -,
+        compress_outputs) and the same error budget; keygen, save_keys (the seeded evaluation keys a server loads), quantize,
+        encrypt, decrypt, dequantize, simulate and failure_budget work; evaluate, evaluate_many, run(simulate=False) and run_many
+        raise: they are a server-side object's, built with engine= a tfhe.Engine after Engine.load_keys of the client's file."""
         self.shape = (n, n)
         self.qfloat_base, self.qfloat_len, self.qfloat_ints = qfloat_base, qfloat_len, qfloat_ints
         self.true_division, self.tensorize = true_division, tensorize
@@ -92,12 +97,21 @@ class EncryptedMatrixInversion:
         if self.unroll and engine is not None and getattr(engine, "unroll", 1) != 2:
             raise ValueError("unroll=True with an engine that is not in unrolled mode: call engine.set_bsk_unroll(2) before its "
                              "keygen, or let this object create the engine")
+        self.client = bool(client)
+        if self.client and engine is not None:
+            raise ValueError("client=True creates its own ClientEngine: pass client=True or an engine, not both")
         self._exec = None
+
+    def _server_only(self, what):
+        if self.client:
+            raise RuntimeError(f"{what} needs a GPU: this object was built with client=True (keys, encryption and decryption on "
+                               "the host).  Evaluate on a server-side EncryptedMatrixInversion built with engine= a tfhe.Engine "
+                               "after Engine.load_keys of the file this client's save_keys wrote")
 
     # ---- key generation / engine -------------------------------------------------------------------
     def _engine(self):
         if self.engine is None:
-            from . import tfhe  # raises BmiError when libbmi_tfhe.so or the GPU is missing: no CPU fallback
+            from . import tfhe  # tfhe.Engine raises BmiError when libbmi_tfhe.so or the GPU is missing: no CPU fallback (client=True: client.py)
             # 4-bit look-ups: the north-star set (N = 1024); 5-bit ones (bases other than 2): N = 2048, same margin
             qb = self.q_bits
             if self.params is not None:    # a named set of the library, or a tfhe.Params
@@ -126,7 +140,11 @@ class EncryptedMatrixInversion:
                     params = tfhe.default_params(q_bits=49, glwe_noise=2.0 ** -41)
                 elif params.q_bits != tfhe.TORUS64:
                     raise ValueError("bootstrap-key unrolling exists on the 49-bit field and on the 2^64 torus")
-            self.engine = tfhe.Engine(params, device=self.device)
+            if self.client:
+                from .client import ClientEngine
+                self.engine = ClientEngine(params)
+            else:
+                self.engine = tfhe.Engine(params, device=self.device)
             if self.unroll:
                 self.engine.set_bsk_unroll(2)
         if self.centred_modswitch and self.engine.modswitch != 1:
@@ -170,6 +188,11 @@ class EncryptedMatrixInversion:
             if self.compress_log_modulus:
                 eng.compression_keygen(*self.COMPRESSION_SHAPE)
 
+    def save_keys(self, path):
+        """the evaluation keys a server needs, in seeded form (Engine.save_keys(path, secret=False, seeded=True): 0.3 of the full
+        file), with the compression key when compress_outputs is set; CSPRNG keys on the 2^64 torus (keygen() without a seed)"""
+        self._engine().save_keys(path, secret=False, seeded=True)
+
     def failure_budget(self, input_variance=None):
         """this instance's error budget (error_budget.engine_failure_probability under its engine, rotation sharing and output
         compression) for inputs of the given variance in torus^2 - a scalar or one value per input; None: fresh encryptions, the
@@ -180,6 +203,7 @@ class EncryptedMatrixInversion:
 
     def _executor(self, batch=1):
         """the executor of this circuit for `batch` input matrices per run (one per batch size, built on first use)"""
+        self._server_only("evaluation")
         if self._exec is None:
             self._exec = {}
         if batch not in self._exec:
@@ -216,6 +240,7 @@ class EncryptedMatrixInversion:
     def _expanded(self, enc):
         """an input of evaluate: seeded ciphertexts are expanded on the GPU, full ones pass as they are"""
         from .tfhe import SeededCiphertexts
+        self._server_only("evaluation")
         return self._engine().expand_seeded(enc) if isinstance(enc, SeededCiphertexts) else enc
 
     def evaluate(self, encrypted_quantized_matrix) -> np.ndarray:
@@ -223,6 +248,7 @@ class EncryptedMatrixInversion:
         is what encrypt() returned (full or seeded), or a tfhe.CompressedCiphertexts of the circuit's inputs in order
         (Engine.compress_host of them, or an earlier circuit's compressed result): its values alone go to the GPU, which
         decompresses them into the executor's input rows.  Such inputs are no fresh encryptions: failure_budget() prices them."""
+        self._server_only("evaluate")
         if self.compress_log_modulus:
             return self._executor().run_compressed(self._expanded(encrypted_quantized_matrix), self.compress_log_modulus)
         return self._executor().run(self._expanded(encrypted_quantized_matrix))
@@ -234,6 +260,7 @@ class EncryptedMatrixInversion:
         compress_outputs: a list of B tfhe.CompressedCiphertexts, every matrix in blocks of its own.  B tfhe.CompressedCiphertexts
         (a list or tuple of them) are decompressed on the GPU as in evaluate(); mixed with other forms they are refused."""
         from .tfhe import CompressedCiphertexts
+        self._server_only("evaluate_many")
         seq = encrypted_quantized_matrices
         if isinstance(seq, (list, tuple)) and any(isinstance(e, CompressedCiphertexts) for e in seq):
             if not all(isinstance(e, CompressedCiphertexts) for e in seq):
@@ -255,6 +282,7 @@ class EncryptedMatrixInversion:
     def run_many(self, matrices, validate=True):
         """run() for a batch of matrices on one GPU: quantize, encrypt, ONE batched encrypted evaluation (evaluate_many), decrypt,
         dequantize - the same inverses as run() matrix by matrix"""
+        self._server_only("run_many")
         if self._dist() is not None:
             raise NotImplementedError("run_many is the one-GPU serving form; under torch.distributed call run() per matrix")
         qs = []
@@ -321,6 +349,7 @@ class EncryptedMatrixInversion:
         assert matrix.shape == self.shape
         quantized_matrix, qfloats_signs = self.quantize(matrix)
         if not simulate:
+            self._server_only("run(simulate=False)")
             if validate:
                 self.simulate(quantized_matrix, qfloats_signs)
             dist = self._dist()

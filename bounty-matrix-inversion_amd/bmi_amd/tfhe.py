@@ -209,7 +209,7 @@ def circuit_prune(n_in, node_ptr, term_leaf, out_leaf):
     term_leaf = np.ascontiguousarray(term_leaf, np.int32)
     out_leaf = np.ascontiguousarray(out_leaf, np.int32)
     live = np.zeros(max(node_ptr.size - 1, 0), np.uint8)
-    rc = load_library().bmi_circuit_prune(int(n_in), live.size, _ptr(node_ptr), _ptr(term_leaf), _ptr(out_leaf),
+    rc = _host_library().bmi_circuit_prune(int(n_in), live.size, _ptr(node_ptr), _ptr(term_leaf), _ptr(out_leaf),
                                           out_leaf.size, _ptr(live))
     if rc != 0:
         raise BmiError(f"bmi_circuit_prune failed ({rc}): malformed circuit arrays")
@@ -222,7 +222,7 @@ def circuit_schedule(n_in, node_ptr, term_leaf, round_, wide_round):
     term_leaf = np.ascontiguousarray(term_leaf, np.int32)
     level = np.zeros(max(node_ptr.size - 1, 0), np.int32)
     depth = C.c_int32(0)
-    rc = load_library().bmi_circuit_schedule(int(n_in), level.size, _ptr(node_ptr), _ptr(term_leaf), int(round_),
+    rc = _host_library().bmi_circuit_schedule(int(n_in), level.size, _ptr(node_ptr), _ptr(term_leaf), int(round_),
                                              int(wide_round), _ptr(level), C.byref(depth))
     if rc != 0:
         raise BmiError(f"bmi_circuit_schedule failed ({rc}): malformed circuit arrays")
@@ -288,10 +288,23 @@ def load_library():
     return _lib
 
 
+def _host_library():
+    """the library behind the context-free host functions that both libraries export (the circuit passes, the parameter tables):
+    libbmi_tfhe.so where it loads, else libbmi_client.so (client.py), which needs neither ROCm nor a GPU"""
+    try:
+        return load_library()
+    except BmiError:
+        from . import client
+        return client.load_client_library()
+
+
 def default_params(q_bits=None, **kw):
     """North-star parameter set; q_bits = 64 (Goldilocks) or 49 (f64 kernels), None = the library's default."""
+    return _default_params(_host_library(), q_bits, kw)
+
+
+def _default_params(lib, q_bits, kw):
     P = Params()
-    lib = load_library()
     rc = lib.bmi_default_params(C.byref(P)) if q_bits is None else lib.bmi_default_params_for(int(q_bits), C.byref(P))
     if rc != 0:
         raise BmiError("unsupported q_bits (64, 49 or TORUS64 = 65)")
@@ -304,8 +317,12 @@ def preset_params(name, **kw):
     """named parameter set of the library: "north_star", "north_star_torus64", "north_star_goldilocks", "secure128"
     (n 742, N 2048: the 128-bit-secure set on the 49-bit field) and "secure128_torus" (the same on q = 2^64, Concrete's
     modulus, l = 3 x 10 bits); include/bmi_tfhe.h"""
+    return _preset_params(_host_library(), name, kw)
+
+
+def _preset_params(lib, name, kw):
     P = Params()
-    if load_library().bmi_preset_params(name.encode(), C.byref(P)) != 0:
+    if lib.bmi_preset_params(name.encode(), C.byref(P)) != 0:
         raise BmiError(f"unknown parameter preset {name!r}")
     for k, v in kw.items():
         setattr(P, k, v)

@@ -13,6 +13,7 @@
 
 #include "../../include/bmi_tfhe.h"
 #include "host_crypto.hpp"
+#include "key_set.hpp"
 #include "bmi_internal.hpp"
 #include "field49.hpp"
 #include "ntt_wave.hpp"
@@ -26,14 +27,14 @@
 
 using gl::i64;
 using gl::u64;
-// The library's cryptography - generators, key rows, encryption, phase, decoding - is host_crypto.hpp; this file holds the context,
-// checks arguments and state, and does the device work.
+// The library's cryptography - generators, key rows, encryption, phase, decoding - is host_crypto.hpp, and the key set with the host
+// half of the entry points (which libbmi_client.so exports too) key_set.hpp; this file holds the context, the order of its refusals,
+// and does the device work.
 using namespace hc;
 static_assert(GOLDILOCKS_P == gl::P && FIELD49_Q == f49::Q, "host_crypto.hpp states the moduli of goldilocks.hpp and field49.hpp");
+static_assert(MAX_LWE_N == BMI_MAX_LWE_N, "key_set.hpp states the largest n of bmi_internal.hpp");
 
 namespace {
-
-thread_local std::string g_create_error;
 
 // One device allocation, owned: freed when the buffer is destroyed, reset or assigned over.  Move-only.
 template <class T>
@@ -75,29 +76,13 @@ using rotplan::Table;
 
 }  // namespace
 
-struct bmi_ctx {
-    bmi_params P{};
-    Fq f;
+// The key set (key_set.hpp: parameters, keys, generators, the flags that decide a word) and the device that evaluates under it
+struct bmi_ctx : hc::KeySet {
     const FieldOps *ops = nullptr;
     int device = 0;
-    uint32_t N = 0, big_n = 0, rows = 0, ks_stride = 0;
+    uint32_t ks_stride = 0;
     hipStream_t stream = nullptr;  // the context's own stream (host-buffer entry points)
-    bool have_keys = false;
-    bool have_secret = false;  // false for a context that imported evaluation keys only (no encrypt / decrypt)
-    u64 seed = 0, enc_counter = 0;
-    int bsk_prec = 64;   // torus: bits of precision the bootstrap key is stored at (64 = exact, 48, 46, 44, 42, 40: t64_common.hpp; bmi_set_bsk_precision)
-    bool bsk_prec_explicit = false;   // set by bmi_set_bsk_precision: bmi_set_bsk_unroll then leaves the precision alone
     int bsk_limbs() const { return t64::limbs_of(bsk_prec); }
-    bool secure_rng = false;       // true: keys / encryptions drawn from the CSPRNG below; false: test-only seeded streams
-    ChaKey rng_secret, rng_public; // independent ChaCha20 keys from getrandom(): secrets + noise / public masks
-    Sampler sampler(u64 of_seed) const { return {of_seed, f, secure_rng, rng_secret, rng_public}; }   // what the generators draw from
-    // Where the mask words of the evaluation keys held came from (beside have_keys; the seeded forms of chacha_expand.hip):
-    // OWN_STREAM = drawn by this context from rng_public (CSPRNG key generation), SEEDED_IMPORT = expanded from the public key of
-    // bmi_import_keys_seeded, which rng_public then holds; OTHER = anything else (bmi_import_keys, the deterministic test streams):
-    // such masks are no function of a public key that may be told.
-    enum class MaskSource { OTHER, OWN_STREAM, SEEDED_IMPORT } mask_src = MaskSource::OTHER;
-    bool bsk3_from_stream = false; // ... and the same for the unrolled key held: its masks are words of rng_public's S_BSK3_MASK streams
-    std::vector<u64> sk_small, sk_big, bsk_std, ksk;
     // Tables (bmi_ctx_create), one per rotplan::Table, where the kernels that read each are listed; empty where the context's
     // modulus and N have no such kernel (rotplan::context_tables).
     DevBuf<void> tables[(int)Table::COUNT];
@@ -111,25 +96,13 @@ struct bmi_ctx {
         for (int k = 0; k < (int)Copy::COUNT; k++)
             if (rotplan::row((Copy)k).unrolled == unrolled) copies[k].reset();
     }
-    // bootstrap-key unrolling (49-bit field at N = 1024 / 2048, 2^64 torus; bmi_set_bsk_unroll): per pair of LWE coefficients the GGSW encryptions of
-    // s s', s (1 - s'), (1 - s) s'; host copy in the standard domain, device copy in the layout of the context's unrolled kernel (upload_bsk3)
-    uint32_t unroll = 1;
-    std::vector<u64> bsk3_std;
-    bool have_bsk3 = false;
-    uint32_t pairs() const { return (P.n + 1) / 2; }
-    size_t bsk3_words() const { return (size_t)pairs() * 3 * rows * (P.k + 1) * N; }
+    // (the unrolled key: its device copy in the layout of the context's unrolled kernel, upload_bsk3)
     bool wide() const { return N == 2048; }
     bool quad() const { return N == 4096; }
     DevBuf<u64> ksk_padded, ks_bias;   // keyswitch key, rows padded to ks_stride words, and its bias vector - keyswitch
     DevBuf<signed char> ks_limbs;      // the keyswitch key as ops->ks_limbs limbs in MFMA operand order - keyswitch_mfma
-    // compression of output ciphertexts (2^64 torus; lwe_pack.hip): the packing keyswitch key [N][pk_levels][2][N] of the key set held
-    // (pk_levels == 0: none; dropped with the key set), its device copy in the same layout, and the product's bias vector [2N]
-    uint32_t pk_levels = 0, pk_base_log = 0;
-    // the (levels, base log) bmi_compression_keygen first used on the key set held (0: not yet): a row's masks and noise are the streams
-    // (key, domain, row number) read from their start, so a second key of ANOTHER shape would reuse them under other messages - refused
-    uint32_t pk_gen_levels = 0, pk_gen_base_log = 0;
-    bool pksk_from_stream = false;     // its masks are words of rng_public's S_PKSK_MASK streams (as bsk3_from_stream)
-    std::vector<u64> pksk;
+    // compression of output ciphertexts (2^64 torus; lwe_pack.hip): the device copy of the packing keyswitch key, in the host copy's
+    // layout, and the product's bias vector [2N]
     DevBuf<u64> pksk_dev, pk_bias;
     DevBuf<u64> sk_mask;               // the big SECRET key as big_n / 64 words of bits, built on first use (ensure_sk_mask), zeroed and
                                        // dropped with the key set (drop_sk_mask) - lwe_phase
@@ -160,25 +133,12 @@ struct bmi_ctx {
     uint32_t modswitch = 0;   // 0 = the rotation kernels' own rounding, 1 = centred (bmi_set_modswitch): bmi_pbs_batch / _shared_batch run
                               // k_modswitch_centre on the scratch small ciphertexts between the keyswitch and the rotation
     bool ks_mfma_ok = false;
-    mutable std::string err;
-    bool f64() const { return f.bits == 49; }
-    bool t64() const { return f.torus; }
 };
 
 namespace {
 
-int fail(const bmi_ctx *c, int code, const std::string &msg) {
-    if (c) c->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-
 // A context as rotation_plan.hpp takes it: its shape, its settings and what it holds.  Which kernel runs, which key copies get
 // built and what the setters accept is decided there, from these three; the entry points below act on the answers.
-rotplan::Shape shape_of(const bmi_params &P) {
-    return {P.q_bits == BMI_Q_TORUS64 ? rotplan::Modulus::torus64 : P.q_bits == 49 ? rotplan::Modulus::field49 : rotplan::Modulus::goldilocks,
-            P.log_N, P.bs_levels, P.bs_base_log};
-}
 rotplan::Settings settings_of(const bmi_ctx *c) { return {c->bsk_prec, c->bsk_prec_explicit, c->unroll, c->variant, c->lat_threshold}; }
 // (the one place where a buffer's presence is read as a fact about the context)
 rotplan::Held held_of(const bmi_ctx *c) {
@@ -300,12 +260,8 @@ void drop_sk_mask(bmi_ctx *c) {
 // a compression key belongs to the key set it was made for: gone with it (queued kernels may still read it)
 // new_key_set: the streams are new as well (or will never be read again): the shape bmi_compression_keygen is held to is forgotten
 void drop_compression_key(bmi_ctx *c, bool new_key_set) {
-    if (new_key_set) c->pk_gen_levels = c->pk_gen_base_log = 0;
     if (!c->pksk_dev.empty()) (void)hipDeviceSynchronize();
-    c->pk_levels = c->pk_base_log = 0;
-    c->pksk_from_stream = false;
-    c->pksk.clear();
-    c->pksk.shrink_to_fit();
+    forget_compression_key(c, new_key_set);
     c->pksk_dev.reset();
     c->pk_bias.reset();
 }
@@ -395,52 +351,6 @@ std::vector<u64> build_twiddles_quad(const Fq &f) {
     return tw;
 }
 
-// (ring size and bootstrap decomposition: the plan's lists; a q_bits not refused yet counts as Goldilocks there, as before)
-bool params_supported(const bmi_params &P, std::string &why) {
-    const rotplan::Shape shape = shape_of(P);
-    if (!(why = rotplan::ring_refusal(shape)).empty()) return false;
-    if (P.k != 1) { why = "only k = 1 has a HIP kernel in this build"; return false; }
-    if (!(why = rotplan::decomposition_refusal(shape)).empty()) return false;
-    if (P.n == 0 || P.n > BMI_MAX_LWE_N) { why = "n must be in [1, 1024]"; return false; }
-    if (P.q_bits != 0 && P.q_bits != 64 && P.q_bits != 49 && P.q_bits != BMI_Q_TORUS64) {
-        why = "q_bits must be 64 (2^64-2^32+1), 49 (2^49-720895) or BMI_Q_TORUS64 (2^64)";
-        return false;
-    }
-    const uint32_t qb = P.q_bits == 49 ? 49 : 64;
-    if (P.ks_levels * P.ks_base_log >= qb || P.ks_base_log > 7 || P.ks_levels == 0) { why = "unsupported keyswitch decomposition"; return false; }
-    return true;
-}
-
-// fresh CSPRNG keys for this context (secret-class and public-class streams, never shared between them)
-int rekey_csprng(bmi_ctx *c) {
-    if (!c->rng_secret.fill_from_os() || !c->rng_public.fill_from_os())
-        return fail(c, -2, "getrandom() failed: no entropy source for key generation");
-    c->secure_rng = true;
-    c->enc_counter = 0;   // a new key: the (key, nonce) pairs of the new streams have never been used
-    return 0;
-}
-int gen_secret_keys(bmi_ctx *c, uint64_t seed) {
-    c->sk_small.assign(c->P.n, 0);
-    c->sk_big.assign(c->big_n, 0);
-    secret_key_bits(c->sampler(seed), S_SK_SMALL, c->P.n, c->sk_small.data());
-    secret_key_bits(c->sampler(seed), S_SK_BIG, c->big_n, c->sk_big.data());
-    return 0;
-}
-
-// GGSW encryptions of the bits msg under the context's GLWE key, drawn from the streams (mask_stream, noise_stream) of `seed`
-void gen_ggsw_rows(bmi_ctx *c, uint64_t seed, u64 mask_stream, u64 noise_stream, const std::vector<u64> &msg, u64 *out) {
-    const bmi_params &P = c->P;
-    ggsw_rows(c->sampler(seed), mask_stream, noise_stream, c->sk_big.data(), c->N, P.k, P.bs_levels, P.bs_base_log, P.glwe_noise, msg.data(),
-              msg.size(), out);
-}
-
-// the unrolled bootstrap key of the secret keys held (host copy only; upload_bsk3 sends it to the device)
-void gen_bsk3(bmi_ctx *c, uint64_t seed) {
-    c->bsk3_std.assign(c->bsk3_words(), 0);
-    gen_ggsw_rows(c, seed, S_BSK3_MASK, S_BSK3_NOISE, unrolled_messages(c->sk_small.data(), c->P.n), c->bsk3_std.data());
-    c->bsk3_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
-}
-
 // Builds a device buffer of `bytes` bytes: fresh (launch(buffer) fills it on the context's stream), and moved into dst only once
 // the launch and the stream synchronisation have succeeded, so that a buffer that is not empty is whole.
 template <class T, class Launch>
@@ -512,12 +422,7 @@ int build_copies(bmi_ctx *c, uint32_t kinds, const std::vector<u64> &std_key) {
 int upload_eval_keys(bmi_ctx *c) {
     const bmi_params &P = c->P;
     const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels;
-    if (c->t64() && c->bsk_prec != 64) {
-        // key stored at 48 / 42 bits of precision: every word rounded (half up, as a signed integer) to a multiple of 2^16 / 2^22.
-        // The rounded key IS the key from here on (bmi_export_keys returns it), so every consumer agrees on it.
-        for (u64 &w : c->bsk_std) w = t64::round_key_word(w, c->bsk_prec);
-    }
-    c->have_keys = false;
+    round_eval_keys(c);   // (the key at the context's precision IS the key from here on)
     c->drop_copies(false);   // the copies of the previous key set
     c->drop_copies(true);
     if (int rc = build_copies(c, rotplan::plain_copies(shape_of(P), c->bsk_prec), c->bsk_std)) return rc;
@@ -551,12 +456,7 @@ int upload_eval_keys(bmi_ctx *c) {
 // unrolled bootstrap key (host copy in c->bsk3_std) -> device, in the layout of the context's unrolled kernel (rotplan::unrolled_copies)
 int upload_bsk3(bmi_ctx *c) {
     HIP_OK(c, hipSetDevice(c->device));
-    const size_t words = c->bsk3_words();
-    if (c->bsk3_std.size() != words) return fail(c, -1, "no unrolled bootstrap key to upload");
-    // torus: the key stored at bsk_prec bits IS the key from here on (what bmi_export_bsk_unrolled returns)
-    if (c->t64() && c->bsk_prec != 64)
-        for (u64 &w : c->bsk3_std) w = t64::round_key_word(w, c->bsk_prec);
-    c->have_bsk3 = false;
+    if (int rc = round_bsk3(c)) return rc;
     c->drop_copies(true);
     if (int rc = build_copies(c, rotplan::unrolled_copies(shape_of(c->P), c->bsk_prec), c->bsk3_std)) return rc;
     c->have_bsk3 = true;
@@ -568,23 +468,7 @@ int gen_eval_keys(bmi_ctx *c, uint64_t seed) {
     HIP_OK(c, hipSetDevice(c->device));
     drop_sk_mask(c);
     drop_compression_key(c, true);
-    const bmi_params &P = c->P;
-    const uint32_t n = P.n, N = c->N, k = P.k, lk = P.ks_levels, rows = c->rows;
-    c->seed = seed;
-    if (!c->secure_rng) c->enc_counter = 0;   // deterministic test keys: encryption i of a key set is reproducible
-    // --- bootstrap key: GGSW(s_i) rows, standard domain
-    c->bsk_std.assign((size_t)n * rows * (k + 1) * N, 0);
-    // (A torus key at 42 bits of precision is ROUNDED from this full-precision key at upload.  Drawing the masks on the
-    // 2^22 grid instead would keep the rounding error away from the secret key - measured: output noise 2^-20 - but the
-    // body's noise, std 2^20, is then rounded to the grid too and vanishes in 95 % of the words: not an LWE sample any more.)
-    gen_ggsw_rows(c, seed, S_BSK_MASK, S_BSK_NOISE, c->sk_small, c->bsk_std.data());
-    c->have_bsk3 = false;
-    c->mask_src = c->secure_rng ? bmi_ctx::MaskSource::OWN_STREAM : bmi_ctx::MaskSource::OTHER;
-    if (c->unroll == 2) gen_bsk3(c, seed);
-    // --- keyswitch key
-    c->ksk.assign((size_t)k * N * lk * (n + 1), 0);
-    ksk_rows(c->sampler(seed), c->sk_small.data(), n, c->sk_big.data(), c->big_n, lk, P.ks_base_log, P.lwe_noise, c->ksk.data());
-    c->have_secret = true;
+    gen_eval_key_words(c, seed);
     if (int rc = upload_eval_keys(c)) return rc;
     return c->unroll == 2 ? upload_bsk3(c) : 0;
 }
@@ -687,52 +571,11 @@ int check_lut_ids(bmi_ctx *c, const uint32_t *lut_ids, uint32_t count) {
 
 extern "C" {
 
-int bmi_default_params_for(uint32_t q_bits, bmi_params *out) {
-    if (!out || (q_bits != 64 && q_bits != 49 && q_bits != BMI_Q_TORUS64)) return -1;
-    // same shape for every modulus; the 49-bit modulus keeps the absolute bootstrap-key noise above the integer grid
-    // the torus set decomposes in base 2^10: the limb sums of its exact products then leave room for a two-limb key (48 bits of
-    // precision) in the plain AND the unrolled blind rotation, and the output noise is lower than at 2^15 (t64_common.hpp)
-    *out = bmi_params{630, 10, 1, 3, q_bits == BMI_Q_TORUS64 ? 10u : 15u, 8, 4, q_bits, std::ldexp(1.0, -25),
-                      std::ldexp(1.0, q_bits == 49 ? -40 : -44)};
-    return 0;
-}
+int bmi_default_params_for(uint32_t q_bits, bmi_params *out) { return default_params_for(q_bits, out); }
 
-int bmi_default_params(bmi_params *out) { return bmi_default_params_for(BMI_DEFAULT_Q_BITS, out); }
+int bmi_default_params(bmi_params *out) { return default_params(out); }
 
-int bmi_preset_params(const char *name, bmi_params *out) {
-    if (!name || !out) return -1;
-    const std::string s(name);
-    if (s == "north_star") return bmi_default_params_for(49, out);
-    if (s == "north_star_torus64") return bmi_default_params_for(BMI_Q_TORUS64, out);
-    if (s == "north_star_goldilocks") return bmi_default_params_for(64, out);
-    if (s == "secure128") {
-        // n = 742 with LWE noise 7.07e-6 (2^-17.11) and a GLWE of size k N = 2048: the two security-relevant pairs of
-        // TFHE-rs' published 128-bit set PARAM_MESSAGE_2_CARRY_2_KS_PBS (see bmi_tfhe.h); the GLWE noise is kept at
-        // 2^-44 >= that set's 2.94e-16, so the GLWE side is at least as hard.  Decompositions are this build's: bootstrap 2 x 15
-        // bits (output noise 2^-19.5: the circuits' linear combinations amplify it up to 75x), keyswitch 8 x 2 bits (its noise,
-        // set by the LWE noise that security dictates, is what bounds the look-up margin: finer digits = less of it).
-        *out = bmi_params{742, 11, 1, 2, 15, 8, 2, 49, 7.069849454709433e-6, std::ldexp(1.0, -44)};
-        return 0;
-    }
-    if (s == "secure128_torus") {
-        // the same two security-relevant pairs (n = 742 at LWE noise 2^-17.11; GLWE of size 2048 at noise 2^-44 >= 2.94e-16) on
-        // Concrete's own modulus q = 2^64.  Decompositions: bootstrap 3 x 10 bits against a key stored at 46 bits of precision
-        // (two 23-bit limbs: exact limb sums through the floating-point transform, fft_quarter_f64.hpp) - output noise 2^-22.9,
-        // below the 49-bit preset's 2^-19.5; keyswitch 8 x 2 bits as there.
-        *out = bmi_params{742, 11, 1, 3, 10, 8, 2, BMI_Q_TORUS64, 7.069849454709433e-6, std::ldexp(1.0, -44)};
-        return 0;
-    }
-    if (s == "secure128_torus_wide") {
-        // the same LWE pair under a GLWE of size 4096 (harder than the 2048 the noise 2^-44 is rated for) on q = 2^64, for the 5-bit
-        // look-ups of the reference's unmodified circuits and of bases other than 2: key at 44 bits of precision (two 22-bit limbs,
-        // fft_eighth_f64.hpp), bootstrap 3 x 10 bits.  The keyswitch noise (4,096 x levels rows at the LWE noise security dictates)
-        // is what bounds the margin: 16 levels of 1 bit (mean-square digit 1/2) put a 5-bit look-up at 5.4 sigma, against 4.6 with
-        // 8 x 2 bits and 4.4 at N = 2048 - whether that carries a circuit is error_budget's call (p_error), look-up count by count.
-        *out = bmi_params{742, 12, 1, 3, 10, 16, 1, BMI_Q_TORUS64, 7.069849454709433e-6, std::ldexp(1.0, -44)};
-        return 0;
-    }
-    return -1;
-}
+int bmi_preset_params(const char *name, bmi_params *out) { return preset_params(name, out); }
 
 const char *bmi_last_error(const bmi_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -747,20 +590,10 @@ int bmi_ctx_create(const bmi_params *params, int device, bmi_ctx **out) {
                                      std::string(hipGetErrorString(e)) + ")");
     if (device < 0 || device >= ndev) return fail(nullptr, -1, "bad device index");
     bmi_ctx *c = new bmi_ctx();
-    c->P = *params;
-    if (c->P.q_bits == 0) c->P.q_bits = 64;
-    if (c->P.q_bits == 49) c->f = Fq{f49::Q, 49};
-    if (c->P.q_bits == BMI_Q_TORUS64) {
-        c->f = Fq{0, 64, true};
-    }
-    const rotplan::Settings initial = rotplan::initial_settings(shape_of(c->P));
-    c->bsk_prec = initial.bsk_prec;
-    c->lat_threshold = initial.lat_threshold;
+    c->init(*params);
+    c->lat_threshold = rotplan::initial_settings(shape_of(c->P)).lat_threshold;
     c->ops = c->f64() ? &bmi49::OPS : c->t64() ? &bmit::OPS : &bmi::OPS;
     c->device = device;
-    c->N = 1u << params->log_N;
-    c->big_n = params->k * c->N;
-    c->rows = (params->k + 1) * params->bs_levels;
     c->ks_stride = (params->n + 1 + 7) & ~7u;
     auto bail = [&](const std::string &m) {   // releases whatever the context holds so far
         bmi_ctx_destroy(c);
@@ -876,69 +709,33 @@ int bmi_keygen_insecure_deterministic(bmi_ctx *c, uint64_t seed) {
 
 int bmi_keygen_from_secret(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big, uint64_t seed) {
     if (!c || !sk_small || !sk_big) return -1;
-    const uint32_t n = c->P.n, kN = c->P.k * c->N;
-    if (!is_binary(sk_small, n) || !is_binary(sk_big, kN)) return fail(c, -1, "secret keys are binary");
-    c->sk_small.assign(sk_small, sk_small + n);
-    c->sk_big.assign(sk_big, sk_big + kN);
-    if (seed == 0) {            // production: masks and noise from the CSPRNG
-        if (int rc = rekey_csprng(c)) return rc;
-    } else {
-        c->secure_rng = false;  // test vectors: deterministic in seed
-    }
+    if (int rc = take_secret_keys(c, sk_small, sk_big, seed)) return rc;
     return gen_eval_keys(c, seed);
 }
 
 // ct words on the 2^64 torus <-> words mod q: the modulus switch round(x * q / 2^64) and back.  Context-free (host).
 int bmi_torus64_to_field(uint32_t q_bits, const uint64_t *in, uint64_t words, uint64_t *out) {
-    if (!in || !out || (q_bits != 64 && q_bits != 49)) return -1;
-    torus64_to_field(q_bits == 49 ? f49::Q : gl::P, in, words, out);
-    return 0;
+    return torus64_to_field_words(q_bits, in, words, out);
 }
 
 int bmi_field_to_torus64(uint32_t q_bits, const uint64_t *in, uint64_t words, uint64_t *out) {
-    if (!in || !out || (q_bits != 64 && q_bits != 49)) return -1;
-    return field_to_torus64(q_bits == 49 ? f49::Q : gl::P, in, words, out) ? 0 : -1;
+    return field_to_torus64_words(q_bits, in, words, out);
 }
 
 int bmi_import_keys(bmi_ctx *c, const uint64_t *sk_small, const uint64_t *sk_big, const uint64_t *bsk, const uint64_t *ksk) {
     if (!c || !bsk || !ksk) return -1;
-    if ((sk_small == nullptr) != (sk_big == nullptr)) return fail(c, -1, "pass both secret keys or neither");
+    if (int rc = import_keys_pairing(c, sk_small, sk_big)) return rc;
     HIP_OK(c, hipSetDevice(c->device));
-    const bmi_params &P = c->P;
-    const size_t bsk_words = (size_t)P.n * c->rows * (P.k + 1) * c->N, ksk_words = (size_t)c->big_n * P.ks_levels * (P.n + 1);
-    for (size_t i = 0; i < bsk_words; i++)
-        if (!c->f.canonical(bsk[i])) return fail(c, -1, "bootstrap key word not reduced mod q");
-    for (size_t i = 0; i < ksk_words; i++)
-        if (!c->f.canonical(ksk[i])) return fail(c, -1, "keyswitch key word not reduced mod q");
+    if (int rc = import_keys_canonical(c, bsk, ksk)) return rc;
     c->have_keys = false;
     drop_sk_mask(c);
     drop_compression_key(c, true);
-    c->have_bsk3 = false;   // an unrolled key belongs to the key set it was generated with: import it again (bmi_import_bsk_unrolled)
-    c->mask_src = bmi_ctx::MaskSource::OTHER;
-    c->bsk_std.assign(bsk, bsk + bsk_words);
-    c->ksk.assign(ksk, ksk + ksk_words);
-    c->have_secret = sk_small != nullptr;
-    if (c->have_secret) {
-        if (!is_binary(sk_small, P.n) || !is_binary(sk_big, c->big_n)) return fail(c, -1, "secret keys are binary");
-        c->sk_small.assign(sk_small, sk_small + P.n);
-        c->sk_big.assign(sk_big, sk_big + c->big_n);
-    } else {
-        c->sk_small.clear();
-        c->sk_big.clear();
-    }
-    if (int rc = rekey_csprng(c)) return rc;   // encryptions under an imported key set draw fresh CSPRNG randomness
+    if (int rc = import_keys_store(c, sk_small, sk_big, bsk, ksk)) return rc;
     return upload_eval_keys(c);
 }
 
 int bmi_export_keys(const bmi_ctx *c, uint64_t *sk_small, uint64_t *sk_big, uint64_t *bsk, uint64_t *ksk) {
-    if (!c) return -1;
-    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    if ((sk_small || sk_big) && !c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
-    if (sk_small) std::memcpy(sk_small, c->sk_small.data(), c->sk_small.size() * 8);
-    if (sk_big) std::memcpy(sk_big, c->sk_big.data(), c->sk_big.size() * 8);
-    if (bsk) std::memcpy(bsk, c->bsk_std.data(), c->bsk_std.size() * 8);
-    if (ksk) std::memcpy(ksk, c->ksk.data(), c->ksk.size() * 8);
-    return 0;
+    return hc::export_keys(c, sk_small, sk_big, bsk, ksk);
 }
 
 int bmi_key_bytes(const bmi_ctx *c, uint64_t *bsk_bytes, uint64_t *ksk_bytes) {
@@ -953,39 +750,14 @@ int bmi_key_bytes(const bmi_ctx *c, uint64_t *bsk_bytes, uint64_t *ksk_bytes) {
     return 0;
 }
 
-// bmi_encrypt (ct_out: [count][k N + 1] words) and bmi_encrypt_seeded (bodies_out: [count] body words; the masks are not kept) are
-// this one routine: ciphertext i takes the encryption counter first + i, its masks from the public stream, its noise from the secret one
-static int encrypt_rows(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *ct_out, uint64_t *bodies_out) {
-    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
-    if (delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
-    // (secure contexts: the counter is never reset while the CSPRNG keys live - one nonce per ciphertext)
-    lwe_encrypt(c->sampler(c->seed), c->sk_big.data(), c->big_n, c->P.glwe_noise, c->enc_counter, msgs, count, delta_log, ct_out, bodies_out);
-    c->enc_counter += count;
-    return 0;
-}
-
 int bmi_encrypt(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *ct_out) {
-    if (!c || !msgs || !ct_out) return -1;
-    return encrypt_rows(c, msgs, count, delta_log, ct_out, nullptr);
+    return hc::encrypt(c, msgs, count, delta_log, ct_out);
 }
 
-int bmi_phase(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint64_t *phase) {
-    if (!c || !ct_in || !phase) return -1;
-    if (!c->have_keys) return fail(c, -1, "no keys: call bmi_keygen first");
-    if (!c->have_secret) return fail(c, -1, "evaluation-only context: it holds no secret key");
-    lwe_phase(c->f, c->sk_big.data(), c->big_n, ct_in, count, phase);
-    return 0;
-}
+int bmi_phase(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint64_t *phase) { return hc::phase(c, ct_in, count, phase); }
 
 int bmi_decrypt(const bmi_ctx *c, const uint64_t *ct_in, uint32_t count, uint32_t delta_log, int64_t *msgs) {
-    if (!c || !ct_in || !msgs) return -1;
-    if (delta_log == 0 || delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
-    std::vector<u64> ph(count);
-    int rc = bmi_phase(c, ct_in, count, ph.data());
-    if (rc) return rc;
-    for (uint32_t i = 0; i < count; i++) msgs[i] = decode(c->f, ph[i], delta_log);
-    return 0;
+    return hc::decrypt(c, ct_in, count, delta_log, msgs);
 }
 
 // the tail of a registration: the test polynomial and, on the torus, its sparse factor go to the device under the next free id
@@ -1082,52 +854,25 @@ int bmi_lut_get(const bmi_ctx *c, uint32_t lut_id, uint64_t *test_vector) {
 
 int bmi_set_bsk_precision(bmi_ctx *c, uint32_t bits) {
     if (!c) return -1;
-    const std::string refusal = rotplan::set_precision_refusal(shape_of(c->P), settings_of(c), held_of(c), bits);
-    if (!refusal.empty()) return fail(c, -1, refusal);
-    c->bsk_prec = (int)bits;
-    c->bsk_prec_explicit = true;
-    return 0;
+    return hc::set_bsk_precision(c, settings_of(c), held_of(c), bits);
 }
 
-int bmi_get_bsk_precision(const bmi_ctx *c, uint32_t *bits) {
-    if (!c || !bits) return -1;
-    *bits = c->t64() ? (uint32_t)c->bsk_prec : 64u;
-    return 0;
-}
+int bmi_get_bsk_precision(const bmi_ctx *c, uint32_t *bits) { return hc::get_bsk_precision(c, bits); }
 
 int bmi_set_bsk_unroll(bmi_ctx *c, uint32_t factor) {
     if (!c) return -1;
-    const rotplan::UnrollChoice ch = rotplan::set_unroll(shape_of(c->P), settings_of(c), held_of(c), factor);
-    if (!ch.refusal.empty()) return fail(c, -1, ch.refusal);
-    c->bsk_prec = ch.bsk_prec;   // (the precision nobody chose follows the mode)
-    c->unroll = factor;
-    if (factor == 2 && c->have_keys && !c->have_bsk3) {
-        if (!c->have_secret) return 0;   // evaluation-only context: the key arrives through bmi_import_bsk_unrolled
-        // the unrolled key of the secret keys already held: fresh masks and noise (CSPRNG, or the seeded test streams)
-        gen_bsk3(c, c->seed);
-        return upload_bsk3(c);
-    }
-    return 0;
+    bool generated = false;
+    if (int rc = hc::set_bsk_unroll(c, settings_of(c), held_of(c), factor, &generated)) return rc;
+    return generated ? upload_bsk3(c) : 0;
 }
 
 int bmi_import_bsk_unrolled(bmi_ctx *c, const uint64_t *bsk3) {
     if (!c || !bsk3) return -1;
-    const std::string refusal = rotplan::import_unrolled_refusal(shape_of(c->P), settings_of(c), held_of(c));
-    if (!refusal.empty()) return fail(c, -1, refusal);
-    const size_t words = c->bsk3_words();
-    for (size_t i = 0; i < words; i++)
-        if (!c->f.canonical(bsk3[i])) return fail(c, -1, "unrolled bootstrap key word not reduced mod q");
-    c->bsk3_std.assign(bsk3, bsk3 + words);
-    c->bsk3_from_stream = false;
+    if (int rc = import_bsk_unrolled_store(c, settings_of(c), held_of(c), bsk3)) return rc;
     return upload_bsk3(c);
 }
 
-int bmi_export_bsk_unrolled(const bmi_ctx *c, uint64_t *bsk3) {
-    if (!c || !bsk3) return -1;
-    if (!c->have_bsk3) return fail(c, -1, "no unrolled bootstrap key: bmi_set_bsk_unroll(ctx, 2) before keygen, or import one");
-    std::memcpy(bsk3, c->bsk3_std.data(), c->bsk3_std.size() * 8);
-    return 0;
-}
+int bmi_export_bsk_unrolled(const bmi_ctx *c, uint64_t *bsk3) { return hc::export_bsk_unrolled(c, bsk3); }
 
 int bmi_set_keyswitch_variant(bmi_ctx *c, int variant) {
     if (!c) return -1;
@@ -1474,22 +1219,7 @@ int bmi_negacyclic_mul_host(bmi_ctx *c, const uint64_t *a, const uint64_t *b, ui
 // ------------------------------------------------------------------- seeded keys and ciphertexts (chacha_expand.hip)
 // The specification of the seeded forms (hc::seeded_mask_words).  Context-free, host only.
 int bmi_seeded_mask_words(const uint32_t pub_key[8], uint64_t nonce, uint64_t first_word, uint64_t count, uint64_t *out) {
-    if (!pub_key || (count && !out)) return -1;
-    seeded_mask_words(pub_key, nonce, first_word, count, out);
-    return 0;
-}
-
-// What the seeded forms need of a context: masks that are words of a public stream whose key may be told.  `what` names the caller.
-static int seeded_ok(const bmi_ctx *c, const char *what) {
-    if (!c->t64())
-        return fail(c, -1, std::string(what) + ": seeded forms exist on the 2^64 torus only - on the 49-bit field and Goldilocks the masks are "
-                           "rejection-sampled, so a mask word's position in the stream depends on the words before it");
-    if (!c->have_keys) return fail(c, -1, std::string(what) + ": no keys: call bmi_keygen first");
-    if (c->mask_src == bmi_ctx::MaskSource::OTHER)
-        return fail(c, -1, std::string(what) + ": the masks of this key set did not come from the context's own public stream (keys loaded by "
-                           "bmi_import_keys, or deterministic test keys, whose stream key is an invertible function of the seed and would "
-                           "reveal the secrets): no seeded form");
-    return 0;
+    return seeded_mask_words_checked(pub_key, nonce, first_word, count, out);
 }
 
 // One seeded array -> its full standard-domain form in `full` ([rows][mask_w + body_w] host words): the compact bodies are uploaded
@@ -1511,12 +1241,7 @@ static int expand_seeded_key(bmi_ctx *c, u64 domain, size_t rows, uint32_t mask_
 }
 
 int bmi_export_keys_seeded(const bmi_ctx *c, uint32_t pub_key[8], uint64_t *bsk_bodies, uint64_t *ksk_bodies) {
-    if (!c || !pub_key || !bsk_bodies || !ksk_bodies) return -1;
-    if (int rc = seeded_ok(c, "bmi_export_keys_seeded")) return rc;
-    std::memcpy(pub_key, c->rng_public.k, sizeof(c->rng_public.k));
-    copy_bodies(c->bsk_std, (size_t)c->P.n * c->rows, c->big_n, c->N, bsk_bodies);
-    copy_bodies(c->ksk, (size_t)c->big_n * c->P.ks_levels, c->P.n, 1, ksk_bodies);
-    return 0;
+    return hc::export_keys_seeded(c, pub_key, bsk_bodies, ksk_bodies);
 }
 
 int bmi_import_keys_seeded(bmi_ctx *c, const uint32_t pub_key[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies) {
@@ -1544,16 +1269,7 @@ int bmi_import_keys_seeded(bmi_ctx *c, const uint32_t pub_key[8], const uint64_t
     return 0;
 }
 
-int bmi_export_bsk_unrolled_seeded(const bmi_ctx *c, uint64_t *bsk3_bodies) {
-    if (!c || !bsk3_bodies) return -1;
-    if (int rc = seeded_ok(c, "bmi_export_bsk_unrolled_seeded")) return rc;
-    if (!c->have_bsk3) return fail(c, -1, "no unrolled bootstrap key: bmi_set_bsk_unroll(ctx, 2) before keygen, or import one");
-    if (!c->bsk3_from_stream)
-        return fail(c, -1, "bmi_export_bsk_unrolled_seeded: the masks of this unrolled key did not come from the context's own public stream "
-                           "(a key loaded by bmi_import_bsk_unrolled): no seeded form");
-    copy_bodies(c->bsk3_std, (size_t)c->pairs() * 3 * c->rows, c->big_n, c->N, bsk3_bodies);
-    return 0;
-}
+int bmi_export_bsk_unrolled_seeded(const bmi_ctx *c, uint64_t *bsk3_bodies) { return hc::export_bsk_unrolled_seeded(c, bsk3_bodies); }
 
 int bmi_import_bsk_unrolled_seeded(bmi_ctx *c, const uint64_t *bsk3_bodies) {
     if (!c || !bsk3_bodies) return -1;
@@ -1570,12 +1286,7 @@ int bmi_import_bsk_unrolled_seeded(bmi_ctx *c, const uint64_t *bsk3_bodies) {
 }
 
 int bmi_encrypt_seeded(bmi_ctx *c, const int64_t *msgs, uint32_t count, uint32_t delta_log, uint64_t *first_counter, uint64_t *bodies) {
-    if (!c || !first_counter || (count && (!msgs || !bodies))) return -1;
-    if (int rc = seeded_ok(c, "bmi_encrypt_seeded")) return rc;
-    const u64 first = c->enc_counter;
-    if (int rc = encrypt_rows(c, msgs, count, delta_log, nullptr, bodies)) return rc;
-    *first_counter = first;
-    return 0;
+    return hc::encrypt_seeded(c, msgs, count, delta_log, first_counter, bodies);
 }
 
 int bmi_expand_seeded_batch(bmi_ctx *c, uint64_t first_counter, const uint64_t *d_bodies, uint32_t count, uint64_t *d_out, void *stream) {
@@ -1600,31 +1311,7 @@ int bmi_expand_seeded_batch_host(bmi_ctx *c, uint64_t first_counter, const uint6
 }
 
 // ------------------------------------------------------------------- compression of output ciphertexts (lwe_pack.hip)
-// What every compression entry point needs of a context, and of a (levels, base log) pair.  `what` names the caller.
-static int compression_ok(const bmi_ctx *c, const char *what) {
-    if (!c->t64())
-        return fail(c, -1, std::string(what) + ": compression of output ciphertexts exists on the 2^64 torus only (not on the 49-bit field or "
-                           "Goldilocks)");
-    if (!c->have_keys) return fail(c, -1, std::string(what) + ": no keys: call bmi_keygen first");
-    return 0;
-}
-static int compression_shape_ok(const bmi_ctx *c, const char *what, uint32_t levels, uint32_t base_log) {
-    if (levels < 1 || levels > 4 || base_log < 1 || base_log > 16 || levels * base_log > 63)
-        return fail(c, -1, std::string(what) + ": the compression key's decomposition needs 1 <= levels <= 4, 1 <= base_log <= 16 and "
-                           "levels * base_log <= 63");
-    return 0;
-}
-static int compression_key_held(const bmi_ctx *c, const char *what) {
-    if (int rc = compression_ok(c, what)) return rc;
-    if (!c->pk_levels)
-        return fail(c, -1, std::string(what) + ": no compression key: call bmi_compression_keygen or import one (a new key set drops it)");
-    return 0;
-}
-static int log_modulus_ok(const bmi_ctx *c, const char *what, uint32_t log_modulus) {
-    if (log_modulus < 2 || log_modulus > 32) return fail(c, -1, std::string(what) + ": log_modulus must be in [2, 32]");
-    return 0;
-}
-
+// (what every compression entry point needs of a context, and of a (levels, base log) pair: key_set.hpp)
 // the compression key (host copy in c->pksk, standard layout) -> device, with the bias vector of the unsigned-digit product:
 // bias[col] = 2^(base_log - 1) * sum over all rows of key[row][col]
 static int upload_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
@@ -1640,25 +1327,12 @@ static int upload_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log
 
 int bmi_compression_keygen(bmi_ctx *c, uint32_t levels, uint32_t base_log) {
     if (!c) return -1;
-    if (int rc = compression_ok(c, "bmi_compression_keygen")) return rc;
-    if (!c->have_secret) return fail(c, -1, "bmi_compression_keygen: evaluation-only context: it holds no secret key");
-    if (int rc = compression_shape_ok(c, "bmi_compression_keygen", levels, base_log)) return rc;
-    // One shape per key set.  Row jr takes its masks from the public stream (S_PKSK_MASK, jr) and its noise from the secret stream
-    // (S_PKSK_NOISE, jr), both from their first word: a key of another shape would give row jr the same A and e under another
-    // message, and the difference of the two bodies is an exact combination of secret-key bits.  The same shape again gives the
-    // same key.
-    if (c->pk_gen_levels && (c->pk_gen_levels != levels || c->pk_gen_base_log != base_log))
-        return fail(c, -1, "bmi_compression_keygen: this key set already has a compression key of shape (" + std::to_string(c->pk_gen_levels) +
-                           ", " + std::to_string(c->pk_gen_base_log) + "); a second one of another shape would reuse the rows' mask and noise "
-                           "streams under other messages and reveal the secret key: generate a new key set first");
+    if (int rc = compression_keygen_refusal(c, levels, base_log)) return rc;
     HIP_OK(c, hipSetDevice(c->device));
     drop_compression_key(c, false);
-    c->pk_gen_levels = levels;
-    c->pk_gen_base_log = base_log;
-    c->pksk.assign((size_t)c->N * levels * 2 * c->N, 0);
-    compression_key_rows(c->sampler(c->seed), c->sk_big.data(), c->N, levels, base_log, c->P.glwe_noise, c->pksk.data());
+    gen_compression_key(c, levels, base_log);
     if (int rc = upload_compression_key(c, levels, base_log)) return rc;
-    c->pksk_from_stream = c->secure_rng && c->mask_src == bmi_ctx::MaskSource::OWN_STREAM;
+    c->pksk_from_stream = compression_key_from_stream(c);
     return 0;
 }
 
@@ -1670,33 +1344,18 @@ int bmi_compression_key_info(const bmi_ctx *c, uint32_t *levels, uint32_t *base_
     return 0;
 }
 
-int bmi_export_compression_key(const bmi_ctx *c, uint64_t *key) {
-    if (!c || !key) return -1;
-    if (int rc = compression_key_held(c, "bmi_export_compression_key")) return rc;
-    std::memcpy(key, c->pksk.data(), c->pksk.size() * 8);
-    return 0;
-}
+int bmi_export_compression_key(const bmi_ctx *c, uint64_t *key) { return hc::export_compression_key(c, key); }
 
 int bmi_import_compression_key(bmi_ctx *c, uint32_t levels, uint32_t base_log, const uint64_t *key) {
     if (!c || !key) return -1;
-    if (int rc = compression_ok(c, "bmi_import_compression_key")) return rc;
-    if (int rc = compression_shape_ok(c, "bmi_import_compression_key", levels, base_log)) return rc;
+    if (int rc = import_compression_key_refusal(c, levels, base_log)) return rc;
     HIP_OK(c, hipSetDevice(c->device));
     drop_compression_key(c, false);
-    c->pksk.assign(key, key + (size_t)c->N * levels * 2 * c->N);
+    import_compression_key_store(c, levels, key);
     return upload_compression_key(c, levels, base_log);
 }
 
-int bmi_export_compression_key_seeded(const bmi_ctx *c, uint64_t *bodies) {
-    if (!c || !bodies) return -1;
-    if (int rc = seeded_ok(c, "bmi_export_compression_key_seeded")) return rc;
-    if (int rc = compression_key_held(c, "bmi_export_compression_key_seeded")) return rc;
-    if (!c->pksk_from_stream)
-        return fail(c, -1, "bmi_export_compression_key_seeded: the masks of this compression key did not come from the context's own public "
-                           "stream (a key loaded by bmi_import_compression_key): no seeded form");
-    copy_bodies(c->pksk, (size_t)c->N * c->pk_levels, c->N, c->N, bodies);
-    return 0;
-}
+int bmi_export_compression_key_seeded(const bmi_ctx *c, uint64_t *bodies) { return hc::export_compression_key_seeded(c, bodies); }
 
 int bmi_import_compression_key_seeded(bmi_ctx *c, uint32_t levels, uint32_t base_log, const uint64_t *bodies) {
     if (!c || !bodies) return -1;
@@ -1713,12 +1372,7 @@ int bmi_import_compression_key_seeded(bmi_ctx *c, uint32_t levels, uint32_t base
     return 0;
 }
 
-int bmi_compressed_words(const bmi_ctx *c, uint32_t count, uint64_t *words) {
-    if (!c || !words) return -1;
-    if (!c->t64()) return fail(c, -1, "bmi_compressed_words: compression of output ciphertexts exists on the 2^64 torus only");
-    *words = ((u64)count + c->N - 1) / c->N * c->N + count;
-    return 0;
-}
+int bmi_compressed_words(const bmi_ctx *c, uint32_t count, uint64_t *words) { return hc::compressed_words(c, count, words); }
 
 int bmi_compress_batch(bmi_ctx *c, const uint64_t *d_in, uint32_t count, uint32_t log_modulus, uint32_t *d_out, void *stream) {
     if (!c || (count && (!d_in || !d_out))) return -1;
@@ -1761,23 +1415,11 @@ int bmi_compress_batch_host(bmi_ctx *c, const uint64_t *in, uint32_t count, uint
 }
 
 int bmi_phase_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint64_t *phase) {
-    if (!c || (count && (!data || !phase))) return -1;
-    if (int rc = compression_ok(c, "bmi_phase_compressed")) return rc;
-    if (!c->have_secret) return fail(c, -1, "bmi_phase_compressed: evaluation-only context: it holds no secret key");
-    if (int rc = log_modulus_ok(c, "bmi_phase_compressed", log_modulus)) return rc;
-    if (!compressed_phase(c->f, c->sk_big.data(), c->N, data, count, log_modulus, phase))
-        return fail(c, -1, "bmi_phase_compressed: a value does not fit log_modulus bits");
-    return 0;
+    return hc::phase_compressed(c, data, count, log_modulus, phase);
 }
 
 int bmi_decrypt_compressed(const bmi_ctx *c, const uint32_t *data, uint32_t count, uint32_t log_modulus, uint32_t delta_log, int64_t *msgs) {
-    if (!c || (count && (!data || !msgs))) return -1;
-    if (int rc = compression_ok(c, "bmi_decrypt_compressed")) return rc;
-    if (delta_log == 0 || delta_log >= c->f.bits - 1) return fail(c, -1, "delta_log out of range");
-    std::vector<u64> ph(count);
-    if (int rc = bmi_phase_compressed(c, data, count, log_modulus, ph.data())) return rc;
-    for (uint32_t i = 0; i < count; i++) msgs[i] = decode(c->f, ph[i], delta_log);
-    return 0;
+    return hc::decrypt_compressed(c, data, count, log_modulus, delta_log, msgs);
 }
 
 // Decompression (lwe_unpack.hip) needs no key of any kind: the modulus, the shape and the arguments are all it checks.

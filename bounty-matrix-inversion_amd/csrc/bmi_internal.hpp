@@ -7,10 +7,6 @@
 #include "goldilocks.hpp"
 #include "rotation_plan.hpp"
 
-#ifndef BMI_DEFAULT_Q_BITS
-#define BMI_DEFAULT_Q_BITS 65  // modulus of bmi_default_params(): 65 = BMI_Q_TORUS64 (q = 2^64, Concrete's own: the default since round 4), 49 (f64 kernels mod 2^49 - 720895) or 64 (Goldilocks)
-#endif
-
 #ifndef BMI_TPX49_PF
 #define BMI_TPX49_PF 13  // exchange-once kernel: where the two GGSW rows of a level are requested (see the kernel)
 #endif

@@ -59,13 +59,8 @@ T64_HD int limb_pre(int prec) { return 64 - prec; }
 // the unrolled step needs b + BITS <= 34
 T64_HD int max_base_log(int prec, bool unrolled) { return (unrolled ? 34 : 37) - limb_bits(prec); }
 
-// The key word stored at `prec` bits of precision: rounded half up (as a signed integer) to a multiple of 2^(64 - prec);
-// unsigned arithmetic, the wrap at the top of the range is the torus's own.
-T64_HD u64 round_key_word(u64 w, int prec) {
-    const int drop = 64 - prec;
-    if (drop == 0) return w;
-    return ((w + ((u64)1 << (drop - 1))) >> drop) << drop;
-}
+// (The key word stored at `prec` bits of precision - rounded half up, as a signed integer, to a multiple of 2^(64 - prec) - is
+// hc::round_key_word, key_set.hpp: the host rounds the key, in both libraries, and the kernels receive it rounded.)
 
 // balanced limb j of a signed 64-bit word at precision `prec`: limb_j in [-2^(BITS-1), 2^(BITS-1)), the last one takes the rest
 T64_HD i64 limb_of(i64 k, int j, int prec) {
